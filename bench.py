@@ -1,12 +1,17 @@
 """bench.py -- train image-instruction pairs/s, LLaVA-1.5-7B (CLIP-ViT-L/14-336 + Vicuna-7B geometry), bf16, MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One step = forward + backward + gradient all-reduce (N > 1, RCCL, overlapped with backward) + AdamW update of all
 6.76 B trainable parameters, on a synthetic batch of SURVEY.md section 8d's config-2 sample (one 336x336 image,
 129 ids with the image placeholder at position 35 -> S = 704), random-init weights.  Prints ONE JSON line.
+
+A plain run sets up, warms up, times K steps and prints the headline figure.  --full adds what takes runs of its own: the every-row
+variant, the exposed communication (N > 1), the GEMM roofline (one HIP-event-instrumented step, PMC records from profiles/) and the
+CPU baseline.  --dump-outputs DIR writes what the last timed step computed (loss, gradient norm, a fixed sample of the updated
+weights) as DIR/<name>.npy, so that two builds can be compared output for output on identical seeded inputs.
 """
 import argparse
 import json
@@ -195,6 +200,32 @@ class GemmTimer:
         return flops, ms, len(self.records), sum(r[3] for r in self.records)
 
 
+DUMP_POSITIONS = 6 * 2 ** 20    # sampled weight positions: two float32 arrays of them stay under the 64 MB the dump may take
+
+
+def dump_outputs(eng, loss, out_dir):
+    """What a caller of the step receives after it: the loss, the global gradient norm before clipping, and the updated weights -- the
+    bf16 trainable buffer and its fp32 master copy, at the same positions.  Weights are sampled per tensor (every element of a small
+    tensor, a seeded subset of a large one, so that each tensor is represented), from a fixed seed: the positions depend on the
+    geometry and workload only."""
+    names = eng.lm.names()
+    per_tensor = max(1, DUMP_POSITIONS // len(names))
+    rng = np.random.default_rng(0)
+    idx = []
+    for name in names:
+        off, n = eng.lm.offsets[name]
+        pos = np.arange(n) if n <= per_tensor else np.sort(rng.choice(n, per_tensor, replace=False))
+        idx.append(off + pos)
+    idx = torch.from_numpy(np.concatenate(idx)).to(eng.lm.flat.device)
+    out = {"loss": np.array([float(loss)], dtype=np.float32),
+           "grad_norm": eng.last_grad_norm.float().cpu().numpy(),
+           "weights_sample": eng.lm.flat[idx].float().cpu().numpy(),
+           "master_weights_sample": eng.master[idx].float().cpu().numpy()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class _StdoutToStderr:
     """RCCL prints a version banner on STDOUT when its first communicator is created; the contract is ONE JSON line on stdout, so file
     descriptor 1 points at stderr while the process group comes up (fd level: the banner is written by the C library)."""
@@ -217,7 +248,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="pairs per GPU per step (global batch 256 at 8 GPUs)")
     ap.add_argument("--geometry", default="llava15_7b")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: every-row variant, exposed communication, GEMM roofline, CPU baseline (each costs runs of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, gradient norm and a fixed sample of the updated weights as DIR/<name>.npy")
     ap.add_argument("--workload", default="cxr", choices=["cxr", "anyres", "lora", "radvlm"],
                     help="cxr = BASELINE configs 2/3 (headline); anyres = config 4 (S=3056); lora = config 5 (r=64 adapters); "
                          "radvlm = SURVEY 8f.1 (Qwen2-7B + SigLIP, anyres_max_9, all parts tunable; use --geometry llava_ov_qwen2_7b --batch 2)")
@@ -234,6 +269,8 @@ def main():
                          "side stream anyway (single-GPU rehearsal of the N > 1 path: stream / event ordering, one-tile GEMM blocks beside the "
                          "collectives).  Not the headline configuration.")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks here (one process per GPU over RCCL), BEFORE anything touches the
@@ -356,11 +393,13 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     pairs = args.batch * world * args.steps
     value = pairs / dt
+    if args.dump_outputs and rank == 0:     # before --full's extra steps change the weights
+        dump_outputs(eng, loss, args.dump_outputs)
 
     # the same step with NOTHING restricted to the labelled rows (every row through the last layer's MLP, the final norm, lm_head and the cross
     # entropy: the reference's own evaluation order), timed beside the headline number on the same box: `config.every_row_variant`
     every_row = None
-    if args.head_rows == "labeled":
+    if args.full and args.head_rows == "labeled":
         eng.head_rows = eng.last_layer_rows = "all"
         for _ in range(max(2, args.warmup)):
             step()
@@ -380,7 +419,7 @@ def main():
 
     # exposed communication: time the compute stream spends waiting for the last gradient buckets (events around finish_grad_sync)
     comm_wait_ms = None
-    if eng.sync is not None:
+    if args.full and eng.sync is not None:
         eng.sync.timing = []
         for _ in range(2):
             step()
@@ -388,51 +427,53 @@ def main():
         comm_wait_ms = sum(a.elapsed_time(b) for a, b in eng.sync.timing) / 2
         eng.sync.timing = None
 
-    # dominant kernel (bf16 MFMA GEMM): algorithmic flops / measured launch time, one extra instrumented step
-    with GemmTimer(ops) as gt:
-        step()
-        gflops, gms, nlaunch, gbytes = gt.summary()
     from radvlm_amd.build_id import kernel_source_sha256
     src_hash = kernel_source_sha256()
-    roofline = {"bound": "mfma", "kernel": "gemm_kernel_256 (all operand forms; 128x128 kernel for small shapes)", "achieved": gflops / (gms * 1e-3) / 1e12, "peak": PEAK_BF16_TFLOPS,
-                "unit": "TFLOP/s", "traffic": None, "launches_per_step": nlaunch, "gemm_ms_per_step": gms,
-                "algorithmic_flops_per_launch": gflops / max(1, nlaunch), "algorithmic_bytes_per_launch": gbytes / max(1, nlaunch),
-                "avg_launch_us": gms * 1e3 / max(1, nlaunch)}
-    roofline["frac"] = roofline["achieved"] / roofline["peak"]
-    # counter-derived fields come from separate `rocprofv3 --pmc` passes of this very command (profiles/README.md); they are quoted
-    # only when they were taken on the kernel sources this run uses (radvlm_amd.build_id) and for the same workload -- else null
-    headline = args.workload == "cxr" and args.batch == 32 and args.geometry == "llava15_7b" and not args.text_lens
+    roofline = None
+    if args.full:
+        # dominant kernel (bf16 MFMA GEMM): algorithmic flops / measured launch time, one extra instrumented step
+        with GemmTimer(ops) as gt:
+            step()
+            gflops, gms, nlaunch, gbytes = gt.summary()
+        roofline = {"bound": "mfma", "kernel": "gemm_kernel_256 (all operand forms; 128x128 kernel for small shapes)", "achieved": gflops / (gms * 1e-3) / 1e12, "peak": PEAK_BF16_TFLOPS,
+                    "unit": "TFLOP/s", "traffic": None, "launches_per_step": nlaunch, "gemm_ms_per_step": gms,
+                    "algorithmic_flops_per_launch": gflops / max(1, nlaunch), "algorithmic_bytes_per_launch": gbytes / max(1, nlaunch),
+                    "avg_launch_us": gms * 1e3 / max(1, nlaunch)}
+        roofline["frac"] = roofline["achieved"] / roofline["peak"]
+        # counter-derived fields come from separate `rocprofv3 --pmc` passes of this very command (profiles/README.md); they are quoted
+        # only when they were taken on the kernel sources this run uses (radvlm_amd.build_id) and for the same workload -- else null
+        headline = args.workload == "cxr" and args.batch == 32 and args.geometry == "llava15_7b" and not args.text_lens
 
-    def pmc(suffix):
-        """The newest profiles/rNN_<suffix> whose kernel-source hash is the one this run executes (else None)."""
-        import glob
-        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_" + suffix)), reverse=True):
-            try:
-                with open(path) as f:
-                    d = json.load(f)
-            except (OSError, ValueError):
-                continue
-            if headline and d.get("kernel_source_sha256") == src_hash:
-                return d, "profiles/" + os.path.basename(path)
-        return None, None
-    tr, tr_path = pmc("pmc_gemm_hbm_traffic.json")
-    if tr:
-        roofline["traffic"] = tr["gemm_kernel_256"]["hbm_bytes_per_launch"]
-        roofline["traffic_over_algorithmic"] = roofline["traffic"] / roofline["algorithmic_bytes_per_launch"]
-        roofline["traffic_source"] = f"{tr_path} (separate --pmc FETCH_SIZE / WRITE_SIZE passes of this command, kernel sources {src_hash})"
-    else:
-        roofline["traffic_source"] = f"null: no PMC pass on record for kernel sources {src_hash} / this workload"
-    mf, _ = pmc("pmc_mfma_util.json")
-    if mf:
-        roofline["pmc_mfma"] = mf["gemm_kernel_256_all_forms"]
-    tf_pair = TF_PER_PAIR.get(args.geometry) if args.workload == "cxr" else None
-    # the whole step against the MFMA peak, from the flops the GEMM launches of one step EXECUTE (measured above), not from a nominal count:
-    # the final norm / lm_head / cross entropy run on the rows that carry a label (engine.head_rows; 64 of 704 rows per pair here), so the
-    # step executes less than SURVEY 8d's 28.75 TF/pair, which counts the head on every row -- that nominal figure is reported beside it
-    roofline["step_executed_gemm_tflops"] = gflops / 1e12 / (ms_per_step * 1e-3)
-    roofline["step_frac_of_mfma_peak"] = roofline["step_executed_gemm_tflops"] / PEAK_BF16_TFLOPS
-    if tf_pair:
-        roofline["step_nominal_tflops_survey_8d"] = tf_pair * args.batch / (ms_per_step * 1e-3)
+        def pmc(suffix):
+            """The newest profiles/rNN_<suffix> whose kernel-source hash is the one this run executes (else None)."""
+            import glob
+            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_" + suffix)), reverse=True):
+                try:
+                    with open(path) as f:
+                        d = json.load(f)
+                except (OSError, ValueError):
+                    continue
+                if headline and d.get("kernel_source_sha256") == src_hash:
+                    return d, "profiles/" + os.path.basename(path)
+            return None, None
+        tr, tr_path = pmc("pmc_gemm_hbm_traffic.json")
+        if tr:
+            roofline["traffic"] = tr["gemm_kernel_256"]["hbm_bytes_per_launch"]
+            roofline["traffic_over_algorithmic"] = roofline["traffic"] / roofline["algorithmic_bytes_per_launch"]
+            roofline["traffic_source"] = f"{tr_path} (separate --pmc FETCH_SIZE / WRITE_SIZE passes of this command, kernel sources {src_hash})"
+        else:
+            roofline["traffic_source"] = f"null: no PMC pass on record for kernel sources {src_hash} / this workload"
+        mf, _ = pmc("pmc_mfma_util.json")
+        if mf:
+            roofline["pmc_mfma"] = mf["gemm_kernel_256_all_forms"]
+        tf_pair = TF_PER_PAIR.get(args.geometry) if args.workload == "cxr" else None
+        # the whole step against the MFMA peak, from the flops the GEMM launches of one step EXECUTE (measured above), not from a nominal count:
+        # the final norm / lm_head / cross entropy run on the rows that carry a label (engine.head_rows; 64 of 704 rows per pair here), so the
+        # step executes less than SURVEY 8d's 28.75 TF/pair, which counts the head on every row -- that nominal figure is reported beside it
+        roofline["step_executed_gemm_tflops"] = gflops / 1e12 / (ms_per_step * 1e-3)
+        roofline["step_frac_of_mfma_peak"] = roofline["step_executed_gemm_tflops"] / PEAK_BF16_TFLOPS
+        if tf_pair:
+            roofline["step_nominal_tflops_survey_8d"] = tf_pair * args.batch / (ms_per_step * 1e-3)
     # sequence length of the spliced decoder input for the fixed-shape cxr workload: image tokens + ids - the placeholder
     v = geo["vision"]
     s_cxr = (v["image"] // v["patch"]) ** 2 + 129 - 1
@@ -453,17 +494,17 @@ def main():
                        "parallelism": f"dp{world}", "final_loss": final_loss, "rows_with_a_label_only": {"all": "nothing", "head": "final norm, lm_head, cross entropy", "labeled": "last layer's o_proj / norm / MLP, final norm, lm_head, cross entropy"}[args.head_rows],
                        **({"every_row_variant": every_row} if every_row else {}),
                        **({"text_lens": args.text_lens, "packed": args.packed} if args.text_lens else {})},
-            "roofline": roofline,
+            **({"roofline": roofline} if args.full else {}),
             "distributed": {"world": world, "ranks_seen": ranks_seen, "backend": backend if not rehearsal else f"{backend} (rehearsal: all ranks on one GPU)",
                             "grad_sync": None if eng.sync is None else "bucketed sum-all-reduce of the flat bf16 gradient buffer, per-layer buckets on a side stream",
-                            "exposed_comm_ms_per_step": comm_wait_ms, "gemm_cu_budget": cu_budget, "reserved_cus": reserved,
+                            **({"exposed_comm_ms_per_step": comm_wait_ms} if args.full else {}), "gemm_cu_budget": cu_budget, "reserved_cus": reserved,
                             # each rank's own time for the K steps before the closing barrier: max - min = straggler spread over ranks
                             "ms_per_step_min": dt_min / args.steps * 1e3, "ms_per_step_max": dt_max / args.steps * 1e3,
                             "bucket_count": None if eng.sync is None else len(eng.sync.last_buckets),
                             "bucket_mbytes": None if eng.sync is None else [round((e - s) * 2 / 2 ** 20, 1) for s, e in eng.sync.last_buckets][:4] + ["..."] * (len(eng.sync.last_buckets) > 4)},
             "build": {"kernel_source_sha256": src_hash},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(geo)
         print(json.dumps(out))
     if world > 1 or force_pg:

@@ -2,8 +2,9 @@
 
     python tools/kernel_stats_per_step.py profiles/r03_bench_b32_kernel_stats.csv 4 [out.json]
 
-`steps` = the number of training steps the profiled command executed (bench.py --steps K --warmup W runs W + K timed steps + one
-GEMM-instrumented step, + 2 more when a process group exists): the CSV holds whole-run totals, so every per-step figure quoted from it
+`steps` = the number of training steps the profiled command executed (bench.py --full --steps K --warmup W runs W + K timed steps,
+max(2, W) + K steps of the every-row variant (--head-rows labeled), one GEMM-instrumented step, + 2 more when a process group exists;
+a plain run only the W + K): the CSV holds whole-run totals, so every per-step figure quoted from it
 in DESIGN.md is total / steps.  Start-up kernels (random init, casts, fills) are listed separately and not divided."""
 import csv
 import json

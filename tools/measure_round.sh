@@ -6,8 +6,8 @@ set -u
 TAG=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-B="--steps 1 --warmup 1 --no-cpu-baseline"
-echo "[measure] kernel trace"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/${TAG}_trace.log 2>&1 || exit 1
+B="--full --steps 1 --warmup 1 --no-cpu-baseline"
+echo "[measure] kernel trace"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/${TAG}_trace.log 2>&1 || exit 1
 cp "$(find $O/${TAG}_trace -name '*kernel_stats.csv' | head -1)" $O/${TAG}_bench_b32_kernel_stats.csv
 echo "[measure] pmc FETCH_SIZE"; rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${TAG}_pmc_fetch -- python3 bench.py $B > $O/${TAG}_pmc_fetch.log 2>&1 || exit 1
 echo "[measure] pmc WRITE_SIZE"; rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${TAG}_pmc_write -- python3 bench.py $B > $O/${TAG}_pmc_write.log 2>&1 || exit 1

@@ -36,7 +36,7 @@ for d, c in disp.items():
     for key, v in c.items():
         fam[k][key] += v
     fam[k]["launches"] += 1
-res = {"source": "rocprofv3 --pmc (own pass, --kernel-trace only) on `python bench.py --steps 1 --warmup 1 --no-cpu-baseline` (b=32), MI355X",
+res = {"source": "rocprofv3 --pmc (own pass, --kernel-trace only) on `python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline` (b=32), MI355X",
        "kernel_source_sha256": kernel_source_sha256(), "git_commit": sys.argv[3] if len(sys.argv) > 3 else None, "kernels": {}}
 tot = defaultdict(float)
 for k, c in sorted(fam.items(), key=lambda kv: -kv[1]["_ns"]):

@@ -1,5 +1,5 @@
 """HBM-side bytes per GEMM launch from two separate rocprofv3 passes (`--pmc FETCH_SIZE` and `--pmc WRITE_SIZE`, each with
---kernel-trace only) of `python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline`.
+--kernel-trace only) of `python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline`.
 
     python tools/pmc_traffic_summary.py FETCH_counter_collection.csv WRITE_counter_collection.csv out.json [git-commit]
 
@@ -35,8 +35,8 @@ def per_kernel(path, counter):
 
 fetch, nf = per_kernel(sys.argv[1], "FETCH_SIZE")
 write, nw = per_kernel(sys.argv[2], "WRITE_SIZE")
-res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) on `python3 bench.py --steps 1 --warmup 1 "
-                 "--no-cpu-baseline` (b=32), MI355X",
+res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) on `python3 bench.py --full --steps 1 "
+                 "--warmup 1 --no-cpu-baseline` (b=32), MI355X",
        "correction": "bytes = counter * 1024; FETCH_SIZE doubled (gfx950 counts half of wide coalesced reads); WRITE_SIZE as is",
        "kernel_source_sha256": kernel_source_sha256(), "git_commit": sys.argv[4] if len(sys.argv) > 4 else None, "per_operand_form": {}}
 if "adamw_kernel" in fetch:

@@ -10,7 +10,7 @@ rocm-smi --showmaxpower 2>/dev/null | grep -i -E "max|cap" | head -3
 ( while true; do echo "T $(date +%s.%N)" >> $O; rocm-smi -P -c -t 2>/dev/null | grep -E "Power|sclk|Temperature \(Sensor (junction|edge)" >> $O; sleep 0.2; done ) &
 SAMPLER=$!
 sleep 1
-python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > gpurun_out/power_probe_bench.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > "$(dirname "$O")/power_probe_bench.json" 2>/dev/null
 kill $SAMPLER 2>/dev/null; wait $SAMPLER 2>/dev/null
 python3 - <<'PY'
 import json, re

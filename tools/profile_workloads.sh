@@ -15,7 +15,7 @@ for w in $WL; do
     *) echo "unknown workload $w"; exit 2 ;;
   esac
   echo "[profile] $w"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace_$w -- python3 bench.py $ARGS --steps 2 --warmup 1 --no-cpu-baseline > $O/${TAG}_trace_$w.log 2>&1 || { tail -5 $O/${TAG}_trace_$w.log; exit 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace_$w -- python3 bench.py $ARGS --full --steps 2 --warmup 1 --no-cpu-baseline > $O/${TAG}_trace_$w.log 2>&1 || { tail -5 $O/${TAG}_trace_$w.log; exit 1; }
   cp "$(find $O/${TAG}_trace_$w -name '*kernel_stats.csv' | head -1)" $O/${TAG}_${w}_kernel_stats.csv
   grep '^{' $O/${TAG}_trace_$w.log > $O/${TAG}_${w}_profiled_bench_line.json || true
   rm -rf $O/${TAG}_trace_$w
