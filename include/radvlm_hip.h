@@ -321,6 +321,36 @@ int rv_cast_bf16_to_f32(const void* in, float* out, int64_t n, void* stream);
 /* y[i] = a[i] + b[i] (bf16). */
 int rv_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream);
 
+/* ---- decode (generate(): one new token per sequence, radvlm_amd/csrc/decode.hip) ---------------------------------------------
+ * The reference decodes through HF generate on inputs_embeds (llava_llama.py generate() -> HF:generation/utils.py greedy search with
+ * a DynamicCache); these four entry points are its per-token arithmetic: the projections at M = batch rows, attention of one query row
+ * against the cache, the cache update and the greedy argmax. */
+/* Skinny NT GEMM: Y[M,N] = X[M,K] W[N,K]^T (+ bias[N]) (+ residual[M,N]) for 1 <= M <= 32 (fp32 accumulation; bf16 Y, or fp32 Y with
+ * out_f32 for the lm_head scores).  Weights are streamed once (16-byte nontemporal loads); the K range is split over workgroups when
+ * N alone gives too few of them (rv_gemv_split(N, K) slices, combined in slice order by a second launch through `workspace`, which
+ * needs split * M * N * 4 bytes when split > 1).  The reduction order is a function of (N, K): row r's result is bit-identical for
+ * every M.  K % 8 == 0, ldx % 8 == 0, ldw % 8 == 0. */
+int rv_gemv_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, void* Y, int64_t ldy, const void* bias, const void* residual,
+                 int64_t ldr, int M, int N, int K, int out_f32, void* workspace, int64_t ws_bytes, void* stream);
+/* Number of K slices rv_gemv_bf16 uses for an [N, K] weight (host function, no launch). */
+int rv_gemv_split(int N, int K);
+/* Decode attention (flash-decoding): for every sequence b and q head h, softmax(scale * q[b,h] K^T) V over the cached keys
+ * [0, kv_len[b]) of kv head h / (H / Hkv), hd in {64, 128}, up to 8 q heads per kv head (GQA), fp32 softmax and accumulation.
+ * cache: bf16 [B][L_max][ld_c] (sequence stride bs_c), K of kv head g at columns g*hd, V at v_off + g*hd.  q: [B, H*hd] rows (ld_q);
+ * out: bf16 [B, H*hd] rows (ld_o).  Keys are split into chunks of `chunk` rows (a multiple of 16 for hd 128, of 32 for hd 64,
+ * <= 512) over workgroups; each writes (o, m, l) partials to `part` (B * H * ceil(L_max / chunk) * (hd + 2) floats) and a second
+ * launch merges a sequence's chunks in chunk order.  kv_len is an int32 device array, values <= L_max. */
+int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
+                        int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk,
+                        float scale, void* stream);
+/* KV cache append: cache[b][pos[b]][0:width] = src[b][0:width] (bf16; rows of the post-RoPE k|v columns of the qkv product);
+ * pos is an int32 device array, slots outside [0, L_max) are skipped.  width % 8 == 0. */
+int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, int64_t ld_c, int64_t bs_c, const int32_t* pos, int L_max, int B,
+                      int width, void* stream);
+/* Greedy token choice: out[r] (int64) = argmax over the first n columns of fp32 row r (torch.argmax: lowest index among equal
+ * maxima, NaN counts as the maximum); columns >= n (vocabulary pad rows of the lm_head) are never read. */
+int rv_argmax_rows_f32(const float* x, int64_t ld, int rows, int n, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

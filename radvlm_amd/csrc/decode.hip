@@ -1,0 +1,381 @@
+// Decode-time kernels for gfx950: the skinny NT GEMM of one generated token per sequence (M = batch, 1..32 rows), flash-decoding
+// attention of one query row per (sequence, q head) against a KV cache, the cache append and the row argmax of greedy decoding.
+// Reductions use a fixed order that depends on the problem shape only (N, K; a sequence's own kv_len) -- never on M, on other rows or
+// on timing -- and no atomics: a row's result is bit-identical whatever else shares its launch.
+// Reference call sites are listed per entry point in include/radvlm_hip.h.
+#include "common.h"
+#include "radvlm_hip.h"
+
+#include <math.h>
+
+namespace {
+
+#define ST ((hipStream_t)stream)
+
+DEVINL bf16x8 zero8() {
+    bf16x8 z;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z[i] = (bf16)0.f;
+    return z;
+}
+
+// weights are read once per token by exactly one CU: nontemporal (MI355X_MICROARCH "nt-weights")
+DEVINL bf16x8 ld_nt(const bf16* p) { return __builtin_nontemporal_load((const bf16x8*)p); }
+
+// ------------------------------------------------------------------------------------------------ skinny NT GEMM
+// Y[M,N] = X[M,K] W[N,K]^T (+ bias) (+ residual), M <= 32.  Block: 4 waves, 64 output columns (four 16-column MFMA tiles); the K steps
+// (32 deep) of the block's K range are split into 4 contiguous runs, one per wave.  Weights go straight from HBM to VGPRs (dwordx4, nt),
+// U steps in flight per wave; the X rows (<= 64 KB, L2-resident) are loaded beside them.  MT = row tiles of 16 (rows >= M read zeros).
+// MFMA 16x16x32: A = X rows (lane l: row l&15, k 8*(l>>4)..+7), B = W rows (lane l: column l&15, same k) -> D[row][col].
+constexpr int GV_COLS = 64;
+constexpr int GV_U = 4;
+
+template <int MT>
+__global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W, long ldw, int M, int N,
+                                                   int K, int split, float* __restrict__ part, void* __restrict__ Y, long ldy,
+                                                   const bf16* __restrict__ bias, const bf16* __restrict__ R, long ldr, int out_f32) {
+    __shared__ float red[4][MT * 16][GV_COLS];
+    const int lane = lane_id(), w = wave_id();
+    const int c = lane & 15, kg = lane >> 4;
+    const int n0 = blockIdx.x * GV_COLS;
+    const int sidx = blockIdx.y;
+    const int ks = (K + 31) / 32;
+    const int unit = sidx * 4 + w, units = split * 4;
+    const int s0 = (int)((long)ks * unit / units), s1 = (int)((long)ks * (unit + 1) / units);
+    const bf16* wp[4];
+    bool n_ok[4];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        const int n = n0 + ct * 16 + c;
+        n_ok[ct] = n < N;
+        wp[ct] = W + (long)(n_ok[ct] ? n : 0) * ldw + kg * 8;
+    }
+    const bf16* xp[MT];
+    bool m_ok[MT];
+#pragma unroll
+    for (int rt = 0; rt < MT; ++rt) {
+        const int m = rt * 16 + c;
+        m_ok[rt] = m < M;
+        xp[rt] = X + (long)(m_ok[rt] ? m : 0) * ldx + kg * 8;
+    }
+    f32x4 acc[MT][4];
+#pragma unroll
+    for (int rt = 0; rt < MT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int st = s0; st < s1; st += GV_U) {
+        bf16x8 wf[GV_U][4], xf[GV_U][MT];
+#pragma unroll
+        for (int u = 0; u < GV_U; ++u) {
+            const int k = (st + u) * 32;
+            const bool kin = (st + u) < s1 && k + kg * 8 < K;       // K % 8 == 0: a lane's 8 elements are all in or all out
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) wf[u][ct] = (kin && n_ok[ct]) ? ld_nt(wp[ct] + k) : zero8();
+#pragma unroll
+            for (int rt = 0; rt < MT; ++rt) xf[u][rt] = (kin && m_ok[rt]) ? *(const bf16x8*)(xp[rt] + k) : zero8();
+        }
+#pragma unroll
+        for (int u = 0; u < GV_U; ++u)
+#pragma unroll
+            for (int rt = 0; rt < MT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = mfma16(xf[u][rt], wf[u][ct], acc[rt][ct]);
+    }
+#pragma unroll
+    for (int rt = 0; rt < MT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[w][rt * 16 + 4 * kg + r][ct * 16 + c] = acc[rt][ct][r];
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < MT * 16 * GV_COLS; idx += 256) {
+        const int m = idx / GV_COLS, col = idx % GV_COLS, n = n0 + col;
+        if (m >= M || n >= N) continue;
+        float v = red[0][m][col];
+        v += red[1][m][col];
+        v += red[2][m][col];
+        v += red[3][m][col];
+        if (split > 1) {
+            part[((long)sidx * M + m) * N + n] = v;
+            continue;
+        }
+        if (bias) v += bf2f(bias[n]);
+        if (R) v += bf2f(R[(long)m * ldr + n]);
+        if (out_f32)
+            ((float*)Y)[(long)m * ldy + n] = v;
+        else
+            ((bf16*)Y)[(long)m * ldy + n] = f2bf(v);
+    }
+}
+
+// split-K combine: the K-slices summed in slice order, then bias / residual / store (same epilogue as above)
+__global__ void gemv_combine_kernel(const float* __restrict__ part, int split, int M, int N, void* __restrict__ Y, long ldy,
+                                    const bf16* __restrict__ bias, const bf16* __restrict__ R, long ldr, int out_f32) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= (long)M * N) return;
+    const int m = (int)(tid / N), n = (int)(tid % N);
+    float v = part[tid];
+    for (int s = 1; s < split; ++s) v += part[(long)s * M * N + tid];
+    if (bias) v += bf2f(bias[n]);
+    if (R) v += bf2f(R[(long)m * ldr + n]);
+    if (out_f32)
+        ((float*)Y)[(long)m * ldy + n] = v;
+    else
+        ((bf16*)Y)[(long)m * ldy + n] = f2bf(v);
+}
+
+// ------------------------------------------------------------------------------------------------ decode attention
+// Block (chunk c, kv head kh, sequence b): keys [c*chunk, min((c+1)*chunk, kv_len[b])) for the G = H / Hkv query heads of kv head kh,
+// which share every K / V read.  LPR = HD/8 lanes read one 16-byte slice each of a key row; a wave covers 64/LPR rows per step.
+// Writes the chunk's (unnormalised o, running max m, sum l) to part[b][h][c][HD + 2]; attn_decode_combine_kernel merges the chunks.
+constexpr int AD_GMAX = 8;
+constexpr int AD_CHUNK_MAX = 512;
+
+template <int HD>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const bf16* __restrict__ q, long ld_q, const bf16* __restrict__ cache, long ld_c,
+                                                          long bs_c, int v_off, const int* __restrict__ kv_len, int L_max, float* __restrict__ part,
+                                                          int H, int Hkv, int chunk, float scale) {
+    constexpr int LPR = HD / 8, RPW = 64 / LPR, RPB = 4 * RPW;
+    __shared__ float sc[AD_GMAX][AD_CHUNK_MAX];
+    __shared__ float ored[4][AD_GMAX][HD];
+    __shared__ float mstat[AD_GMAX];
+    const int c = blockIdx.x, kh = blockIdx.y, b = blockIdx.z;
+    const int G = H / Hkv;
+    const int nch = gridDim.x;
+    const int len = min(kv_len[b], L_max);
+    const int j0 = c * chunk;
+    if (j0 >= len) return;                     // the combine reads chunks < ceil(len / chunk) only
+    const int j1 = min(j0 + chunk, len), n = j1 - j0;
+    const int lane = lane_id(), w = wave_id();
+    const int li = lane % LPR, lr = lane / LPR;
+    const bf16* kbase = cache + (long)b * bs_c + kh * HD + li * 8;
+    const bf16* vbase = kbase + v_off;
+    float qv[AD_GMAX][8];
+#pragma unroll
+    for (int g = 0; g < AD_GMAX; ++g) {
+        if (g < G) {
+            const bf16x8 t = *(const bf16x8*)(q + (long)b * ld_q + (kh * G + g) * HD + li * 8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) qv[g][i] = bf2f(t[i]);
+        }
+    }
+    // scores
+    for (int jb = j0; jb < j1; jb += RPB) {
+        const int j = jb + w * RPW + lr;
+        const bool ok = j < j1;
+        const bf16x8 kt = ok ? *(const bf16x8*)(kbase + (long)j * ld_c) : zero8();
+#pragma unroll
+        for (int g = 0; g < AD_GMAX; ++g) {
+            if (g < G) {
+                float d = 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) d += qv[g][i] * bf2f(kt[i]);
+#pragma unroll
+                for (int o = 1; o < LPR; o <<= 1) d += __shfl_xor(d, o, 64);
+                if (ok && li == 0) sc[g][j - j0] = d * scale;
+            }
+        }
+    }
+    __syncthreads();
+    // chunk softmax statistics: wave w owns heads w and w + 4
+    for (int g = w; g < G; g += 4) {
+        float m = -INFINITY;
+        for (int j = lane; j < n; j += 64) m = fmaxf(m, sc[g][j]);
+        m = wave_max(m);
+        float l = 0.f;
+        for (int j = lane; j < n; j += 64) {
+            const float p = expf(sc[g][j] - m);
+            sc[g][j] = p;
+            l += p;
+        }
+        l = wave_sum(l);
+        if (lane == 0) {
+            mstat[g] = m;
+            float* pp = part + (((long)b * H + kh * G + g) * nch + c) * (HD + 2);
+            pp[HD] = m;
+            pp[HD + 1] = l;
+        }
+    }
+    __syncthreads();
+    // P V
+    float acc[AD_GMAX][8];
+#pragma unroll
+    for (int g = 0; g < AD_GMAX; ++g)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[g][i] = 0.f;
+    for (int jb = j0; jb < j1; jb += RPB) {
+        const int j = jb + w * RPW + lr;
+        if (j < j1) {
+            const bf16x8 vt = *(const bf16x8*)(vbase + (long)j * ld_c);
+#pragma unroll
+            for (int g = 0; g < AD_GMAX; ++g) {
+                if (g < G) {
+                    const float p = sc[g][j - j0];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) acc[g][i] += p * bf2f(vt[i]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < AD_GMAX; ++g) {
+        if (g < G) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                float a = acc[g][i];
+#pragma unroll
+                for (int o = LPR; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
+                if (lr == 0) ored[w][g][li * 8 + i] = a;
+            }
+        }
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < G * HD; idx += 256) {
+        const int g = idx / HD, dd = idx % HD;
+        float o = ored[0][g][dd];
+        o += ored[1][g][dd];
+        o += ored[2][g][dd];
+        o += ored[3][g][dd];
+        part[(((long)b * H + kh * G + g) * nch + c) * (HD + 2) + dd] = o;
+    }
+}
+
+// one block of HD threads per (sequence, q head): chunks merged in chunk order, bf16 out [B, H*HD]
+template <int HD>
+__global__ __launch_bounds__(HD) void attn_decode_combine_kernel(const float* __restrict__ part, const int* __restrict__ kv_len, int L_max,
+                                                                 bf16* __restrict__ out, long ld_o, int H, int nch, int chunk) {
+    const int bh = blockIdx.x, b = bh / H, h = bh % H, dd = threadIdx.x;
+    const int len = min(kv_len[b], L_max);
+    const int nc = min((len + chunk - 1) / chunk, nch);
+    const float* pp = part + (long)bh * nch * (HD + 2);
+    float M = -INFINITY;
+    for (int c = 0; c < nc; ++c) M = fmaxf(M, pp[c * (HD + 2) + HD]);
+    float L = 0.f, o = 0.f;
+    for (int c = 0; c < nc; ++c) {
+        const float e = expf(pp[c * (HD + 2) + HD] - M);
+        L += pp[c * (HD + 2) + HD + 1] * e;
+        o += pp[c * (HD + 2) + dd] * e;
+    }
+    out[(long)b * ld_o + h * HD + dd] = f2bf(nc > 0 ? o / L : 0.f);
+}
+
+// ------------------------------------------------------------------------------------------------ cache append
+// cache[b][pos[b]][0:width] = src[b][0:width]; slots outside [0, L_max) are not written
+__global__ void kv_append_kernel(const bf16* __restrict__ src, long ld_src, bf16* __restrict__ cache, long ld_c, long bs_c,
+                                 const int* __restrict__ pos, int L_max, int width) {
+    const int b = blockIdx.x;
+    const int p = pos[b];
+    if (p < 0 || p >= L_max) return;
+    for (int e = threadIdx.x * 8; e < width; e += blockDim.x * 8)
+        *(bf16x8*)(cache + (long)b * bs_c + (long)p * ld_c + e) = *(const bf16x8*)(src + (long)b * ld_src + e);
+}
+
+// ------------------------------------------------------------------------------------------------ row argmax
+// torch.argmax semantics over the first n columns: the lowest index among equal maxima, NaN above everything
+DEVINL bool am_better(float v, int i, float bv, int bi) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > bv || (v == bv && i < bi);
+}
+
+__global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, long ld, int n, int64_t* __restrict__ out) {
+    __shared__ float rv[4];
+    __shared__ int ri[4];
+    const float* row = x + (long)blockIdx.x * ld;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const float v = row[j];
+        if (am_better(v, j, bv, bi)) { bv = v; bi = j; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (am_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane_id() == 0) { rv[wave_id()] = bv; ri[wave_id()] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k)
+            if (am_better(rv[k], ri[k], bv, bi)) { bv = rv[k]; bi = ri[k]; }
+        out[blockIdx.x] = bi;
+    }
+}
+
+inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
+
+}  // namespace
+
+extern "C" int rv_gemv_split(int N, int K) {
+    // K slices per column block: enough blocks for >= 2 per CU on 256 CUs, every wave keeps >= 2 of its 32-deep K steps.  A function of
+    // (N, K) only, so a row's reduction order never depends on M.
+    const long nb = (N + GV_COLS - 1) / GV_COLS, ks = (K + 31) / 32;
+    int split = 1;
+    while (nb * split < 512 && split < 16 && ks >= (long)split * 2 * 4 * 2) split *= 2;
+    return split;
+}
+
+extern "C" int rv_gemv_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, void* Y, int64_t ldy, const void* bias, const void* residual,
+                            int64_t ldr, int M, int N, int K, int out_f32, void* workspace, int64_t ws_bytes, void* stream) {
+    if (!X || !W || !Y || M < 1 || M > 32 || N <= 0 || K <= 0 || (K & 7) || (ldx & 7) || (ldw & 7) || ldx < K || ldw < K || ldy < N ||
+        (residual && ldr < N))
+        return RV_ERR_ARG;
+    const int split = rv_gemv_split(N, K);
+    float* part = nullptr;
+    if (split > 1) {
+        if (!workspace || ws_bytes < (int64_t)split * M * N * 4) return RV_ERR_ARG;
+        part = (float*)workspace;
+    }
+    const dim3 grid(cdiv(N, GV_COLS), split);
+    if (M <= 16)
+        hipLaunchKernelGGL(gemv_kernel<1>, grid, dim3(256), 0, ST, (const bf16*)X, (long)ldx, (const bf16*)W, (long)ldw, M, N, K, split, part, Y,
+                           (long)ldy, (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32);
+    else
+        hipLaunchKernelGGL(gemv_kernel<2>, grid, dim3(256), 0, ST, (const bf16*)X, (long)ldx, (const bf16*)W, (long)ldw, M, N, K, split, part, Y,
+                           (long)ldy, (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32);
+    if (split > 1)
+        hipLaunchKernelGGL(gemv_combine_kernel, dim3(cdiv((long)M * N, 256)), dim3(256), 0, ST, (const float*)part, split, M, N, Y, (long)ldy,
+                           (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32);
+    return rv_check_launch();
+}
+
+extern "C" int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
+                                   int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk,
+                                   float scale, void* stream) {
+    if (!q || !cache || !kv_len || !out || !part || B <= 0 || Hkv <= 0 || H % Hkv || H / Hkv > AD_GMAX || (hd != 64 && hd != 128) ||
+        L_max <= 0 || chunk <= 0 || chunk > AD_CHUNK_MAX || chunk % (hd == 128 ? 16 : 32) || (ld_q & 7) || (ld_c & 7) || (bs_c & 7) ||
+        (v_off & 7) || ld_c < v_off + (int64_t)Hkv * hd || bs_c < (int64_t)L_max * ld_c)
+        return RV_ERR_ARG;
+    const int nch = (L_max + chunk - 1) / chunk;
+    if (part_bytes < (int64_t)B * H * nch * (hd + 2) * 4) return RV_ERR_ARG;
+    const dim3 grid(nch, Hkv, B);
+    if (hd == 128) {
+        hipLaunchKernelGGL(attn_decode_kernel<128>, grid, dim3(256), 0, ST, (const bf16*)q, (long)ld_q, (const bf16*)cache, (long)ld_c, (long)bs_c,
+                           v_off, kv_len, L_max, (float*)part, H, Hkv, chunk, scale);
+        hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(B * H), dim3(128), 0, ST, (const float*)part, kv_len, L_max, (bf16*)out,
+                           (long)ld_o, H, nch, chunk);
+    } else {
+        hipLaunchKernelGGL(attn_decode_kernel<64>, grid, dim3(256), 0, ST, (const bf16*)q, (long)ld_q, (const bf16*)cache, (long)ld_c, (long)bs_c,
+                           v_off, kv_len, L_max, (float*)part, H, Hkv, chunk, scale);
+        hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(B * H), dim3(64), 0, ST, (const float*)part, kv_len, L_max, (bf16*)out,
+                           (long)ld_o, H, nch, chunk);
+    }
+    return rv_check_launch();
+}
+
+extern "C" int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, int64_t ld_c, int64_t bs_c, const int32_t* pos, int L_max, int B,
+                                 int width, void* stream) {
+    if (!src || !cache || !pos || B <= 0 || width <= 0 || (width & 7) || (ld_src & 7) || (ld_c & 7) || (bs_c & 7) || ld_c < width ||
+        bs_c < (int64_t)L_max * ld_c)
+        return RV_ERR_ARG;
+    hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, ST, (const bf16*)src, (long)ld_src, (bf16*)cache, (long)ld_c, (long)bs_c, pos,
+                       L_max, width);
+    return rv_check_launch();
+}
+
+extern "C" int rv_argmax_rows_f32(const float* x, int64_t ld, int rows, int n, int64_t* out, void* stream) {
+    if (!x || !out || rows <= 0 || n <= 0 || ld < n) return RV_ERR_ARG;
+    hipLaunchKernelGGL(argmax_rows_kernel, dim3(rows), dim3(256), 0, ST, x, (long)ld, n, out);
+    return rv_check_launch();
+}

@@ -629,6 +629,21 @@ class LlavaEngine:
             acts["attn_sel"] = attn_sel
         return x_out, acts
 
+    def _pixels(self, images):
+        """The images of a batch (list of [3,H,W] / [T,3,H,W], host or device, float or uint8) -> one bf16 [n,3,H,W] device tensor."""
+        dev = self.device
+        pix = torch.cat([(im if im.ndim == 4 else im[None]) for im in images], 0)
+        if pix.device.type == "cpu" and not pix.is_pinned() and dev.type == "cuda":
+            pix = pix.pin_memory()                                                          # pinned: the copy does not stall the stream
+        pix = pix.to(dev, non_blocking=True)          # images already on the device (HF Trainer._prepare_inputs moves them) pass through
+        if pix.dtype == torch.uint8:
+            # device-side normalisation (SURVEY 8f.4): uint8 HWC tiles from the host (resize / crop / pad only), rescale + (x - mean) / std
+            # + channel-first layout + bf16 cast here, in the processors' own fp32 arithmetic
+            pix = ops.normalize_tiles_u8(pix.contiguous(), self.v["image"], self.image_mean, self.image_std, mode=1 if self.siglip else 0)
+        else:
+            pix = pix if pix.dtype == BF16 else ops.to_bf16(pix.float())
+        return pix.contiguous()
+
     def forward(self, input_ids, attention_mask, labels, images, image_sizes=None, want_logits=False, loss_scale=None):
         """One training forward. Returns loss (fp32 device tensor [1], never scaled); keeps the context for backward().
         loss_scale multiplies the GRADIENTS only (default: self.loss_scale; a trainer sets 1 / gradient_accumulation_steps, which is
@@ -640,18 +655,9 @@ class LlavaEngine:
         self._select_gemm_launch_shape()
         plan = self.plan(input_ids, attention_mask, labels, images, image_sizes)
         self.lora_step += 1
-        pix = torch.cat([(im if im.ndim == 4 else im[None]) for im in images], 0)
-        if pix.device.type == "cpu" and not pix.is_pinned() and dev.type == "cuda":
-            pix = pix.pin_memory()                                                          # pinned: the copy does not stall the stream
-        pix = pix.to(dev, non_blocking=True)          # images already on the device (HF Trainer._prepare_inputs moves them) pass through
-        if pix.dtype == torch.uint8:
-            # device-side normalisation: uint8 HWC tiles from the host (resize / crop / pad only), rescale + (x - mean) / std
-            # + channel-first layout + bf16 cast here, in the processors' own fp32 arithmetic
-            pix = ops.normalize_tiles_u8(pix.contiguous(), self.v["image"], self.image_mean, self.image_std, mode=1 if self.siglip else 0)
-        else:
-            pix = pix if pix.dtype == BF16 else ops.to_bf16(pix.float())
+        pix = self._pixels(images)
         ctx = dict(plan=plan)
-        table = self.encode_images(pix.contiguous(), save=ctx, plan=plan)
+        table = self.encode_images(pix, save=ctx, plan=plan)
         B = int(np.asarray(input_ids).shape[0])   # samples (a sample may hold several images: images are consumed in order)
         S = plan["S"]
         s_pad = _ru(S, 64)
@@ -809,6 +815,101 @@ class LlavaEngine:
             loss, _ = self._cross_entropy(logits_bf, self._dev(tgt), self.vocab, (1.0 / count) if count else float("nan"), 0.0)
         self.last_logits = logits
         return loss, logits
+
+    # ------------------------------------------------------------------ generation (KV-cached greedy decode)
+    # Rows up to this many per decode GEMM go to rv_gemv_bf16, larger batches to the tiled GEMM.  Same-box A/B of the two at M = 1, 4,
+    # 16, 32 on the 7B decode shapes (DESIGN.md "Decode", profiles/decode_ab_gemv.jsonl): the skinny kernel wins at every M on every
+    # shape except the 152,064-row Qwen2 lm_head, where it wins at M <= 4 only (0.93x at 16, 0.79x at 32: one K slice, and the tiled
+    # GEMM's 256-row tiles amortise the weight stream over the rows better there).
+    gemv_max_m = 32
+    gemv_max_m_wide = 4          # weights with >= 65,536 rows
+
+    def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16):
+        max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
+        if x.shape[0] <= min(max_m, ops.GEMV_MAX_M):
+            return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
+        return ops.gemm_nt(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
+
+    def _check_generation(self):
+        if self.lora:
+            raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first (the reference merges "
+                                      "adapters before evaluation)")
+
+    def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0):
+        """The prompt pass of generation: multimodal splice (plan / encode_images, as in forward) and every decoder layer in the packed
+        varlen layout, sequence b at cache rows and positions 0 .. len_b - 1 whatever the padding side.  Each layer's post-RoPE K|V rows go
+        into a KVCache of len_b + max_new_tokens slots per sequence; the activations are dropped.  No loss, no saved context (self.ctx and
+        the optimizer state are not touched).  images None: text-only prompts, embedded directly.
+        Returns (cache, fp32 logits [B, vocab] of every sequence's last prompt row)."""
+        self._check_generation()
+        dev, l = self.device, self.l
+        d, L, kvd = l["d"], l["layers"], self.kvd
+        from .splice import IMAGE_TOKEN_INDEX
+        ids = np.asarray(input_ids)
+        B = int(ids.shape[0])
+        imgs = [] if images is None else list(images)
+        if not imgs and (ids == IMAGE_TOKEN_INDEX).any():
+            raise ValueError("the prompt holds an image token but no images were passed")
+        plan = self.plan(ids, attention_mask, None, imgs, image_sizes)
+        if imgs:
+            table = self.encode_images(self._pixels(imgs), plan=plan)
+        else:
+            table = torch.zeros(1, d, dtype=BF16, device=dev)          # no feature rows: the splice reads token embeddings only
+        lens = plan["lens"].astype(np.int64)
+        if (lens == 0).any():
+            raise ValueError("generation needs at least one prompt token per sequence")
+        valid = plan["attention_mask"].reshape(-1)
+        S = int(lens.max())
+        L_max = int(lens.max()) + int(max_new_tokens)
+        cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+        pos = np.concatenate([np.arange(n, dtype=np.int32) for n in lens])
+        geom = dict(B=B, S=S, s_pad=_ru(S, 64), lens=None, cu=self._dev(cu), pos=self._dev(pos), cs=self.rope_table(L_max))
+        x = ops.gather_rows(self._dev(plan["idx"][valid].astype(np.int32)), d, self.W("model.embed_tokens.weight"), table)
+        slots = self._dev(np.concatenate([b * L_max + np.arange(n) for b, n in enumerate(lens)]).astype(np.int64))
+        layers = []
+        for i in range(L):
+            x, acts = self._layer_forward(i, x, geom)
+            kv = torch.zeros(B, L_max, 2 * kvd, dtype=BF16, device=dev)
+            kv.view(B * L_max, 2 * kvd).index_copy_(0, slots, acts["qkv"][:, d:])
+            layers.append(kv)
+            del acts
+        last = self._dev((cu[1:] - 1).astype(np.int32))
+        hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
+        logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
+        return KVCache(layers, lens, L_max), logits[:, :self.vocab]
+
+    def decode_step(self, cache, tokens):
+        """One generated token per sequence: tokens [B] (int, host or device) at position cache.lens[b] -> fp32 logits [B, vocab].
+        Per layer: RMSNorm, q|k|v projection, RoPE at the token's position, cache append, decode attention over the sequence's cached
+        keys, o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual; then the final norm and the lm_head (fp32 scores)."""
+        self._check_generation()
+        l = self.l
+        d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
+        hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
+        B = cache.B
+        if (cache.lens >= cache.L_max).any():
+            raise ValueError(f"the KV cache is full ({cache.L_max} slots per sequence)")
+        tok = tokens.to(self.device, torch.int32) if torch.is_tensor(tokens) else self._dev(np.asarray(tokens, dtype=np.int32))
+        assert tok.numel() == B
+        pos = self._dev(cache.lens.astype(np.int32))
+        kv_len = self._dev((cache.lens + 1).astype(np.int32))
+        cs = self.rope_table(cache.L_max)
+        x = ops.gather_rows(tok.contiguous(), d, self.W("model.embed_tokens.weight"))
+        for i in range(L):
+            lv = self._layer_views(i)
+            h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"))
+            ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
+            ops.kv_append(qkv[:, d:], cache.layers[i], pos)
+            attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            x_mid = self._decode_linear(attn, lv["o"], residual=x)
+            h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"]), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid)
+        hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
+        logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
+        cache.lens += 1
+        return logits[:, :self.vocab]
 
     def _cross_entropy(self, logits, tgt, V, inv, gscale):
         from . import lib
@@ -1154,3 +1255,21 @@ class LlavaEngine:
         if strict and (missing or rest):
             raise KeyError(f"missing={missing[:4]} unexpected={rest[:4]}")
         return missing, rest
+
+
+class KVCache:
+    """Keys and values of one generate() call: per decoder layer a bf16 [B, L_max, 2 * kvd] tensor holding each position's post-RoPE
+    K | V row as it sits in the q|k|v product (sequence b at rows 0 .. lens[b] - 1), and the host-side lengths.  Freed with the object."""
+    chunk = 128           # keys per decode-attention workgroup: fixed, so a sequence's result never depends on the batch around it
+
+    def __init__(self, layers, lens, L_max):
+        self.layers = layers
+        self.lens = np.asarray(lens, dtype=np.int64).copy()
+        self.L_max = int(L_max)
+
+    @property
+    def B(self):
+        return int(self.lens.shape[0])
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.layers)

@@ -264,6 +264,23 @@ class LlavaLlamaForCausalLM:
 
     __call__ = forward
 
+    @torch.no_grad()
+    def generate(self, inputs=None, images=None, image_sizes=None, modalities=("image",), **kwargs):
+        """Greedy generation (the reference's generate(): the multimodal splice once, then HF generate on the spliced inputs_embeds).
+        inputs: prompt token ids [B, T] (IMAGE_TOKEN_INDEX where an image goes); images / image_sizes as in forward (None: text only).
+        Returns the NEW tokens only, LongTensor [B, T_new]; rows that finished (EOS or a stopping criterion) are filled with
+        pad_token_id.  Keywords: max_new_tokens (default 20), max_length, eos_token_id, pad_token_id, attention_mask, stopping_criteria,
+        use_cache (the result is the same either way), output_scores + return_dict_in_generate (.sequences, .scores).  Sampling, beam
+        search, streamers, inputs_embeds and LoRA models raise NotImplementedError.  The training state (weights, optimizer, RNG
+        counters) is not touched."""
+        from ...generation import greedy_generate, parse_generate_kwargs
+        cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
+                                    config_pad=getattr(self.config, "pad_token_id", None))
+        if inputs is None:
+            raise ValueError("generate() needs the prompt token ids (`inputs`)")
+        imgs = None if images is None else (list(images) if not torch.is_tensor(images) else [im for im in images])
+        return greedy_generate(self.engine, inputs, cfg.attention_mask, imgs, image_sizes, cfg)
+
     def save_config(self, out_dir):
         """config.json in HF's key vocabulary (what model.config.save_pretrained leaves next to the weights), plus the tower
         geometry under 'mm_vision_geometry' so that the directory is loadable as --model_name_or_path on its own."""

@@ -543,3 +543,72 @@ def to_f32(x):
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     lib.call("rv_cast_bf16_to_f32", x.contiguous(), out, x.numel())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ decode (generate)
+GEMV_MAX_M = 32
+
+
+def gemv_split(N, K):
+    """K slices rv_gemv_bf16 uses for an [N, K] weight (a function of the weight shape alone)."""
+    return int(lib.load().rv_gemv_split(int(N), int(K)))
+
+
+def gemv(x, w, out=None, bias=None, residual=None, out_dtype=BF16, workspace=None):
+    """out[M,N] = x[M,K] @ w[N,K]^T (+ bias) (+ residual) for M <= 32 rows (decode): rv_gemv_bf16, weights streamed once.
+    Row r of the result is bit-identical for every M."""
+    _chk(x), _chk(w)
+    M, K = x.shape
+    N = w.shape[0]
+    assert 1 <= M <= GEMV_MAX_M and w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype in (BF16, torch.float32)
+    if bias is not None:
+        _chk(bias)
+        assert bias.numel() == N and bias.is_contiguous()
+    ldr = 0
+    if residual is not None:
+        _chk(residual)
+        assert residual.shape == (M, N) and residual.stride(1) == 1
+        ldr = residual.stride(0)
+    if workspace is None:
+        workspace = default_workspace(x.device)
+    lib.call("rv_gemv_bf16", x, x.stride(0), w, w.stride(0), out, out.stride(0), bias, residual, ldr, M, N, K,
+             int(out.dtype == torch.float32), workspace, workspace.numel() * workspace.element_size())
+    return out
+
+
+def attn_decode(q, cache, kv_len, H, Hkv, hd, v_off, out=None, chunk=128, scale=None):
+    """One query row per (sequence, q head) against the cached keys [0, kv_len[b]): q [B, H*hd] rows; cache bf16 [B, L_max, width]
+    with K of kv head g at columns g*hd and V at v_off + g*hd; kv_len int32 [B] (device).  Returns bf16 [B, H*hd]."""
+    _chk(q), _chk(cache), _chk(kv_len, torch.int32)
+    B, L_max, width = cache.shape
+    assert q.shape == (B, H * hd) and q.stride(1) == 1 and cache.is_contiguous() and kv_len.numel() == B and kv_len.is_contiguous()
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if out is None:
+        out = torch.empty(B, H * hd, dtype=BF16, device=q.device)
+    nch = (L_max + chunk - 1) // chunk
+    part = torch.empty(B * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    lib.call("rv_attn_decode_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len, L_max, out, out.stride(0), part,
+             part.numel() * 4, B, H, Hkv, hd, chunk, float(scale))
+    return out
+
+
+def kv_append(src, cache, pos):
+    """cache[b, pos[b], :] = src[b, :] (src [B, width] bf16 rows, e.g. the k|v columns of the qkv product; pos int32 [B] device)."""
+    _chk(src), _chk(cache), _chk(pos, torch.int32)
+    B, L_max, width = cache.shape
+    assert src.shape == (B, width) and src.stride(1) == 1 and cache.is_contiguous() and pos.numel() == B and pos.is_contiguous()
+    lib.call("rv_kv_append_bf16", src, src.stride(0), cache, width, L_max * width, pos, L_max, B, width)
+    return cache
+
+
+def argmax_rows(x, n, out=None):
+    """int64 [rows]: torch.argmax of each fp32 row over its first n columns (lowest index on ties)."""
+    _chk(x, torch.float32)
+    rows = x.shape[0]
+    assert x.dim() == 2 and x.stride(1) == 1 and 0 < n <= x.shape[1]
+    out = torch.empty(rows, dtype=torch.int64, device=x.device) if out is None else out
+    lib.call("rv_argmax_rows_f32", x, x.stride(0), rows, int(n), out)
+    return out
