@@ -351,6 +351,13 @@ int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, int64_t ld_c
  * maxima, NaN counts as the maximum); columns >= n (vocabulary pad rows of the lm_head) are never read. */
 int rv_argmax_rows_f32(const float* x, int64_t ld, int rows, int n, int64_t* out, void* stream);
 
+/* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
+ * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any
+ * grid and any placement of W.  W: bf16 rows of ldw elements (a row slice of a fused q|k|v or gate|up store is fine), 16-byte aligned,
+ * K % 8 == 0, ldw % 8 == 0.  B: bf16 [N, r] rows of ldb; A: bf16 [r, K] rows of lda.  No workspace. */
+int rv_lora_merge_bf16(void* W, int64_t ldw, const void* B, int64_t ldb, const void* A, int64_t lda, int N, int K, int r, float scale,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -832,8 +832,8 @@ class LlavaEngine:
 
     def _check_generation(self):
         if self.lora:
-            raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first (the reference merges "
-                                      "adapters before evaluation)")
+            raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
+                                      "model.merge_and_unload() (the reference merges adapters before evaluation)")
 
     def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0):
         """The prompt pass of generation: multimodal splice (plan / encode_images, as in forward) and every decoder layer in the packed
@@ -1240,6 +1240,76 @@ class LlavaEngine:
             else:
                 others[n] = self.lm.view(n)
         return adapters, others
+
+    # ------------------------------------------------------------------ LoRA merge (peft merge_and_unload)
+    def merge_lora_(self, adapters, scale):
+        """W <- bf16(W + scale * B A) in place (rv_lora_merge_bf16) for every entry of `adapters`: {"model.layers.{i}.{module}": (A [r, in],
+        B [out, r])}, module one of the seven adapted decoder linears.  W is wherever the weight lives -- the trainable buffer or the frozen
+        base store, a row slice of the fused q|k|v / gate|up storage.  Every entry is checked before the first one is merged (KeyError on
+        an unknown module or a shape that does not match its weight).  Biases, norms, embeddings, lm_head, the projector and the tower are
+        not touched."""
+        targets = {t for t, _, _ in LORA_TARGETS}
+        work = []
+        for name, (A, B) in adapters.items():
+            parts = name.split(".", 3)
+            wname = name + ".weight"
+            if len(parts) != 4 or parts[:2] != ["model", "layers"] or parts[3] not in targets or not (
+                    wname in self.lm.offsets or (self.base is not None and wname in self.base.offsets)):
+                raise KeyError(f"{name}: not an adapted decoder linear of this model")
+            w = self.W(wname)
+            if A.dim() != 2 or B.dim() != 2 or A.shape[0] != B.shape[1] or A.shape[1] != w.shape[1] or B.shape[0] != w.shape[0]:
+                raise KeyError(f"{name}: lora_A {tuple(A.shape)} / lora_B {tuple(B.shape)} do not match the weight {tuple(w.shape)}")
+            work.append((wname, w, A.to(self.device, BF16).contiguous(), B.to(self.device, BF16).contiguous()))
+        for wname, w, A, B in work:
+            ops.lora_merge(w, A, B, scale)
+        self.weights_changed()
+        if self.master is not None:
+            for wname, w, _, _ in work:
+                if wname in self.lm.offsets:
+                    off, n = self.lm.offsets[wname]
+                    self.master[off:off + n].copy_(ops.to_f32(w.reshape(-1)))
+
+    def merge_lora(self):
+        """Merge this engine's own adapters into the frozen base (scale alpha / r), then become the projector-only layout
+        (freeze_lm=True): frozen language model in self.base, projector and image_newline in the trainable buffer.  The adapters,
+        their gradients and their AdamW state are dropped; the projector keeps its optimizer state.  A later training step follows
+        the projector-only semantics (tune_mm_mlp_adapter): the projector trains, image_newline and the decoder are frozen."""
+        if not self.lora:
+            raise ValueError("merge_lora(): this engine has no LoRA adapters")
+        from collections import OrderedDict
+        pairs = {}
+        for i in range(self.l["layers"]):
+            for t, _, _ in LORA_TARGETS:
+                pre = f"model.layers.{i}.{t}"
+                pairs[pre] = (self.lm.view(pre + ".lora_A.weight"), self.lm.view(pre + ".lora_B.weight"))
+        self.merge_lora_(pairs, self.lora_scale)
+        old = self.lm
+        keep = [n for n in old.names() if ".lora_" not in n]
+        new = FlatParams(OrderedDict((n, old.shapes[n]) for n in keep), self.device)
+        for n in keep:
+            new.view(n).copy_(old.view(n))
+        if self.master is not None:
+            state = []
+            for buf in (self.master, self.m, self.vv):
+                nb = new.like(torch.float32)
+                for n in keep:
+                    new.view(n, nb).copy_(old.view(n, buf))
+                state.append(nb)
+            self.master, self.m, self.vv = state
+        self.lm = new
+        self.grads = new.like(BF16)
+        self.grad_accum_started = False
+        self.ctx = None
+        self._ws = None
+        if self.sync is not None:
+            from .ddp import FlatGradSync
+            self.sync = FlatGradSync(self.grads, self.pg, force=self.force_grad_sync)
+        self.lora = None
+        self.freeze_lm = True
+        self.frozen_names = {n for n in self.frozen_names if n in new.offsets}
+        if "model.image_newline" in new.offsets:
+            self.frozen_names.add("model.image_newline")
+        self.weights_changed()
 
     def load_state_dict(self, sd, strict=False):
         from .params import load_named

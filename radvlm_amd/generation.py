@@ -40,8 +40,8 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
     if kwargs.get("streamer") is not None:
         raise NotImplementedError("streamer: token streaming is not implemented")
     if lora:
-        raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first (the reference merges "
-                                  "adapters before evaluation)")
+        raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
+                                  "model.merge_and_unload() (the reference merges adapters before evaluation)")
     eos = kwargs.get("eos_token_id", config_eos)
     eos = [] if eos is None else ([int(eos)] if isinstance(eos, (int, np.integer)) else [int(e) for e in eos])
     pad = kwargs.get("pad_token_id", config_pad)

@@ -321,6 +321,16 @@ class LlavaLlamaForCausalLM:
             return
         save_file(cpu(self.engine.state_dict()), os.path.join(out_dir, "model.safetensors"))
 
+    def merge_and_unload(self):
+        """peft's merge_and_unload: W += (alpha / r) B A for every adapted linear (rv_lora_merge_bf16), the adapters are dropped and the
+        model is a plain one (config.lora cleared; save_pretrained then writes the full model.safetensors).  The engine keeps the
+        projector-only layout (LlavaEngine.merge_lora).  Returns self."""
+        if not self.engine.lora:
+            raise ValueError("merge_and_unload() needs a model with LoRA adapters")
+        self.engine.merge_lora()
+        self.config.lora = None
+        return self
+
     def load_adapter(self, path):
         """Inverse of the LoRA branch of save_pretrained (resume / continued training): adapter_model.bin + non_lora_trainables.bin."""
         e = self.engine

@@ -612,3 +612,15 @@ def argmax_rows(x, n, out=None):
     out = torch.empty(rows, dtype=torch.int64, device=x.device) if out is None else out
     lib.call("rv_argmax_rows_f32", x, x.stride(0), rows, int(n), out)
     return out
+
+
+def lora_merge(w, A, B, scale):
+    """In place: w[N,K] <- bf16(w + scale * B[N,r] @ A[r,K]) (rv_lora_merge_bf16: fp32 sum in a fixed order, one rounding).  w may be a
+    row slice of a fused store (any row stride); r <= 256.  Returns w."""
+    _chk(w), _chk(A), _chk(B)
+    N, K = w.shape
+    r = A.shape[0]
+    assert A.dim() == 2 and B.dim() == 2 and A.shape[1] == K and tuple(B.shape) == (N, r), (tuple(w.shape), tuple(A.shape), tuple(B.shape))
+    assert w.stride(1) == 1 and A.stride(1) == 1 and B.stride(1) == 1
+    lib.call("rv_lora_merge_bf16", w, w.stride(0), B, B.stride(0), A, A.stride(0), N, K, r, float(scale))
+    return w
