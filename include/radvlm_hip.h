@@ -177,11 +177,6 @@ int rv_attn_fwd_gqa(const void* q, int64_t ld_q, const void* k, int64_t ld_k, co
 int rv_attn_fwd_nat(const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, void* out, int64_t ld_o,
                     float* lse, const int32_t* lens, const int32_t* cu_rows, int B, int H, int H_kv, int S, int S_pad, int hd, int causal,
                     float scale, const void* zeros16, void* stream);
-/* Kernel family behind the head_dim 128 natural-layout forward (rv_attn_fwd_nat), process-wide.  Measurement hook (A/B tools and tests
- * only): 0 = default, 1 = two waves per SIMD, 32 query rows per wave (attention.hip; what the default selects), 2 = one wave per SIMD,
- * 64 query rows per wave, hand-placed softmax (attention_w64.hip; measured slower, kept for the A/B record).  Same results up to the
- * rounding of the running maximum's granularity (64- vs 32-key steps). */
-int rv_attn_select_kernel(int which);
 /* 1 when rv_attn_fwd_nat runs a causal [B, H, S] batch as query-block pairs on the current device, 0 for single query blocks (test hook). */
 int rv_attn_fwd_nat_pairs(int B, int H, int S, int causal);
 int rv_attn_bwd_gqa(const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, const void* o,

@@ -103,8 +103,7 @@ _SIGS = {
     "rv_lora_merge_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
 }
 
-EXPORTED_SYMBOLS = ["rv_version", "rv_gemm_select_kernel", "rv_gemm_set_cu_budget", "rv_attn_select_kernel", "rv_attn_fwd_nat_pairs",
-                    "rv_gemv_split"] + sorted(_SIGS)
+EXPORTED_SYMBOLS = ["rv_version", "rv_gemm_select_kernel", "rv_gemm_set_cu_budget", "rv_attn_fwd_nat_pairs", "rv_gemv_split"] + sorted(_SIGS)
 
 _lib = None
 

@@ -1,4 +1,4 @@
-"""Diagnostic (ONLY=attention tools/build_variant.sh lib_S.so -DRV_ATTN_STAMPS): when and where every block of the forward attention kernel ran
+"""Diagnostic (radvlm_amd/csrc/build.sh lib_S.so -DRV_ATTN_STAMPS): when and where every block of the forward attention kernel ran
 (s_memtime at start / end, HW_ID, XCC_ID) -> how many blocks each CU held over the launch, and the gaps between a block's end and its successor's
 start on the same CU."""
 import ctypes, os, sys

@@ -1,4 +1,4 @@
-"""Diagnostic (tools/build_variant.sh lib_S.so -DRV_ATTN_STAMPS): where the forward attention kernel's waves spend their cycles --
+"""Diagnostic (radvlm_amd/csrc/build.sh lib_S.so -DRV_ATTN_STAMPS): where the forward attention kernel's waves spend their cycles --
 parked at the tile's wait + barrier, in the K reads + score MFMAs, in the softmax, in the P V MFMAs -- per wave, summed over its tiles
 (s_memtime stamps; the instrumentation itself costs ~10 % of the wave's cycles)."""
 import ctypes, os, sys

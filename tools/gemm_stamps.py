@@ -1,4 +1,4 @@
-"""Diagnostic (tools/build_variant.sh lib_S.so -DRV_STAMPS): where a 256x256 GEMM tile spends its time.
+"""Diagnostic (radvlm_amd/csrc/build.sh lib_S.so -DRV_STAMPS): where a 256x256 GEMM tile spends its time.
 Per block: entry -> first barrier (prologue: 2 K-tiles issued, tile 0 landed), K loop, epilogue; plus the idle gap of a CU
 between consecutive blocks, by matching every block to its predecessor on the same CU slot (greedy on start times)."""
 import ctypes, os, sys

@@ -1,4 +1,5 @@
-// Probe of v_permlane16_swap_b32 / v_permlane32_swap_b32 lane semantics on gfx950 (the attention_w64 epilogue and row reductions rely on them).
+// Probe of v_permlane16_swap_b32 / v_permlane32_swap_b32 lane semantics on gfx950 (the retired one-wave-per-SIMD attention forward,
+// last in commit 32d7f59, used them in its epilogue and row reductions).
 //   hipcc --offload-arch=gfx950 tools/probe/permlane_probe.hip -o tools/probe/permlane_probe && tools/probe/permlane_probe
 #include <hip/hip_runtime.h>
 #include <stdio.h>
