@@ -318,8 +318,8 @@ int rv_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream);
 
 /* ---- decode (generate(): one new token per sequence, radvlm_amd/csrc/decode.hip) ---------------------------------------------
  * The reference decodes through HF generate on inputs_embeds (llava_llama.py generate() -> HF:generation/utils.py greedy search with
- * a DynamicCache); these four entry points are its per-token arithmetic: the projections at M = batch rows, attention of one query row
- * against the cache, the cache update and the greedy argmax. */
+ * a DynamicCache); these entry points are its per-token arithmetic: the projections at M = batch rows, attention of one query row
+ * against the cache, the cache update, the greedy logits processors and the greedy argmax. */
 /* Skinny NT GEMM: Y[M,N] = X[M,K] W[N,K]^T (+ bias[N]) (+ residual[M,N]) for 1 <= M <= 32 (fp32 accumulation; bf16 Y, or fp32 Y with
  * out_f32 for the lm_head scores).  Weights are streamed once (16-byte nontemporal loads); the K range is split over workgroups when
  * N alone gives too few of them (rv_gemv_split(N, K) slices, combined in slice order by a second launch through `workspace`, which
@@ -345,6 +345,22 @@ int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, int64_t ld_c
 /* Greedy token choice: out[r] (int64) = argmax over the first n columns of fp32 row r (torch.argmax: lowest index among equal
  * maxima, NaN counts as the maximum); columns >= n (vocabulary pad rows of the lm_head) are never read. */
 int rv_argmax_rows_f32(const float* x, int64_t ld, int rows, int n, int64_t* out, void* stream);
+/* Greedy logits processors fused with the argmax (HF: GenerationMixin._get_logits_processor, generation/logits_process.py, run on the
+ * scores of each greedy step): in place on fp32 row r (first n columns, n <= 262144), in HF's order,
+ *   RepetitionPenaltyLogitsProcessor   every DISTINCT token of the row's history: x < 0 ? x * p : x / p (IEEE fp32; p = 1: off);
+ *   NoRepeatNGramLogitsProcessor       ngram > 0, t >= ngram: every window i <= t - ngram whose first ngram - 1 tokens equal the last
+ *                                      ngram - 1 generated ones bans its last token (ngram = 1 bans every generated token);
+ *   NoBadWordsLogitsProcessor          multi-token sequences, CSR (bad_tok, bad_off[n_bad + 1]): a sequence of length L is checked
+ *                                      when t >= L; if its first L - 1 tokens equal the last L - 1 generated ones, its last token is banned;
+ *   ban[0 .. n_ban)                    ids banned on every row this step, composed by the caller: SuppressTokens, SuppressTokensAtBegin
+ *                                      (t == 0), MinLength / MinNewTokensLength (EOS while t < the minimum), one-token bad words;
+ * a banned entry becomes -inf; then out[r] = argmax of the processed row (rv_argmax_rows_f32's semantics).  hist: int32 [rows, >= t]
+ * rows of ld_hist, the t tokens generated so far (pads of finished rows included, the prompt excluded: HF's input_ids of inputs_embeds
+ * generation).  Ids outside [0, n) are ignored.  Only entries a processor touches are written.  Rows are independent (no atomics to
+ * global memory).  Differs from HF in one case: HF ADDS -inf for a bad word, so a +inf / NaN entry there becomes NaN; here it becomes -inf. */
+int rv_logits_process_argmax_f32(float* x, int64_t ld, int rows, int n, const int32_t* hist, int64_t ld_hist, int t, float rep_penalty,
+                                 int ngram, const int32_t* ban, int n_ban, const int32_t* bad_tok, const int32_t* bad_off, int n_bad,
+                                 int64_t* out, void* stream);
 
 /* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
  * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any

@@ -303,6 +303,94 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------ greedy logits processors + argmax
+// HF's greedy logits processors (repetition penalty, no-repeat n-gram, bad words, min length / min new tokens, suppress, begin-suppress)
+// fused with the row argmax above.  One workgroup per row.  Phase 1 walks the row's generated tokens h[0..t) and sets two LDS bitmaps
+// with LDS atomicOr: `pen` (one bit per distinct history token: the penalty lands once per token, as HF's gather -> scatter does) and
+// `ban` (n-gram continuations, bad-word continuations whose prefix ends h, the host-composed static list).  Phase 2 reads the row once,
+// applies x < 0 ? x * p : x / p on `pen` bits (IEEE fp32 division: no reciprocal) and then -inf on `ban` bits, writes back only the
+// touched entries and feeds the fixed-order argmax.  Ids outside [0, n) set no bit.  The bitmaps are dynamic LDS, n / 4 bytes.
+// One difference from HF: HF adds -inf for a bad word (so +inf / NaN become NaN), here a bad word sets -inf like every other ban.
+constexpr int LP_MAX_N = 262144;                // 2 x 32 KB of bitmap: Qwen2's 152,064 plus resize_token_embeddings growth
+constexpr int LP_U = 8;
+
+DEVINL void lp_set(unsigned* bm, int tok, int n) {
+    if (tok >= 0 && tok < n) atomicOr(&bm[tok >> 5], 1u << (tok & 31));
+}
+
+__global__ __launch_bounds__(256) void logits_process_argmax_kernel(float* __restrict__ x, long ld, int n, const int32_t* __restrict__ hist,
+                                                                    long ld_hist, int t, float pen_p, int ngram, const int32_t* __restrict__ ban,
+                                                                    int n_ban, const int32_t* __restrict__ bad_tok,
+                                                                    const int32_t* __restrict__ bad_off, int n_bad, int64_t* __restrict__ out) {
+    extern __shared__ unsigned lp_bits[];
+    const int words = (n + 31) >> 5;
+    unsigned* pen = lp_bits;
+    unsigned* bnd = lp_bits + words;
+    float* row = x + (long)blockIdx.x * ld;
+    const int32_t* h = hist + (long)blockIdx.x * ld_hist;
+    const int tid = threadIdx.x;
+    for (int w = tid; w < 2 * words; w += 256) lp_bits[w] = 0u;
+    __syncthreads();
+    if (pen_p != 1.0f)
+        for (int i = tid; i < t; i += 256) lp_set(pen, h[i], n);
+    if (ngram > 0 && t >= ngram) {
+        // window i (i <= t - ngram) bans its last token when its first ngram - 1 tokens equal the last ngram - 1 generated ones
+        for (int i = tid; i <= t - ngram; i += 256) {
+            bool eq = true;
+            for (int k = 0; k < ngram - 1 && eq; ++k) eq = h[i + k] == h[t - ngram + 1 + k];
+            if (eq) lp_set(bnd, h[i + ngram - 1], n);
+        }
+    }
+    for (int j = tid; j < n_ban; j += 256) lp_set(bnd, ban[j], n);
+    for (int s = tid; s < n_bad; s += 256) {
+        const int o = bad_off[s], L = bad_off[s + 1] - o;
+        if (L < 2 || t < L) continue;            // HF skips a sequence longer than the generated tokens (t >= L, not L - 1)
+        bool eq = true;
+        for (int k = 0; k < L - 1 && eq; ++k) eq = bad_tok[o + k] == h[t - L + 1 + k];
+        if (eq) lp_set(bnd, bad_tok[o + L - 1], n);
+    }
+    __syncthreads();
+    // LP_U independent loads in flight per thread: one workgroup streams the whole row, so the sweep is latency-bound without them
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int j0 = tid; j0 < n; j0 += 256 * LP_U) {
+        float vs[LP_U];
+#pragma unroll
+        for (int u = 0; u < LP_U; ++u) {
+            const int j = j0 + u * 256;
+            vs[u] = j < n ? row[j] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < LP_U; ++u) {
+            const int j = j0 + u * 256;
+            if (j >= n) break;
+            float v = vs[u];
+            const unsigned m = 1u << (j & 31);
+            const bool pj = pen[j >> 5] & m, bj = bnd[j >> 5] & m;
+            if (pj) v = v < 0.f ? v * pen_p : v / pen_p;
+            if (bj) v = -INFINITY;
+            if (pj || bj) row[j] = v;
+            if (am_better(v, j, bv, bi)) { bv = v; bi = j; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (am_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    __syncthreads();                             // every bitmap read is done: the reduction scratch reuses the bitmap's first words
+    float* rv = (float*)lp_bits;
+    int* ri = (int*)(lp_bits + 4);
+    if (lane_id() == 0) { rv[wave_id()] = bv; ri[wave_id()] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < 4; ++k)
+            if (am_better(rv[k], ri[k], bv, bi)) { bv = rv[k]; bi = ri[k]; }
+        out[blockIdx.x] = bi;
+    }
+}
+
 inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace
@@ -377,5 +465,17 @@ extern "C" int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, i
 extern "C" int rv_argmax_rows_f32(const float* x, int64_t ld, int rows, int n, int64_t* out, void* stream) {
     if (!x || !out || rows <= 0 || n <= 0 || ld < n) return RV_ERR_ARG;
     hipLaunchKernelGGL(argmax_rows_kernel, dim3(rows), dim3(256), 0, ST, x, (long)ld, n, out);
+    return rv_check_launch();
+}
+
+extern "C" int rv_logits_process_argmax_f32(float* x, int64_t ld, int rows, int n, const int32_t* hist, int64_t ld_hist, int t, float rep_penalty,
+                                            int ngram, const int32_t* ban, int n_ban, const int32_t* bad_tok, const int32_t* bad_off, int n_bad,
+                                            int64_t* out, void* stream) {
+    if (!x || !out || rows <= 0 || n <= 0 || n > LP_MAX_N || ld < n || t < 0 || (t > 0 && (!hist || ld_hist < t)) || !(rep_penalty > 0.f) ||
+        ngram < 0 || n_ban < 0 || (n_ban > 0 && !ban) || n_bad < 0 || (n_bad > 0 && (!bad_tok || !bad_off)))
+        return RV_ERR_ARG;
+    const size_t lds = (size_t)2 * ((n + 31) / 32) * sizeof(unsigned);     // >= 32 bytes (the reduction scratch) for every n >= 1
+    hipLaunchKernelGGL(logits_process_argmax_kernel, dim3(rows), dim3(256), lds < 32 ? 32 : lds, ST, x, (long)ld, n, hist, (long)ld_hist, t,
+                       rep_penalty, ngram, ban, n_ban, bad_tok, bad_off, n_bad, out);
     return rv_check_launch();
 }

@@ -3,8 +3,10 @@
 HF semantics followed (HF: = transformers as pinned by the reference): GenerationMixin.generate -> _sample with do_sample=False
 (HF:generation/utils.py), for a decoder-only model called with inputs_embeds, which is how the reference's generate() calls it after
 the multimodal splice (llava_llama.py generate()).  The returned sequences then hold the NEW tokens only.  Every row is generated as
-if it were alone (left-padded HF generation: the row's own positions 0 .. len - 1).  The bookkeeping below is host code without a
-device, so it is tested on its own (tests/test_generate_host.py).
+if it were alone (left-padded HF generation: the row's own positions 0 .. len - 1).  HF's greedy logits processors run on each step's fp32 scores
+(HF:generation/logits_process.py); with inputs_embeds HF's input_ids start empty, so they see the generated tokens only, never the
+prompt.  The bookkeeping below is host code without a device, so it is tested on its own (tests/test_generate_host.py,
+tests/test_logits_process_host.py).
 """
 from types import SimpleNamespace
 
@@ -12,12 +14,17 @@ import numpy as np
 import torch
 
 _IGNORED_WHEN_GREEDY = ("temperature", "top_p", "top_k", "typical_p")     # sampling knobs HF ignores (with a warning) when do_sample=False
+# HF's greedy logits processors (HF: generation/logits_process.py, wired by GenerationMixin._get_logits_processor)
+_PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "suppress_tokens",
+               "begin_suppress_tokens")
 _ACCEPTED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "attention_mask", "stopping_criteria", "use_cache", "do_sample",
-             "num_beams", "streamer", "output_scores", "return_dict_in_generate", "num_return_sequences", "position_ids", "inputs_embeds") + _IGNORED_WHEN_GREEDY
+             "num_beams", "streamer", "output_scores", "output_logits", "return_dict_in_generate", "num_return_sequences", "position_ids",
+             "inputs_embeds") + _PROCESSORS + _IGNORED_WHEN_GREEDY
 
 
 class GenerateDecoderOnlyOutput(SimpleNamespace):
-    """HF's return_dict_in_generate output: .sequences [B, T_new], .scores (one fp32 [B, vocab] tensor per step) or None."""
+    """HF's return_dict_in_generate output: .sequences [B, T_new]; .scores (output_scores: the processed fp32 [B, vocab] scores of each
+    step) and .logits (output_logits: the raw ones), each a tuple or None."""
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -57,7 +64,124 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
             raise TypeError(f"stopping criterion {c!r} is not callable")
     return SimpleNamespace(eos=eos, pad=int(pad), max_new_tokens=None if mnt is None else int(mnt), max_length=None if ml is None else int(ml),
                            stopping_criteria=crit, output_scores=bool(kwargs.get("output_scores", False)),
-                           return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"))
+                           output_logits=bool(kwargs.get("output_logits", False)),
+                           return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
+                           **_parse_processors(kwargs, eos))
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _token_list(name, v):
+    if v is None:
+        return None
+    try:
+        ids = list(v)
+    except TypeError:
+        raise ValueError(f"`{name}` has to be a list of token ids, but is {v!r}") from None
+    if any(not _is_int(i) for i in ids):
+        raise ValueError(f"`{name}` has to be a list of token ids, but is {v!r}")
+    return [int(i) for i in ids]
+
+
+def _parse_processors(kwargs, eos):
+    """The greedy logits-processor settings, validated as HF's processor constructors do (ValueError for a bad value).  Off: None, a
+    repetition_penalty of 1.0, a no_repeat_ngram_size of 0."""
+    p = kwargs.get("repetition_penalty")
+    if p is not None and p != 1.0:
+        if not isinstance(p, float) or not p > 0:
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {p!r}")
+    p = None if p is None or p == 1.0 else float(p)
+    ng = kwargs.get("no_repeat_ngram_size")
+    if ng is not None and (not _is_int(ng) or ng < 0):
+        raise ValueError(f"`no_repeat_ngram_size` has to be a non-negative integer, but is {ng!r}")
+    bw = kwargs.get("bad_words_ids")
+    if bw is not None:
+        if not isinstance(bw, list) or len(bw) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bw!r}")
+        if any(not isinstance(w, list) for w in bw):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bw!r}")
+        if any(len(w) == 0 or any(not _is_int(i) or i < 0 for i in w) for w in bw):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a non-empty list of non-negative integers, but is {bw!r}")
+        # HF: NoBadWordsLogitsProcessor drops the sequences [eos]; the rest become the keys of a dict (duplicates merge)
+        bw = list(dict.fromkeys(tuple(int(i) for i in w) for w in bw if not any(list(w) == [e] for e in eos)))
+        if not bw:
+            raise ValueError("`bad_words_ids` holds only EOS sequences: nothing is left to ban")
+    vals = {}
+    for k in ("min_length", "min_new_tokens"):
+        v = kwargs.get(k)
+        if v is not None and (not _is_int(v) or v < 0):
+            raise ValueError(f"`{k}` has to be a non-negative integer, but is {v!r}")
+        vals[k] = None if v is None else int(v)
+    return dict(repetition_penalty=p, no_repeat_ngram_size=int(ng or 0), bad_words_ids=bw, min_length=vals["min_length"],
+                min_new_tokens=vals["min_new_tokens"], suppress_tokens=_token_list("suppress_tokens", kwargs.get("suppress_tokens")),
+                begin_suppress_tokens=_token_list("begin_suppress_tokens", kwargs.get("begin_suppress_tokens")))
+
+
+def min_new_length(cfg, prompt_len):
+    """Tokens before which EOS is banned.  HF for inputs_embeds generation: min_new_tokens wins; else min_length counts the prompt
+    embeddings (min_length <- max(min_length - inputs_embeds.shape[1], 0)).  0 without an EOS id (HF then adds neither processor)."""
+    if not cfg.eos:
+        return 0
+    if cfg.min_new_tokens is not None:
+        return cfg.min_new_tokens
+    return max((cfg.min_length or 0) - int(prompt_len), 0)
+
+
+def min_needs_prompt_len(cfg):
+    return bool(cfg.eos) and cfg.min_new_tokens is None and bool(cfg.min_length)
+
+
+class LogitsProcessors:
+    """The active processors of one generate() call on a vocabulary of `vocab` ids.  `active` is False when none of them can change a
+    score; greedy_generate then keeps the plain argmax.  The ids banned on every row of step t (suppress_tokens, begin_suppress_tokens
+    at t == 0, EOS while t < min_new, one-token bad words) are composed here; they change only at t == 0 and at t == min_new."""
+
+    def __init__(self, cfg, vocab, prompt_len=0):
+        self.vocab = int(vocab)
+        self.penalty = cfg.repetition_penalty if cfg.repetition_penalty is not None else 1.0
+        self.ngram = cfg.no_repeat_ngram_size
+        bw = cfg.bad_words_ids or []
+        bad_ids = sorted({i for w in bw for i in w if i >= self.vocab})
+        if bad_ids:
+            raise ValueError(f"The model vocabulary size is {self.vocab}, but the following tokens were being biased: {bad_ids}")
+        inv = lambda ids: [i for i in (ids or []) if 0 <= i < self.vocab]           # HF: torch.isin over arange(vocab)
+        self.suppress = inv(cfg.suppress_tokens)
+        self.begin = inv(cfg.begin_suppress_tokens)
+        self.eos = inv(cfg.eos)
+        self.one = [w[0] for w in bw if len(w) == 1]
+        self.multi = [w for w in bw if len(w) > 1]
+        self.min_new = min_new_length(cfg, prompt_len)
+        self.active = (self.penalty != 1.0 or self.ngram > 0 or bool(bw) or bool(self.suppress) or bool(self.begin) or
+                       (self.min_new > 0 and bool(self.eos)))
+        self._dev = {}
+
+    def static_ban(self, t):
+        """Sorted distinct ids banned on every row at step t (t = tokens generated so far)."""
+        ids = set(self.suppress) | set(self.one)
+        if t == 0:
+            ids |= set(self.begin)
+        if t < self.min_new:
+            ids |= set(self.eos)
+        return sorted(ids)
+
+    def bad_csr(self):
+        """(tokens, offsets) of the multi-token bad words, int32 numpy."""
+        off = np.cumsum([0] + [len(w) for w in self.multi]).astype(np.int32)
+        tok = np.array([i for w in self.multi for i in w], dtype=np.int32)
+        return tok, off
+
+    def device_args(self, t, device):
+        """(ban, bad_tok, bad_off) device int32 tensors for step t (None where empty); uploaded once per distinct list."""
+        key = (t == 0, t < self.min_new)
+        if key not in self._dev:
+            ban = self.static_ban(t)
+            if "bad" not in self._dev:
+                tok, off = self.bad_csr()
+                self._dev["bad"] = ((torch.from_numpy(tok).to(device), torch.from_numpy(off).to(device)) if self.multi else (None, None))
+            self._dev[key] = torch.tensor(ban, dtype=torch.int32, device=device) if ban else None
+        return (self._dev[key],) + self._dev["bad"]
 
 
 def new_token_budget(cfg, prompt_len):
@@ -120,21 +244,33 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     dev = engine.device
     # prompt length in HF's sense: the spliced inputs_embeds width (the longest spliced prompt of the batch)
     plan_len = None
-    if cfg.max_new_tokens is None and cfg.max_length is not None:
+    if (cfg.max_new_tokens is None and cfg.max_length is not None) or min_needs_prompt_len(cfg):
         plan_len = int(engine.plan(ids, am, None, list(images) if images is not None else [], image_sizes)["S"])
     T = new_token_budget(cfg, plan_len or 0)
+    lp = LogitsProcessors(cfg, engine.vocab, plan_len or 0)
+    raw = []
     if T > 0:
+        # the tokens generated so far, pads of finished rows included (HF's input_ids of inputs_embeds generation: no prompt)
+        hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active else None
         cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T)
         for t in range(T):
-            nxt = ops.argmax_rows(logits, engine.vocab)
+            if cfg.output_logits:
+                raw.append(logits.clone())
+            if lp.active:                 # in place: logits become HF's processed scores
+                nxt = ops.logits_process_argmax(logits, engine.vocab, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
+            else:
+                nxt = ops.argmax_rows(logits, engine.vocab)
             if cfg.output_scores:
                 scores.append(logits.clone())
             tok = st.step(nxt, logits, device=dev)
+            if hist is not None:
+                hist[:, t] = torch.from_numpy(tok.astype(np.int32)).to(dev)
             if st.all_done or t == T - 1:
                 break
             logits = engine.decode_step(cache, torch.from_numpy(tok))
         del cache
     seq = torch.from_numpy(st.sequences()).to(dev)
     if cfg.return_dict:
-        return GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None)
+        return GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
+                                         logits=tuple(raw) if cfg.output_logits else None)
     return seq

@@ -270,9 +270,12 @@ class LlavaLlamaForCausalLM:
         inputs: prompt token ids [B, T] (IMAGE_TOKEN_INDEX where an image goes); images / image_sizes as in forward (None: text only).
         Returns the NEW tokens only, LongTensor [B, T_new]; rows that finished (EOS or a stopping criterion) are filled with
         pad_token_id.  Keywords: max_new_tokens (default 20), max_length, eos_token_id, pad_token_id, attention_mask, stopping_criteria,
-        use_cache (the result is the same either way), output_scores + return_dict_in_generate (.sequences, .scores).  Sampling, beam
-        search, streamers, inputs_embeds and LoRA models raise NotImplementedError.  The training state (weights, optimizer, RNG
-        counters) is not touched."""
+        use_cache (the result is the same either way), output_scores / output_logits + return_dict_in_generate (.sequences, .scores =
+        the processed scores, .logits = the raw ones).  HF's greedy logits processors: repetition_penalty, no_repeat_ngram_size,
+        bad_words_ids, min_length, min_new_tokens, suppress_tokens, begin_suppress_tokens; as in HF generation from inputs_embeds they
+        see only the generated tokens (pads included), never the prompt; a bad value raises ValueError.  Sampling, beam search,
+        streamers, inputs_embeds and LoRA models raise NotImplementedError.  The training state (weights, optimizer, RNG counters) is
+        not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
                                     config_pad=getattr(self.config, "pad_token_id", None))

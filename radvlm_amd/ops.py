@@ -614,6 +614,34 @@ def argmax_rows(x, n, out=None):
     return out
 
 
+LOGITS_PROCESS_MAX_N = 262144
+
+
+def logits_process_argmax(x, n, hist, t, rep_penalty=1.0, ngram=0, ban=None, bad_tok=None, bad_off=None, out=None):
+    """Greedy logits processors + argmax (rv_logits_process_argmax_f32): processes fp32 rows x[:, :n] IN PLACE -- repetition penalty on
+    the distinct tokens of hist[:, :t], n-gram bans, multi-token bad words (CSR bad_tok / bad_off int32, bad_off of n_bad + 1 entries),
+    -inf on the ids of `ban` (int32, shared by every row) -- and returns the int64 argmax of each processed row.  hist: int32 [rows, >= t]
+    (the tokens generated so far), may be None when t == 0."""
+    _chk(x, torch.float32)
+    rows = x.shape[0]
+    assert x.dim() == 2 and x.stride(1) == 1 and 0 < n <= min(x.shape[1], LOGITS_PROCESS_MAX_N)
+    ld_hist = 0
+    if t > 0:
+        _chk(hist, torch.int32)
+        assert hist.dim() == 2 and hist.shape[0] == rows and hist.shape[1] >= t and hist.stride(1) == 1
+        ld_hist = hist.stride(0)
+    for a in (ban, bad_tok, bad_off):
+        if a is not None:
+            _chk(a, torch.int32)
+            assert a.is_contiguous()
+    n_bad = 0 if bad_off is None else bad_off.numel() - 1
+    assert n_bad <= 0 or bad_tok is not None
+    out = torch.empty(rows, dtype=torch.int64, device=x.device) if out is None else out
+    lib.call("rv_logits_process_argmax_f32", x, x.stride(0), rows, int(n), hist if t > 0 else None, ld_hist, int(t), float(rep_penalty),
+             int(ngram), ban, 0 if ban is None else ban.numel(), bad_tok, bad_off, max(n_bad, 0), out)
+    return out
+
+
 def lora_merge(w, A, B, scale):
     """In place: w[N,K] <- bf16(w + scale * B[N,r] @ A[r,K]) (rv_lora_merge_bf16: fp32 sum in a fixed order, one rounding).  w may be a
     row slice of a fused store (any row stride); r <= 256.  Returns w."""

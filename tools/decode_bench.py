@@ -2,6 +2,9 @@
 
   python tools/decode_bench.py [--geos llava15_7b,llava_ov_qwen2_7b] [--batches 1,8,32] [--prompt 704] [--new 128] [--out FILE]
   python tools/decode_bench.py --ab [--out FILE]     # rv_gemv_bf16 vs rv_gemm_nt_bf16 at M = 1, 4, 16, 32, interleaved on one box
+  python tools/decode_bench.py --processors [--geos ..] [--batches 1,32] [--out FILE]
+        # plain greedy argmax vs the logits processors (repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=new/2 with an EOS)
+        # through rv_logits_process_argmax_f32, interleaved (plain, processors, plain, ...) on one engine
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -102,6 +105,52 @@ def ab(reps=20):
     return out
 
 
+def _decode_loop(eng, ids, new, lp=None, warm=8):
+    """Median decode step (decode_step + token choice) in ms; with `lp` (generation.LogitsProcessors) the token comes from
+    rv_logits_process_argmax_f32 and is recorded in the device history, as greedy_generate does."""
+    B = ids.shape[0]
+    cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new)
+    hist = torch.zeros(B, new, dtype=torch.int32, device=logits.device) if lp is not None else None
+
+    def choose(lg, t):
+        if lp is None:
+            return ops.argmax_rows(lg, eng.vocab)
+        tk = ops.logits_process_argmax(lg, eng.vocab, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, lg.device))
+        hist[:, t] = tk.to(torch.int32)
+        return tk
+
+    tok = choose(logits, 0)
+    times = []
+    for t in range(1, new):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        logits = eng.decode_step(cache, tok.to(torch.int32))
+        tok = choose(logits, t)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    del cache
+    return times[warm:]
+
+
+def processors_ab(geo, B, prompt, new, reps=3):
+    from radvlm_amd.generation import LogitsProcessors, parse_generate_kwargs
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+    cfg = parse_generate_kwargs(dict(repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=new // 2, eos_token_id=2))
+    lp = LogitsProcessors(cfg, eng.vocab)
+    ts = {"plain": [], "processors": []}
+    _decode_loop(eng, ids, 16)                                      # warm-up of both paths
+    _decode_loop(eng, ids, 16, lp)
+    for _ in range(reps):
+        ts["plain"] += _decode_loop(eng, ids, new)
+        ts["processors"] += _decode_loop(eng, ids, new, lp)
+    p, q = float(np.median(ts["plain"])), float(np.median(ts["processors"]))
+    return dict(geo=geo, B=B, prompt=prompt, new_tokens=new, mode="processors_ab", processors="repetition_penalty=1.2,no_repeat_ngram_size=3,"
+                f"min_new_tokens={new // 2},eos=2", plain_ms_per_step=round(p, 3), processors_ms_per_step=round(q, 3),
+                delta_ms=round(q - p, 4), delta_share=round((q - p) / p, 4), steps_timed_each=len(ts["plain"]), reps=reps,
+                kernel_src=_src_hash())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--geos", default="llava15_7b,llava_ov_qwen2_7b")
@@ -109,10 +158,16 @@ def main():
     ap.add_argument("--prompt", type=int, default=704)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--processors", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.cuda.set_device(0)
-    recs = ab() if a.ab else [case(g, b, a.prompt, a.new) for g in a.geos.split(",") for b in map(int, a.batches.split(","))]
+    if a.ab:
+        recs = ab()
+    elif a.processors:
+        recs = [processors_ab(g, b, a.prompt, a.new) for g in a.geos.split(",") for b in map(int, a.batches.split(","))]
+    else:
+        recs = [case(g, b, a.prompt, a.new) for g in a.geos.split(",") for b in map(int, a.batches.split(","))]
     for r in recs:
         r["kernel_src"] = r.get("kernel_src") or _src_hash()
         line = json.dumps(r)
