@@ -338,6 +338,17 @@ int rv_gemv_split(int N, int K);
 int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
                         int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk,
                         float scale, void* stream);
+/* Extend attention (the prompt pass of a continued generation, over a reused KV cache): sequence b has n_b = cu_q[b+1] - cu_q[b] >= 1
+ * new query rows q[cu_q[b] .. cu_q[b+1]) at positions r[b] .. r[b] + n_b - 1, whose K|V rows are already in the cache; query i attends
+ * causally to the keys [0, r[b] + i] of kv head h / (H / Hkv).  hd in {64, 128}, up to 8 q heads per kv head, fp32 softmax and
+ * accumulation, bf16 MFMA for Q K^T and P V.  cache / q / out as for rv_attn_decode_bf16 (q and out: [M, H*hd] rows, M = cu_q[B]);
+ * cu_q (B + 1 entries) and r (B entries) are int32 device arrays with r[b] + n_b <= L_max; max_q >= every n_b.  Keys are split into
+ * chunks of `chunk` positions (a multiple of 64) fixed in absolute key position; each workgroup (chunk, kv head, tile of query rows
+ * of one sequence) writes (o, m, l) partials to `part` (M * H * ceil(L_max / chunk) * (hd + 2) floats) and a second launch merges a
+ * row's chunks in chunk order: a row's result is bit-identical whatever else shares the launch. */
+int rv_attn_extend_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* cu_q,
+                        const int32_t* r, int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int M, int max_q,
+                        int H, int Hkv, int hd, int chunk, float scale, void* stream);
 /* KV cache append: cache[b][pos[b]][0:width] = src[b][0:width] (bf16; rows of the post-RoPE k|v columns of the qkv product);
  * pos is an int32 device array, slots outside [0, L_max) are skipped.  width % 8 == 0. */
 int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, int64_t ld_c, int64_t bs_c, const int32_t* pos, int L_max, int B,

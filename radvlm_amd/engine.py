@@ -37,6 +37,7 @@ class LlavaEngine:
                  freeze_projector=False,
                  padding_side="right", force_grad_sync=False, recompute=False):
         self.geo = geo
+        self.weights_version = 0              # bumped by every write to the weights (weights_changed): a GenerationCache of an older one is stale
         assert recompute in (False, True, "auto")
         self.recompute = recompute            # activation recompute policy of the decoder layers (_recompute_layers)
         self.head_rows = "labeled"            # final norm + lm_head + cross entropy on the rows that carry a label ("all": every row)
@@ -255,7 +256,8 @@ class LlavaEngine:
 
     def weights_changed(self, tower=True):
         """Call after any in-place edit of the flat parameters (load_state_dict, optimizer step): drops the derived
-        copies of tower weights (padded patch / attention projections) when the tower may have changed."""
+        copies of tower weights (padded patch / attention projections) when the tower may have changed, and bumps weights_version."""
+        self.weights_version += 1
         if tower:
             self._patch_w = None
             self._vis_pad = {}
@@ -506,11 +508,13 @@ class LlavaEngine:
         tiles = [1 if im.ndim == 3 else im.shape[0] for im in images]
         n_proj = sum(tiles) * self.P
         extra = dict(next=n_proj, src=[], w=[])     # rows created by anyres_max down-sampling follow the projector rows
-        rows, r0 = [], 0
+        rows, r0, image_rows = [], 0, []
         for i, t in enumerate(tiles):
+            e0 = extra["next"]
             rows.append(merged_feature_rows(r0, t, self.side, self.merge_type, self.aspect,
                                             tuple(image_sizes[i]) if image_sizes is not None else None, self.pinpoints,
                                             self.v["image"], extra=extra))
+            image_rows.append((r0, r0 + t * self.P, e0, extra["next"]))
             r0 += t * self.P
         n_extra = extra["next"] - n_proj
         ids = np.asarray(input_ids)
@@ -520,6 +524,7 @@ class LlavaEngine:
         plan["n_feat_rows"] = n_proj + n_extra
         plan["n_proj_rows"] = n_proj
         plan["n_extra_rows"] = n_extra
+        plan["image_rows"] = image_rows      # per image: its projector rows [p0, p1) and anyres_max-created rows [e0, e1) of the feature table
         if extra.get("pool_src"):   # maxpool2x2: created rows = elementwise max of four projector rows
             win = np.concatenate(extra["pool_src"]).astype(np.int32)
             assert (plan["feat_pos"][np.unique(win)] < 0).all()
@@ -910,6 +915,76 @@ class LlavaEngine:
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
         cache.lens += 1
         return logits[:, :self.vocab]
+
+    def extend(self, cache, input_ids, attention_mask=None, images=None, image_sizes=None, reuse=None, max_new_tokens=0, plan=None):
+        """The prompt pass of a continued generation over a KV cache of an earlier call on the same weights: sequence b's positions
+        0 .. reuse[b] - 1 are kept from `cache` (a KVCache; later positions are dropped), its positions reuse[b] .. len_b - 1 (at least one)
+        run through every decoder layer as one packed batch of M = sum(len_b - reuse[b]) rows -- RMSNorm, q|k|v, RoPE at the explicit
+        positions, the K|V rows written into their cache slots, extend attention against the sequence's cached keys (rv_attn_extend_bf16),
+        o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual -- then the final norm and the lm_head on each sequence's last row.
+        The vision tower runs only when an image feature row (image_newline aside) is among the new rows.  The cache grows (one copy of
+        the kept rows) when len_b + max_new_tokens exceeds its slots.  Every reuse[b] == 0 (or no cache): prefill(), bit for bit.
+        plan: this prompt's self.plan(...), when the caller has it already.  Returns (cache, fp32 logits [B, vocab])."""
+        if cache is None or reuse is None or not np.any(reuse):
+            return self.prefill(input_ids, attention_mask, images, image_sizes, max_new_tokens=max_new_tokens)
+        self._check_generation()
+        from .generation import grown_length
+        l = self.l
+        d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
+        hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
+        ids = np.asarray(input_ids)
+        B = int(ids.shape[0])
+        imgs = [] if images is None else list(images)
+        if plan is None:
+            plan = self.plan(ids, attention_mask, None, imgs, image_sizes)
+        lens = plan["lens"].astype(np.int64)
+        r = np.asarray(reuse, dtype=np.int64).reshape(-1)
+        if cache.B != B or r.shape[0] != B:
+            raise ValueError(f"the cache holds {cache.B} sequences, the prompt {B}")
+        if (r < 0).any() or (r > cache.lens).any() or (r >= lens).any():
+            raise ValueError("reuse[b] must lie in [0, min(cached length, prompt length - 1)]")
+        n = lens - r
+        L_new = grown_length(cache.L_max, int((lens + int(max_new_tokens)).max()))
+        if L_new > cache.L_max:
+            cache.grow(L_new, int(r.max()))
+        cache.lens = r.copy()
+        L_max = cache.L_max
+        valid = plan["attention_mask"].reshape(-1)
+        flat = plan["idx"][valid]
+        cu_full = np.concatenate([[0], np.cumsum(lens)])
+        src = np.concatenate([flat[cu_full[b] + r[b]:cu_full[b + 1]] for b in range(B)]).astype(np.int32)
+        nl_code = -int(plan["n_feat_rows"]) - 2
+        if ((src <= -2) & (src != nl_code)).any():
+            if not imgs:
+                raise ValueError("the prompt holds an image token but no images were passed")
+            table = self.encode_images(self._pixels(imgs), plan=plan)
+        else:       # no image feature rows among the new ones (image_newline aside): a one-row table, the tower does not run
+            table = (self.W("model.image_newline").reshape(1, d) if self.with_newline else
+                     torch.zeros(1, d, dtype=BF16, device=self.device))
+            src = np.where(src == nl_code, -2, src).astype(np.int32)
+        pos = np.concatenate([np.arange(r[b], lens[b]) for b in range(B)])
+        cu_q = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+        slots = self._dev(np.concatenate([b * L_max + np.arange(r[b], lens[b]) for b in range(B)]).astype(np.int64))
+        pos_d, cu_d, r_d = self._dev(pos.astype(np.int32)), self._dev(cu_q), self._dev(r.astype(np.int32))
+        cs = self.rope_table(L_max)
+        x = ops.gather_rows(self._dev(src), d, self.W("model.embed_tokens.weight"), table)
+        for i in range(L):
+            lv = self._layer_views(i)
+            h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"))
+            ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
+            kv = cache.layers[i]
+            kv.view(B * L_max, 2 * kvd).index_copy_(0, slots, qkv[:, d:])
+            attn = ops.attn_extend(qkv[:, :d], kv, cu_d, r_d, H, Hkv, hd, kvd, int(n.max()))
+            x_mid = self._decode_linear(attn, lv["o"], residual=x)
+            h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"]), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid)
+        last = self._dev((cu_q[1:] - 1).astype(np.int32))
+        hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
+        logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
+        cache.lens = lens.copy()
+        return cache, logits[:, :self.vocab]
 
     def _cross_entropy(self, logits, tgt, V, inv, gscale):
         from . import lib
@@ -1340,6 +1415,15 @@ class KVCache:
     @property
     def B(self):
         return int(self.lens.shape[0])
+
+    def grow(self, L_new, keep):
+        """Reallocate every layer to L_new slots per sequence, copying the first `keep` rows of each sequence (what is still valid)."""
+        assert L_new >= self.L_max and 0 <= keep <= self.L_max
+        for i, t in enumerate(self.layers):
+            nt = torch.zeros(t.shape[0], L_new, t.shape[2], dtype=t.dtype, device=t.device)
+            nt[:, :keep].copy_(t[:, :keep])
+            self.layers[i] = nt
+        self.L_max = int(L_new)
 
     def nbytes(self):
         return sum(t.numel() * t.element_size() for t in self.layers)

@@ -19,7 +19,7 @@ _PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "bad_words_ids", "m
                "begin_suppress_tokens")
 _ACCEPTED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "attention_mask", "stopping_criteria", "use_cache", "do_sample",
              "num_beams", "streamer", "output_scores", "output_logits", "return_dict_in_generate", "num_return_sequences", "position_ids",
-             "inputs_embeds") + _PROCESSORS + _IGNORED_WHEN_GREEDY
+             "inputs_embeds", "past_key_values") + _PROCESSORS + _IGNORED_WHEN_GREEDY
 
 
 class GenerateDecoderOnlyOutput(SimpleNamespace):
@@ -46,6 +46,13 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
         raise NotImplementedError("num_return_sequences > 1 needs sampling or beam search")
     if kwargs.get("streamer") is not None:
         raise NotImplementedError("streamer: token streaming is not implemented")
+    pkv = kwargs.get("past_key_values")
+    if pkv is not None:
+        if not isinstance(pkv, GenerationCache):
+            raise TypeError(f"past_key_values must be a radvlm_amd.generation.GenerationCache (create an empty one with GenerationCache() "
+                            f"and pass it to every call of the conversation), not {type(pkv).__name__}")
+        if kwargs.get("use_cache") is False:
+            raise ValueError("use_cache=False contradicts past_key_values: pass one or the other")
     if lora:
         raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
                                   "model.merge_and_unload() (the reference merges adapters before evaluation)")
@@ -66,6 +73,7 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
                            stopping_criteria=crit, output_scores=bool(kwargs.get("output_scores", False)),
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
+                           past_key_values=pkv,
                            **_parse_processors(kwargs, eos))
 
 
@@ -230,8 +238,130 @@ class GreedyState:
         return np.stack(self.tokens, 1) if self.tokens else np.zeros((B, 0), dtype=np.int64)
 
 
+# ------------------------------------------------------------------------------------------------ reuse of a conversation's KV cache
+NEWLINE_RECORD = -1           # record of an image_newline row (the same learned vector whatever the image)
+_LOCAL_BITS = 24              # image row records: -(2 + (image uid << 24) + row index within the image's merged rows)
+
+
+def position_records(plan, image_uids):
+    """What every spliced position of a plan holds, one int64 array per sequence (its valid positions 0 .. len_b - 1, whatever the padding
+    side): a token id (>= 0); NEWLINE_RECORD; or an image feature row, -(2 + (uid << 24) + k) with uid = image_uids[i] of the image the row
+    comes from (equal uids: bit-identical pixels and image_size) and k its row in that image's feature rows (projector rows, then the
+    rows anyres_max creates), which the splice plan fixes (plan["idx"], plan["image_rows"]).  Equal records at positions 0 .. p on the same
+    weights give the same K|V at p."""
+    B = plan["attention_mask"].shape[0]
+    idx = plan["idx"].reshape(B, -1).astype(np.int64)
+    am = plan["attention_mask"].astype(bool)
+    nfr = int(plan["n_feat_rows"])
+    code = np.zeros(nfr + 1, dtype=np.int64)
+    code[nfr] = NEWLINE_RECORD
+    for i, (p0, p1, e0, e1) in enumerate(plan.get("image_rows", [])):
+        base = 2 + (int(image_uids[i]) << _LOCAL_BITS)
+        code[p0:p1] = -(base + np.arange(p1 - p0))
+        code[e0:e1] = -(base + (p1 - p0) + np.arange(e1 - e0))
+    out = []
+    for b in range(B):
+        v = idx[b][am[b]]
+        out.append(np.where(v >= 0, v, code[np.clip(-v - 2, 0, nfr)]))
+    return out
+
+
+def reuse_lengths(cached, new):
+    """Positions of each sequence whose cached K|V a continued call keeps: the longest common prefix of the cached records and the new
+    ones, capped at len_b - 1 (the last prompt position is always recomputed: its logits start the decoding).  int64 [B]."""
+    r = np.zeros(len(new), dtype=np.int64)
+    for b, (c, n) in enumerate(zip(cached, new)):
+        k = min(len(c), len(n))
+        neq = np.nonzero(np.asarray(c[:k]) != np.asarray(n[:k]))[0]
+        r[b] = min(int(neq[0]) if neq.size else k, max(len(n) - 1, 0))
+    return r
+
+
+def grown_length(L_max, need):
+    """Slots per sequence of a cache that must hold `need` positions: L_max when they fit, else need rounded up to 256."""
+    return int(L_max) if need <= L_max else (int(need) + 255) // 256 * 256
+
+
+def _same_pixels(a, b):
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    a = a.detach().contiguous().view(torch.uint8).reshape(-1)
+    b = b.detach().to(a.device).contiguous().view(torch.uint8).reshape(-1)
+    return bool(torch.equal(a, b))
+
+
+class GenerationCache:
+    """A conversation's KV cache across generate() calls, HF's `past_key_values` idiom: create an empty one (GenerationCache(), as HF's
+    DynamicCache()), pass it to each call with the FULL prompt and images, and every call reuses the positions it already holds -- the
+    longest common prefix of what each cached position holds (a token id, or an image feature row identified by the image's bits, its
+    image_size and the row's index) and the new spliced prompt, at most len_b - 1 -- and recomputes only the rest (LlavaEngine.extend).
+    It holds the engine's KVCache (bf16 [B, L_max, 2 * kvd] per layer, sequence b at positions 0 .. n_b - 1), the per-position records,
+    the images they refer to and the engine and weights version they were computed with: a cache of older weights (an optimizer step,
+    load_state_dict, a LoRA merge, a vocabulary resize, a checkpoint load since) is emptied and the call runs as a fresh one."""
+
+    def __init__(self):
+        self.kv = None
+        self.records = None
+        self.images = []              # (uid, pixels, image_size) of the images the records refer to
+        self.engine = None
+        self.weights_version = None
+        self._next_uid = 0
+
+    @property
+    def batch_size(self):
+        return None if self.kv is None else self.kv.B
+
+    def get_seq_length(self, layer_idx=0):
+        """Positions held by the longest cached sequence (0 when empty)."""
+        return 0 if self.kv is None else int(self.kv.lens.max())
+
+    def crop(self, max_length):
+        """Keep at most max_length positions per sequence (a negative value drops that many from the longest, as HF's crop)."""
+        if self.kv is None:
+            return
+        if max_length < 0:
+            max_length = self.get_seq_length() - abs(max_length)
+        n = max(int(max_length), 0)
+        self.kv.lens = np.minimum(self.kv.lens, n)
+        self.records = [r[:n] for r in self.records]
+
+    def reset(self):
+        self.kv, self.records, self.images = None, None, []
+
+    def _bind(self, engine, B):
+        """Checks before a call: ValueError for another engine or another batch size; a stale cache is emptied."""
+        if self.engine is not None and self.engine is not engine:
+            raise ValueError("this GenerationCache was filled by another model: use one cache per model")
+        if self.kv is not None and self.kv.B != B:
+            raise ValueError(f"the GenerationCache holds {self.kv.B} sequences, the prompt has {B}")
+        if self.kv is not None and self.weights_version != engine.weights_version:
+            self.reset()
+        self.engine = engine
+
+    def _image_uids(self, images, image_sizes):
+        """uid of each image of a call: the uid of a cached image with the same bits and image_size, else a new one."""
+        uids = []
+        for i, im in enumerate(images or []):
+            size = None if image_sizes is None else tuple(int(v) for v in image_sizes[i])
+            hit = next((u for u, px, sz in self.images if sz == size and _same_pixels(px, im)), None)
+            if hit is None:
+                hit = self._next_uid
+                self._next_uid += 1
+            uids.append(hit)
+        return uids
+
+    def _store(self, kv, records, images, image_sizes, uids, engine):
+        self.kv, self.records = kv, records
+        held = {u: px for u, px, _ in self.images}            # an image already held is not copied again
+        self.images = [(u, held[u] if u in held else im.detach().clone(), None if image_sizes is None else tuple(int(v) for v in image_sizes[i]))
+                       for i, (u, im) in enumerate(zip(uids, images or []))]
+        self.engine, self.weights_version = engine, engine.weights_version
+
+
 def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg):
-    """prefill once, then decode_step per token until every row has finished or the budget is spent."""
+    """prefill once, then decode_step per token until every row has finished or the budget is spent.  With cfg.past_key_values (a
+    GenerationCache) the prompt pass reuses what the cache holds (LlavaEngine.extend; an empty cache: prefill as without one) and the
+    cache keeps the prompt and every generated token but the last."""
     from . import ops
     ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids)
     if ids.ndim == 1:
@@ -239,6 +369,9 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     am = cfg.attention_mask
     am = None if am is None else np.asarray(am.cpu() if torch.is_tensor(am) else am)
     B = ids.shape[0]
+    gc = cfg.past_key_values
+    if gc is not None:
+        gc._bind(engine, B)
     st = GreedyState(B, cfg)
     scores = []
     dev = engine.device
@@ -252,7 +385,19 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     if T > 0:
         # the tokens generated so far, pads of finished rows included (HF's input_ids of inputs_embeds generation: no prompt)
         hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active else None
-        cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T)
+        if gc is None:
+            cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T)
+        else:
+            imgs = list(images) if images is not None else []
+            plan = engine.plan(ids, am, None, imgs, image_sizes)
+            uids = gc._image_uids(imgs, image_sizes)
+            recs = position_records(plan, uids)
+            reuse = np.zeros(B, dtype=np.int64) if gc.kv is None else reuse_lengths(gc.records, recs)
+            kv, gc.kv, gc.records = gc.kv, None, None         # an unused cache is freed before prefill allocates the new one
+            if not reuse.any():
+                kv = None
+            cache, logits = engine.extend(kv, ids, am, images, image_sizes, reuse=reuse, max_new_tokens=T, plan=plan)
+            del kv
         for t in range(T):
             if cfg.output_logits:
                 raw.append(logits.clone())
@@ -268,9 +413,12 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             if st.all_done or t == T - 1:
                 break
             logits = engine.decode_step(cache, torch.from_numpy(tok))
+        if gc is not None:          # the prompt and the tokens fed to decode_step (every emitted one but the last; pads of finished rows)
+            fed = st.sequences()[:, :int(cache.lens[0] - plan["lens"][0])]
+            gc._store(cache, [np.concatenate([recs[b], fed[b]]) for b in range(B)], imgs, image_sizes, uids, engine)
         del cache
     seq = torch.from_numpy(st.sequences()).to(dev)
     if cfg.return_dict:
         return GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
-                                         logits=tuple(raw) if cfg.output_logits else None)
+                                         logits=tuple(raw) if cfg.output_logits else None, past_key_values=cfg.past_key_values)
     return seq

@@ -98,6 +98,8 @@ _SIGS = {
                      _c_void_p],
     "rv_attn_decode_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32,
                             _i32, _i32, _f32, _c_void_p],
+    "rv_attn_extend_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
+                            _i32, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
     "rv_kv_append_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _c_void_p, _i32, _i32, _i32, _c_void_p],
     "rv_argmax_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p],
     "rv_logits_process_argmax_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _i64, _i32, _f32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p, _i32,

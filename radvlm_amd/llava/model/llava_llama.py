@@ -228,6 +228,7 @@ class LlavaLlamaForCausalLM:
                 else:
                     raise ValueError(f"Unexpected embed_tokens_weight shape. Pretrained: {tuple(w.shape)}. Current: {(e.vocab, emb.shape[1])}. "
                                      f"Numer of new tokens: {num_new}.")
+                e.weights_changed(tower=False)
                 if e.master is not None:
                     from ... import ops
                     e.master.copy_(ops.to_f32(e.lm.flat))
@@ -271,7 +272,8 @@ class LlavaLlamaForCausalLM:
         Returns the NEW tokens only, LongTensor [B, T_new]; rows that finished (EOS or a stopping criterion) are filled with
         pad_token_id.  Keywords: max_new_tokens (default 20), max_length, eos_token_id, pad_token_id, attention_mask, stopping_criteria,
         use_cache (the result is the same either way), output_scores / output_logits + return_dict_in_generate (.sequences, .scores =
-        the processed scores, .logits = the raw ones).  HF's greedy logits processors: repetition_penalty, no_repeat_ngram_size,
+        the processed scores, .logits = the raw ones, .past_key_values).  past_key_values: a generation.GenerationCache() reused across
+        the calls of a conversation (each with the full prompt and images; the cached common prefix is not recomputed).  HF's greedy logits processors: repetition_penalty, no_repeat_ngram_size,
         bad_words_ids, min_length, min_new_tokens, suppress_tokens, begin_suppress_tokens; as in HF generation from inputs_embeds they
         see only the generated tokens (pads included), never the prompt; a bad value raises ValueError.  Sampling, beam search,
         streamers, inputs_embeds and LoRA models raise NotImplementedError.  The training state (weights, optimizer, RNG counters) is

@@ -595,6 +595,28 @@ def attn_decode(q, cache, kv_len, H, Hkv, hd, v_off, out=None, chunk=128, scale=
     return out
 
 
+EXTEND_CHUNK = 256        # keys per extend-attention workgroup: fixed, so a row's result never depends on the batch around it
+
+
+def attn_extend(q, cache, cu_q, r, H, Hkv, hd, v_off, max_q, out=None, chunk=EXTEND_CHUNK, scale=None):
+    """Causal attention of new query rows against a KV cache (rv_attn_extend_bf16): q [M, H*hd] rows, sequence b's rows
+    cu_q[b] .. cu_q[b+1] - 1 at positions r[b] + i, their own K|V already in cache (bf16 [B, L_max, width], K of kv head g at columns
+    g*hd, V at v_off + g*hd); cu_q (B + 1) / r (B) int32 device arrays, max_q >= every sequence's row count.  Returns bf16 [M, H*hd]."""
+    _chk(q), _chk(cache), _chk(cu_q, torch.int32), _chk(r, torch.int32)
+    B, L_max, width = cache.shape
+    M = q.shape[0]
+    assert q.shape == (M, H * hd) and q.stride(1) == 1 and cache.is_contiguous() and cu_q.numel() == B + 1 and r.numel() == B
+    assert cu_q.is_contiguous() and r.is_contiguous() and 1 <= max_q <= M
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if out is None:
+        out = torch.empty(M, H * hd, dtype=BF16, device=q.device)
+    nch = (L_max + chunk - 1) // chunk
+    part = torch.empty(M * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    lib.call("rv_attn_extend_bf16", q, q.stride(0), cache, width, L_max * width, v_off, cu_q, r, L_max, out, out.stride(0), part,
+             part.numel() * 4, B, M, int(max_q), H, Hkv, hd, chunk, float(scale))
+    return out
+
+
 def kv_append(src, cache, pos):
     """cache[b, pos[b], :] = src[b, :] (src [B, width] bf16 rows, e.g. the k|v columns of the qkv product; pos int32 [B] device)."""
     _chk(src), _chk(cache), _chk(pos, torch.int32)

@@ -2,6 +2,11 @@
 
   python tools/decode_bench.py [--geos llava15_7b,llava_ov_qwen2_7b] [--batches 1,8,32] [--prompt 704] [--new 128] [--out FILE]
   python tools/decode_bench.py --ab [--out FILE]     # rv_gemv_bf16 vs rv_gemm_nt_bf16 at M = 1, 4, 16, 32, interleaved on one box
+  python tools/decode_bench.py --continue [--geos ..] [--batches 1,8] [--reps 5] [--out FILE]
+        # a two-turn conversation per config on one engine: turn 2 = turn 1's prompt + its 64 generated tokens + a 40-token follow-up;
+        # time to first token of turn 2 through a GenerationCache (LlavaEngine.extend) vs a fresh full call, interleaved, and decode
+        # ms / step after the continuation vs after a fresh prefill.  llava15_7b: one 336 px image; llava_ov_qwen2_7b: one anyres_max_9
+        # image (10 tiles of 384 px, S = 7499)
   python tools/decode_bench.py --processors [--geos ..] [--batches 1,32] [--out FILE]
         # plain greedy argmax vs the logits processors (repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=new/2 with an EOS)
         # through rv_logits_process_argmax_f32, interleaved (plain, processors, plain, ...) on one engine
@@ -151,6 +156,97 @@ def processors_ab(geo, B, prompt, new, reps=3):
                 kernel_src=_src_hash())
 
 
+def _conversation(geo, B, seed=0):
+    """Engine + turn-1 batch of the --continue configs: ids as bench.py's synthetic batch (129 ids, the image token at 35)."""
+    g = GEOMETRIES[geo]
+    kw = {}
+    if geo == "llava_ov_qwen2_7b":
+        kw = dict(merge_type="spatial_unpad", image_aspect_ratio="anyres_max_9", image_grid_pinpoints="(1x1),...,(6x6)")
+    eng = LlavaEngine(g, device="cuda:0", init="fast", seed=0, **kw)
+    rng = np.random.default_rng(seed)
+    ids = rng.integers(3, eng.vocab, size=(B, 129), dtype=np.int64)
+    ids[:, 35] = -200
+    gen = torch.Generator().manual_seed(seed)
+    img = g["vision"]["image"]
+    if kw:
+        images = [torch.randn(10, 3, img, img, generator=gen).to(torch.bfloat16) for _ in range(B)]
+        sizes = [(1024, 1024)] * B
+    else:
+        images = [torch.randn(3, img, img, generator=gen).to(torch.bfloat16) for _ in range(B)]
+        sizes = [(img, img)] * B
+    return eng, ids, images, sizes
+
+
+def _snapshot(gc):
+    from radvlm_amd.engine import KVCache
+    kv = gc.kv
+    return (KVCache([t.clone() for t in kv.layers], kv.lens, kv.L_max), [r.copy() for r in gc.records], list(gc.images),
+            gc.weights_version, gc._next_uid)
+
+
+def _restore(gc, snap):
+    from radvlm_amd.engine import KVCache
+    kv, recs, imgs, ver, uid = snap
+    gc.kv = KVCache([t.clone() for t in kv.layers], kv.lens, kv.L_max)
+    gc.records, gc.images, gc.weights_version, gc._next_uid = [r.copy() for r in recs], list(imgs), ver, uid
+
+
+def continue_case(geo, B, reps=5, turn1_new=64, follow=40, new=64, warm=8):
+    from radvlm_amd.generation import GenerationCache, greedy_generate, parse_generate_kwargs, position_records, reuse_lengths
+    eng, ids1, images, sizes = _conversation(geo, B)
+    gc = GenerationCache()
+    t1 = greedy_generate(eng, ids1, None, images, sizes, parse_generate_kwargs(dict(max_new_tokens=turn1_new, past_key_values=gc)))
+    ids2 = np.concatenate([ids1, t1.cpu().numpy(), np.random.default_rng(1).integers(3, eng.vocab, (B, follow))], axis=1)
+    snap = _snapshot(gc)
+    first = lambda cache: parse_generate_kwargs(dict(max_new_tokens=1, **({} if cache is None else dict(past_key_values=cache))))
+
+    def ttft(cached):
+        if cached:
+            _restore(gc, snap)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        greedy_generate(eng, ids2, None, images, sizes, first(gc if cached else None))
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    ttft(True), ttft(False)                                           # warm-up of both paths
+    ts = {"cached": [], "fresh": []}
+    for _ in range(reps):
+        ts["cached"].append(ttft(True))
+        ts["fresh"].append(ttft(False))
+    # decode after the continuation (K|V of turn 1 from the decode path, extend rows) vs after a fresh prefill of the turn-2 prompt
+    plan = eng.plan(ids2, None, None, images, sizes)
+    _restore(gc, snap)
+    reuse = reuse_lengths(gc.records, position_records(plan, gc._image_uids(images, sizes)))
+    steps = {}
+    for mode in ("fresh", "cached"):
+        if mode == "cached":
+            _restore(gc, snap)
+            cache, logits = eng.extend(gc.kv, ids2, None, images, sizes, reuse=reuse, max_new_tokens=new, plan=plan)
+        else:
+            cache, logits = eng.prefill(ids2, None, images, sizes, max_new_tokens=new)
+        tok = ops.argmax_rows(logits, eng.vocab)
+        times = []
+        for _ in range(new - 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            logits = eng.decode_step(cache, tok.to(torch.int32))
+            tok = ops.argmax_rows(logits, eng.vocab)
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+        steps[mode] = float(np.median(times[warm:]))
+        del cache
+    gc.reset()
+    lens = plan["lens"].astype(np.int64)
+    c, f = float(np.median(ts["cached"])), float(np.median(ts["fresh"]))
+    return dict(geo=geo, B=B, mode="continue", prompt_turn1=int(lens.max()) - turn1_new - follow, turn1_new_tokens=turn1_new,
+                follow_up_tokens=follow, prompt_turn2=int(lens.max()), reused_per_row=reuse.tolist()[:1] + ([] if B == 1 else ["..."]),
+                new_rows_total=int((lens - reuse).sum()), ttft_cached_ms=round(c, 2), ttft_fresh_ms=round(f, 2), ttft_speedup=round(f / c, 2),
+                ttft_cached_all=[round(x, 2) for x in ts["cached"]], ttft_fresh_all=[round(x, 2) for x in ts["fresh"]], reps=reps,
+                decode_ms_per_step_after_continue=round(steps["cached"], 3), decode_ms_per_step_plain=round(steps["fresh"], 3),
+                extend_kv_floor_bytes_per_layer=int(lens.sum() * 2 * eng.kvd * 2), kernel_src=_src_hash())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--geos", default="llava15_7b,llava_ov_qwen2_7b")
@@ -159,11 +255,16 @@ def main():
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--processors", action="store_true")
+    ap.add_argument("--continue", dest="cont", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.ab:
         recs = ab()
+    elif a.cont:
+        batches = a.batches if a.batches != ap.get_default("batches") else "1,8"
+        recs = [continue_case(g, b, reps=a.reps) for g in a.geos.split(",") for b in map(int, batches.split(","))]
     elif a.processors:
         recs = [processors_ab(g, b, a.prompt, a.new) for g in a.geos.split(",") for b in map(int, a.batches.split(","))]
     else:
