@@ -372,6 +372,20 @@ int rv_argmax_rows_f32(const float* x, int64_t ld, int rows, int n, int64_t* out
 int rv_logits_process_argmax_f32(float* x, int64_t ld, int rows, int n, const int32_t* hist, int64_t ld_hist, int t, float rep_penalty,
                                  int ngram, const int32_t* ban, int n_ban, const int32_t* bad_tok, const int32_t* bad_off, int n_bad,
                                  int64_t* out, void* stream);
+/* The same processors for rows at different steps (continuous batching, generate_batch): row r is at step t[r] with EOS minimum
+ * min_new[r] (int32 device arrays of `rows` entries, as slot[]); its history is hist[slot[r]][0 .. t[r]) of an int32 [hist_rows,
+ * hist_cols] array of row stride ld_hist (hist may be NULL with hist_rows = 0: no history), so a history row stays with its KV-cache
+ * slot.  The ban lists are passed apart and composed per row: ban_always on every row (suppress_tokens, one-token bad words), ban_begin
+ * where t[r] == 0, ban_eos where t[r] < min_new[r].  Penalty, n-gram and multi-token bad words as rv_logits_process_argmax_f32; with
+ * every t[r] equal (and the lists composed as that entry's ban) the processed rows and out[] are bit-identical to it.  logprob (fp32
+ * [rows] or NULL): logprob[r] = processed[out[r]] - logsumexp(processed row), from a running max and rescaled sum kept in the same
+ * sweep and merged in a fixed order (the row is read once).  One workgroup per row, no global atomics: a row's result does not depend
+ * on the other rows of the launch.  History reads are clamped to [0, hist_cols) and a slot outside [0, hist_rows) reads none. */
+int rv_logits_process_argmax_rows_f32(float* x, int64_t ld, int rows, int n, const int32_t* hist, int64_t ld_hist, int hist_rows,
+                                      int hist_cols, const int32_t* slot, const int32_t* t, const int32_t* min_new, float rep_penalty,
+                                      int ngram, const int32_t* ban_always, int n_always, const int32_t* ban_begin, int n_begin,
+                                      const int32_t* ban_eos, int n_eos, const int32_t* bad_tok, const int32_t* bad_off, int n_bad,
+                                      int64_t* out, float* logprob, void* stream);
 
 /* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
  * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any

@@ -391,6 +391,128 @@ __global__ __launch_bounds__(256) void logits_process_argmax_kernel(float* __res
     }
 }
 
+// The same processors for rows that sit at different steps (continuous batching): row r has its own step t[r] and EOS minimum
+// min_new[r], and its history is hist[slot[r], 0 .. t[r]), so a history row stays with its KV-cache slot.  The ban lists come apart:
+// `always` (suppress_tokens, one-token bad words), `begin` (t[r] == 0) and `eos` (t[r] < min_new[r]); each row composes its own.
+// The phases are those of logits_process_argmax_kernel, so at equal t the processed row and token are the same bits.  LOGP: the same
+// sweep also keeps a running (max, sum of exp(x - max)) per thread -- per batch of LP_U loads: the batch maximum, one rescale, then
+// LP_U independent exponentials summed in order, so no exp waits on the previous one -- merged in a fixed order (lanes by xor
+// butterfly, then waves 0..3), and logprob[r] = (x[tok] - max) - log(sum): the log-softmax of the processed row at the chosen token,
+// the row read once.
+DEVINL void lse_merge(float& m, float& s, float om, float os) {
+    const float M = fmaxf(m, om);
+    if (M == -INFINITY) return;                  // both empty
+    s = s * expf(m - M) + os * expf(om - M);
+    m = M;
+}
+
+template <bool LOGP>
+__global__ __launch_bounds__(256) void logits_process_argmax_rows_kernel(
+    float* __restrict__ x, long ld, int n, const int32_t* __restrict__ hist, long ld_hist, int hist_rows, int hist_cols,
+    const int32_t* __restrict__ slot, const int32_t* __restrict__ tv, const int32_t* __restrict__ min_new, float pen_p, int ngram,
+    const int32_t* __restrict__ ban_a, int n_a, const int32_t* __restrict__ ban_b, int n_b, const int32_t* __restrict__ ban_e, int n_e,
+    const int32_t* __restrict__ bad_tok, const int32_t* __restrict__ bad_off, int n_bad, int64_t* __restrict__ out,
+    float* __restrict__ logprob) {
+    extern __shared__ unsigned lp_bits[];
+    const int words = (n + 31) >> 5;
+    unsigned* pen = lp_bits;
+    unsigned* bnd = lp_bits + words;
+    float* row = x + (long)blockIdx.x * ld;
+    const int tid = threadIdx.x;
+    const int t = tv[blockIdx.x], s = slot[blockIdx.x];
+    // history reads stay inside hist[0 .. hist_rows) x [0 .. hist_cols) whatever the caller passed: a slot out of range reads none
+    const int th = (hist && s >= 0 && s < hist_rows) ? min(max(t, 0), hist_cols) : 0;
+    const int32_t* h = th > 0 ? hist + (long)s * ld_hist : nullptr;
+    for (int w = tid; w < 2 * words; w += 256) lp_bits[w] = 0u;
+    __syncthreads();
+    if (pen_p != 1.0f)
+        for (int i = tid; i < th; i += 256) lp_set(pen, h[i], n);
+    if (ngram > 0 && th >= ngram) {
+        for (int i = tid; i <= th - ngram; i += 256) {
+            bool eq = true;
+            for (int k = 0; k < ngram - 1 && eq; ++k) eq = h[i + k] == h[th - ngram + 1 + k];
+            if (eq) lp_set(bnd, h[i + ngram - 1], n);
+        }
+    }
+    for (int j = tid; j < n_a; j += 256) lp_set(bnd, ban_a[j], n);
+    if (t == 0)
+        for (int j = tid; j < n_b; j += 256) lp_set(bnd, ban_b[j], n);
+    if (t < min_new[blockIdx.x])
+        for (int j = tid; j < n_e; j += 256) lp_set(bnd, ban_e[j], n);
+    for (int q = tid; q < n_bad; q += 256) {
+        const int o = bad_off[q], L = bad_off[q + 1] - o;
+        if (L < 2 || th < L) continue;
+        bool eq = true;
+        for (int k = 0; k < L - 1 && eq; ++k) eq = bad_tok[o + k] == h[th - L + 1 + k];
+        if (eq) lp_set(bnd, bad_tok[o + L - 1], n);
+    }
+    __syncthreads();
+    float bv = -INFINITY, lm = -INFINITY, ls = 0.f;
+    int bi = 0x7fffffff;
+    for (int j0 = tid; j0 < n; j0 += 256 * LP_U) {
+        float vs[LP_U];
+#pragma unroll
+        for (int u = 0; u < LP_U; ++u) {
+            const int j = j0 + u * 256;
+            vs[u] = j < n ? row[j] : -INFINITY;
+        }
+#pragma unroll
+        for (int u = 0; u < LP_U; ++u) {
+            const int j = j0 + u * 256;
+            if (j >= n) break;
+            float v = vs[u];
+            const unsigned m = 1u << (j & 31);
+            const bool pj = pen[j >> 5] & m, bj = bnd[j >> 5] & m;
+            if (pj) v = v < 0.f ? v * pen_p : v / pen_p;
+            if (bj) v = -INFINITY;
+            if (pj || bj) row[j] = v;
+            if (am_better(v, j, bv, bi)) { bv = v; bi = j; }
+            vs[u] = v;
+        }
+        if (LOGP) {
+            float mb = lm;
+#pragma unroll
+            for (int u = 0; u < LP_U; ++u) mb = fmaxf(mb, vs[u]);
+            if (mb != -INFINITY) {
+                float acc = 0.f;
+#pragma unroll
+                for (int u = 0; u < LP_U; ++u) acc += __expf(vs[u] - mb);
+                ls = ls * __expf(lm - mb) + acc;
+                lm = mb;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (am_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        if (LOGP) {
+            const float om = __shfl_xor(lm, o, 64), os = __shfl_xor(ls, o, 64);
+            lse_merge(lm, ls, om, os);
+        }
+    }
+    __syncthreads();                             // every bitmap read is done: the reduction scratch reuses the bitmap's first words
+    float* rv = (float*)lp_bits;
+    int* ri = (int*)(lp_bits + 4);
+    float* rm = (float*)(lp_bits + 8);
+    float* rs = (float*)(lp_bits + 12);
+    if (lane_id() == 0) {
+        rv[wave_id()] = bv;
+        ri[wave_id()] = bi;
+        if (LOGP) { rm[wave_id()] = lm; rs[wave_id()] = ls; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < 4; ++k) {
+            if (am_better(rv[k], ri[k], bv, bi)) { bv = rv[k]; bi = ri[k]; }
+            if (LOGP) lse_merge(lm, ls, rm[k], rs[k]);
+        }
+        out[blockIdx.x] = bi;
+        if (LOGP) logprob[blockIdx.x] = (bv - lm) - logf(ls);
+    }
+}
+
 inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace
@@ -477,5 +599,29 @@ extern "C" int rv_logits_process_argmax_f32(float* x, int64_t ld, int rows, int 
     const size_t lds = (size_t)2 * ((n + 31) / 32) * sizeof(unsigned);     // >= 32 bytes (the reduction scratch) for every n >= 1
     hipLaunchKernelGGL(logits_process_argmax_kernel, dim3(rows), dim3(256), lds < 32 ? 32 : lds, ST, x, (long)ld, n, hist, (long)ld_hist, t,
                        rep_penalty, ngram, ban, n_ban, bad_tok, bad_off, n_bad, out);
+    return rv_check_launch();
+}
+
+extern "C" int rv_logits_process_argmax_rows_f32(float* x, int64_t ld, int rows, int n, const int32_t* hist, int64_t ld_hist, int hist_rows,
+                                                 int hist_cols, const int32_t* slot, const int32_t* t, const int32_t* min_new,
+                                                 float rep_penalty, int ngram, const int32_t* ban_always, int n_always,
+                                                 const int32_t* ban_begin, int n_begin, const int32_t* ban_eos, int n_eos,
+                                                 const int32_t* bad_tok, const int32_t* bad_off, int n_bad, int64_t* out, float* logprob,
+                                                 void* stream) {
+    if (!x || !out || !slot || !t || !min_new || rows <= 0 || n <= 0 || n > LP_MAX_N || ld < n || hist_rows < 0 || hist_cols < 0 ||
+        (hist_rows > 0 && hist_cols > 0 && (!hist || ld_hist < hist_cols)) || !(rep_penalty > 0.f) || ngram < 0 || n_always < 0 ||
+        (n_always > 0 && !ban_always) || n_begin < 0 || (n_begin > 0 && !ban_begin) || n_eos < 0 || (n_eos > 0 && !ban_eos) ||
+        n_bad < 0 || (n_bad > 0 && (!bad_tok || !bad_off)))
+        return RV_ERR_ARG;
+    if (hist_rows == 0 || hist_cols == 0) hist = nullptr;
+    const size_t lds = (size_t)2 * ((n + 31) / 32) * sizeof(unsigned);     // the reduction scratch needs 64 bytes
+    if (logprob)
+        hipLaunchKernelGGL(logits_process_argmax_rows_kernel<true>, dim3(rows), dim3(256), lds < 64 ? 64 : lds, ST, x, (long)ld, n, hist,
+                           (long)ld_hist, hist_rows, hist_cols, slot, t, min_new, rep_penalty, ngram, ban_always, n_always, ban_begin,
+                           n_begin, ban_eos, n_eos, bad_tok, bad_off, n_bad, out, logprob);
+    else
+        hipLaunchKernelGGL(logits_process_argmax_rows_kernel<false>, dim3(rows), dim3(256), lds < 64 ? 64 : lds, ST, x, (long)ld, n, hist,
+                           (long)ld_hist, hist_rows, hist_cols, slot, t, min_new, rep_penalty, ngram, ban_always, n_always, ban_begin,
+                           n_begin, ban_eos, n_eos, bad_tok, bad_off, n_bad, out, logprob);
     return rv_check_launch();
 }

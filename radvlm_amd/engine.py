@@ -840,11 +840,28 @@ class LlavaEngine:
             raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
                                       "model.merge_and_unload() (the reference merges adapters before evaluation)")
 
-    def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0):
+    def kv_cache_bytes(self, B, L_max):
+        """Bytes of a KVCache of B sequences x L_max positions (bf16 K|V rows of every layer)."""
+        return self.l["layers"] * int(B) * int(L_max) * 2 * self.kvd * 2
+
+    def free_device_bytes(self):
+        """Device memory a new allocation can take: free HBM plus what torch's caching allocator holds unused."""
+        free, _ = torch.cuda.mem_get_info(self.device)
+        return int(free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device))
+
+    def new_kv_cache(self, B, L_max):
+        """An empty KVCache of B sequences (every length 0) x L_max positions, to be filled by prefill(..., cache=, slots=)."""
+        L = self.l["layers"]
+        return KVCache([torch.zeros(B, L_max, 2 * self.kvd, dtype=BF16, device=self.device) for _ in range(L)], np.zeros(B, np.int64), L_max)
+
+    def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0, cache=None, slots=None):
         """The prompt pass of generation: multimodal splice (plan / encode_images, as in forward) and every decoder layer in the packed
         varlen layout, sequence b at cache rows and positions 0 .. len_b - 1 whatever the padding side.  Each layer's post-RoPE K|V rows go
         into a KVCache of len_b + max_new_tokens slots per sequence; the activations are dropped.  No loss, no saved context (self.ctx and
         the optimizer state are not touched).  images None: text-only prompts, embedded directly.
+        cache / slots (generate_batch): sequence b's K|V rows go instead into slot slots[b] of the existing KVCache `cache` (positions
+        0 .. len_b - 1; the slot's later positions are left as they are) and cache.lens[slots[b]] = len_b; the arithmetic is the same, so
+        the logits and K|V rows are the bits prefill() gives the same group on a cache of cache.L_max positions.  Other slots are untouched.
         Returns (cache, fp32 logits [B, vocab] of every sequence's last prompt row)."""
         self._check_generation()
         dev, l = self.device, self.l
@@ -865,23 +882,38 @@ class LlavaEngine:
             raise ValueError("generation needs at least one prompt token per sequence")
         valid = plan["attention_mask"].reshape(-1)
         S = int(lens.max())
-        L_max = int(lens.max()) + int(max_new_tokens)
+        if cache is None:
+            L_max = int(lens.max()) + int(max_new_tokens)
+            seq = np.arange(B)
+        else:
+            seq = np.asarray(slots, dtype=np.int64).reshape(-1)
+            if seq.shape[0] != B or np.unique(seq).shape[0] != B or (seq < 0).any() or (seq >= cache.B).any():
+                raise ValueError(f"slots must be {B} distinct indices into the cache's {cache.B} sequences, got {seq.tolist()}")
+            L_max = cache.L_max
+            if (lens + int(max_new_tokens) > L_max).any():
+                raise ValueError(f"the prompts need {int(lens.max()) + int(max_new_tokens)} positions, the cache holds {L_max}")
         cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
         pos = np.concatenate([np.arange(n, dtype=np.int32) for n in lens])
         geom = dict(B=B, S=S, s_pad=_ru(S, 64), lens=None, cu=self._dev(cu), pos=self._dev(pos), cs=self.rope_table(L_max))
         x = ops.gather_rows(self._dev(plan["idx"][valid].astype(np.int32)), d, self.W("model.embed_tokens.weight"), table)
-        slots = self._dev(np.concatenate([b * L_max + np.arange(n) for b, n in enumerate(lens)]).astype(np.int64))
+        rows = self._dev(np.concatenate([seq[b] * L_max + np.arange(n) for b, n in enumerate(lens)]).astype(np.int64))   # cache rows
         layers = []
         for i in range(L):
             x, acts = self._layer_forward(i, x, geom)
-            kv = torch.zeros(B, L_max, 2 * kvd, dtype=BF16, device=dev)
-            kv.view(B * L_max, 2 * kvd).index_copy_(0, slots, acts["qkv"][:, d:])
-            layers.append(kv)
+            if cache is None:
+                kv = torch.zeros(B, L_max, 2 * kvd, dtype=BF16, device=dev)
+                layers.append(kv)
+            else:
+                kv = cache.layers[i]
+            kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:])
             del acts
         last = self._dev((cu[1:] - 1).astype(np.int32))
         hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
-        return KVCache(layers, lens, L_max), logits[:, :self.vocab]
+        if cache is None:
+            return KVCache(layers, lens, L_max), logits[:, :self.vocab]
+        cache.lens[seq] = lens
+        return cache, logits[:, :self.vocab]
 
     def decode_step(self, cache, tokens):
         """One generated token per sequence: tokens [B] (int, host or device) at position cache.lens[b] -> fp32 logits [B, vocab].

@@ -422,3 +422,250 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
         return GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
                                          logits=tuple(raw) if cfg.output_logits else None, past_key_values=cfg.past_key_values)
     return seq
+
+
+# ------------------------------------------------------------------------------------------------ continuous batching: generate_batch
+# Admission threshold in free slots.  Picked from the sweep over 1, 4, 8 and 16 (profiles/decode_bench.jsonl, mode
+# generate_batch_sweep; DESIGN.md §5b "Batched generation"): 4 had the shortest wall time for both 7B models on the mixed-budget split.
+ADMIT_FREE_SLOTS = 4
+_NO_PER_REQUEST = ("attention_mask", "past_key_values", "position_ids", "output_scores", "output_logits", "return_dict_in_generate")
+
+
+class GenerationOutput(SimpleNamespace):
+    """One request's result, with HF 5.x continuous batching's field names: request_id ("req_<i>"), prompt_ids (list[int], as given),
+    generated_tokens (list[int]: up to and including the EOS token, or the token after which a stopping criterion returned True; no
+    padding), logprobs (list[float], one per generated token with return_logprobs, else empty), error (None), status."""
+
+    def is_finished(self):
+        return self.status == "finished"
+
+
+def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
+    """generate_batch() keywords: generate()'s greedy settings, validated by parse_generate_kwargs and applied per request;
+    max_new_tokens may also be a list of n budgets (cfg.budgets).  TypeError for arguments without a per-request meaning."""
+    given = sorted(k for k in _NO_PER_REQUEST if kwargs.get(k) is not None and kwargs.get(k) is not False)
+    if given:
+        raise TypeError(f"generate_batch() got arguments without a per-request meaning: {given}")
+    kw = {k: v for k, v in kwargs.items() if k not in _NO_PER_REQUEST}
+    budgets = None
+    mnt = kw.get("max_new_tokens")
+    if mnt is not None and not _is_int(mnt):
+        if not isinstance(mnt, (list, tuple)):
+            raise TypeError(f"max_new_tokens must be an int or a list of {n} ints, not {type(mnt).__name__}")
+        if len(mnt) != n:
+            raise ValueError(f"max_new_tokens holds {len(mnt)} budgets for {n} requests")
+        if any(not _is_int(b) or b < 0 for b in mnt):
+            raise ValueError(f"every max_new_tokens budget must be an int >= 0, got {list(mnt)}")
+        budgets = [int(b) for b in mnt]
+        del kw["max_new_tokens"]
+    cfg = parse_generate_kwargs(kw, lora=lora, config_eos=config_eos, config_pad=config_pad)
+    cfg.budgets = budgets
+    return cfg
+
+
+def _per_request(name, v, n):
+    if v is None:
+        return [None] * n
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"`{name}` must be None or a list of {n} entries, one per request")
+    if len(v) != n:
+        raise ValueError(f"`{name}` has {len(v)} entries for {n} requests")
+    return list(v)
+
+
+def _size_list(v):
+    if v is None:
+        return None
+    v = v.tolist() if torch.is_tensor(v) else list(v)
+    if v and _is_int(v[0]):
+        return [tuple(int(x) for x in v)]                     # one (h, w)
+    return [tuple(int(x) for x in s) for s in v]
+
+
+def batch_requests(inputs, images=None, image_sizes=None):
+    """The requests of generate_batch(), normalised: ids (int64 numpy, as given), images (the request's tensors in image-token order)
+    and sizes (one (h, w) per image, or None).  ValueError for a list of the wrong length or images that do not match the image tokens."""
+    from .splice import IMAGE_TOKEN_INDEX
+    inputs = list(inputs)
+    n = len(inputs)
+    ims, szs = _per_request("images", images, n), _per_request("image_sizes", image_sizes, n)
+    reqs = []
+    for i, p in enumerate(inputs):
+        ids = np.asarray(p.detach().cpu() if torch.is_tensor(p) else p)
+        if ids.ndim != 1 or ids.size == 0 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f"request {i}: a prompt is a non-empty 1-D sequence of token ids, got shape {ids.shape}, dtype {ids.dtype}")
+        im = [] if ims[i] is None else ([ims[i]] if torch.is_tensor(ims[i]) else list(ims[i]))
+        sz = _size_list(szs[i])
+        k = int((ids == IMAGE_TOKEN_INDEX).sum())
+        if k and not im:
+            raise ValueError(f"request {i}: the prompt holds an image token but no images were passed")
+        if k != len(im):
+            raise ValueError(f"request {i}: the prompt holds {k} image tokens but {len(im)} images were passed")
+        if sz is not None and len(sz) != len(im):
+            raise ValueError(f"request {i}: {len(sz)} image sizes for {len(im)} images")
+        reqs.append(SimpleNamespace(index=i, ids=ids.astype(np.int64), images=im, sizes=sz))
+    with_img = [r for r in reqs if r.images]
+    if any(r.sizes is None for r in with_img) and any(r.sizes is not None for r in with_img):
+        raise ValueError("image_sizes: give the sizes of every request's images or of none")
+    return reqs
+
+
+class DevicePicker:
+    """Token choice of one generate_batch() step on the device, for rows at different steps: rv_argmax_rows_f32 when no processor is
+    active and no logprobs are asked for, else rv_logits_process_argmax_rows_f32 (row r at its own step t[r] with its own EOS minimum).
+    The emitted tokens go into the device history, int32 [slots, max budget], at (slot, t); a slot's history restarts at t = 0 with
+    each request admitted into it."""
+
+    def __init__(self, engine, cfg, slots, max_budget, logprobs, any_min_new):
+        lp = LogitsProcessors(cfg, engine.vocab)
+        self.engine, self.vocab, self.logprobs = engine, engine.vocab, bool(logprobs)
+        self.penalty, self.ngram = lp.penalty, lp.ngram
+        self.active = (lp.penalty != 1.0 or lp.ngram > 0 or bool(cfg.bad_words_ids) or bool(lp.suppress) or bool(lp.begin) or
+                       (any_min_new and bool(lp.eos)))
+        dev = engine.device
+        i32 = lambda ids: torch.tensor(ids, dtype=torch.int32, device=dev) if ids else None
+        self.bans = (i32(sorted(set(lp.suppress) | set(lp.one))), i32(sorted(set(lp.begin))), i32(sorted(set(lp.eos))))
+        tok, off = lp.bad_csr()
+        self.bad = (torch.from_numpy(tok).to(dev), torch.from_numpy(off).to(dev)) if lp.multi else (None, None)
+        self.hist = torch.zeros(slots, max(int(max_budget), 1), dtype=torch.int32, device=dev) if self.active else None
+
+    def __call__(self, logits, slot, t, min_new):
+        """logits: fp32 [rows, vocab] (processed in place); slot / t / min_new: numpy ints [rows].  Returns (tokens, logprobs or None)."""
+        from . import ops
+        if not (self.active or self.logprobs):
+            return ops.argmax_rows(logits, self.vocab).cpu().numpy(), None
+        cols = 1 if self.hist is None else self.hist.shape[1]
+        info = self.engine._dev(np.stack([slot, t, min_new, slot * cols + t]).astype(np.int32))
+        lpo = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device) if self.logprobs else None
+        tok = ops.logits_process_argmax_rows(logits, self.vocab, self.hist, info[0], info[1], info[2], self.penalty, self.ngram, *self.bans,
+                                             *self.bad, logprob=lpo)
+        if self.hist is not None:
+            self.hist.view(-1).index_copy_(0, info[3].long(), tok.to(torch.int32))
+        return tok.cpu().numpy(), None if lpo is None else lpo.cpu().numpy()
+
+
+class BatchScheduler:
+    """Continuous batching of greedy requests over one KVCache of `slots` sequences (generate_batch).  Host code: it reaches the engine
+    through plan, kv_cache_bytes, free_device_bytes, new_kv_cache, prefill(..., cache=, slots=) and decode_step, and chooses tokens
+    through `picker` (default DevicePicker), so a fake engine and picker can drive it on the CPU.
+
+    Every request is planned once (spliced length, budget, EOS minimum).  Waiting requests enter free slots in input order; those admitted
+    together are prefilled together (one prefill, their images encoded together).  A group is admitted when `admit_free` slots are free,
+    when nothing is decoding, or when every waiting request fits.  Each decode step runs all slots: an idle slot is fed token 0 at
+    position 0 (its length is 0 before and after the step) and its logits are ignored.  A request finishes on an EOS token, its budget or a
+    stopping criterion (called as generate() calls it at B = 1: the request's tokens [1, t] and its processed scores [1, vocab]), and
+    frees its slot.  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t)."""
+
+    def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None):
+        if not _is_int(max_batch_size) or max_batch_size < 1:
+            raise ValueError(f"max_batch_size must be an int >= 1, got {max_batch_size!r}")
+        self.engine, self.reqs, self.cfg = engine, reqs, cfg
+        self.logprobs = bool(return_logprobs)
+        n = len(reqs)
+        self.spliced = [int(engine.plan(r.ids[None], None, None, r.images, r.sizes)["lens"][0]) for r in reqs]
+        self.budget = [cfg.budgets[i] if cfg.budgets is not None else new_token_budget(cfg, self.spliced[i]) for i in range(n)]
+        self.min_new = [min_new_length(cfg, self.spliced[i]) for i in range(n)]
+        self.runs = [i for i in range(n) if self.budget[i] > 0]
+        self.slots = min(int(max_batch_size), len(self.runs))
+        self.L_max = max([self.spliced[i] + self.budget[i] for i in self.runs], default=0)
+        self.max_budget = max([self.budget[i] for i in self.runs], default=0)
+        self.admit_free = max(1, min(ADMIT_FREE_SLOTS if admit_free is None else int(admit_free), self.slots))
+        self.picker = picker
+        self.events = []
+        self.tokens = [[] for _ in range(n)]
+        self.logps = [[] for _ in range(n)]
+
+    def run(self):
+        """Generate every request; returns {"req_<i>": GenerationOutput} in input order."""
+        if self.runs:
+            self._run()
+        return {f"req_{i}": GenerationOutput(request_id=f"req_{i}", prompt_ids=[int(v) for v in r.ids], generated_tokens=list(self.tokens[i]),
+                                             logprobs=list(self.logps[i]), error=None, status="finished")
+                for i, r in enumerate(self.reqs)}
+
+    def _run(self):
+        eng, S = self.engine, self.slots
+        need = eng.kv_cache_bytes(S, self.L_max)
+        free = eng.free_device_bytes()
+        if free is not None and need > free:
+            raise ValueError(f"generate_batch: the KV cache of {S} slots x {self.L_max} positions needs {need} bytes, but only {free} bytes "
+                             f"of device memory are free: lower max_batch_size or the token budgets")
+        if self.picker is None:
+            self.picker = DevicePicker(eng, self.cfg, S, self.max_budget, self.logprobs, any(self.min_new[i] > 0 for i in self.runs))
+        self.cache = eng.new_kv_cache(S, self.L_max)
+        self.owner = np.full(S, -1, dtype=np.int64)           # request in each slot, -1: idle
+        self.t = np.zeros(S, dtype=np.int64)                  # tokens the slot's request has generated
+        self.mn = np.zeros(S, dtype=np.int64)                 # its EOS minimum
+        self.pending = np.zeros(S, dtype=np.int64)            # its last token, fed to the next decode step
+        self.free = list(range(S))
+        waiting = list(self.runs)
+        while waiting or (self.owner >= 0).any():
+            while waiting and (len(self.free) >= self.admit_free or not (self.owner >= 0).any() or len(waiting) <= len(self.free)):
+                k = min(len(self.free), len(waiting))
+                group, waiting = waiting[:k], waiting[k:]
+                gslots, self.free = self.free[:k], self.free[k:]
+                self._admit(group, gslots)
+            if (self.owner >= 0).any():
+                self._decode()
+        del self.cache
+
+    def _admit(self, group, gslots):
+        eng = self.engine
+        self.events.append(("admit", tuple(group), tuple(gslots)))
+        for q, s in zip(group, gslots):
+            self.owner[s], self.t[s], self.mn[s] = q, 0, self.min_new[q]
+        # image requests first: in a batch the splice gives a text-only prompt a (dummy) image slot, which must not shift later images
+        order = sorted(range(len(group)), key=lambda j: not self.reqs[group[j]].images)
+        rq = [self.reqs[group[j]] for j in order]
+        rs = [gslots[j] for j in order]
+        T = max(r.ids.size for r in rq)
+        ids = np.zeros((len(rq), T), dtype=np.int64)
+        am = np.zeros((len(rq), T), dtype=bool)
+        for b, r in enumerate(rq):
+            ids[b, :r.ids.size], am[b, :r.ids.size] = r.ids, True
+        imgs = [im for r in rq for im in r.images]
+        sizes = [s for r in rq for s in (r.sizes or [])] if any(r.sizes is not None for r in rq) else None
+        _, logits = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs)
+        self._step(logits, rs)
+
+    def _decode(self):
+        idle = self.owner < 0
+        self.events.append(("decode", tuple(int(s) for s in np.flatnonzero(~idle))))
+        self.cache.lens[idle] = 0
+        logits = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending))
+        self.cache.lens[idle] = 0
+        self._step(logits, list(range(self.slots)))
+
+    def _step(self, logits, row_slots):
+        """Choose the tokens of logits' rows (row r belongs to slot row_slots[r]) and book them per request."""
+        cfg = self.cfg
+        sl = np.asarray(row_slots, dtype=np.int64)
+        tok, lps = self.picker(logits, sl, self.t[sl], self.mn[sl])
+        for r, s in enumerate(row_slots):
+            q = int(self.owner[s])
+            if q < 0:
+                continue
+            tk = int(tok[r])
+            self.tokens[q].append(tk)
+            if self.logprobs:
+                self.logps[q].append(float(lps[r]))
+            n = len(self.tokens[q])
+            done = tk in cfg.eos or n >= self.budget[q]
+            if cfg.stopping_criteria:
+                ids = torch.tensor([self.tokens[q]], dtype=torch.int64, device=self.engine.device)
+                for c in cfg.stopping_criteria:
+                    res = c(ids, logits[r:r + 1])
+                    res = res.detach().cpu().numpy() if torch.is_tensor(res) else np.asarray(res)
+                    done = done or bool(res.astype(bool).any())
+            if done:
+                self.events.append(("finish", q, int(s), n))
+                self.owner[s], self.t[s], self.mn[s] = -1, 0, 0
+                self.free = sorted(self.free + [int(s)])
+            else:
+                self.pending[s], self.t[s] = tk, n
+
+
+def generate_batch(engine, inputs, images, image_sizes, cfg, max_batch_size=32, return_logprobs=False):
+    """Continuous batching over many prompts (LlavaLlamaForCausalLM.generate_batch); cfg from parse_batch_kwargs.  Each request's
+    generated tokens are what generate() returns for it alone (B = 1, the same settings), up to rounding."""
+    return BatchScheduler(engine, batch_requests(inputs, images, image_sizes), cfg, max_batch_size, return_logprobs).run()

@@ -104,6 +104,9 @@ _SIGS = {
     "rv_argmax_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p],
     "rv_logits_process_argmax_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _i64, _i32, _f32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p, _i32,
                                      _c_void_p, _c_void_p],
+    "rv_logits_process_argmax_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _f32,
+                                          _i32, _c_void_p, _i32, _c_void_p, _i32, _c_void_p, _i32, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                          _c_void_p, _c_void_p],
     "rv_lora_merge_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
 }
 

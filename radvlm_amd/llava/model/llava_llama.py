@@ -286,6 +286,24 @@ class LlavaLlamaForCausalLM:
         imgs = None if images is None else (list(images) if not torch.is_tensor(images) else [im for im in images])
         return greedy_generate(self.engine, inputs, cfg.attention_mask, imgs, image_sizes, cfg)
 
+    @torch.no_grad()
+    def generate_batch(self, inputs, images=None, image_sizes=None, max_batch_size=32, return_logprobs=False, **kwargs):
+        """Continuous batching over many independent prompts (transformers 5.x `generate_batch`), greedy only.
+        inputs: a list of N unpadded 1-D prompts (token ids; IMAGE_TOKEN_INDEX where an image goes).  images / image_sizes: None or a list
+        of N entries, each None (text only), one tensor or a list of tensors (the request's images in image-token order) / their sizes.
+        max_batch_size: requests decoded together (KV-cache slots).  Keywords: generate()'s greedy settings, applied per request
+        (max_new_tokens may be a list of N budgets; pad_token_id is accepted, nothing is padded); attention_mask, past_key_values,
+        position_ids, output_scores, output_logits and return_dict_in_generate raise TypeError; sampling, beam search, streamers,
+        inputs_embeds and LoRA models raise NotImplementedError as in generate().
+        Returns {"req_0": GenerationOutput, ...} in input order: .generated_tokens are what generate() returns for the request alone,
+        ending at its EOS token or where a stopping criterion returned True; .logprobs (return_logprobs) the log-softmax of each step's
+        processed scores at the emitted token.  The training state is not touched."""
+        from ...generation import generate_batch, parse_batch_kwargs
+        inputs = list(inputs)
+        cfg = parse_batch_kwargs(kwargs, len(inputs), lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
+                                 config_pad=getattr(self.config, "pad_token_id", None))
+        return generate_batch(self.engine, inputs, images, image_sizes, cfg, max_batch_size=max_batch_size, return_logprobs=return_logprobs)
+
     def save_config(self, out_dir):
         """config.json in HF's key vocabulary (what model.config.save_pretrained leaves next to the weights), plus the tower
         geometry under 'mm_vision_geometry' so that the directory is loadable as --model_name_or_path on its own."""

@@ -664,6 +664,40 @@ def logits_process_argmax(x, n, hist, t, rep_penalty=1.0, ngram=0, ban=None, bad
     return out
 
 
+def logits_process_argmax_rows(x, n, hist, slot, t, min_new, rep_penalty=1.0, ngram=0, ban_always=None, ban_begin=None, ban_eos=None,
+                               bad_tok=None, bad_off=None, out=None, logprob=None):
+    """logits_process_argmax for rows at different steps (rv_logits_process_argmax_rows_f32): row r is at step t[r] with EOS minimum
+    min_new[r] and reads its history from hist[slot[r], :t[r]] (slot, t, min_new: int32 [rows]; hist: int32 [slots, cols] or None).
+    ban_always on every row, ban_begin where t[r] == 0, ban_eos where t[r] < min_new[r].  Processes x[:, :n] IN PLACE and returns the
+    int64 argmax of each processed row; with `logprob` (fp32 [rows]) also writes the log-softmax of the processed row at that token."""
+    _chk(x, torch.float32)
+    rows = x.shape[0]
+    assert x.dim() == 2 and x.stride(1) == 1 and 0 < n <= min(x.shape[1], LOGITS_PROCESS_MAX_N)
+    for a in (slot, t, min_new):
+        _chk(a, torch.int32)
+        assert a.dim() == 1 and a.numel() == rows and a.stride(0) == 1
+    hist_rows = hist_cols = ld_hist = 0
+    if hist is not None:
+        _chk(hist, torch.int32)
+        assert hist.dim() == 2 and hist.stride(1) == 1
+        hist_rows, hist_cols, ld_hist = hist.shape[0], hist.shape[1], hist.stride(0)
+    for a in (ban_always, ban_begin, ban_eos, bad_tok, bad_off):
+        if a is not None:
+            _chk(a, torch.int32)
+            assert a.is_contiguous()
+    n_bad = 0 if bad_off is None else bad_off.numel() - 1
+    assert n_bad <= 0 or bad_tok is not None
+    if logprob is not None:
+        _chk(logprob, torch.float32)
+        assert logprob.numel() == rows and logprob.is_contiguous()
+    out = torch.empty(rows, dtype=torch.int64, device=x.device) if out is None else out
+    cnt = lambda a: 0 if a is None else a.numel()
+    lib.call("rv_logits_process_argmax_rows_f32", x, x.stride(0), rows, int(n), hist, ld_hist, hist_rows, hist_cols, slot, t, min_new,
+             float(rep_penalty), int(ngram), ban_always, cnt(ban_always), ban_begin, cnt(ban_begin), ban_eos, cnt(ban_eos), bad_tok, bad_off,
+             max(n_bad, 0), out, logprob)
+    return out
+
+
 def lora_merge(w, A, B, scale):
     """In place: w[N,K] <- bf16(w + scale * B[N,r] @ A[r,K]) (rv_lora_merge_bf16: fp32 sum in a fixed order, one rounding).  w may be a
     row slice of a fused store (any row stride); r <= 256.  Returns w."""

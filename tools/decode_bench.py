@@ -10,6 +10,15 @@
   python tools/decode_bench.py --processors [--geos ..] [--batches 1,32] [--out FILE]
         # plain greedy argmax vs the logits processors (repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=new/2 with an EOS)
         # through rv_logits_process_argmax_f32, interleaved (plain, processors, plain, ...) on one engine
+  python tools/decode_bench.py --batch-eval [--geos ..] [--requests 256] [--reps 3] [--out FILE]
+        # an evaluation split: N requests of --prompt tokens, EOS disabled, budgets mixed (portable_rng in [32, 512]) or equal (256);
+        # (a) generate_batch(max_batch_size=32), (b) static groups of 32 through generate() (a per-row criterion ends each row at its
+        # budget), (c) generate() at B = 1 on the first 16 requests; interleaved, medians; useful tokens / s and the prefill share of
+        # wall time; then the admission-threshold sweep (1, 4, 8, 16 free slots) and rv_logits_process_argmax_rows_f32 vs
+        # rv_logits_process_argmax_f32 at 32 rows x vocab
+  python tools/decode_bench.py --batch-kernel-ab [--geos ..]  # the kernel A/B of --batch-eval alone
+  python tools/decode_bench.py --batch-trace [--geos ..]     # generate_batch with processors + logprobs, then generate() B = 32 with
+        # the same processors: the workload of `rocprofv3 --kernel-trace --stats` for the two kernels side by side
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -247,6 +256,165 @@ def continue_case(geo, B, reps=5, turn1_new=64, follow=40, new=64, warm=8):
                 extend_kv_floor_bytes_per_layer=int(lens.sum() * 2 * eng.kvd * 2), kernel_src=_src_hash())
 
 
+class _PrefillClock:
+    """Wall time spent in engine.prefill (synchronised around each call; the schedulers synchronise every step anyway)."""
+
+    def __init__(self, eng):
+        self.eng, self.ms, self.calls = eng, 0.0, 0
+        self._pf = eng.prefill
+
+        def pf(*a, **k):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = self._pf(*a, **k)
+            torch.cuda.synchronize()
+            self.ms += (time.perf_counter() - t0) * 1e3
+            self.calls += 1
+            return r
+
+        eng.prefill = pf
+
+    def reset(self):
+        self.ms, self.calls = 0.0, 0
+
+    def close(self):
+        del self.eng.prefill
+
+
+def _eval_requests(eng, n, prompt, workload):
+    from radvlm_amd import portable_rng
+    ids = np.random.default_rng(0).integers(0, eng.vocab, (n, prompt))
+    if workload == "mixed":
+        budgets = portable_rng.integers(0, portable_rng.name_tag("batch_eval_budgets"), (n,), 32, 513).tolist()
+    else:
+        budgets = [256] * n
+    return [ids[i] for i in range(n)], [int(b) for b in budgets]
+
+
+def _arm(eng, clock, arm, prompts, budgets, admit=None):
+    """One timed run of an arm -> (wall ms, useful tokens, prefill ms, prefills)."""
+    from radvlm_amd.generation import BatchScheduler, batch_requests, greedy_generate, parse_batch_kwargs, parse_generate_kwargs
+    clock.reset()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if arm == "a":
+        cfg = parse_batch_kwargs(dict(max_new_tokens=budgets, eos_token_id=None), len(prompts))
+        out = BatchScheduler(eng, batch_requests(prompts), cfg, 32, admit_free=admit).run()
+        useful = sum(len(o.generated_tokens) for o in out.values())
+    elif arm == "b":                        # static groups of 32 through generate(), each to its group's largest budget
+        useful = 0
+        for g0 in range(0, len(prompts), 32):
+            bud = budgets[g0:g0 + 32]
+            crit = lambda ids, s, bud=bud: torch.tensor([ids.shape[1] >= b for b in bud])
+            cfg = parse_generate_kwargs(dict(max_new_tokens=max(bud), eos_token_id=None, stopping_criteria=[crit]))
+            seq = greedy_generate(eng, np.stack(prompts[g0:g0 + 32]), None, None, None, cfg)
+            useful += sum(min(b, seq.shape[1]) for b in bud)
+    else:                                   # generate() at B = 1 on the first 16 requests
+        useful = 0
+        for p, b in zip(prompts[:16], budgets[:16]):
+            seq = greedy_generate(eng, p[None], None, None, None, parse_generate_kwargs(dict(max_new_tokens=b, eos_token_id=None)))
+            useful += seq.shape[1]
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, useful, clock.ms, clock.calls
+
+
+def _kernel_ab(n, rows=32, t=64, reps=50):
+    """rv_logits_process_argmax_rows_f32 (without / with logprobs) vs rv_logits_process_argmax_f32 at `rows` x n (the vocabulary), every
+    row at step t, the processors of --processors; interleaved, device time per launch (median µs)."""
+    from radvlm_amd.generation import LogitsProcessors, parse_generate_kwargs
+    cfg = parse_generate_kwargs(dict(repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=2 * t, eos_token_id=2))
+    lp = LogitsProcessors(cfg, n)
+    rng = np.random.default_rng(1)
+    x0 = torch.from_numpy((rng.standard_normal((rows, n)) * 4).astype(np.float32)).cuda()
+    hist = torch.from_numpy(rng.integers(0, n, (rows, 2 * t)).astype(np.int32)).cuda()
+    info = torch.from_numpy(np.stack([np.arange(rows), np.full(rows, t), np.full(rows, lp.min_new)]).astype(np.int32)).cuda()
+    i32 = lambda ids: torch.tensor(ids, dtype=torch.int32, device="cuda") if ids else None
+    bans = (i32(sorted(set(lp.suppress) | set(lp.one))), i32(lp.begin), i32(lp.eos))
+    lpo = torch.empty(rows, dtype=torch.float32, device="cuda")
+    x = x0.clone()
+    fns = {"uniform": lambda: ops.logits_process_argmax(x, n, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, x.device)),
+           "rows": lambda: ops.logits_process_argmax_rows(x, n, hist, info[0], info[1], info[2], lp.penalty, lp.ngram, *bans),
+           "rows_logprob": lambda: ops.logits_process_argmax_rows(x, n, hist, info[0], info[1], info[2], lp.penalty, lp.ngram, *bans,
+                                                                  logprob=lpo)}
+    ts = {k: [] for k in fns}
+    for f in fns.values():
+        f()
+    for _ in range(reps):
+        for k, f in fns.items():
+            x.copy_(x0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            ts[k].append(e0.elapsed_time(e1) * 1e3)
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    return dict(rows=rows, vocab=n, t=t, uniform_us=round(med["uniform"], 2), rows_us=round(med["rows"], 2),
+                rows_logprob_us=round(med["rows_logprob"], 2), ratio_rows=round(med["rows"] / med["uniform"], 3),
+                ratio_rows_logprob=round(med["rows_logprob"] / med["uniform"], 3), reps=reps)
+
+
+def batch_eval(geo, n=256, prompt=704, reps=3, sweep=(1, 4, 8, 16)):
+    """--batch-eval: N requests of `prompt` tokens, EOS disabled, budgets mixed (portable_rng in [32, 512]) or equal (256); arms (a)
+    generate_batch(max_batch_size=32), (b) static groups of 32 through generate(), (c) generate() at B = 1 on the first 16 requests;
+    interleaved, `reps` reps, medians.  Then the admission-threshold sweep on mixed (one run each) and the kernel A/B."""
+    from radvlm_amd.generation import ADMIT_FREE_SLOTS
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    clock = _PrefillClock(eng)
+    recs = []
+    work = {w: _eval_requests(eng, n, prompt, w) for w in ("mixed", "equal")}
+    _arm(eng, clock, "a", work["equal"][0][:8], [8] * 8)            # warm-up of both paths
+    _arm(eng, clock, "b", work["equal"][0][:8], [8] * 8)
+    for w, (prompts, budgets) in work.items():
+        runs = {k: [] for k in "abc"}
+        for _ in range(reps):
+            for arm in "abc":
+                runs[arm].append(_arm(eng, clock, arm, prompts, budgets))
+                print(f"# {geo} {w} arm {arm}: {runs[arm][-1][0] / 1e3:.2f} s", file=sys.stderr, flush=True)
+        rec = dict(geo=geo, mode="generate_batch", workload=w, requests=n, prompt=prompt, budget_sum=int(sum(budgets)),
+                   budget_mean=round(float(np.mean(budgets)), 1), budget_max=int(max(budgets)), max_batch_size=32,
+                   admit_free_slots=ADMIT_FREE_SLOTS, reps=reps)
+        for arm, rs in runs.items():
+            wall = [r[0] for r in rs]
+            i = int(np.argsort(wall)[len(wall) // 2])
+            ms, useful, pms, pcalls = rs[i]
+            rec[arm] = dict(wall_s=round(ms / 1e3, 3), useful_tokens=useful, tokens_per_s=round(useful * 1e3 / ms, 1),
+                            prefill_share=round(pms / ms, 4), prefills=pcalls, wall_s_all=[round(r[0] / 1e3, 3) for r in rs])
+        rec["a_over_b"] = round(rec["a"]["tokens_per_s"] / rec["b"]["tokens_per_s"], 3)
+        rec["c_note"] = "arm c: generate() at B = 1 over the first 16 requests only, tokens/s as measured on those"
+        recs.append(rec)
+    prompts, budgets = work["mixed"]
+    sweep_rec = dict(geo=geo, mode="generate_batch_sweep", workload="mixed", requests=n, prompt=prompt, max_batch_size=32, runs=[])
+    for thr in sweep:
+        ms, useful, pms, pcalls = _arm(eng, clock, "a", prompts, budgets, admit=thr)
+        print(f"# {geo} sweep {thr}: {ms / 1e3:.2f} s", file=sys.stderr, flush=True)
+        sweep_rec["runs"].append(dict(admit_free_slots=thr, wall_s=round(ms / 1e3, 3), tokens_per_s=round(useful * 1e3 / ms, 1),
+                                      prefill_share=round(pms / ms, 4), prefills=pcalls))
+    recs.append(sweep_rec)
+    clock.close()
+    recs.append(dict(geo=geo, mode="generate_batch_kernel_ab", **_kernel_ab(eng.vocab)))
+    for r in recs:
+        r["kernel_src"] = _src_hash()
+    return recs
+
+
+def batch_trace(geo, n=48):
+    """--batch-trace (run under rocprofv3 --kernel-trace --stats): generate_batch with processors and logprobs (rows at different
+    steps: rv_logits_process_argmax_rows_f32 at 32 rows), then generate() at B = 32 with the same processors
+    (rv_logits_process_argmax_f32 at 32 rows) on the same engine and vocabulary."""
+    from radvlm_amd.generation import generate_batch, greedy_generate, parse_batch_kwargs, parse_generate_kwargs
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    prompts, _ = _eval_requests(eng, n, 704, "mixed")
+    budgets = np.random.default_rng(2).integers(16, 65, n).tolist()
+    proc = dict(repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=8, eos_token_id=2)
+    out = generate_batch(eng, prompts, None, None, parse_batch_kwargs(dict(max_new_tokens=budgets, **proc), n), max_batch_size=32,
+                         return_logprobs=True)
+    greedy_generate(eng, np.stack(prompts[:32]), None, None, None, parse_generate_kwargs(dict(max_new_tokens=64, **proc)))
+    torch.cuda.synchronize()
+    return [dict(geo=geo, mode="generate_batch_trace", requests=n, generated=sum(len(o.generated_tokens) for o in out.values()),
+                 kernel_src=_src_hash())]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--geos", default="llava15_7b,llava_ov_qwen2_7b")
@@ -256,12 +424,22 @@ def main():
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--processors", action="store_true")
     ap.add_argument("--continue", dest="cont", action="store_true")
+    ap.add_argument("--batch-eval", action="store_true")
+    ap.add_argument("--batch-trace", action="store_true")
+    ap.add_argument("--batch-kernel-ab", action="store_true")
+    ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.ab:
         recs = ab()
+    elif a.batch_eval:
+        recs = [r for g in a.geos.split(",") for r in batch_eval(g, n=a.requests, prompt=a.prompt, reps=min(a.reps, 3))]
+    elif a.batch_kernel_ab:
+        recs = [dict(geo=g, mode="generate_batch_kernel_ab", **_kernel_ab(GEOMETRIES[g]["lm"]["vocab"])) for g in a.geos.split(",")]
+    elif a.batch_trace:
+        recs = [r for g in a.geos.split(",") for r in batch_trace(g)]
     elif a.cont:
         batches = a.batches if a.batches != ap.get_default("batches") else "1,8"
         recs = [continue_case(g, b, reps=a.reps) for g in a.geos.split(",") for b in map(int, batches.split(","))]
