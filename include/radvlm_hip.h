@@ -329,6 +329,22 @@ int rv_gemv_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, void* Y
                  int64_t ldr, int M, int N, int K, int out_f32, void* workspace, int64_t ws_bytes, void* stream);
 /* Number of K slices rv_gemv_bf16 uses for an [N, K] weight (host function, no launch). */
 int rv_gemv_split(int N, int K);
+/* Weight-only int8 decoding (reference: load_pretrained_model(load_8bit=True), model/builder.py:27-31, bitsandbytes row-wise int8
+ * with lm_head left in 16 bits).  For a bf16 row w of K entries: s = max|w| / 127 (fp32 IEEE division; 1 for a zero row),
+ * q = clamp(rint(float(w) / s), -127, 127) (IEEE division, round half to even), W^ = bf16_rne(float(q) * s).  One pass over
+ * W[N, K] (rows of ldw elements; a row slice of the fused q|k|v or gate|up store is fine) writes W^ over W, s to scale[N] and q to
+ * packed[N][ldp] (int8; ldp = rv_w8_row_bytes(K) bytes).  The packed layout is private to this entry and rv_gemv_w8_bf16: 64 bytes
+ * per pair of 32-deep K steps, the 8 weights of steps 2j and 2j + 1 that one MFMA lane group reads side by side, zero padding past K.
+ * Quantising W^ again does not give W^ back: call it once.  Non-finite weights are outside the contract.  K % 8 == 0, ldw % 8 == 0. */
+int rv_quantize_rows_w8_bf16(void* W, int64_t ldw, void* packed, int64_t ldp, float* scale, int N, int K, void* stream);
+/* Bytes of one packed row for K input features (host function, no launch). */
+int64_t rv_w8_row_bytes(int K);
+/* rv_gemv_bf16 with the weight given as (packed, scale) of rv_quantize_rows_w8_bf16: the bf16 operand bf16_rne(float(q) * s) is rebuilt
+ * in registers, the K split, the k-to-lane assignment and the accumulation order are rv_gemv_bf16's, so Y is bit-identical to
+ * rv_gemv_bf16 on W^ for every M.  Half the weight bytes per call.  Same workspace rule. */
+int rv_gemv_w8_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp, const float* scale, void* Y, int64_t ldy,
+                    const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
+                    int64_t ws_bytes, void* stream);
 /* Decode attention (flash-decoding): for every sequence b and q head h, softmax(scale * q[b,h] K^T) V over the cached keys
  * [0, kv_len[b]) of kv head h / (H / Hkv), hd in {64, 128}, up to 8 q heads per kv head (GQA), fp32 softmax and accumulation.
  * cache: bf16 [B][L_max][ld_c] (sequence stride bs_c), K of kv head g at columns g*hd, V at v_off + g*hd.  q: [B, H*hd] rows (ld_q);

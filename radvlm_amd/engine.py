@@ -38,6 +38,7 @@ class LlavaEngine:
                  padding_side="right", force_grad_sync=False, recompute=False):
         self.geo = geo
         self.weights_version = 0              # bumped by every write to the weights (weights_changed): a GenerationCache of an older one is stale
+        self.w8 = None                        # per layer {name: (packed int8, fp32 scale)} after quantize_decoder_(); dropped by weights_changed
         assert recompute in (False, True, "auto")
         self.recompute = recompute            # activation recompute policy of the decoder layers (_recompute_layers)
         self.head_rows = "labeled"            # final norm + lm_head + cross entropy on the rows that carry a label ("all": every row)
@@ -258,6 +259,7 @@ class LlavaEngine:
         """Call after any in-place edit of the flat parameters (load_state_dict, optimizer step): drops the derived
         copies of tower weights (padded patch / attention projections) when the tower may have changed, and bumps weights_version."""
         self.weights_version += 1
+        self.w8 = None           # the int8 copies describe the weights they were made from: a changed engine is a plain bf16 engine again
         if tower:
             self._patch_w = None
             self._vis_pad = {}
@@ -828,12 +830,52 @@ class LlavaEngine:
     # GEMM's 256-row tiles amortise the weight stream over the rows better there).
     gemv_max_m = 32
     gemv_max_m_wide = 4          # weights with >= 65,536 rows
+    # On a quantised engine (quantize_decoder_) the skinny route reads the int8 copy; False forces the bf16 kernel on the same
+    # (dequantised) weights.  The two are bit-identical, so this switch changes time only: it is the A/B arm of tools/decode_bench.py --w8.
+    w8_decode = True
 
-    def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16):
+    def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16, w8=None):
         max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
         if x.shape[0] <= min(max_m, ops.GEMV_MAX_M):
+            if w8 is not None:
+                return ops.gemv_w8(x, w8[0], w8[1], w.shape[1], bias=bias, residual=residual, out_dtype=out_dtype)
             return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
         return ops.gemm_nt(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
+
+    def _layer_w8(self, i):
+        return self.w8[i] if (self.w8 is not None and self.w8_decode) else {}
+
+    @property
+    def is_quantized(self):
+        return self.w8 is not None
+
+    W8_MATRICES = ("qkv", "o", "gu", "down")
+
+    def quantize_decoder_(self):
+        """Weight-only int8 for decoding (the reference's load_8bit): every layer's fused q|k|v, o_proj, fused gate|up and down_proj are
+        quantised row-wise (s = max|row| / 127, q = clamp(rint(w / s), -127, 127)) and the bf16 weight is OVERWRITTEN with the
+        dequantised bf16(float(q) * s), which is the model's weight from then on: prefill, extend, forward and state_dict() read it
+        through the unchanged bf16 code, and decode steps read (q, s) through rv_gemv_w8_bf16, which rebuilds the same bits -- one
+        function, half the weight bytes per generated token.  lm_head, embeddings, norms, biases, projector and tower stay as they
+        are.  The int8 copies are kept beside the bf16 weights (about 1.5x the memory of these matrices).  A one-time act: a second
+        call raises (quantising the dequantised weight would round again), and any later write to the weights (load_state_dict,
+        optimizer_step, merge_lora_, resize_token_embeddings) drops the int8 copies.  When optimizer state exists, the fp32 master copy
+        of the quantised matrices is rewritten from the dequantised weights (as merge_lora_ does), so a later optimizer_step starts from
+        them instead of restoring the unquantised values.  Non-finite weights are outside the contract."""
+        self._check_generation()
+        if self.w8 is not None:
+            raise RuntimeError("quantize_decoder_(): the decoder is already quantised; a second pass would round the weights again")
+        w8 = []
+        for i in range(self.l["layers"]):
+            lv = self._layer_views(i)
+            w8.append({n: ops.quantize_rows_w8(lv[n]) for n in self.W8_MATRICES})
+        self.weights_changed(tower=False)
+        self.w8 = w8
+        if self.master is not None and self.base is None:
+            for i in range(self.l["layers"]):
+                for t, _, _ in LORA_TARGETS:
+                    off, n = self.lm.offsets[f"model.layers.{i}.{t}.weight"]
+                    self.master[off:off + n].copy_(ops.to_f32(self.lm.flat[off:off + n]))
 
     def _check_generation(self):
         if self.lora:
@@ -933,16 +975,16 @@ class LlavaEngine:
         cs = self.rope_table(cache.L_max)
         x = ops.gather_rows(tok.contiguous(), d, self.W("model.embed_tokens.weight"))
         for i in range(L):
-            lv = self._layer_views(i)
+            lv, q8 = self._layer_views(i), self._layer_w8(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"))
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), w8=q8.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
             ops.kv_append(qkv[:, d:], cache.layers[i], pos)
             attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
-            x_mid = self._decode_linear(attn, lv["o"], residual=x)
+            x_mid = self._decode_linear(attn, lv["o"], residual=x, w8=q8.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"]), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid)
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], w8=q8.get("gu")), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid, w8=q8.get("down"))
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
         cache.lens += 1
@@ -1001,17 +1043,17 @@ class LlavaEngine:
         cs = self.rope_table(L_max)
         x = ops.gather_rows(self._dev(src), d, self.W("model.embed_tokens.weight"), table)
         for i in range(L):
-            lv = self._layer_views(i)
+            lv, q8 = self._layer_views(i), self._layer_w8(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"))
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), w8=q8.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
             kv = cache.layers[i]
             kv.view(B * L_max, 2 * kvd).index_copy_(0, slots, qkv[:, d:])
             attn = ops.attn_extend(qkv[:, :d], kv, cu_d, r_d, H, Hkv, hd, kvd, int(n.max()))
-            x_mid = self._decode_linear(attn, lv["o"], residual=x)
+            x_mid = self._decode_linear(attn, lv["o"], residual=x, w8=q8.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"]), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid)
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], w8=q8.get("gu")), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid, w8=q8.get("down"))
         last = self._dev((cu_q[1:] - 1).astype(np.int32))
         hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)

@@ -96,6 +96,9 @@ _SIGS = {
     "rv_add_bf16": [_c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p],
     "rv_gemv_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _i32, _c_void_p, _i64,
                      _c_void_p],
+    "rv_quantize_rows_w8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p],
+    "rv_gemv_w8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _i32,
+                        _c_void_p, _i64, _c_void_p],
     "rv_attn_decode_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32,
                             _i32, _i32, _f32, _c_void_p],
     "rv_attn_extend_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
@@ -110,7 +113,8 @@ _SIGS = {
     "rv_lora_merge_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
 }
 
-EXPORTED_SYMBOLS = ["rv_version", "rv_gemm_select_kernel", "rv_gemm_set_cu_budget", "rv_attn_fwd_nat_pairs", "rv_gemv_split"] + sorted(_SIGS)
+EXPORTED_SYMBOLS = ["rv_version", "rv_gemm_select_kernel", "rv_gemm_set_cu_budget", "rv_attn_fwd_nat_pairs", "rv_gemv_split",
+                    "rv_w8_row_bytes"] + sorted(_SIGS)
 
 _lib = None
 
@@ -129,6 +133,8 @@ def load():
                                  "(or __graft_entry__.build()); there is no CPU fallback")
         lib = ctypes.CDLL(path)
         lib.rv_version.restype = ctypes.c_char_p
+        lib.rv_w8_row_bytes.argtypes = [_i32]
+        lib.rv_w8_row_bytes.restype = _i64
         for name, sig in _SIGS.items():
             fn = getattr(lib, name)
             fn.argtypes = sig

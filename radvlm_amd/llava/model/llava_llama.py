@@ -344,6 +344,19 @@ class LlavaLlamaForCausalLM:
             return
         save_file(cpu(self.engine.state_dict()), os.path.join(out_dir, "model.safetensors"))
 
+    def quantize_decoder_(self):
+        """The reference's load_8bit for decoding: row-wise int8 copies of every decoder layer's four matrices, the bf16 weights replaced by
+        their dequantised values (LlavaEngine.quantize_decoder_; lm_head, embeddings, norms, projector and tower untouched).  generate(),
+        generate_batch() and GenerationCache work unchanged and read half the weight bytes per generated token.  state_dict() and
+        save_pretrained() then hold the dequantised bf16 weights.  A one-time act: a second call raises; models with unmerged LoRA
+        adapters are refused (merge_and_unload() first).  Returns self."""
+        self.engine.quantize_decoder_()
+        return self
+
+    @property
+    def is_quantized(self):
+        return self.engine.is_quantized
+
     def merge_and_unload(self):
         """peft's merge_and_unload: W += (alpha / r) B A for every adapted linear (rv_lora_merge_bf16), the adapters are dropped and the
         model is a plain one (config.lora cleared; save_pretrained then writes the full model.safetensors).  The engine keeps the

@@ -579,6 +579,52 @@ def gemv(x, w, out=None, bias=None, residual=None, out_dtype=BF16, workspace=Non
     return out
 
 
+def w8_row_bytes(K):
+    """Bytes of one packed int8 row for K input features: 64 per pair of 32-deep K steps (a function of K alone, no library call)."""
+    return ((int(K) + 31) // 32 + 1) // 2 * 64
+
+
+def quantize_rows_w8(w):
+    """Row-wise int8 quantisation of a bf16 [N, K] weight IN PLACE (rv_quantize_rows_w8_bf16): s = max|row| / 127 (1 for a zero row),
+    q = clamp(rint(w / s), -127, 127), w <- bf16(float(q) * s).  w may be a row-major view with a row stride (the fused q|k|v and
+    gate|up views).  Returns (packed int8 [N, w8_row_bytes(K)] in gemv_w8's private layout, scale fp32 [N]).  Quantising the result
+    again rounds again: call it once per weight.  Non-finite weights are outside the contract."""
+    _chk(w)
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    assert K % 8 == 0 and w.stride(0) % 8 == 0
+    packed = torch.empty(N, w8_row_bytes(K), dtype=torch.int8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    lib.call("rv_quantize_rows_w8_bf16", w, w.stride(0), packed, packed.stride(0), scale, N, K)
+    return packed, scale
+
+
+def gemv_w8(x, packed, scale, K, out=None, bias=None, residual=None, out_dtype=BF16, workspace=None):
+    """gemv() with the weight given as quantize_rows_w8's (packed, scale) of a [N, K] weight: rv_gemv_w8_bf16, half the weight bytes,
+    bit-identical to gemv(x, w) on the dequantised weight quantize_rows_w8 left in place."""
+    _chk(x), _chk(packed, torch.int8), _chk(scale, torch.float32)
+    M = x.shape[0]
+    N = packed.shape[0]
+    assert 1 <= M <= GEMV_MAX_M and x.shape[1] == K and x.stride(1) == 1
+    assert packed.is_contiguous() and packed.shape[1] == w8_row_bytes(K) and scale.numel() == N and scale.is_contiguous()
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype in (BF16, torch.float32)
+    if bias is not None:
+        _chk(bias)
+        assert bias.numel() == N and bias.is_contiguous()
+    ldr = 0
+    if residual is not None:
+        _chk(residual)
+        assert residual.shape == (M, N) and residual.stride(1) == 1
+        ldr = residual.stride(0)
+    if workspace is None:
+        workspace = default_workspace(x.device)
+    lib.call("rv_gemv_w8_bf16", x, x.stride(0), packed, packed.stride(0), scale, out, out.stride(0), bias, residual, ldr, M, N, K,
+             int(out.dtype == torch.float32), workspace, workspace.numel() * workspace.element_size())
+    return out
+
+
 def attn_decode(q, cache, kv_len, H, Hkv, hd, v_off, out=None, chunk=128, scale=None):
     """One query row per (sequence, q head) against the cached keys [0, kv_len[b]): q [B, H*hd] rows; cache bf16 [B, L_max, width]
     with K of kv head g at columns g*hd and V at v_off + g*hd; kv_len int32 [B] (device).  Returns bf16 [B, H*hd]."""

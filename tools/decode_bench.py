@@ -19,6 +19,15 @@
   python tools/decode_bench.py --batch-kernel-ab [--geos ..]  # the kernel A/B of --batch-eval alone
   python tools/decode_bench.py --batch-trace [--geos ..]     # generate_batch with processors + logprobs, then generate() B = 32 with
         # the same processors: the workload of `rocprofv3 --kernel-trace --stats` for the two kernels side by side
+  python tools/decode_bench.py --w8 [--geos ..] [--batches 1,8,32] [--out FILE]
+        # int8 decoder weights: one engine per geometry, quantize_decoder_(), then the decode loop with engine.w8_decode False / True
+        # interleaved three times (bf16 kernel on the dequantised weights vs rv_gemv_w8_bf16: same output bits); medians per arm, the
+        # bf16 arm's spread, bytes per step and the implied HBM rate; plus how far the quantised model's logits and greedy tokens are
+        # from the unquantised model's on the same prompt (a property of the scheme, reported, never gated)
+  python tools/decode_bench.py --w8-shapes [--out FILE]   # per-shape kernel A/B: rv_gemv_bf16 on the dequantised weight vs
+        # rv_gemv_w8_bf16, the 7B Llama and Qwen2-7B decoder shapes, M = 1, 4, 8, 16, 32, cold weights, interleaved
+  python tools/decode_bench.py --w8-quality   # the toy goldens' models: logits distance and greedy-token agreement, int8 vs unquantised
+  python tools/decode_bench.py --w8-trace [--geos llava15_7b]   # a B = 1 int8 decode run: the workload of `rocprofv3 --kernel-trace --stats`
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -117,6 +126,133 @@ def ab(reps=20):
                                 gemv_TBps=round(2 * N * K / (g * 1e-6) / 1e12, 3), split=ops.gemv_split(N, K)))
             del w, flush
     return out
+
+
+def w8_shapes(reps=20):
+    """rv_gemv_bf16 on the dequantised weight vs rv_gemv_w8_bf16 per decoder shape, interleaved, cold weights (as ab())."""
+    out = []
+    for geo in ("llava15_7b", "llava_ov_qwen2_7b"):
+        l = GEOMETRIES[geo]["lm"]
+        d, F = l["d"], l["ffn"]
+        kvd = l.get("kv_heads", l["heads"]) * (d // l["heads"])
+        for name, N, K in [("qkv", d + 2 * kvd, d), ("o", d, d), ("gu", 2 * F, d), ("down", d, F)]:
+            w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02
+            packed, scale = ops.quantize_rows_w8(w)
+            flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
+            for M in (1, 4, 8, 16, 32):
+                x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+                fns = {"bf16": lambda: ops.gemv(x, w), "w8": lambda: ops.gemv_w8(x, packed, scale, K)}
+                assert torch.equal(fns["bf16"](), fns["w8"]())
+                ts = {k: [] for k in fns}
+                for _ in range(reps):
+                    for k, f in fns.items():
+                        flush.zero_()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        f()
+                        e1.record()
+                        e1.synchronize()
+                        ts[k].append(e0.elapsed_time(e1) * 1e3)
+                b, q = float(np.median(ts["bf16"])), float(np.median(ts["w8"]))
+                out.append(dict(mode="w8", geo=geo, shape=name, N=N, K=K, M=M, bf16_us=round(b, 2), w8_us=round(q, 2), speedup=round(b / q, 3),
+                                bf16_TBps=round(2 * N * K / (b * 1e-6) / 1e12, 3), w8_TBps=round((N * packed.shape[1] + 4 * N) / (q * 1e-6) / 1e12, 3),
+                                split=ops.gemv_split(N, K), layout="16-byte interleaved step pairs",
+                                build=os.path.basename(os.environ.get("RADVLM_HIP_LIB", "default")), kernel_src=_src_hash()))
+            del w, packed, flush
+    return out
+
+
+def w8_weight_bytes(eng):
+    """Weight bytes a decode step reads on the int8 route: packed rows + scales of the four decoder matrices, bf16 lm_head."""
+    l = eng.l
+    q = sum(p.numel() + 4 * s.numel() for layer in eng.w8 for p, s in layer.values())
+    return int(q + 2 * l["vocab"] * l["d"])
+
+
+def w8_ab(geo, batches, prompt, new, reps=3):
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    rng = np.random.default_rng(0)
+    ids1 = rng.integers(0, eng.vocab, (1, prompt))
+
+    def greedy(n):
+        cache, logits = eng.prefill(ids1, None, None, None, max_new_tokens=n)
+        first = logits[0].clone()
+        toks = [ops.argmax_rows(logits, eng.vocab)]
+        for _ in range(n - 1):
+            toks.append(ops.argmax_rows(eng.decode_step(cache, toks[-1].to(torch.int32)), eng.vocab))
+        return first, torch.cat(toks).cpu().numpy()
+
+    lg0, tk0 = greedy(64)                                             # the unquantised model on the prompt of the timed runs
+    eng.quantize_decoder_()
+    lg1, tk1 = greedy(64)
+    quality = dict(logits_rel_l2=round(float((lg1 - lg0).norm() / lg0.norm()), 5), greedy_tokens_agree=round(float((tk0 == tk1).mean()), 4),
+                   first_disagreement=int(np.argmax(tk0 != tk1)) if (tk0 != tk1).any() else None, tokens=64)
+    recs = []
+    for B in batches:
+        ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+        ts = {False: [], True: []}
+        for flag in (False, True):                                     # warm-up: one untimed repetition of both routes
+            eng.w8_decode = flag
+            _decode_loop(eng, ids, new)
+        for _ in range(reps):
+            for flag in (False, True):
+                eng.w8_decode = flag
+                ts[flag].append(float(np.median(_decode_loop(eng, ids, new))))
+        eng.w8_decode = True
+        b, q = float(np.median(ts[False])), float(np.median(ts[True]))
+        kv = int(2 * eng.l["layers"] * 2 * eng.kvd * (prompt + new // 2) * B)
+        wb, w8b = weight_bytes(eng), w8_weight_bytes(eng)
+        recs.append(dict(geo=geo, mode="w8_ab", B=B, prompt=prompt, new_tokens=new, reps=reps, bf16_ms_per_step=round(b, 3),
+                         w8_ms_per_step=round(q, 3), bf16_ms_all=[round(x, 3) for x in ts[False]], w8_ms_all=[round(x, 3) for x in ts[True]],
+                         bf16_spread_ms=round(max(ts[False]) - min(ts[False]), 3), delta_ms=round(b - q, 3), speedup=round(b / q, 3),
+                         w8_faster_by_more_than_bf16_spread=bool(b - q > max(ts[False]) - min(ts[False])),
+                         bf16_tokens_per_s=round(B * 1e3 / b, 1), w8_tokens_per_s=round(B * 1e3 / q, 1), bf16_weight_bytes=wb,
+                         w8_weight_bytes=w8b, weight_bytes_ratio=round(w8b / wb, 3), kv_bytes_per_step=kv,
+                         bf16_implied_TBps=round((wb + kv) / (b * 1e-3) / 1e12, 3), w8_implied_TBps=round((w8b + kv) / (q * 1e-3) / 1e12, 3),
+                         quality_vs_unquantised=quality, kernel_src=_src_hash()))
+    return recs
+
+
+def w8_quality_toy(new=32):
+    """How far int8 decoder weights move the toy goldens' models (portable-init weights, the golden prompts with their images): relative
+    L2 of the last prompt row's logits and the share of greedy tokens that agree with the unquantised model.  Reported, never gated."""
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    recs = []
+    for geo, golden in (("toy", "toy_e2e"), ("toy_qwen", "toy_qwen_e2e")):
+        g = np.load(os.path.join(root, golden + ".npz"))
+        n = len([k for k in g.files if k.startswith("image") and k[5:].isdigit()])
+        images = [torch.from_numpy(g[f"image{i}"]) for i in range(n)]
+        sizes = [tuple(x) for x in g["image_sizes"].tolist()]
+        eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="portable", seed=0)
+
+        def run():
+            out = []
+            for b in range(n):
+                p = g["input_ids"][b][g["attention_mask"][b].astype(bool)].astype(np.int64)
+                cache, logits = eng.prefill(p[None], None, [images[b]], [sizes[b]], max_new_tokens=new)
+                toks = [ops.argmax_rows(logits, eng.vocab)]
+                for _ in range(new - 1):
+                    toks.append(ops.argmax_rows(eng.decode_step(cache, toks[-1].to(torch.int32)), eng.vocab))
+                out.append((logits[0].clone(), torch.cat(toks).cpu().numpy()))
+            return out
+
+        a = run()
+        eng.quantize_decoder_()
+        b = run()
+        recs.append(dict(geo=geo, mode="w8_quality_toy", prompts=n, new_tokens=new,
+                         logits_rel_l2=[round(float((y[0] - x[0]).norm() / x[0].norm()), 5) for x, y in zip(a, b)],
+                         greedy_tokens_agree=[round(float((x[1] == y[1]).mean()), 4) for x, y in zip(a, b)]))
+    return recs
+
+
+def w8_trace(geo, prompt, new):
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    eng.quantize_decoder_()
+    ids = np.random.default_rng(0).integers(0, eng.vocab, (1, prompt))
+    ts = _decode_loop(eng, ids, new)
+    torch.cuda.synchronize()
+    return [dict(geo=geo, mode="w8_trace", B=1, prompt=prompt, new_tokens=new, w8_ms_per_step_under_trace=round(float(np.median(ts)), 3),
+                 kernel_src=_src_hash())]
 
 
 def _decode_loop(eng, ids, new, lp=None, warm=8):
@@ -427,6 +563,10 @@ def main():
     ap.add_argument("--batch-eval", action="store_true")
     ap.add_argument("--batch-trace", action="store_true")
     ap.add_argument("--batch-kernel-ab", action="store_true")
+    ap.add_argument("--w8", action="store_true")
+    ap.add_argument("--w8-shapes", action="store_true")
+    ap.add_argument("--w8-trace", action="store_true")
+    ap.add_argument("--w8-quality", action="store_true")
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -434,6 +574,14 @@ def main():
     torch.cuda.set_device(0)
     if a.ab:
         recs = ab()
+    elif a.w8_shapes:
+        recs = w8_shapes()
+    elif a.w8:
+        recs = [r for g in a.geos.split(",") for r in w8_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new)]
+    elif a.w8_quality:
+        recs = w8_quality_toy()
+    elif a.w8_trace:
+        recs = [r for g in a.geos.split(",") for r in w8_trace(g, a.prompt, a.new)]
     elif a.batch_eval:
         recs = [r for g in a.geos.split(",") for r in batch_eval(g, n=a.requests, prompt=a.prompt, reps=min(a.reps, 3))]
     elif a.batch_kernel_ab:
