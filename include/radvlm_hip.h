@@ -403,6 +403,36 @@ int rv_logits_process_argmax_rows_f32(float* x, int64_t ld, int rows, int n, con
                                       const int32_t* ban_eos, int n_eos, const int32_t* bad_tok, const int32_t* bad_off, int n_bad,
                                       int64_t* out, float* logprob, void* stream);
 
+/* Seeded sampling (generate(do_sample=True, seed=...); HF: GenerationMixin._sample with do_sample=True, the warpers of
+ * generation/logits_process.py in HF's order, then softmax and one draw).  Per fp32 row r (first n columns, n <= 262144; the greedy
+ * processors above run first when one is active), with x the row as it comes in:
+ *   TemperatureLogitsWarper  s_i = x_i / temperature (IEEE fp32 division; temperature > 0);
+ *   TopKLogitsWarper         top_k > 0: v = the k'-th largest s, k' = min(top_k, n); s_i < v is removed, every tie with v stays (0: off);
+ *   TopPLogitsWarper         top_p < 1: p = softmax(s) over what remains; i is removed iff sum{p_j : s_j <= s_i} <= 1 - top_p.  The
+ *                            maximum always stays.  Among EQUAL scores at the cut HF's sort order is unspecified: here all of them stay;
+ *   MinPLogitsWarper         min_p > 0: i is removed iff p_i < min_p * max_j p_j, evaluated as fl(s_i - max s) < fl(log(min_p));
+ *   draw                     q = softmax over the kept set, u = (b + 0.5) * 2^-24 with b the top 24 bits of splitmix64(t[r] *
+ *                            0xD1342543DE82EF95 + splitmix64(seed[r] * 1000003)) (portable_rng._stream(seed, 0, t + 1)[t] >> 40; the
+ *                            kernel holds u as the integer 2 b + 1 over 2^25, never as a float); out[r] = the lowest id i with sum{q_j : j <= i, j kept} > u, the sum in TOKEN-ID order.
+ * seed (uint64) and t (int32, the row's own step) are device arrays of `rows` entries.  write_scores != 0: the row is overwritten with
+ * the warped scores, s_i (bit-equal to the fp32 quotient) where kept and -inf where removed (HF's output_scores under sampling);
+ * write_scores == 0: the row is only read.  logprob (fp32 [rows] or NULL): log q[out[r]].  A row that holds a NaN or +inf, or no finite
+ * entry, cannot be sampled: out[r] = -1, logprob[r] = NaN, and the row is left as it is.
+ * A fixed number of workgroups (8) share a row, each with a fixed run of its tiles; every sweep is a launch, and the partial maxima and
+ * integer histograms of one launch are merged in a fixed order by the next.  No sort, no float atomics, no global atomics: probabilities enter every sum as 64-bit fixed point, rne(exp(s_i - max s) * 2^40),
+ * added as integers, so the token, the written scores and logprob of a row are the same bits on every launch, for every `rows` and
+ * whatever the other rows hold.  depth = 1: the one fp32 addition a term of the CDF sum passes through is the fma that applies the
+ * rounding residual of s_i - max s to its exponential; the sum itself is integer.  A normalised partial sum is within
+ * (depth + 4) * 2^-23 of exact arithmetic on the fp32 s (csrc/sample.hip derives it).  Two sweeps of the row with every warper off,
+ * four more for top-k, four more for top-p; one launch per sweep and one for the draw.  ws: device scratch of ws_bytes >=
+ * rv_sample_ws_bytes(rows) bytes, 8-byte aligned, contents arbitrary; it must not be shared by launches that can overlap. */
+int rv_sample_rows_f32(float* x, int64_t ld, int rows, int n, const uint64_t* seed, const int32_t* t, float temperature, int top_k,
+                       float top_p, float min_p, int write_scores, int64_t* out, float* logprob, void* ws, int64_t ws_bytes, void* stream);
+/* Host function: the bytes of scratch rv_sample_rows_f32 needs for `rows` rows. */
+int64_t rv_sample_ws_bytes(int rows);
+/* Host function: the 24 bits b of the draw above for (seed, t), the same code the kernel runs. */
+uint32_t rv_sample_uniform24(uint64_t seed, int32_t t);
+
 /* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
  * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any
  * grid and any placement of W.  W: bf16 rows of ldw elements (a row slice of a fused q|k|v or gate|up store is fine), 16-byte aligned,

@@ -1,4 +1,4 @@
-"""Greedy generation over the engine's KV-cached decode (LlavaLlamaForCausalLM.generate).
+"""Greedy and seeded-sampling generation over the engine's KV-cached decode (LlavaLlamaForCausalLM.generate).
 
 HF semantics followed (HF: = transformers as pinned by the reference): GenerationMixin.generate -> _sample with do_sample=False
 (HF:generation/utils.py), for a decoder-only model called with inputs_embeds, which is how the reference's generate() calls it after
@@ -7,19 +7,25 @@ if it were alone (left-padded HF generation: the row's own positions 0 .. len - 
 (HF:generation/logits_process.py); with inputs_embeds HF's input_ids start empty, so they see the generated tokens only, never the
 prompt.  The bookkeeping below is host code without a device, so it is tested on its own (tests/test_generate_host.py,
 tests/test_logits_process_host.py).
+
+Sampling (do_sample=True together with seed=): after the processors HF runs the warpers temperature -> top-k -> top-p -> min-p, takes the
+softmax and draws one token (HF: _sample with do_sample=True).  Here the draw is counter-based: row or request i at its own step t uses
+u(seed_i, t) (sample_uniform below), so a result is reproducible by construction and does not depend on batching or scheduling.  It is NOT
+torch's global generator stream, which is why a bare do_sample=True keeps raising.
 """
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-_IGNORED_WHEN_GREEDY = ("temperature", "top_p", "top_k", "typical_p")     # sampling knobs HF ignores (with a warning) when do_sample=False
+# sampling knobs HF ignores (with a warning) when do_sample=False
+_IGNORED_WHEN_GREEDY = ("temperature", "top_p", "top_k", "typical_p", "min_p", "epsilon_cutoff", "eta_cutoff")
 # HF's greedy logits processors (HF: generation/logits_process.py, wired by GenerationMixin._get_logits_processor)
 _PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "suppress_tokens",
                "begin_suppress_tokens")
 _ACCEPTED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "attention_mask", "stopping_criteria", "use_cache", "do_sample",
              "num_beams", "streamer", "output_scores", "output_logits", "return_dict_in_generate", "num_return_sequences", "position_ids",
-             "inputs_embeds", "past_key_values") + _PROCESSORS + _IGNORED_WHEN_GREEDY
+             "inputs_embeds", "past_key_values", "seed") + _PROCESSORS + _IGNORED_WHEN_GREEDY
 
 
 class GenerateDecoderOnlyOutput(SimpleNamespace):
@@ -31,15 +37,18 @@ class GenerateDecoderOnlyOutput(SimpleNamespace):
 
 
 def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
-    """Validate generate() keyword arguments; returns a namespace with the normalised settings.  Raises NotImplementedError for what this
-    build does not do (sampling, beam search, streamers, caller-supplied inputs_embeds, LoRA engines) and TypeError for unknown names."""
+    """Validate generate() keyword arguments; returns a namespace with the normalised settings (.sampling: None for greedy, else the
+    warper settings and the seed as given; sampling_seeds() resolves it per row).  Raises NotImplementedError for what this build does
+    not do (do_sample=True without seed=, beam search, streamers, caller-supplied inputs_embeds, LoRA engines) and TypeError for unknown
+    names."""
     unknown = sorted(k for k in kwargs if k not in _ACCEPTED)
     if unknown:
         raise TypeError(f"generate() got unexpected keyword arguments {unknown}")
     if kwargs.get("inputs_embeds") is not None:
         raise NotImplementedError("`inputs_embeds` is not supported")      # the reference's generate() raises the same
-    if kwargs.get("do_sample"):
-        raise NotImplementedError("do_sample=True: only greedy decoding is implemented")
+    if kwargs.get("do_sample") and kwargs.get("seed") is None:
+        raise NotImplementedError("do_sample=True without seed=: drawing from torch's global RNG is not implemented; pass seed= (an int, "
+                                  "or one int per row) for counter-based, reproducible sampling")
     if (kwargs.get("num_beams") or 1) > 1:
         raise NotImplementedError("num_beams > 1: beam search is not implemented")
     if (kwargs.get("num_return_sequences") or 1) > 1:
@@ -73,12 +82,95 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
                            stopping_criteria=crit, output_scores=bool(kwargs.get("output_scores", False)),
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
-                           past_key_values=pkv,
+                           past_key_values=pkv, sampling=_parse_sampling(kwargs),
                            **_parse_processors(kwargs, eos))
 
 
 def _is_int(v):
     return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+SEED_LIMIT = 1 << 63          # seeds are uint64 on the device; below 2^63 they also fit the int64 tensor that carries them
+
+
+def _parse_sampling(kwargs):
+    """The sampling settings (do_sample=True with seed=), validated as HF's warper constructors do; None for greedy decoding.  Defaults
+    are HF's GenerationConfig: temperature 1.0, top_k 50, top_p 1.0, min_p None; top_k None or 0 is off; min_tokens_to_keep is 1."""
+    seed = kwargs.get("seed")
+    if not kwargs.get("do_sample"):
+        if seed is not None:
+            raise ValueError("seed= is given but do_sample is not True: a seed only has a meaning for sampling")
+        return None
+    for k in ("typical_p", "epsilon_cutoff", "eta_cutoff"):
+        v = kwargs.get(k)
+        if v is not None and v != (1.0 if k == "typical_p" else 0.0):
+            raise NotImplementedError(f"{k}: typical / epsilon / eta sampling is not implemented")
+    T = kwargs.get("temperature")
+    T = 1.0 if T is None else T
+    # the kernel takes it as fp32: a value that rounds to 0 or inf there is as bad as 0 or inf
+    T32 = None
+    if not isinstance(T, bool) and isinstance(T, (int, float, np.floating, np.integer)):
+        with np.errstate(all="ignore"):
+            T32 = np.float32(min(max(T, -1), 1e39))                      # an int beyond the floats is inf like any other
+    if T32 is None or not T32 > 0 or not np.isfinite(T32):
+        raise ValueError(f"`temperature` (={T!r}) has to be a strictly positive float")
+    k = kwargs.get("top_k", 50)
+    k = 0 if k is None else k
+    if not _is_int(k) or k < 0:
+        raise ValueError(f"`top_k` has to be a strictly positive integer, but is {k!r}")
+    vals = {}
+    for name, default in (("top_p", 1.0), ("min_p", 0.0)):
+        v = kwargs.get(name)
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0 <= v <= 1.0:
+            raise ValueError(f"`{name}` has to be a float in the [0, 1] interval, but is {v!r}")
+        vals[name] = float(v)
+    if _is_int(seed):
+        seeds = int(seed)
+    else:
+        if isinstance(seed, (str, bytes)) or not hasattr(seed, "__iter__"):
+            raise ValueError(f"`seed` has to be an int or a list with one int per row, but is {seed!r}")
+        seeds = list(seed.tolist() if hasattr(seed, "tolist") else seed)
+        if any(not _is_int(v) for v in seeds):
+            raise ValueError(f"`seed` has to be an int or a list with one int per row, but is {seed!r}")
+        seeds = [int(v) for v in seeds]
+    if any(not 0 <= v < SEED_LIMIT for v in ([seeds] if isinstance(seeds, int) else seeds)):
+        raise ValueError(f"every seed has to be in [0, 2^63), but `seed` is {seed!r}")
+    return SimpleNamespace(temperature=float(T), top_k=int(k), top_p=vals["top_p"], min_p=vals["min_p"], seed=seeds)
+
+
+def sampling_seeds(sampling, n):
+    """The seed of each of n rows (generate) or requests (generate_batch): an int s gives row i the seed s + i, a list gives its entries.
+    ValueError for a list of another length."""
+    s = sampling.seed
+    if isinstance(s, int):
+        seeds = [s + i for i in range(n)]
+    else:
+        if len(s) != n:
+            raise ValueError(f"`seed` holds {len(s)} seeds for {n} rows")
+        seeds = list(s)
+    if any(not 0 <= v < SEED_LIMIT for v in seeds):
+        raise ValueError("every row's seed has to be in [0, 2^63)")
+    return seeds
+
+
+def sample_uniform(seed, t):
+    """The uniform of row seed `seed` at its step t (the tokens it has generated so far), in (0, 1):
+    ((portable_rng._stream(seed, 0, t + 1)[t] >> 40) + 0.5) * 2^-24, an odd multiple of 2^-25 (exact in float64; rv_sample_rows_f32
+    restates it on the device and keeps it as an integer)."""
+    from .portable_rng import _splitmix64
+    with np.errstate(over="ignore"):
+        base = _splitmix64(np.array([(int(seed) * 1000003) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))
+        v = _splitmix64(np.array([int(t)], dtype=np.uint64) * np.uint64(0xD1342543DE82EF95) + base)[0]
+    return (float(int(v) >> 40) + 0.5) * 2.0 ** -24
+
+
+def _check_sampled(tok, rows=None):
+    """rv_sample_rows_f32 marks a row it cannot sample with -1 (as torch.multinomial raises in HF)."""
+    bad = [int(r) for r in (range(len(tok)) if rows is None else rows) if tok[r] < 0]
+    if bad:
+        raise ValueError(f"sampling: the scores of rows {bad} hold a NaN or +inf, or no finite entry (probability tensor contains "
+                         f"either `inf`, `nan` or element < 0)")
 
 
 def _token_list(name, v):
@@ -361,7 +453,9 @@ class GenerationCache:
 def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg):
     """prefill once, then decode_step per token until every row has finished or the budget is spent.  With cfg.past_key_values (a
     GenerationCache) the prompt pass reuses what the cache holds (LlavaEngine.extend; an empty cache: prefill as without one) and the
-    cache keeps the prompt and every generated token but the last."""
+    cache keeps the prompt and every generated token but the last.  With cfg.sampling each step's token is drawn by ops.sample_rows
+    from the processed scores (row b with seed_b at step t) instead of their argmax; output_scores and the stopping criteria then get
+    the warped scores, output_logits the raw ones as before."""
     from . import ops
     ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids)
     if ids.ndim == 1:
@@ -382,9 +476,17 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     T = new_token_budget(cfg, plan_len or 0)
     lp = LogitsProcessors(cfg, engine.vocab, plan_len or 0)
     raw = []
+    sm = cfg.sampling
+    if sm is not None:
+        seeds = sampling_seeds(sm, B)
     if T > 0:
+        if sm is not None:
+            sm_seed = torch.tensor(seeds, dtype=torch.int64, device=dev)
+            sm_t = torch.arange(T, dtype=torch.int32, device=dev)[:, None].expand(T, B).contiguous()     # row t: every row at step t
+            sm_write = cfg.output_scores or bool(cfg.stopping_criteria)
         # the tokens generated so far, pads of finished rows included (HF's input_ids of inputs_embeds generation: no prompt)
         hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active else None
+        sm_ws = ops.sample_rows_workspace(B, dev) if sm is not None else None      # the sampler's scratch, once per call
         if gc is None:
             cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T)
         else:
@@ -403,8 +505,13 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                 raw.append(logits.clone())
             if lp.active:                 # in place: logits become HF's processed scores
                 nxt = ops.logits_process_argmax(logits, engine.vocab, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
-            else:
+            elif sm is None:
                 nxt = ops.argmax_rows(logits, engine.vocab)
+            if sm is not None:            # in place when someone reads them: the processed scores become HF's warped scores
+                nxt = ops.sample_rows(logits, engine.vocab, sm_seed, sm_t[t], sm.temperature, sm.top_k, sm.top_p, sm.min_p, write_scores=sm_write,
+                                      ws=sm_ws)
+                nxt = nxt.cpu().numpy()
+                _check_sampled(nxt, np.flatnonzero(st.unfinished))
             if cfg.output_scores:
                 scores.append(logits.clone())
             tok = st.step(nxt, logits, device=dev)
@@ -441,7 +548,7 @@ class GenerationOutput(SimpleNamespace):
 
 
 def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
-    """generate_batch() keywords: generate()'s greedy settings, validated by parse_generate_kwargs and applied per request;
+    """generate_batch() keywords: generate()'s greedy and sampling settings (seed: an int, or a list of n ints), validated by parse_generate_kwargs and applied per request;
     max_new_tokens may also be a list of n budgets (cfg.budgets).  TypeError for arguments without a per-request meaning."""
     given = sorted(k for k in _NO_PER_REQUEST if kwargs.get(k) is not None and kwargs.get(k) is not False)
     if given:
@@ -460,6 +567,8 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
         del kw["max_new_tokens"]
     cfg = parse_generate_kwargs(kw, lora=lora, config_eos=config_eos, config_pad=config_pad)
     cfg.budgets = budgets
+    if cfg.sampling is not None:
+        sampling_seeds(cfg.sampling, n)                       # a list of another length: ValueError here, before anything runs
     return cfg
 
 
@@ -514,11 +623,14 @@ class DevicePicker:
     """Token choice of one generate_batch() step on the device, for rows at different steps: rv_argmax_rows_f32 when no processor is
     active and no logprobs are asked for, else rv_logits_process_argmax_rows_f32 (row r at its own step t[r] with its own EOS minimum).
     The emitted tokens go into the device history, int32 [slots, max budget], at (slot, t); a slot's history restarts at t = 0 with
-    each request admitted into it."""
+    each request admitted into it.  With cfg.sampling the token of row r is drawn by rv_sample_rows_f32 with the seed of the slot's
+    request at t[r], after the processors when one is active; the logprob is then log q of the drawn token, and the warped scores are
+    written back only when a stopping criterion will read them."""
 
     def __init__(self, engine, cfg, slots, max_budget, logprobs, any_min_new):
         lp = LogitsProcessors(cfg, engine.vocab)
         self.engine, self.vocab, self.logprobs = engine, engine.vocab, bool(logprobs)
+        self.sampling, self.write_scores = cfg.sampling, bool(cfg.stopping_criteria)
         self.penalty, self.ngram = lp.penalty, lp.ngram
         self.active = (lp.penalty != 1.0 or lp.ngram > 0 or bool(cfg.bad_words_ids) or bool(lp.suppress) or bool(lp.begin) or
                        (any_min_new and bool(lp.eos)))
@@ -528,10 +640,14 @@ class DevicePicker:
         tok, off = lp.bad_csr()
         self.bad = (torch.from_numpy(tok).to(dev), torch.from_numpy(off).to(dev)) if lp.multi else (None, None)
         self.hist = torch.zeros(slots, max(int(max_budget), 1), dtype=torch.int32, device=dev) if self.active else None
+        self.ws, self.ws_rows = None, 0                       # the sampler's scratch, kept across steps
 
-    def __call__(self, logits, slot, t, min_new):
-        """logits: fp32 [rows, vocab] (processed in place); slot / t / min_new: numpy ints [rows].  Returns (tokens, logprobs or None)."""
+    def __call__(self, logits, slot, t, min_new, seed=None):
+        """logits: fp32 [rows, vocab] (processed in place); slot / t / min_new: numpy ints [rows]; seed: the rows' request seeds when
+        sampling.  Returns (tokens, logprobs or None)."""
         from . import ops
+        if self.sampling is not None:
+            return self._sample(logits, slot, t, min_new, seed)
         if not (self.active or self.logprobs):
             return ops.argmax_rows(logits, self.vocab).cpu().numpy(), None
         cols = 1 if self.hist is None else self.hist.shape[1]
@@ -543,9 +659,30 @@ class DevicePicker:
             self.hist.view(-1).index_copy_(0, info[3].long(), tok.to(torch.int32))
         return tok.cpu().numpy(), None if lpo is None else lpo.cpu().numpy()
 
+    def _sample(self, logits, slot, t, min_new, seed):
+        from . import ops
+        sm, rows = self.sampling, logits.shape[0]
+        cols = 1 if self.hist is None else self.hist.shape[1]
+        host = np.empty(6 * rows, dtype=np.int32)             # one upload: slot, t, min_new, history index (int32), then the int64 seeds
+        host[:4 * rows] = np.stack([slot, t, min_new, slot * cols + t]).astype(np.int32).reshape(-1)
+        host[4 * rows:].view(np.int64)[:] = np.asarray(seed, dtype=np.int64)
+        d = self.engine._dev(host)
+        info, seeds = d[:4 * rows].view(4, rows), d[4 * rows:].view(torch.int64)
+        if self.active:
+            ops.logits_process_argmax_rows(logits, self.vocab, self.hist, info[0], info[1], info[2], self.penalty, self.ngram, *self.bans,
+                                           *self.bad)
+        if self.ws is None or self.ws_rows < rows:            # grows to the largest step (all slots) and stays
+            self.ws, self.ws_rows = ops.sample_rows_workspace(rows, logits.device), rows
+        lpo = torch.empty(rows, dtype=torch.float32, device=logits.device) if self.logprobs else None
+        tok = ops.sample_rows(logits, self.vocab, seeds, info[1], sm.temperature, sm.top_k, sm.top_p, sm.min_p,
+                              write_scores=self.write_scores, logprob=lpo, ws=self.ws)
+        if self.hist is not None:
+            self.hist.view(-1).index_copy_(0, info[3].long(), tok.clamp(min=0).to(torch.int32))
+        return tok.cpu().numpy(), None if lpo is None else lpo.cpu().numpy()
+
 
 class BatchScheduler:
-    """Continuous batching of greedy requests over one KVCache of `slots` sequences (generate_batch).  Host code: it reaches the engine
+    """Continuous batching of greedy or sampled requests over one KVCache of `slots` sequences (generate_batch).  Host code: it reaches the engine
     through plan, kv_cache_bytes, free_device_bytes, new_kv_cache, prefill(..., cache=, slots=) and decode_step, and chooses tokens
     through `picker` (default DevicePicker), so a fake engine and picker can drive it on the CPU.
 
@@ -554,7 +691,9 @@ class BatchScheduler:
     when nothing is decoding, or when every waiting request fits.  Each decode step runs all slots: an idle slot is fed token 0 at
     position 0 (its length is 0 before and after the step) and its logits are ignored.  A request finishes on an EOS token, its budget or a
     stopping criterion (called as generate() calls it at B = 1: the request's tokens [1, t] and its processed scores [1, vocab]), and
-    frees its slot.  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t)."""
+    frees its slot.  With cfg.sampling request i carries its own seed (sampling_seeds: an int s gives s + i) and the picker is called with
+    seed=, the seeds of the rows' requests (0 for an idle slot), next to each row's step t: what a request draws depends on neither the
+    slot nor the schedule.  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t)."""
 
     def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None):
         if not _is_int(max_batch_size) or max_batch_size < 1:
@@ -565,6 +704,7 @@ class BatchScheduler:
         self.spliced = [int(engine.plan(r.ids[None], None, None, r.images, r.sizes)["lens"][0]) for r in reqs]
         self.budget = [cfg.budgets[i] if cfg.budgets is not None else new_token_budget(cfg, self.spliced[i]) for i in range(n)]
         self.min_new = [min_new_length(cfg, self.spliced[i]) for i in range(n)]
+        self.seeds = None if getattr(cfg, "sampling", None) is None else sampling_seeds(cfg.sampling, n)
         self.runs = [i for i in range(n) if self.budget[i] > 0]
         self.slots = min(int(max_batch_size), len(self.runs))
         self.L_max = max([self.spliced[i] + self.budget[i] for i in self.runs], default=0)
@@ -640,12 +780,18 @@ class BatchScheduler:
         """Choose the tokens of logits' rows (row r belongs to slot row_slots[r]) and book them per request."""
         cfg = self.cfg
         sl = np.asarray(row_slots, dtype=np.int64)
-        tok, lps = self.picker(logits, sl, self.t[sl], self.mn[sl])
+        if self.seeds is None:
+            tok, lps = self.picker(logits, sl, self.t[sl], self.mn[sl])
+        else:
+            seed = np.array([self.seeds[q] if q >= 0 else 0 for q in self.owner[sl]], dtype=np.int64)
+            tok, lps = self.picker(logits, sl, self.t[sl], self.mn[sl], seed=seed)
         for r, s in enumerate(row_slots):
             q = int(self.owner[s])
             if q < 0:
                 continue
             tk = int(tok[r])
+            if tk < 0:
+                _check_sampled(tok, [r])
             self.tokens[q].append(tk)
             if self.logprobs:
                 self.logps[q].append(float(lps[r]))

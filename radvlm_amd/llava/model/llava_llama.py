@@ -267,7 +267,7 @@ class LlavaLlamaForCausalLM:
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, modalities=("image",), **kwargs):
-        """Greedy generation (the reference's generate(): the multimodal splice once, then HF generate on the spliced inputs_embeds).
+        """Greedy or seeded-sampling generation (the reference's generate(): the multimodal splice once, then HF generate on the spliced inputs_embeds).
         inputs: prompt token ids [B, T] (IMAGE_TOKEN_INDEX where an image goes); images / image_sizes as in forward (None: text only).
         Returns the NEW tokens only, LongTensor [B, T_new]; rows that finished (EOS or a stopping criterion) are filled with
         pad_token_id.  Keywords: max_new_tokens (default 20), max_length, eos_token_id, pad_token_id, attention_mask, stopping_criteria,
@@ -275,8 +275,17 @@ class LlavaLlamaForCausalLM:
         the processed scores, .logits = the raw ones, .past_key_values).  past_key_values: a generation.GenerationCache() reused across
         the calls of a conversation (each with the full prompt and images; the cached common prefix is not recomputed).  HF's greedy logits processors: repetition_penalty, no_repeat_ngram_size,
         bad_words_ids, min_length, min_new_tokens, suppress_tokens, begin_suppress_tokens; as in HF generation from inputs_embeds they
-        see only the generated tokens (pads included), never the prompt; a bad value raises ValueError.  Sampling, beam search,
-        streamers, inputs_embeds and LoRA models raise NotImplementedError.  The training state (weights, optimizer, RNG counters) is
+        see only the generated tokens (pads included), never the prompt; a bad value raises ValueError.
+        Sampling: do_sample=True together with seed= (an int s: row i draws with seed s + i; or a list with one int per row, each in
+        [0, 2^63)).  After the processors HF's warpers run in HF's order -- temperature (default 1.0), top_k (50; None or 0: off),
+        top_p (1.0), min_p (None) -- then one token is drawn from the softmax with a counter-based uniform of (the row's seed, the
+        number of tokens the row has generated), so a call is reproducible by construction and a row draws the same alone or in any
+        batch.  output_scores then returns the warped scores (-inf where a warper removed the entry), output_logits the raw ones;
+        stopping criteria get the warped scores.  Scores with a NaN, +inf or no finite entry raise ValueError.  do_sample=True WITHOUT
+        seed= raises NotImplementedError: draws from torch's global generator are not implemented.  With do_sample=False the sampling
+        keywords are accepted and ignored, as in HF; seed= without do_sample=True is a ValueError.  typical_p, epsilon_cutoff and
+        eta_cutoff (at a non-default value), beam search, num_return_sequences > 1, streamers, inputs_embeds and LoRA models raise
+        NotImplementedError.  The training state (weights, optimizer, RNG counters) is
         not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
@@ -288,16 +297,19 @@ class LlavaLlamaForCausalLM:
 
     @torch.no_grad()
     def generate_batch(self, inputs, images=None, image_sizes=None, max_batch_size=32, return_logprobs=False, **kwargs):
-        """Continuous batching over many independent prompts (transformers 5.x `generate_batch`), greedy only.
+        """Continuous batching over many independent prompts (transformers 5.x `generate_batch`), greedy or sampled.
         inputs: a list of N unpadded 1-D prompts (token ids; IMAGE_TOKEN_INDEX where an image goes).  images / image_sizes: None or a list
         of N entries, each None (text only), one tensor or a list of tensors (the request's images in image-token order) / their sizes.
         max_batch_size: requests decoded together (KV-cache slots).  Keywords: generate()'s greedy settings, applied per request
         (max_new_tokens may be a list of N budgets; pad_token_id is accepted, nothing is padded); attention_mask, past_key_values,
-        position_ids, output_scores, output_logits and return_dict_in_generate raise TypeError; sampling, beam search, streamers,
-        inputs_embeds and LoRA models raise NotImplementedError as in generate().
+        position_ids, output_scores, output_logits and return_dict_in_generate raise TypeError; do_sample=True without seed=, beam
+        search, streamers, inputs_embeds and LoRA models raise NotImplementedError as in generate().  Sampling: do_sample=True with
+        seed= (an int s: request i draws with seed s + i; or a list of N ints) and generate()'s temperature / top_k / top_p / min_p;
+        request i draws at its step t with u(seed_i, t), i.e. exactly what generate() draws for it alone with seed=seed_i, whatever
+        the slot and the schedule (up to the rounding of the scores themselves).
         Returns {"req_0": GenerationOutput, ...} in input order: .generated_tokens are what generate() returns for the request alone,
         ending at its EOS token or where a stopping criterion returned True; .logprobs (return_logprobs) the log-softmax of each step's
-        processed scores at the emitted token.  The training state is not touched."""
+        processed scores at the emitted token (when sampling: log q of the drawn token, q the softmax over what the warpers kept).  The training state is not touched."""
         from ...generation import generate_batch, parse_batch_kwargs
         inputs = list(inputs)
         cfg = parse_batch_kwargs(kwargs, len(inputs), lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),

@@ -744,6 +744,35 @@ def logits_process_argmax_rows(x, n, hist, slot, t, min_new, rep_penalty=1.0, ng
     return out
 
 
+def sample_rows_workspace(rows, device):
+    """Scratch for sample_rows on up to `rows` rows (int64, never zeroed).  One per generation loop: calls that share it must run on one stream."""
+    return torch.empty(lib.load().rv_sample_ws_bytes(int(rows)) // 8, dtype=torch.int64, device=device)
+
+
+def sample_rows(x, n, seed, t, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, write_scores=False, out=None, logprob=None, ws=None):
+    """Seeded sampling (rv_sample_rows_f32): one token per fp32 row x[r, :n] after HF's warpers temperature -> top-k -> top-p -> min-p,
+    drawn with the counter-based uniform of (seed[r], t[r]) (seed: int64 [rows] holding the uint64 bits, t: int32 [rows]).  write_scores:
+    x[:, :n] becomes the warped scores (-inf where removed), else x is only read.  Returns int64 [rows]; -1 marks a row that cannot be
+    sampled (NaN, +inf or no finite entry).  logprob (fp32 [rows]): log q of the drawn token.  ws: sample_rows_workspace(>= rows), allocated
+    here when not given."""
+    _chk(x, torch.float32)
+    rows = x.shape[0]
+    assert x.dim() == 2 and x.stride(1) == 1 and 0 < n <= min(x.shape[1], LOGITS_PROCESS_MAX_N)
+    _chk(seed, torch.int64), _chk(t, torch.int32)
+    for a in (seed, t):
+        assert a.dim() == 1 and a.numel() == rows and a.stride(0) == 1
+    if logprob is not None:
+        _chk(logprob, torch.float32)
+        assert logprob.numel() == rows and logprob.is_contiguous()
+    out = torch.empty(rows, dtype=torch.int64, device=x.device) if out is None else out
+    ws = sample_rows_workspace(rows, x.device) if ws is None else ws
+    _chk(ws, torch.int64)
+    assert ws.is_contiguous() and ws.numel() * 8 >= lib.load().rv_sample_ws_bytes(rows)
+    lib.call("rv_sample_rows_f32", x, x.stride(0), rows, int(n), seed, t, float(temperature), int(top_k or 0), float(top_p), float(min_p),
+             1 if write_scores else 0, out, logprob, ws, ws.numel() * 8)
+    return out
+
+
 def lora_merge(w, A, B, scale):
     """In place: w[N,K] <- bf16(w + scale * B[N,r] @ A[r,K]) (rv_lora_merge_bf16: fp32 sum in a fixed order, one rounding).  w may be a
     row slice of a fused store (any row stride); r <= 256.  Returns w."""

@@ -28,6 +28,13 @@
         # rv_gemv_w8_bf16, the 7B Llama and Qwen2-7B decoder shapes, M = 1, 4, 8, 16, 32, cold weights, interleaved
   python tools/decode_bench.py --w8-quality   # the toy goldens' models: logits distance and greedy-token agreement, int8 vs unquantised
   python tools/decode_bench.py --w8-trace [--geos llava15_7b]   # a B = 1 int8 decode run: the workload of `rocprofv3 --kernel-trace --stats`
+  python tools/decode_bench.py --sample [--geos ..] [--batches 1,8,32] [--out FILE]
+        # seeded sampling: (1) rv_sample_rows_f32 (the chat default T=0.2 top_k=50 top_p=0.7, and every warper on) vs
+        # rv_logits_process_argmax_rows_f32 with logprobs (one read of the row) at 1 and 32 rows x 32,000 and 152,064, device time,
+        # interleaved; (2) the decode step with the token drawn by the sampler vs the greedy argmax on one engine: one untimed
+        # repetition, the two arms alternated three times, medians of medians, and the gate sampled <= greedy + the greedy arm's
+        # spread + the cost of the launches sampling adds (10 with the chat default: one launch per sweep and one for the draw in
+        # place of the argmax launch) at the step's enqueue rate, greedy step / DECODE_LAUNCHES
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -255,14 +262,21 @@ def w8_trace(geo, prompt, new):
                  kernel_src=_src_hash())]
 
 
-def _decode_loop(eng, ids, new, lp=None, warm=8):
+def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None):
     """Median decode step (decode_step + token choice) in ms; with `lp` (generation.LogitsProcessors) the token comes from
-    rv_logits_process_argmax_f32 and is recorded in the device history, as greedy_generate does."""
+    rv_logits_process_argmax_f32 and is recorded in the device history, as greedy_generate does; with `sm` (the sampling settings of
+    parse_generate_kwargs) it is drawn by rv_sample_rows_f32, row b with seed sm.seed + b, as greedy_generate does."""
     B = ids.shape[0]
     cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new)
     hist = torch.zeros(B, new, dtype=torch.int32, device=logits.device) if lp is not None else None
+    if sm is not None:
+        seeds = torch.tensor([sm.seed + b for b in range(B)], dtype=torch.int64, device=logits.device)
+        steps = torch.arange(new, dtype=torch.int32, device=logits.device)[:, None].expand(new, B).contiguous()
+        ws = ops.sample_rows_workspace(B, logits.device)
 
     def choose(lg, t):
+        if sm is not None:
+            return ops.sample_rows(lg, eng.vocab, seeds, steps[t], sm.temperature, sm.top_k, sm.top_p, sm.min_p, ws=ws)
         if lp is None:
             return ops.argmax_rows(lg, eng.vocab)
         tk = ops.logits_process_argmax(lg, eng.vocab, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, lg.device))
@@ -299,6 +313,72 @@ def processors_ab(geo, B, prompt, new, reps=3):
                 f"min_new_tokens={new // 2},eos=2", plain_ms_per_step=round(p, 3), processors_ms_per_step=round(q, 3),
                 delta_ms=round(q - p, 4), delta_share=round((q - p) / p, 4), steps_timed_each=len(ts["plain"]), reps=reps,
                 kernel_src=_src_hash())
+
+
+SAMPLE_SETTINGS = {"chat_default": dict(temperature=0.2, top_k=50, top_p=0.7), "everything": dict(temperature=0.7, top_k=50, top_p=0.9, min_p=0.05)}
+SAMPLE_SWEEPS = 10                # sweeps of the row rv_sample_rows_f32 makes with top-k and top-p on: max, 4 + 4 radix passes, the tile sums
+SAMPLE_LAUNCHES = SAMPLE_SWEEPS + 1   # one launch per sweep (8 workgroups share a row and meet at launch boundaries) and one for the draw
+DECODE_LAUNCHES = 420             # kernel launches of one greedy decode step at 7B (from a kernel trace)
+
+
+def sample_kernel_ab(reps=30):
+    """rv_sample_rows_f32 vs rv_logits_process_argmax_rows_f32 with logprobs (no processor active: one read of the row) on the same
+    rows; interleaved, device time per launch (median µs)."""
+    from radvlm_amd.generation import parse_generate_kwargs
+    recs = []
+    for n in (32000, 152064):
+        for rows in (1, 32):
+            x = torch.from_numpy((np.random.default_rng(1).standard_normal((rows, n)) * 4).astype(np.float32)).cuda()
+            info = torch.zeros(3, rows, dtype=torch.int32, device="cuda")
+            seeds = torch.arange(rows, dtype=torch.int64, device="cuda")
+            lpo = torch.empty(rows, dtype=torch.float32, device="cuda")
+            ws = ops.sample_rows_workspace(rows, "cuda")
+            fns = {"argmax_logprob": lambda: ops.logits_process_argmax_rows(x, n, None, info[0], info[1], info[2], logprob=lpo)}
+            for name, kw in SAMPLE_SETTINGS.items():
+                sm = parse_generate_kwargs(dict(do_sample=True, seed=0, **kw)).sampling
+                fns[name] = (lambda sm=sm: ops.sample_rows(x, n, seeds, info[1], sm.temperature, sm.top_k, sm.top_p, sm.min_p, logprob=lpo, ws=ws))
+            ts = {k: [] for k in fns}
+            for f in fns.values():
+                f()
+            for _ in range(reps):
+                for k, f in fns.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    f()
+                    e1.record()
+                    e1.synchronize()
+                    ts[k].append(e0.elapsed_time(e1) * 1e3)
+            med = {k: float(np.median(v)) for k, v in ts.items()}
+            recs.append(dict(mode="sample_kernel_ab", rows=rows, vocab=n, reps=reps, sweeps=SAMPLE_SWEEPS, launches=SAMPLE_LAUNCHES,
+                             **{k + "_us": round(v, 2) for k, v in med.items()},
+                             **{"ratio_" + k: round(med[k] / med["argmax_logprob"], 2) for k in SAMPLE_SETTINGS}))
+    return recs
+
+
+def sample_ab(geo, batches, prompt, new, reps=3):
+    """The decode step with the token drawn by rv_sample_rows_f32 (chat default) against the greedy argmax, on one engine."""
+    from radvlm_amd.generation import parse_generate_kwargs
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    sm = parse_generate_kwargs(dict(do_sample=True, seed=0, **SAMPLE_SETTINGS["chat_default"])).sampling
+    recs = []
+    for B in batches:
+        ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+        ts = {"greedy": [], "sampled": []}
+        for arm in ts:                                                 # one untimed repetition of both arms
+            _decode_loop(eng, ids, new, sm=sm if arm == "sampled" else None)
+        for _ in range(reps):
+            for arm in ts:
+                ts[arm].append(float(np.median(_decode_loop(eng, ids, new, sm=sm if arm == "sampled" else None))))
+        g, q = float(np.median(ts["greedy"])), float(np.median(ts["sampled"]))
+        spread = max(ts["greedy"]) - min(ts["greedy"])
+        added = SAMPLE_LAUNCHES - 1                                    # the sampler's launches take the place of the argmax launch
+        gate = spread + added * g / DECODE_LAUNCHES                    # the added launches at the step's enqueue rate
+        recs.append(dict(geo=geo, mode="sample_ab", B=B, prompt=prompt, new_tokens=new, reps=reps, setting="chat_default",
+                         greedy_ms_per_step=round(g, 3), sampled_ms_per_step=round(q, 3), greedy_ms_all=[round(v, 3) for v in ts["greedy"]],
+                         sampled_ms_all=[round(v, 3) for v in ts["sampled"]], greedy_spread_ms=round(spread, 3), launches_added=added,
+                         delta_ms=round(q - g, 3), gate_ms=round(gate, 3), gate_holds=bool(q - g <= gate), holds_on_spread_alone=bool(q - g <= spread),
+                         kernel_src=_src_hash()))
+    return recs
 
 
 def _conversation(geo, B, seed=0):
@@ -567,6 +647,7 @@ def main():
     ap.add_argument("--w8-shapes", action="store_true")
     ap.add_argument("--w8-trace", action="store_true")
     ap.add_argument("--w8-quality", action="store_true")
+    ap.add_argument("--sample", action="store_true")
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -582,6 +663,8 @@ def main():
         recs = w8_quality_toy()
     elif a.w8_trace:
         recs = [r for g in a.geos.split(",") for r in w8_trace(g, a.prompt, a.new)]
+    elif a.sample:
+        recs = sample_kernel_ab() + [r for g in a.geos.split(",") for r in sample_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new)]
     elif a.batch_eval:
         recs = [r for g in a.geos.split(",") for r in batch_eval(g, n=a.requests, prompt=a.prompt, reps=min(a.reps, 3))]
     elif a.batch_kernel_ab:
