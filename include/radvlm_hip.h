@@ -350,7 +350,8 @@ int rv_gemv_w8_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp,
  * cache: bf16 [B][L_max][ld_c] (sequence stride bs_c), K of kv head g at columns g*hd, V at v_off + g*hd.  q: [B, H*hd] rows (ld_q);
  * out: bf16 [B, H*hd] rows (ld_o).  Keys are split into chunks of `chunk` rows (a multiple of 16 for hd 128, of 32 for hd 64,
  * <= 512) over workgroups; each writes (o, m, l) partials to `part` (B * H * ceil(L_max / chunk) * (hd + 2) floats) and a second
- * launch merges a sequence's chunks in chunk order.  kv_len is an int32 device array, values <= L_max. */
+ * launch merges a sequence's chunks in chunk order.  kv_len is an int32 device array, values <= L_max (0: the row is all zeros).
+ * ld_q < H*hd or ld_o < H*hd is refused (RV_ERR_ARG), as in rv_attn_extend_bf16. */
 int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
                         int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk,
                         float scale, void* stream);
@@ -366,7 +367,8 @@ int rv_attn_extend_bf16(const void* q, int64_t ld_q, const void* cache, int64_t 
                         const int32_t* r, int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int M, int max_q,
                         int H, int Hkv, int hd, int chunk, float scale, void* stream);
 /* KV cache append: cache[b][pos[b]][0:width] = src[b][0:width] (bf16; rows of the post-RoPE k|v columns of the qkv product);
- * pos is an int32 device array, slots outside [0, L_max) are skipped.  width % 8 == 0. */
+ * pos is an int32 device array, slots outside [0, L_max) are skipped.  width % 8 == 0.  ld_src < width or ld_c < width is refused
+ * (RV_ERR_ARG). */
 int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, int64_t ld_c, int64_t bs_c, const int32_t* pos, int L_max, int B,
                       int width, void* stream);
 /* Greedy token choice: out[r] (int64) = argmax over the first n columns of fp32 row r (torch.argmax: lowest index among equal

@@ -734,7 +734,7 @@ extern "C" int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cach
                                    float scale, void* stream) {
     if (!q || !cache || !kv_len || !out || !part || B <= 0 || Hkv <= 0 || H % Hkv || H / Hkv > AD_GMAX || (hd != 64 && hd != 128) ||
         L_max <= 0 || chunk <= 0 || chunk > AD_CHUNK_MAX || chunk % (hd == 128 ? 16 : 32) || (ld_q & 7) || (ld_c & 7) || (bs_c & 7) ||
-        (v_off & 7) || ld_c < v_off + (int64_t)Hkv * hd || bs_c < (int64_t)L_max * ld_c)
+        (v_off & 7) || ld_q < (int64_t)H * hd || ld_o < (int64_t)H * hd || ld_c < v_off + (int64_t)Hkv * hd || bs_c < (int64_t)L_max * ld_c)
         return RV_ERR_ARG;
     const int nch = (L_max + chunk - 1) / chunk;
     if (part_bytes < (int64_t)B * H * nch * (hd + 2) * 4) return RV_ERR_ARG;
@@ -755,8 +755,8 @@ extern "C" int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cach
 
 extern "C" int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, int64_t ld_c, int64_t bs_c, const int32_t* pos, int L_max, int B,
                                  int width, void* stream) {
-    if (!src || !cache || !pos || B <= 0 || width <= 0 || (width & 7) || (ld_src & 7) || (ld_c & 7) || (bs_c & 7) || ld_c < width ||
-        bs_c < (int64_t)L_max * ld_c)
+    if (!src || !cache || !pos || B <= 0 || width <= 0 || (width & 7) || (ld_src & 7) || (ld_c & 7) || (bs_c & 7) || ld_src < width ||
+        ld_c < width || bs_c < (int64_t)L_max * ld_c)
         return RV_ERR_ARG;
     hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, ST, (const bf16*)src, (long)ld_src, (bf16*)cache, (long)ld_c, (long)bs_c, pos,
                        L_max, width);
