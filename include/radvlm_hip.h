@@ -435,6 +435,42 @@ int64_t rv_sample_ws_bytes(int rows);
 /* Host function: the 24 bits b of the draw above for (seed, t), the same code the kernel runs. */
 uint32_t rv_sample_uniform24(uint64_t seed, int32_t t);
 
+/* ---- beam search (generate_beams(), radvlm_amd/csrc/beam.hip) ----------------------------------------------------------------------
+ * The reference reaches beam search through HF generate(num_beams=...) (finetuning/llava/eval/model_vqa.py --num_beams ->
+ * HF:generation/utils.py _beam_search), which reorders the whole KV cache by the chosen parents after every token.  Here the cache is
+ * never reordered: every beam appends to its own cache row and attention follows the beam's ancestry through a table. */
+/* rv_attn_decode_bf16 with a per-key row lookup: key position j of query row r (rows of them, one q row and one kv_len each) is read,
+ * at that same position j, from cache row  j < prefix_len[r] ? prefix_row[r] : tail_src[r * ld_t + (j - prefix_len[r])].
+ * prefix_row, prefix_len (int32 [rows]) and tail_src (int32 rows of ld_t, tail_cols valid columns; NULL with tail_cols = 0) are device
+ * arrays.  cache holds cache_rows rows of bs_c elements; every looked-up row is clamped into [0, cache_rows), a negative prefix_len
+ * counts as 0 and a tail position >= tail_cols reads prefix_row[r], so no table content makes the kernel read outside the cache.
+ * Entries for positions >= kv_len[r] are never read.  Chunking is by absolute key position with the same `chunk`, the per-chunk
+ * arithmetic and the combine are rv_attn_decode_bf16's: out is BIT-IDENTICAL to rv_attn_decode_bf16 on the cache materialised by that
+ * gather, for hd 64 and 128, up to 8 q heads per kv head and kv_len 0 .. L_max.  The lookup is resolved per chunk into LDS; the K / V
+ * loads stay 16 bytes per lane.  part: rows * H * ceil(L_max / chunk) * (hd + 2) floats.  ld_q < H*hd or ld_o < H*hd is refused
+ * (RV_ERR_ARG), as there. */
+int rv_attn_decode_beam_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
+                             int L_max, const int32_t* prefix_row, const int32_t* prefix_len, const int32_t* tail_src, int64_t ld_t,
+                             int tail_cols, int cache_rows, void* out, int64_t ld_o, void* part, int64_t part_bytes, int rows, int H,
+                             int Hkv, int hd, int chunk, float scale, void* stream);
+/* HF _beam_search's nn.functional.log_softmax(logits, dim=-1) on the fp32 scores, in place on the first n columns (n <= 262144) of
+ * each row: x_i <- fl(fl(x_i - m) - L), m = max x, L = fl32(log(sum exp(x_i - m))), the sum in fp64 in a fixed order (per thread in
+ * index order, lanes by xor butterfly, waves 0..3).  One workgroup per row: a row's bits depend on neither `rows` nor the other rows.
+ * Columns >= n are never touched.  -inf entries stay -inf; a row with a NaN, a +inf or no finite entry becomes NaN throughout, as in
+ * torch.  |result - exact| <= 2^-24 (2 |result| + 4 ln n + 3) on a finite row (csrc/beam.hip derives it). */
+int rv_log_softmax_rows_f32(float* x, int64_t ld, int rows, int n, void* stream);
+/* HF _get_top_k_continuations' torch.topk over the accumulated log-probs: for each of `groups` prompts, over its nb consecutive rows
+ * r of x (row g * nb + r, first n columns), v(r, i) = fl(x[r][i] + score[g * nb + r]) (one fp32 add) and out_v / out_i [groups, K]
+ * are the K best candidates as (v, flat index r * n + i), ordered by v descending, then flat index ascending, NaN ranking highest
+ * (rv_argmax_rows_f32's rule).  The order is total where torch leaves ties open, so the output is the same bits for any grid.
+ * 1 <= nb <= 16, 1 <= K <= min(64, nb * n), n <= 262144.  Slices of the candidates are reduced to their K best by K rounds of a
+ * workgroup argmax and merged by a second launch: no sort of a row, no float atomics, no global atomics.  ws: device scratch of
+ * ws_bytes >= rv_beam_topk_ws_bytes(groups, nb, n, K), contents arbitrary; not to be shared by launches that can overlap. */
+int rv_beam_topk_f32(const float* x, int64_t ld, int groups, int nb, int n, const float* score, int K, float* out_v, int32_t* out_i,
+                     void* ws, int64_t ws_bytes, void* stream);
+/* Host function: the bytes of scratch rv_beam_topk_f32 needs. */
+int64_t rv_beam_topk_ws_bytes(int groups, int nb, int n, int K);
+
 /* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
  * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any
  * grid and any placement of W.  W: bf16 rows of ldw elements (a row slice of a fused q|k|v or gate|up store is fine), 16-byte aligned,

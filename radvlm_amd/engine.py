@@ -957,10 +957,15 @@ class LlavaEngine:
         cache.lens[seq] = lens
         return cache, logits[:, :self.vocab]
 
-    def decode_step(self, cache, tokens):
+    def decode_step(self, cache, tokens, beams=None):
         """One generated token per sequence: tokens [B] (int, host or device) at position cache.lens[b] -> fp32 logits [B, vocab].
         Per layer: RMSNorm, q|k|v projection, RoPE at the token's position, cache append, decode attention over the sequence's cached
-        keys, o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual; then the final norm and the lm_head (fp32 scores)."""
+        keys, o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual; then the final norm and the lm_head (fp32 scores).
+        beams (beam search, generation.beam_generate): .prefix_row / .prefix_len (int32 [B] device) and .tail_src (int32 [B, >=
+        .tail_cols] device, or None).  Row r still appends its K|V at position cache.lens[r] of its OWN row, but reads key position j
+        from row prefix_row[r] while j < prefix_len[r] and from row tail_src[r, j - prefix_len[r]] after it (rv_attn_decode_beam_bf16,
+        bit-identical to the plain kernel on the gathered cache), so beams share their prompt's rows and their ancestors' tokens and
+        nothing in the cache moves.  Without it every call is what it was."""
         self._check_generation()
         l = self.l
         d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
@@ -980,7 +985,11 @@ class LlavaEngine:
             qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), w8=q8.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
             ops.kv_append(qkv[:, d:], cache.layers[i], pos)
-            attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            if beams is None:
+                attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            else:
+                attn = ops.attn_decode_beam(qkv[:, :d], cache.layers[i], kv_len, beams.prefix_row, beams.prefix_len, beams.tail_src, H, Hkv,
+                                            hd, kvd, tail_cols=beams.tail_cols, chunk=cache.chunk)
             x_mid = self._decode_linear(attn, lv["o"], residual=x, w8=q8.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
             act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], w8=q8.get("gu")), F)

@@ -50,7 +50,7 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
         raise NotImplementedError("do_sample=True without seed=: drawing from torch's global RNG is not implemented; pass seed= (an int, "
                                   "or one int per row) for counter-based, reproducible sampling")
     if (kwargs.get("num_beams") or 1) > 1:
-        raise NotImplementedError("num_beams > 1: beam search is not implemented")
+        raise NotImplementedError("num_beams > 1: beam search is not implemented here; call model.generate_beams(...)")
     if (kwargs.get("num_return_sequences") or 1) > 1:
         raise NotImplementedError("num_return_sequences > 1 needs sampling or beam search")
     if kwargs.get("streamer") is not None:
@@ -815,3 +815,269 @@ def generate_batch(engine, inputs, images, image_sizes, cfg, max_batch_size=32, 
     """Continuous batching over many prompts (LlavaLlamaForCausalLM.generate_batch); cfg from parse_batch_kwargs.  Each request's
     generated tokens are what generate() returns for it alone (B = 1, the same settings), up to rounding."""
     return BatchScheduler(engine, batch_requests(inputs, images, image_sizes), cfg, max_batch_size, return_logprobs).run()
+
+
+# ------------------------------------------------------------------------------------------------ beam search: generate_beams
+# HF semantics followed: GenerationMixin._beam_search of transformers 5.x (HF: generation/utils.py) for a decoder-only model called with
+# inputs_embeds: input_ids start empty, decoder_prompt_len = 0, lengths count generated tokens only, the sequences hold the new tokens
+# only.  BeamState restates its bookkeeping step for step in numpy fp32.  One place is stricter than HF: torch.topk leaves the order
+# among equal values open; every top-K here is total (value descending, then the lower flat index beam * vocab + token, or the lower
+# candidate slot).  The division by length ** length_penalty is an fp32 division by the fp32-rounded power (torch's CPU result).
+BEAM_MAX = 16                 # num_beams limit (rv_beam_topk_f32)
+BEAM_TOPK_MAX = 64            # candidates kept per prompt and step, K = max(2, 1 + n_eos) * num_beams
+_BEAM_ONLY = ("length_penalty", "early_stopping")
+_NEG = np.float32(-1.0e9)
+
+
+class GenerateBeamDecoderOnlyOutput(SimpleNamespace):
+    """HF's return_dict_in_generate output of beam search: .sequences [B * num_return_sequences, T_out]; .sequences_scores (None unless
+    output_scores); .scores (output_scores: per step the processed log-probs [B * num_beams, vocab]); .logits (output_logits: the raw
+    ones); .beam_indices [B * num_return_sequences, T_out] (-1 past a hypothesis' end); .past_key_values (the engine's beam KVCache)."""
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+
+def beams_to_keep(num_beams, n_eos):
+    return max(2, 1 + int(n_eos)) * int(num_beams)
+
+
+def parse_beam_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
+    """Validate generate_beams() keyword arguments: generate()'s, plus length_penalty (float, default 1.0), early_stopping (False, True
+    or "never") and num_return_sequences <= num_beams.  ValueError for num_beams outside [1, 16] or K = max(2, 1 + n_eos) * num_beams
+    above 64; NotImplementedError for do_sample=True (beam sampling), past_key_values, streamer, inputs_embeds and LoRA engines;
+    TypeError for unknown names.  The sampling knobs HF ignores when greedy stay ignored."""
+    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _BEAM_ONLY)
+    if unknown:
+        raise TypeError(f"generate_beams() got unexpected keyword arguments {unknown}")
+    if kwargs.get("do_sample"):
+        raise NotImplementedError("do_sample=True with beams: beam sampling is not implemented")
+    if kwargs.get("past_key_values") is not None:
+        raise NotImplementedError("past_key_values: a GenerationCache across generate_beams() calls is not implemented")
+    nb = kwargs.get("num_beams")
+    nb = 1 if nb is None else nb
+    if not _is_int(nb) or not 1 <= nb <= BEAM_MAX:
+        raise ValueError(f"`num_beams` has to be an integer in [1, {BEAM_MAX}], but is {nb!r}")
+    nrs = kwargs.get("num_return_sequences")
+    nrs = 1 if nrs is None else nrs
+    if not _is_int(nrs) or nrs < 1:
+        raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {nrs!r}")
+    if nrs > nb:
+        raise ValueError(f"`num_return_sequences` (={nrs}) has to be smaller or equal to `num_beams` (={nb})")
+    pen = kwargs.get("length_penalty")
+    pen = 1.0 if pen is None else pen
+    if isinstance(pen, bool) or not isinstance(pen, (int, float, np.floating, np.integer)) or not np.isfinite(pen):
+        raise ValueError(f"`length_penalty` has to be a finite float, but is {pen!r}")
+    es = kwargs.get("early_stopping")
+    es = False if es is None else es
+    if not (es is True or es is False or es == "never"):
+        raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {es!r}")
+    kw = {k: v for k, v in kwargs.items() if k not in _BEAM_ONLY and k not in ("num_beams", "num_return_sequences")}
+    cfg = parse_generate_kwargs(kw, lora=lora, config_eos=config_eos, config_pad=config_pad)
+    K = beams_to_keep(nb, len(cfg.eos))
+    if K > BEAM_TOPK_MAX:
+        raise ValueError(f"num_beams={nb} with {len(cfg.eos)} EOS ids keeps max(2, 1 + n_eos) * num_beams = {K} candidates per step; the limit is "
+                         f"{BEAM_TOPK_MAX}")
+    # HF: output_fill_value = pad_token_id or eos_token_id[0] if eos_token_id is not None else -1 (generate() has set a missing
+    # pad_token_id to the first EOS id by then).  Read as Python reads it: without an EOS id the fill is -1 whatever the pad.
+    pad = kwargs.get("pad_token_id", config_pad)
+    cfg.fill = (int(pad) if pad else cfg.eos[0]) if cfg.eos else -1
+    cfg.num_beams, cfg.num_return_sequences, cfg.length_penalty, cfg.early_stopping, cfg.K = int(nb), int(nrs), float(pen), es, K
+    return cfg
+
+
+def _topk_desc(v, k):
+    """Indices of the k best entries of each row of v [B, N]: value descending, then the lower index (a stable sort of -v)."""
+    return np.argsort(-v, axis=1, kind="stable")[:, :k]
+
+
+def _take(a, idx):
+    """HF's _gather_beams: a [B, N, ...] at idx [B, k] along dim 1."""
+    return np.take_along_axis(a, idx.reshape(idx.shape + (1,) * (a.ndim - 2)), axis=1)
+
+
+def advance_tail_src(tail_src, parent_rows, i):
+    """The ancestry table after the beam step that chose the running beams of generated position i: row r continues row parent_rows[r]
+    (cache rows, b * num_beams + beam), so it inherits that row's first i entries, and its own position i lives in row r itself.
+    tail_src: int32 [rows, T]; returns a new array, the input is not modified."""
+    rows = tail_src.shape[0]
+    new = tail_src[np.asarray(parent_rows, dtype=np.int64).reshape(rows)].copy()
+    new[:, i] = np.arange(rows, dtype=tail_src.dtype)
+    return new
+
+
+class BeamState:
+    """The bookkeeping of HF's _beam_search for B prompts x num_beams beams over a vocabulary of `vocab` ids and at most max_new
+    generated tokens (HF's max_length under inputs_embeds generation).  numpy, fp32, no device.  It receives each step's K = max(2, 1 +
+    n_eos) * num_beams best candidates per prompt (it does not compute them): step() returns the parent beam and the token of every
+    next running beam; `done` is HF's `this_peer_finished`; finalize() the returned hypotheses.
+    running_*: the live beams (sequences [B, nb, max_new] filled with `fill`, scores starting at [0, -1e9, ...], beam indices filled
+    with -1); sequences / beam_scores / beam_indices / is_sent_finished: the finished set; unsat: the early-stop heuristic flag."""
+
+    def __init__(self, B, num_beams, vocab, max_new, eos=(), length_penalty=1.0, early_stopping=False, fill=-1):
+        self.B, self.nb, self.vocab, self.T = int(B), int(num_beams), int(vocab), int(max_new)
+        self.eos = [int(e) for e in eos]
+        self.K = beams_to_keep(self.nb, len(self.eos))
+        self.length_penalty, self.early_stopping = length_penalty, early_stopping
+        B, nb, T = self.B, self.nb, self.T
+        self.running_sequences = np.full((B, nb, T), int(fill), dtype=np.int64)
+        self.sequences = self.running_sequences.copy()
+        self.running_scores = np.zeros((B, nb), dtype=np.float32)
+        self.running_scores[:, 1:] = _NEG
+        self.beam_scores = np.full((B, nb), _NEG, dtype=np.float32)
+        self.is_sent_finished = np.zeros((B, nb), dtype=bool)
+        self.unsat = np.ones((B, 1), dtype=bool)
+        self.hits = np.zeros((B, nb), dtype=bool)
+        self.running_beam_indices = np.full((B, nb, T), -1, dtype=np.int32)
+        self.beam_indices = self.running_beam_indices.copy()
+        self.cur = 0
+        self.done = self.T == 0
+
+    def candidates(self, topk_flat_idx):
+        """The K candidate sequences of a step, flattened as HF hands them to the stopping criteria: int64 [B * K, cur + 1]."""
+        flat = np.asarray(topk_flat_idx, dtype=np.int64).reshape(self.B, self.K)
+        seq = _take(self.running_sequences, flat // self.vocab)[:, :, :self.cur + 1].copy()
+        seq[:, :, self.cur] = flat % self.vocab
+        return seq.reshape(self.B * self.K, self.cur + 1)
+
+    def step(self, topk_vals, topk_flat_idx, hits_user_criteria=None):
+        """topk_vals fp32 [B, K] / topk_flat_idx [B, K] (beam * vocab + token): the step's K best accumulated log-probs per prompt, best
+        first; hits_user_criteria: None or bool [B, K] (or [B * K]), the OR of the user's stopping criteria on candidates().
+        Returns (parent [B, nb], token [B, nb]) of the next running beams."""
+        assert not self.done
+        B, nb, K, cur = self.B, self.nb, self.K, self.cur
+        vals = np.asarray(topk_vals, dtype=np.float32).reshape(B, K)
+        flat = np.asarray(topk_flat_idx, dtype=np.int64).reshape(B, K)
+        beam, tok = flat // self.vocab, flat % self.vocab
+        # _get_top_k_continuations
+        topk_seq = _take(self.running_sequences, beam)
+        topk_seq[:, :, cur] = tok
+        topk_idx = _take(self.running_beam_indices, beam)
+        topk_idx[:, :, cur] = (beam + np.arange(B)[:, None] * nb).astype(np.int32)
+        # stopping criteria on the candidates: the length budget, an EOS id, the user's
+        hits = np.full((B, K), cur + 1 >= self.T, dtype=bool)
+        if self.eos:
+            hits |= np.isin(tok, self.eos)
+        if hits_user_criteria is not None:
+            hits |= np.asarray(hits_user_criteria, dtype=bool).reshape(B, K)
+        # _get_running_beams_for_next_iteration
+        run_vals = vals + hits.astype(np.float32) * _NEG
+        nxt = _topk_desc(run_vals, nb)
+        self.running_sequences = _take(topk_seq, nxt)
+        self.running_scores = _take(run_vals, nxt)
+        self.running_beam_indices = _take(topk_idx, nxt)
+        # _update_finished_beams
+        just = hits & (np.arange(K) < nb)[None, :]
+        fin = vals / np.float32(float(cur + 1) ** self.length_penalty)
+        full = self.is_sent_finished.all(axis=-1, keepdims=True) & (self.early_stopping is True)
+        fin = fin + full.astype(np.float32) * _NEG
+        fin = fin + (~self.unsat).astype(np.float32) * _NEG
+        fin = fin + (~just).astype(np.float32) * _NEG
+        m_scores = np.concatenate([self.beam_scores, fin], axis=1)
+        best = _topk_desc(m_scores, nb)
+        self.sequences = _take(np.concatenate([self.sequences, topk_seq], axis=1), best)
+        self.beam_scores = _take(m_scores, best)
+        self.beam_indices = _take(np.concatenate([self.beam_indices, topk_idx], axis=1), best)
+        self.is_sent_finished = _take(np.concatenate([self.is_sent_finished, just], axis=1), best)
+        self.hits = hits
+        self.cur = cur = cur + 1
+        # _check_early_stop_heuristic
+        if self.early_stopping == "never" and self.length_penalty > 0.0:
+            best_len = self.T
+        else:
+            best_len = cur
+        best_run = self.running_scores[:, :1] / np.float32(float(best_len) ** self.length_penalty)
+        worst = np.where(self.is_sent_finished, self.beam_scores.min(axis=1, keepdims=True), _NEG)
+        self.unsat = self.unsat & (best_run > worst).any(axis=-1, keepdims=True)
+        # _beam_search_has_unfinished_sequences
+        unfinished = self.unsat.any() and not (self.is_sent_finished.all() and self.early_stopping is True) and not hits.all()
+        self.done = not unfinished
+        return _take(beam, nxt), _take(tok, nxt)
+
+    def finalize(self, num_return_sequences=1):
+        """(sequences int64 [B * nrs, T_out], scores fp32 [B * nrs], beam_indices int32 [B * nrs, T_out]), cropped as HF crops them."""
+        n = int(num_return_sequences)
+        seq = self.sequences[:, :n].reshape(self.B * n, self.T)
+        sc = self.beam_scores[:, :n].reshape(self.B * n)
+        bi = self.beam_indices[:, :n].reshape(self.B * n, self.T)
+        T_out = int((bi != -1).sum(axis=1).max()) if bi.size else 0
+        return seq[:, :T_out].copy(), sc.copy(), bi[:, :T_out].copy()
+
+
+def beam_generate(engine, input_ids, attention_mask, images, image_sizes, cfg):
+    """Beam search over the engine (LlavaLlamaForCausalLM.generate_beams); cfg from parse_beam_kwargs.  The prompts are prefilled once,
+    prompt b into cache row b * num_beams of a KVCache of B * num_beams rows; every beam then appends its K|V to its own row and decode
+    attention follows the beam's ancestry (engine.decode_step(beams=)), so no cache position is ever copied.  Per step, on the device:
+    log-softmax of the raw scores, the logits processors (history: the running beams' tokens), the running score added inside the
+    top-K; one device-to-host copy of the B * K values and indices feeds BeamState on the host."""
+    from . import ops
+    ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids)
+    if ids.ndim == 1:
+        ids = ids[None]
+    am = cfg.attention_mask
+    am = None if am is None else np.asarray(am.cpu() if torch.is_tensor(am) else am)
+    engine._check_generation()
+    B, nb, K, V, dev = ids.shape[0], cfg.num_beams, cfg.K, engine.vocab, engine.device
+    rows = B * nb
+    imgs = list(images) if images is not None else []
+    plan = engine.plan(ids, am, None, imgs, image_sizes)
+    lens = plan["lens"].astype(np.int64)
+    T = new_token_budget(cfg, int(plan["S"]))
+    lp = LogitsProcessors(cfg, V, int(plan["S"]))
+    st = BeamState(B, nb, V, T, cfg.eos, cfg.length_penalty, cfg.early_stopping, cfg.fill)
+    scores, raw, cache = [], [], None
+    if T > 0:
+        if K > nb * V:
+            raise ValueError(f"generate_beams: {K} candidates per step do not exist on {nb} beams over a vocabulary of {V} ids")
+        if rows > 65535:
+            raise ValueError(f"generate_beams: {B} prompts x {nb} beams = {rows} cache rows; a decode step takes at most 65535")
+        L_max = int(lens.max()) + T
+        need, free = engine.kv_cache_bytes(rows, L_max), engine.free_device_bytes()
+        if free is not None and need > free:
+            raise ValueError(f"generate_beams: the KV cache of {B} prompts x {nb} beams x {L_max} positions needs {need} bytes, but only "
+                             f"{free} bytes of device memory are free: lower num_beams, the batch or the token budget")
+        cache = engine.new_kv_cache(rows, L_max)
+        roots = np.arange(B) * nb
+        _, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, cache=cache, slots=roots)
+        cache.lens[:] = np.repeat(lens, nb)
+        logits = logits.repeat_interleave(nb, dim=0)              # step 0 is not special: every beam carries the prefill scores
+        geo = SimpleNamespace(prefix_row=engine._dev(np.repeat(roots, nb).astype(np.int32)),
+                              prefix_len=engine._dev(np.repeat(lens, nb).astype(np.int32)), tail_src=None, tail_cols=0)
+        tail = np.zeros((rows, T), dtype=np.int32)
+        ws = ops.beam_topk_workspace(B, nb, V, K, dev)
+        hist = None
+        keep_scores = cfg.output_scores and cfg.return_dict
+        for t in range(T):
+            if cfg.output_logits:
+                raw.append(logits.clone())
+            ops.log_softmax_rows(logits, V)
+            if lp.active:                 # in place on the log-probs; all rows share t, the argmax it returns is not used
+                ops.logits_process_argmax(logits, V, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
+            if cfg.output_scores:
+                scores.append(logits.clone())
+            top = ops.beam_topk(logits, V, nb, engine._dev(st.running_scores.reshape(-1)), K, ws=ws).cpu()     # the step's one sync
+            vals, flat = top[0].view(torch.float32).numpy(), top[1].numpy()
+            hit = None
+            if cfg.stopping_criteria:
+                cand = torch.from_numpy(st.candidates(flat)).to(dev)
+                hit = np.zeros(B * K, dtype=bool)
+                for c in cfg.stopping_criteria:
+                    r = c(cand, tuple(scores) if keep_scores else None)
+                    r = r.detach().cpu().numpy() if torch.is_tensor(r) else np.asarray(r)
+                    hit |= np.broadcast_to(r.astype(bool).reshape(-1) if r.ndim else r.astype(bool), hit.shape)
+            parent, tok = st.step(vals, flat, hit)
+            if st.done:
+                break
+            tail = advance_tail_src(tail, (roots[:, None] + parent).reshape(-1), t)
+            geo.tail_src, geo.tail_cols = engine._dev(tail), t + 1
+            if lp.active:                 # the running beams' tokens, re-gathered by parent inside BeamState
+                hist = engine._dev(st.running_sequences.reshape(rows, T).astype(np.int32))
+            logits = engine.decode_step(cache, tok.reshape(-1), beams=geo)
+    seq, sc, bi = st.finalize(cfg.num_return_sequences)
+    seq = torch.from_numpy(seq).to(dev)
+    if cfg.return_dict:
+        return GenerateBeamDecoderOnlyOutput(sequences=seq, sequences_scores=torch.from_numpy(sc).to(dev) if cfg.output_scores else None,
+                                             scores=tuple(scores) if cfg.output_scores else None,
+                                             logits=tuple(raw) if cfg.output_logits else None, beam_indices=torch.from_numpy(bi).to(dev),
+                                             past_key_values=cache)
+    return seq

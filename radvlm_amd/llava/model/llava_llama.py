@@ -316,6 +316,28 @@ class LlavaLlamaForCausalLM:
                                  config_pad=getattr(self.config, "pad_token_id", None))
         return generate_batch(self.engine, inputs, images, image_sizes, cfg, max_batch_size=max_batch_size, return_logprobs=return_logprobs)
 
+    @torch.no_grad()
+    def generate_beams(self, inputs=None, images=None, image_sizes=None, num_beams=1, modalities=("image",), **kwargs):
+        """Beam search (HF generate(num_beams=...) on the spliced inputs_embeds: transformers 5.x GenerationMixin._beam_search, restated
+        in generation.BeamState).  inputs / images / image_sizes as in generate().  Returns the NEW tokens only, LongTensor
+        [B * num_return_sequences, T_out], hypothesis j of prompt b in row b * num_return_sequences + j, best first, shorter ones
+        filled with pad_token_id (HF's output_fill_value).  Keywords: generate()'s max_new_tokens / max_length, eos_token_id,
+        pad_token_id, attention_mask, stopping_criteria (called once per step with the K = max(2, 1 + n_eos) * num_beams candidates of
+        every prompt, [B * K, t + 1]), use_cache, the logits processors (applied to the log-probs, history: the beam's own tokens),
+        output_scores / output_logits + return_dict_in_generate (.sequences, .sequences_scores, .scores, .logits, .beam_indices); plus
+        num_beams (1 .. 16, K <= 64), num_return_sequences (<= num_beams), length_penalty (1.0) and early_stopping (False, True,
+        "never").  Ties between equal scores go to the lower beam * vocab + token (HF leaves them open).  The KV cache holds B *
+        num_beams rows; the prompt is prefilled once per prompt and never copied, and no cache row is reordered (the engine's decode
+        attention follows each beam's ancestry instead).  do_sample=True (beam sampling), past_key_values, streamers, inputs_embeds
+        and LoRA models raise NotImplementedError.  The training state is not touched."""
+        from ...generation import beam_generate, parse_beam_kwargs
+        cfg = parse_beam_kwargs(dict(kwargs, num_beams=num_beams), lora=bool(self.engine.lora),
+                                config_eos=getattr(self.config, "eos_token_id", None), config_pad=getattr(self.config, "pad_token_id", None))
+        if inputs is None:
+            raise ValueError("generate_beams() needs the prompt token ids (`inputs`)")
+        imgs = None if images is None else (list(images) if not torch.is_tensor(images) else [im for im in images])
+        return beam_generate(self.engine, inputs, cfg.attention_mask, imgs, image_sizes, cfg)
+
     def save_config(self, out_dir):
         """config.json in HF's key vocabulary (what model.config.save_pretrained leaves next to the weights), plus the tower
         geometry under 'mm_vision_geometry' so that the directory is loadable as --model_name_or_path on its own."""

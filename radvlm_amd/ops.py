@@ -773,6 +773,74 @@ def sample_rows(x, n, seed, t, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, w
     return out
 
 
+def attn_decode_beam(q, cache, kv_len, prefix_row, prefix_len, tail_src, H, Hkv, hd, v_off, tail_cols=None, out=None, chunk=128, scale=None):
+    """attn_decode for beams that share cache rows (rv_attn_decode_beam_bf16): query row r reads key position j from cache row
+    prefix_row[r] while j < prefix_len[r], else from tail_src[r, j - prefix_len[r]] (int32 device tensors: [rows], [rows], [rows, >=
+    tail_cols]; tail_src None or tail_cols 0: no tail).  q [rows, H*hd]; cache bf16 [cache_rows, L_max, width]; kv_len int32 [rows].
+    Bit-identical to attn_decode on the gathered cache.  Returns bf16 [rows, H*hd]."""
+    _chk(q), _chk(cache), _chk(kv_len, torch.int32), _chk(prefix_row, torch.int32), _chk(prefix_len, torch.int32)
+    cache_rows, L_max, width = cache.shape
+    rows = q.shape[0]
+    assert q.shape == (rows, H * hd) and q.stride(1) == 1 and cache.is_contiguous()
+    for a in (kv_len, prefix_row, prefix_len):
+        assert a.dim() == 1 and a.numel() == rows and a.is_contiguous()
+    ld_t = 0
+    if tail_src is None:
+        tail_cols = 0
+    else:
+        _chk(tail_src, torch.int32)
+        assert tail_src.dim() == 2 and tail_src.shape[0] == rows and tail_src.stride(1) == 1
+        tail_cols = tail_src.shape[1] if tail_cols is None else int(tail_cols)
+        assert 0 <= tail_cols <= tail_src.shape[1]
+        ld_t = tail_src.stride(0)
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if out is None:
+        out = torch.empty(rows, H * hd, dtype=BF16, device=q.device)
+    nch = (L_max + chunk - 1) // chunk
+    part = torch.empty(rows * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    lib.call("rv_attn_decode_beam_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len, L_max, prefix_row, prefix_len,
+             tail_src if tail_cols else None, ld_t, tail_cols, cache_rows, out, out.stride(0), part, part.numel() * 4, rows, H, Hkv, hd, chunk,
+             float(scale))
+    return out
+
+
+def log_softmax_rows(x, n):
+    """In place: x[r, :n] <- log_softmax(x[r, :n]) for every fp32 row (rv_log_softmax_rows_f32); columns >= n are not touched."""
+    _chk(x, torch.float32)
+    assert x.dim() == 2 and x.stride(1) == 1 and 0 < n <= min(x.shape[1], LOGITS_PROCESS_MAX_N)
+    lib.call("rv_log_softmax_rows_f32", x, x.stride(0), x.shape[0], int(n))
+    return x
+
+
+BEAM_MAX = 16             # beams per prompt (rv_beam_topk_f32)
+BEAM_TOPK_MAX = 64        # candidates kept per prompt and step
+
+
+def beam_topk_workspace(groups, nb, n, K, device):
+    """Scratch for beam_topk at these sizes (int64, never zeroed); calls that share it must run on one stream."""
+    return torch.empty(max(lib.load().rv_beam_topk_ws_bytes(int(groups), int(nb), int(n), int(K)) // 8, 1), dtype=torch.int64, device=device)
+
+
+def beam_topk(x, n, nb, score, K, out=None, ws=None):
+    """The K best of each prompt's nb * n candidates x[g * nb + r, i] + score[g * nb + r] (rv_beam_topk_f32): x fp32 [groups * nb, >= n],
+    score fp32 [groups * nb].  Returns one int32 tensor [2, groups, K]: [0] holds the fp32 values' bits (view(torch.float32)), [1] the
+    flat indices r * n + i; value descending, then index ascending.  One tensor, so one copy brings both to the host."""
+    _chk(x, torch.float32), _chk(score, torch.float32)
+    rows = x.shape[0]
+    assert x.dim() == 2 and x.stride(1) == 1 and 0 < n <= min(x.shape[1], LOGITS_PROCESS_MAX_N)
+    assert 1 <= nb <= BEAM_MAX and rows % nb == 0 and score.numel() == rows and score.is_contiguous()
+    groups = rows // nb
+    assert 1 <= K <= min(BEAM_TOPK_MAX, nb * n)
+    out = torch.empty(2, groups, K, dtype=torch.int32, device=x.device) if out is None else out
+    _chk(out, torch.int32)
+    assert tuple(out.shape) == (2, groups, K) and out.is_contiguous()
+    ws = beam_topk_workspace(groups, nb, n, K, x.device) if ws is None else ws
+    _chk(ws, torch.int64)
+    assert ws.is_contiguous() and ws.numel() * 8 >= lib.load().rv_beam_topk_ws_bytes(groups, nb, int(n), int(K))
+    lib.call("rv_beam_topk_f32", x, x.stride(0), groups, int(nb), int(n), score, int(K), out[0], out[1], ws, ws.numel() * 8)
+    return out
+
+
 def lora_merge(w, A, B, scale):
     """In place: w[N,K] <- bf16(w + scale * B[N,r] @ A[r,K]) (rv_lora_merge_bf16: fp32 sum in a fixed order, one rounding).  w may be a
     row slice of a fused store (any row stride); r <= 256.  Returns w."""

@@ -35,6 +35,12 @@
         # repetition, the two arms alternated three times, medians of medians, and the gate sampled <= greedy + the greedy arm's
         # spread + the cost of the launches sampling adds (10 with the chat default: one launch per sweep and one for the draw in
         # place of the argmax launch) at the step's enqueue rate, greedy step / DECODE_LAUNCHES
+  python tools/decode_bench.py --beams [--geos ..] [--prompt 704] [--new 48] [--out FILE]
+        # beam search: (a) ms per beam step (log-softmax, top-K, the one device-to-host copy, BeamState on the host, the ancestry table
+        # upload, decode_step(beams=)) for num_beams 1, 3, 5 at B = 1 and 8, beside this build's plain decode step (decode_step + argmax)
+        # at batch B * num_beams, the two arms alternated three times on one engine; (b) rv_attn_decode_beam_bf16 with an identity
+        # table vs rv_attn_decode_bf16 on the same cache, device time, interleaved; (c) kv_cache_bytes of the B * num_beams rows, which
+        # a per-step reorder of the cache (HF's reorder_cache) would read and write once per generated token
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -294,6 +300,101 @@ def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None):
         times.append((time.perf_counter() - t0) * 1e3)
     del cache
     return times[warm:]
+
+
+def _beam_loop(eng, ids, nb, new, warm=8):
+    """The steps of generation.beam_generate (no EOS id, so every step runs), each timed from the scores of the previous decode step to
+    the synchronised end of the next one; returns the ms of the steps after `warm`."""
+    from types import SimpleNamespace
+    from radvlm_amd.generation import BeamState, advance_tail_src
+    B, V, dev = ids.shape[0], eng.vocab, eng.device
+    rows = B * nb
+    lens = np.full(B, ids.shape[1], dtype=np.int64)
+    st = BeamState(B, nb, V, new)
+    cache = eng.new_kv_cache(rows, ids.shape[1] + new)
+    roots = np.arange(B) * nb
+    _, logits = eng.prefill(ids, None, None, None, max_new_tokens=new, cache=cache, slots=roots)
+    cache.lens[:] = np.repeat(lens, nb)
+    logits = logits.repeat_interleave(nb, dim=0)
+    geo = SimpleNamespace(prefix_row=eng._dev(np.repeat(roots, nb).astype(np.int32)), prefix_len=eng._dev(np.repeat(lens, nb).astype(np.int32)),
+                          tail_src=None, tail_cols=0)
+    tail = np.zeros((rows, new), dtype=np.int32)
+    ws = ops.beam_topk_workspace(B, nb, V, st.K, dev)
+    times = []
+    for t in range(new - 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ops.log_softmax_rows(logits, V)
+        top = ops.beam_topk(logits, V, nb, eng._dev(st.running_scores.reshape(-1)), st.K, ws=ws).cpu()
+        parent, tok = st.step(top[0].view(torch.float32).numpy(), top[1].numpy())
+        tail = advance_tail_src(tail, (roots[:, None] + parent).reshape(-1), t)
+        geo.tail_src, geo.tail_cols = eng._dev(tail), t + 1
+        logits = eng.decode_step(cache, tok.reshape(-1), beams=geo)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    del cache
+    return times[warm:]
+
+
+def beams_step_ab(geo, prompt, new, reps=3):
+    """(a) and (c): the beam step beside the plain decode step at the same number of rows, one engine per geometry."""
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    recs = []
+    for B in (1, 8):
+        ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+        for nb in (1, 3, 5):
+            wide = np.repeat(ids, nb, axis=0)                        # the plain arm: B * nb independent rows, each with its own prompt copy
+            ts = {"plain": [], "beam": []}
+            _decode_loop(eng, wide, 12)                              # one untimed pass of both arms
+            _beam_loop(eng, ids, nb, 12)
+            for _ in range(reps):
+                ts["plain"].append(float(np.median(_decode_loop(eng, wide, new))))
+                ts["beam"].append(float(np.median(_beam_loop(eng, ids, nb, new))))
+            p, q = float(np.median(ts["plain"])), float(np.median(ts["beam"]))
+            recs.append(dict(geo=geo, mode="beams_step", B=B, num_beams=nb, rows=B * nb, prompt=prompt, new_tokens=new, reps=reps,
+                             plain_ms_per_step=round(p, 3), beam_ms_per_step=round(q, 3), plain_ms_all=[round(v, 3) for v in ts["plain"]],
+                             beam_ms_all=[round(v, 3) for v in ts["beam"]], plain_spread_ms=round(max(ts["plain"]) - min(ts["plain"]), 3),
+                             delta_ms=round(q - p, 3), delta_share=round((q - p) / p, 4),
+                             kv_cache_bytes=eng.kv_cache_bytes(B * nb, prompt + new),
+                             reorder_bytes_per_step_not_moved=2 * eng.kv_cache_bytes(B * nb, prompt + new // 2),
+                             gemv_route=bool(B * nb <= eng.gemv_max_m), kernel_src=_src_hash()))
+    return recs
+
+
+def beams_kernel_ab(geo, prompt, new=48, reps=50):
+    """(b): rv_attn_decode_beam_bf16 with an identity table (prefix in the row itself, every tail entry the row itself) against
+    rv_attn_decode_bf16 on the same cache and queries; device time per launch pair, interleaved."""
+    l = GEOMETRIES[geo]["lm"]
+    H, Hkv = l["heads"], l.get("kv_heads", l["heads"])
+    hd = l["d"] // H
+    kvd = Hkv * hd
+    recs = []
+    for rows in (1, 3, 5, 8, 24, 40):
+        L_max = prompt + new
+        cache = (torch.randn(rows, L_max, 2 * kvd, device="cuda", dtype=torch.float32) * 0.5).to(torch.bfloat16)
+        q = torch.randn(rows, H * hd, device="cuda", dtype=torch.bfloat16)
+        kv_len = torch.full((rows,), prompt + new // 2, dtype=torch.int32, device="cuda")
+        own = torch.arange(rows, dtype=torch.int32, device="cuda")
+        plen = torch.full((rows,), prompt, dtype=torch.int32, device="cuda")
+        tail = own[:, None].expand(rows, new).contiguous()
+        fns = {"plain": lambda: ops.attn_decode(q, cache, kv_len, H, Hkv, hd, kvd),
+               "beam": lambda: ops.attn_decode_beam(q, cache, kv_len, own, plen, tail, H, Hkv, hd, kvd)}
+        assert torch.equal(fns["plain"](), fns["beam"]())
+        ts = {k: [] for k in fns}
+        for _ in range(reps):
+            for k, f in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                f()
+                e1.record()
+                e1.synchronize()
+                ts[k].append(e0.elapsed_time(e1) * 1e3)
+        a, b = float(np.median(ts["plain"])), float(np.median(ts["beam"]))
+        recs.append(dict(geo=geo, mode="beams_kernel_ab", rows=rows, H=H, Hkv=Hkv, hd=hd, kv_len=prompt + new // 2, L_max=L_max, reps=reps,
+                         plain_us=round(a, 2), beam_us=round(b, 2), plain_p10_p90=[round(float(np.percentile(ts["plain"], p)), 2) for p in (10, 90)],
+                         beam_p10_p90=[round(float(np.percentile(ts["beam"], p)), 2) for p in (10, 90)], ratio=round(b / a, 3),
+                         kernel_src=_src_hash()))
+    return recs
 
 
 def processors_ab(geo, B, prompt, new, reps=3):
@@ -648,6 +749,7 @@ def main():
     ap.add_argument("--w8-trace", action="store_true")
     ap.add_argument("--w8-quality", action="store_true")
     ap.add_argument("--sample", action="store_true")
+    ap.add_argument("--beams", action="store_true")
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -665,6 +767,9 @@ def main():
         recs = [r for g in a.geos.split(",") for r in w8_trace(g, a.prompt, a.new)]
     elif a.sample:
         recs = sample_kernel_ab() + [r for g in a.geos.split(",") for r in sample_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new)]
+    elif a.beams:
+        new = a.new if a.new != ap.get_default("new") else 48
+        recs = [r for g in a.geos.split(",") for r in beams_kernel_ab(g, a.prompt, new) + beams_step_ab(g, a.prompt, new, reps=min(a.reps, 3))]
     elif a.batch_eval:
         recs = [r for g in a.geos.split(",") for r in batch_eval(g, n=a.requests, prompt=a.prompt, reps=min(a.reps, 3))]
     elif a.batch_kernel_ab:
