@@ -471,6 +471,23 @@ int rv_beam_topk_f32(const float* x, int64_t ld, int groups, int nb, int n, cons
 /* Host function: the bytes of scratch rv_beam_topk_f32 needs. */
 int64_t rv_beam_topk_ws_bytes(int groups, int nb, int n, int K);
 
+/* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens=), radvlm_amd/csrc/lookup.hip) ----------------------------------------
+ * The reference reaches it through HF generate(prompt_lookup_num_tokens=k) (HF:generation/candidate_generator.py
+ * PromptLookupCandidateGenerator -> _assisted_decoding): k tokens drafted from n-gram repeats of the sequence are verified by one
+ * forward pass of k + 1 rows.  Here that pass is a decode step of R = k + 1 rows on one cache row (LlavaEngine.verify_step). */
+/* rv_attn_decode_bf16 for R consecutive query rows per sequence: query row b * R + i (0 <= i < R, 1 <= R <= 32) attends the keys
+ * [0, min(kv_len0[b] + i, L_max)) of sequence b (kv_len0: int32 [B], device), whose own K|V rows are in the cache already.  hd 64 or
+ * 128, up to 8 q heads per kv head, `chunk` as there; part: B * R * H * ceil(L_max / chunk) * (hd + 2) floats.  A workgroup takes a
+ * chunk of one kv head for a group of rows (16 / (H / Hkv) of them) and loads and converts each K and V fragment once for the group;
+ * a key a row may not see is skipped, never multiplied by zero, so positions at or past a row's key count may hold anything (NaN
+ * included).  Chunking by absolute key position, the key-to-lane assignment, each lane's summation order, the shuffle trees, the
+ * wave 0..3 merge and the combine's chunk order are rv_attn_decode_bf16's: every row of out is BIT-IDENTICAL to rv_attn_decode_bf16
+ * run on that row alone with kv_len = kv_len0[b] + i.  No global atomics.  R outside 1 .. 32, a short `part`, ld_q < H*hd or
+ * ld_o < H*hd are refused (RV_ERR_ARG), as there. */
+int rv_attn_decode_verify_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len0,
+                               int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int R, int H, int Hkv, int hd,
+                               int chunk, float scale, void* stream);
+
 /* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
  * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any
  * grid and any placement of W.  W: bf16 rows of ldw elements (a row slice of a fused q|k|v or gate|up store is fine), 16-byte aligned,

@@ -834,9 +834,11 @@ class LlavaEngine:
     # (dequantised) weights.  The two are bit-identical, so this switch changes time only: it is the A/B arm of tools/decode_bench.py --w8.
     w8_decode = True
 
-    def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16, w8=None):
+    def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16, w8=None, skinny=False):
+        """skinny: the skinny kernel whatever the row count (<= ops.GEMV_MAX_M) and the weight's height -- verify_step, whose rows must
+        carry the bits of the one-row decode step, which always takes that kernel."""
         max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
-        if x.shape[0] <= min(max_m, ops.GEMV_MAX_M):
+        if skinny or x.shape[0] <= min(max_m, ops.GEMV_MAX_M):
             if w8 is not None:
                 return ops.gemv_w8(x, w8[0], w8[1], w.shape[1], bias=bias, residual=residual, out_dtype=out_dtype)
             return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
@@ -997,6 +999,78 @@ class LlavaEngine:
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
         cache.lens += 1
+        return logits[:, :self.vocab]
+
+    # verify_step's attention.  rv_attn_decode_verify_bf16 reads a chunk once for a group of 16 / G rows; the same rows through
+    # rv_attn_decode_beam_bf16 (prefix_row 0, prefix_len L_max) give the same bits from R times as many, smaller workgroups.  Same-box
+    # A/B on the two 7B head shapes, R = 4, 8, 16, 32 at 704 and 7,603 keys (DESIGN.md 5b "Prompt-lookup decoding",
+    # profiles/decode_bench.jsonl mode lookup_kernel_ab): with one q head per kv head (llava15) the new kernel wins at 7,603 keys
+    # (0.43 - 0.72x) and at R = 32, and loses at 704 keys with R <= 16 (1.25 - 1.40x: too few workgroups to fill the machine); with
+    # 7 q heads per kv head (Qwen2: 2 rows per group) it loses in every cell (1.19 - 1.51x).  The losing cells go to the beam kernel;
+    # between two measured cells the nearer one (in log distance) decides: R 16 | 32 -> 23, keys 704 | 7,603 -> 2,313.  Group sizes
+    # that were not measured (2 .. 6, 8) sit between the two measured shapes, on the slope of the losing one (fewer rows per group, more
+    # serial work per workgroup): they take the beam kernel until a measurement says otherwise.  verify_route: None = this table;
+    # "verify" / "beam" force one kernel.
+    verify_route = None
+
+    def _verify_use_beam(self, R, keys):
+        if self.verify_route is not None:
+            return self.verify_route == "beam"
+        G = self.l["heads"] // self.Hkv
+        return G > 1 or (R < 23 and keys < 2313)
+
+    def verify_step(self, cache, tokens):
+        """Prompt-lookup verification on a B = 1 cache: tokens [R] (1 <= R <= 32; the last emitted token, then R - 1 drafted ones) are
+        fed at positions cache.lens[0] .. cache.lens[0] + R - 1 -> fp32 logits [R, vocab], row i being bit for bit what decode_step
+        returns at that position after tokens[:i] were fed one by one.  decode_step's sequence on R rows: RMSNorm, q|k|v, RoPE at each
+        row's position, one launch that writes the R K|V rows into the cache row, attention where row i sees the keys
+        [0, lens[0] + i + 1) (rv_attn_decode_verify_bf16: the chunk's K / V read once for a group of rows), o_proj + residual,
+        RMSNorm, gate|up, SwiGLU, down + residual, final norm, lm_head.  Every product takes the skinny kernel (a row's bits do not
+        depend on M there), the lm_head included whatever its height.  cache.lens is NOT advanced: the caller adds the number of
+        tokens it emits; the K|V rows of rejected drafts stay past lens as stale rows, which every kernel ignores."""
+        self._check_generation()
+        l = self.l
+        d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
+        hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
+        if cache.B != 1:
+            raise ValueError(f"verify_step() takes a cache of one sequence, this one holds {cache.B}")
+        tok = tokens.to(self.device, torch.int32) if torch.is_tensor(tokens) else self._dev(np.asarray(tokens, dtype=np.int32))
+        R, n0, L_max = int(tok.numel()), int(cache.lens[0]), cache.L_max
+        if not 1 <= R <= min(ops.GEMV_MAX_M, ops.VERIFY_MAX_R):
+            raise ValueError(f"verify_step() takes 1 .. {min(ops.GEMV_MAX_M, ops.VERIFY_MAX_R)} tokens, got {R}")
+        if n0 + R > L_max:
+            raise ValueError(f"the KV cache holds {L_max} positions; {R} tokens from position {n0} do not fit")
+        use_beam = self._verify_use_beam(R, n0 + 1)
+        # one upload: positions, key counts, the beam route's prefix row and prefix length, kv_len0, then the cache slots as int64
+        off = (4 * R + 2) // 2 * 2
+        host = np.zeros(off + 2 * R, dtype=np.int32)
+        host[:R] = n0 + np.arange(R)
+        host[R:2 * R] = n0 + 1 + np.arange(R)
+        host[3 * R:4 * R] = L_max
+        host[4 * R] = n0 + 1
+        host[off:].view(np.int64)[:] = n0 + np.arange(R)
+        hd_ = self._dev(host)
+        pos, kv_len, zero, plen, kv0 = hd_[:R], hd_[R:2 * R], hd_[2 * R:3 * R], hd_[3 * R:4 * R], hd_[4 * R:4 * R + 1]
+        slots = hd_[off:].view(torch.int64)
+        cs = self.rope_table(L_max)
+        x = ops.gather_rows(tok.contiguous().view(-1), d, self.W("model.embed_tokens.weight"))
+        for i in range(L):
+            lv, q8 = self._layer_views(i), self._layer_w8(i)
+            h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), w8=q8.get("qkv"), skinny=True)
+            ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
+            kv = cache.layers[i]
+            kv.view(L_max, 2 * kvd).index_copy_(0, slots, qkv[:, d:])
+            if use_beam:
+                attn = ops.attn_decode_beam(qkv[:, :d], kv, kv_len, zero, plen, None, H, Hkv, hd, kvd, chunk=cache.chunk)
+            else:
+                attn = ops.attn_decode_verify(qkv[:, :d], kv, kv0, R, H, Hkv, hd, kvd, chunk=cache.chunk)
+            x_mid = self._decode_linear(attn, lv["o"], residual=x, w8=q8.get("o"), skinny=True)
+            h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], w8=q8.get("gu"), skinny=True), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid, w8=q8.get("down"), skinny=True)
+        hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
+        logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32, skinny=True)
         return logits[:, :self.vocab]
 
     def extend(self, cache, input_ids, attention_mask=None, images=None, image_sizes=None, reuse=None, max_new_tokens=0, plan=None):

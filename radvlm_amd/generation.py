@@ -26,6 +26,9 @@ _PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "bad_words_ids", "m
 _ACCEPTED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "attention_mask", "stopping_criteria", "use_cache", "do_sample",
              "num_beams", "streamer", "output_scores", "output_logits", "return_dict_in_generate", "num_return_sequences", "position_ids",
              "inputs_embeds", "past_key_values", "seed") + _PROCESSORS + _IGNORED_WHEN_GREEDY
+# prompt-lookup decoding (HF's names): generate() alone takes them, generate_batch() and generate_beams() reject them as unknown
+_LOOKUP = ("prompt_lookup_num_tokens", "max_matching_ngram_size")
+LOOKUP_MAX_TOKENS = 31        # k drafted tokens are verified as k + 1 rows, and the skinny GEMM takes ops.GEMV_MAX_M = 32
 
 
 class GenerateDecoderOnlyOutput(SimpleNamespace):
@@ -36,12 +39,13 @@ class GenerateDecoderOnlyOutput(SimpleNamespace):
         return getattr(self, k)
 
 
-def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
+def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, lookup=False):
     """Validate generate() keyword arguments; returns a namespace with the normalised settings (.sampling: None for greedy, else the
     warper settings and the seed as given; sampling_seeds() resolves it per row).  Raises NotImplementedError for what this build does
     not do (do_sample=True without seed=, beam search, streamers, caller-supplied inputs_embeds, LoRA engines) and TypeError for unknown
-    names."""
-    unknown = sorted(k for k in kwargs if k not in _ACCEPTED)
+    names.  lookup: also take prompt_lookup_num_tokens / max_matching_ngram_size (.lookup: None, or .k and .max_ngram; .drafter: None,
+    greedy_generate then builds a PromptLookupDrafter; a test or a benchmark may set another object with propose(seq))."""
+    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and not (lookup and k in _LOOKUP))
     if unknown:
         raise TypeError(f"generate() got unexpected keyword arguments {unknown}")
     if kwargs.get("inputs_embeds") is not None:
@@ -82,8 +86,24 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
                            stopping_criteria=crit, output_scores=bool(kwargs.get("output_scores", False)),
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
-                           past_key_values=pkv, sampling=_parse_sampling(kwargs),
+                           past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
                            **_parse_processors(kwargs, eos))
+
+
+def _parse_lookup(kwargs):
+    """prompt_lookup_num_tokens (an int in 1 .. 31) and max_matching_ngram_size (an int >= 1, HF's default 2); None when unset."""
+    k = kwargs.get("prompt_lookup_num_tokens")
+    if k is None:
+        return None
+    if not _is_int(k) or not 1 <= k <= LOOKUP_MAX_TOKENS:
+        raise ValueError(f"`prompt_lookup_num_tokens` has to be an integer in [1, {LOOKUP_MAX_TOKENS}], but is {k!r}")
+    ng = kwargs.get("max_matching_ngram_size")
+    ng = 2 if ng is None else ng
+    if not _is_int(ng) or ng < 1:
+        raise ValueError(f"`max_matching_ngram_size` has to be a strictly positive integer, but is {ng!r}")
+    if kwargs.get("do_sample"):
+        raise NotImplementedError("prompt_lookup_num_tokens with do_sample=True: speculative sampling is not implemented")
+    return SimpleNamespace(k=int(k), max_ngram=int(ng))
 
 
 def _is_int(v):
@@ -450,6 +470,120 @@ class GenerationCache:
         self.engine, self.weights_version = engine, engine.weights_version
 
 
+# ------------------------------------------------------------------------------------------------ prompt-lookup decoding
+class PromptLookupDrafter:
+    """HF's PromptLookupCandidateGenerator.get_candidates (called with logits_processor=None) on the host: the draft is the continuation
+    of an earlier occurrence of the sequence's last n-gram.  n runs from min(max_ngram, len - 1) down to 1; the first (leftmost)
+    occurrence with a non-empty continuation wins; the continuation is at most k tokens, ends where the sequence ends and is cut before
+    its first EOS id (a match cut to nothing ends the search, as in HF).  It is also cut before the first id outside [0, vocab), which
+    is how an image placeholder (a negative id, left in place so that the text after it can still match) never becomes a draft."""
+
+    def __init__(self, k, max_ngram=2, eos=(), vocab=None):
+        if not _is_int(k) or k < 1 or not _is_int(max_ngram) or max_ngram < 1:
+            raise ValueError("Invalid max_matching_ngram_size or num_output_tokens")
+        self.k, self.max_ngram, self.vocab = int(k), int(max_ngram), None if vocab is None else int(vocab)
+        self.eos = np.asarray(sorted(int(e) for e in (eos if eos is not None else [])), dtype=np.int64)
+
+    def propose(self, seq):
+        """seq: the prompt ids as passed (masked positions removed) followed by the emitted tokens.  Returns the draft, int64 [0 .. k]."""
+        seq = np.asarray(seq, dtype=np.int64).reshape(-1)
+        n = seq.shape[0]
+        for ng in range(min(self.max_ngram, n - 1), 0, -1):
+            win = np.lib.stride_tricks.sliding_window_view(seq, ng)
+            idx = np.flatnonzero((win[:n - ng] == seq[n - ng:]).all(1))          # windows with at least one token after them
+            if idx.size == 0:
+                continue
+            start = int(idx[0]) + ng
+            out = seq[start:min(start + self.k, n)]
+            if self.eos.size:
+                hit = np.flatnonzero(np.isin(out, self.eos))
+                if hit.size:
+                    out = out[:int(hit[0])]
+            return clamp_draft(out, self.k, self.vocab)
+        return np.zeros(0, dtype=np.int64)
+
+
+def clamp_draft(draft, limit, vocab=None):
+    """The draft cut to `limit` tokens and before its first id outside [0, vocab) (negative ids when vocab is None): what the accept
+    loop applies to any drafter's proposal, so that no token past the budget, no position past the cache's L_max and no id without an
+    embedding row is ever fed."""
+    d = np.asarray(draft, dtype=np.int64).reshape(-1)[:max(int(limit), 0)]
+    bad = np.flatnonzero(d < 0) if vocab is None else np.flatnonzero((d < 0) | (d >= vocab))
+    return d[:int(bad[0])].copy() if bad.size else d.copy()
+
+
+def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw):
+    """The accept loop of prompt-lookup decoding on one sequence, from the prompt pass's logits to the end of generation.  Each round
+    holds fp32 logits [R, vocab]: row 0 from feeding the last emitted token, row i from feeding draft i - 1 after it, so row i is the
+    plain loop's step t + i provided the drafts before it were right.  The R token choices run in one launch (rv_argmax_rows_f32, or
+    rv_logits_process_argmax_rows_f32 with row i at step t + i reading the history `emitted + drafts[:i]`, its begin / EOS bans composed
+    per row) and come to the host in one copy; drafts are accepted while draft[i] == choice[i], and the round emits them and the
+    choice after them through GreedyState.step, one token at a time with that token's own score row, stopping at the first EOS, at the
+    budget or where a criterion says so.  The next round feeds the last emitted token and a new draft: verify_step, or decode_step when
+    the draft is empty.  cache.lens advances by the tokens emitted, so it always counts the prompt and every emitted token but the
+    last; the K|V rows of rejected drafts stay past it.  Returns dict(steps=, drafted=, accepted=): engine steps after the prompt pass,
+    draft tokens fed and draft tokens that matched."""
+    from . import ops
+    dev, V = engine.device, engine.vocab
+    stats = dict(steps=0, drafted=0, accepted=0)
+    seq = [int(v) for v in prompt_ids]
+    hist = None
+    if lp.active:
+        hist = torch.zeros(1, T, dtype=torch.int32, device=dev)
+        i32 = lambda ids: torch.tensor(ids, dtype=torch.int32, device=dev) if ids else None
+        bans = (i32(sorted(set(lp.suppress) | set(lp.one))), i32(sorted(set(lp.begin))), i32(sorted(set(lp.eos))))
+        btok, boff = lp.bad_csr()
+        bad = (torch.from_numpy(btok).to(dev), torch.from_numpy(boff).to(dev)) if lp.multi else (None, None)
+    draft = np.zeros(0, dtype=np.int64)
+    t, fed = 0, False                      # fed: the round's rows come from a step that wrote K|V rows (every round but the first)
+    while True:
+        R = 1 + draft.shape[0]
+        if cfg.output_logits:
+            raw_rows = logits.clone()
+        if lp.active:
+            # one upload: slot, step and EOS minimum of every row, then the drafts
+            info = engine._dev(np.stack([np.zeros(R), t + np.arange(R), np.full(R, lp.min_new), np.append(draft, 0)]).astype(np.int32))
+            if R > 1:                      # the drafts go behind the emitted tokens: row i reads hist[0, :t + i]
+                hist[0, t:t + R - 1] = info[3, :R - 1]
+            nxt = ops.logits_process_argmax_rows(logits, V, hist, info[0], info[1], info[2], lp.penalty, lp.ngram, *bans, *bad)
+            hist[0, t:t + R] = nxt         # the choices: the drafts while they are accepted, then the token after them
+        else:
+            nxt = ops.argmax_rows(logits, V)
+        if cfg.output_scores:
+            score_rows = logits.clone()
+        choice = np.asarray(nxt.cpu() if torch.is_tensor(nxt) else nxt, dtype=np.int64).reshape(-1)
+        a = 0
+        while a < R - 1 and draft[a] == choice[a]:
+            a += 1
+        stats["drafted"] += R - 1
+        stats["accepted"] += a
+        n_emit = 0
+        for i in range(a + 1):
+            if cfg.output_logits:
+                raw.append(raw_rows[i:i + 1])
+            if cfg.output_scores:
+                scores.append(score_rows[i:i + 1])
+            st.step(choice[i:i + 1], logits[i:i + 1], device=dev)
+            seq.append(int(choice[i]))
+            n_emit += 1
+            t += 1
+            if st.all_done or t == T:
+                break
+        if fed:
+            cache.lens += n_emit
+        if st.all_done or t == T:
+            return stats
+        room = min(T - t - 1, cache.L_max - int(cache.lens[0]) - 1)
+        draft = clamp_draft(cfg.drafter.propose(np.asarray(seq, dtype=np.int64)), room, V) if room > 0 else np.zeros(0, dtype=np.int64)
+        if draft.shape[0]:
+            logits = engine.verify_step(cache, np.concatenate([[seq[-1]], draft]))
+        else:
+            logits = engine.decode_step(cache, np.asarray([seq[-1]]))
+            cache.lens -= 1                # decode_step counts the token it was fed; this loop counts it once the round has emitted
+        stats["steps"] += 1
+        fed = True
+
+
 def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg):
     """prefill once, then decode_step per token until every row has finished or the budget is spent.  With cfg.past_key_values (a
     GenerationCache) the prompt pass reuses what the cache holds (LlavaEngine.extend; an empty cache: prefill as without one) and the
@@ -466,6 +600,12 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     gc = cfg.past_key_values
     if gc is not None:
         gc._bind(engine, B)
+    lookup = getattr(cfg, "lookup", None) is not None or getattr(cfg, "drafter", None) is not None
+    if lookup and B != 1:
+        raise ValueError(f"prompt_lookup_num_tokens takes one prompt row (HF's assisted generation is batch-size-1 too), got {B}")
+    if lookup and cfg.sampling is not None:
+        raise NotImplementedError("prompt_lookup_num_tokens with do_sample=True: speculative sampling is not implemented")
+    lookup_stats = dict(steps=0, drafted=0, accepted=0)
     st = GreedyState(B, cfg)
     scores = []
     dev = engine.device
@@ -485,7 +625,7 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             sm_t = torch.arange(T, dtype=torch.int32, device=dev)[:, None].expand(T, B).contiguous()     # row t: every row at step t
             sm_write = cfg.output_scores or bool(cfg.stopping_criteria)
         # the tokens generated so far, pads of finished rows included (HF's input_ids of inputs_embeds generation: no prompt)
-        hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active else None
+        hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active and not lookup else None      # the accept loop keeps its own
         sm_ws = ops.sample_rows_workspace(B, dev) if sm is not None else None      # the sampler's scratch, once per call
         if gc is None:
             cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T)
@@ -500,7 +640,13 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                 kv = None
             cache, logits = engine.extend(kv, ids, am, images, image_sizes, reuse=reuse, max_new_tokens=T, plan=plan)
             del kv
-        for t in range(T):
+        if lookup:
+            if cfg.drafter is None:
+                cfg.drafter = PromptLookupDrafter(cfg.lookup.k, cfg.lookup.max_ngram, cfg.eos, engine.vocab)
+            prompt_ids = ids[0] if am is None else ids[0][np.asarray(am).reshape(B, -1)[0].astype(bool)]
+            lookup_stats = _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
+        plain_steps = 0 if lookup else T     # the accept loop above has run the whole generation
+        for t in range(plain_steps):
             if cfg.output_logits:
                 raw.append(logits.clone())
             if lp.active:                 # in place: logits become HF's processed scores
@@ -526,8 +672,11 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
         del cache
     seq = torch.from_numpy(st.sequences()).to(dev)
     if cfg.return_dict:
-        return GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
-                                         logits=tuple(raw) if cfg.output_logits else None, past_key_values=cfg.past_key_values)
+        out = GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
+                                        logits=tuple(raw) if cfg.output_logits else None, past_key_values=cfg.past_key_values)
+        if lookup:
+            out.lookup_stats = lookup_stats
+        return out
     return seq
 
 

@@ -285,11 +285,19 @@ class LlavaLlamaForCausalLM:
         seed= raises NotImplementedError: draws from torch's global generator are not implemented.  With do_sample=False the sampling
         keywords are accepted and ignored, as in HF; seed= without do_sample=True is a ValueError.  typical_p, epsilon_cutoff and
         eta_cutoff (at a non-default value), beam search, num_return_sequences > 1, streamers, inputs_embeds and LoRA models raise
-        NotImplementedError.  The training state (weights, optimizer, RNG counters) is
-        not touched."""
+        NotImplementedError.
+        Prompt-lookup decoding: prompt_lookup_num_tokens=k (an int, 1 .. 31; HF's name) drafts up to k tokens per step from n-gram
+        repeats of the prompt and of the tokens generated so far (HF's PromptLookupCandidateGenerator rule; max_matching_ngram_size,
+        default 2) and verifies them in one k + 1 row engine step (LlavaEngine.verify_step).  The result -- sequences, scores, logits,
+        what a GenerationCache holds afterwards -- is bit for bit that of the same call without it, in fewer steps when the drafts
+        are right; with return_dict_in_generate the output gains .lookup_stats = dict(steps=, drafted=, accepted=).  One prompt row
+        only (ValueError otherwise, HF's assisted generation is batch-size-1 too); with do_sample=True NotImplementedError; k outside
+        1 .. 31 or a non-int ValueError.  Every other greedy keyword keeps its meaning; stopping criteria are called once per emitted
+        token, in order, with that token's own score row.
+        The training state (weights, optimizer, RNG counters) is not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
-                                    config_pad=getattr(self.config, "pad_token_id", None))
+                                    config_pad=getattr(self.config, "pad_token_id", None), lookup=True)
         if inputs is None:
             raise ValueError("generate() needs the prompt token ids (`inputs`)")
         imgs = None if images is None else (list(images) if not torch.is_tensor(images) else [im for im in images])

@@ -804,6 +804,29 @@ def attn_decode_beam(q, cache, kv_len, prefix_row, prefix_len, tail_src, H, Hkv,
     return out
 
 
+VERIFY_MAX_R = 32         # query rows per sequence of attn_decode_verify (rv_attn_decode_verify_bf16)
+
+
+def attn_decode_verify(q, cache, kv_len0, R, H, Hkv, hd, v_off, out=None, chunk=128, scale=None):
+    """attn_decode for R consecutive query rows per sequence (rv_attn_decode_verify_bf16): q [B * R, H*hd] rows, row b * R + i attends
+    the keys [0, min(kv_len0[b] + i, L_max)) of cache row b (bf16 [B, L_max, width], as attn_decode); kv_len0 int32 [B] (device).  Each
+    K / V fragment is read once for a group of rows.  Every row is bit-identical to attn_decode on that row alone with
+    kv_len = kv_len0[b] + i.  Returns bf16 [B * R, H*hd]."""
+    _chk(q), _chk(cache), _chk(kv_len0, torch.int32)
+    B, L_max, width = cache.shape
+    R = int(R)
+    assert q.shape == (B * R, H * hd) and q.stride(1) == 1 and cache.is_contiguous() and kv_len0.numel() == B and kv_len0.is_contiguous()
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if out is None:
+        out = torch.empty(B * R, H * hd, dtype=BF16, device=q.device)
+    assert out.shape == (B * R, H * hd) and out.stride(1) == 1
+    nch = (L_max + chunk - 1) // chunk
+    part = torch.empty(B * R * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    lib.call("rv_attn_decode_verify_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len0, L_max, out, out.stride(0), part,
+             part.numel() * 4, B, R, H, Hkv, hd, chunk, float(scale))
+    return out
+
+
 def log_softmax_rows(x, n):
     """In place: x[r, :n] <- log_softmax(x[r, :n]) for every fp32 row (rv_log_softmax_rows_f32); columns >= n are not touched."""
     _chk(x, torch.float32)

@@ -41,6 +41,16 @@
         # at batch B * num_beams, the two arms alternated three times on one engine; (b) rv_attn_decode_beam_bf16 with an identity
         # table vs rv_attn_decode_bf16 on the same cache, device time, interleaved; (c) kv_cache_bytes of the B * num_beams rows, which
         # a per-step reorder of the cache (HF's reorder_cache) would read and write once per generated token
+  python tools/decode_bench.py --lookup [--geos ..] [--prompt 704] [--new 128] [--out FILE]
+        # prompt-lookup decoding: (a) generate() at B = 1 plain vs prompt_lookup_num_tokens = 3, 7, 15 on one engine, bf16 and then int8
+        # weights, every arm run once untimed and then three times interleaved, ms per emitted token after the prompt pass (the call's
+        # wall time less that of the same call with max_new_tokens=1), medians over the three; the drafter is injected: an oracle (the
+        # plain run's own continuation: k + 1 tokens per step, the ceiling), one that is never right (the cost of a wasted verify
+        # step, the floor) and the real PromptLookupDrafter on this random-weight model (labelled as such: it says nothing about a
+        # trained checkpoint); the break-even acceptance the floor implies; (b) rv_attn_decode_verify_bf16 vs the same R rows through
+        # rv_attn_decode_beam_bf16 (prefix_row 0, prefix_len L_max: the same bits) for R = 4, 8, 16, 32 at 704 and 7603 keys, device
+        # time, interleaved, three medians per arm
+  python tools/decode_bench.py --lookup-kernel-ab [--geos ..]   # (b) alone
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -397,6 +407,121 @@ def beams_kernel_ab(geo, prompt, new=48, reps=50):
     return recs
 
 
+class _ScriptDrafter:
+    """Benchmark drafters: proposes the plain run's own next k tokens (right=True: every draft is accepted) or tokens that differ
+    from them (right=False: none is)."""
+
+    def __init__(self, ref, prompt_len, k, right, vocab):
+        self.ref, self.P, self.k, self.right, self.V = np.asarray(ref, dtype=np.int64), prompt_len, k, right, vocab
+
+    def propose(self, seq):
+        t = len(seq) - self.P
+        d = self.ref[t:t + self.k]
+        return d if self.right else (d + 1) % self.V
+
+
+def lookup_e2e(geo, prompt, new, reps=3, ks=(3, 7, 15)):
+    """(a) of --lookup: one engine per geometry, bf16 weights and then quantize_decoder_()."""
+    from radvlm_amd.generation import greedy_generate, parse_generate_kwargs
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    ids = np.random.default_rng(0).integers(0, eng.vocab, (1, prompt))
+    recs = []
+
+    def call(n, k=None, drafter=None):
+        kw = dict(max_new_tokens=n, eos_token_id=None, return_dict_in_generate=True)
+        if k is not None:
+            kw["prompt_lookup_num_tokens"] = k
+        cfg = parse_generate_kwargs(kw, lookup=True)
+        cfg.drafter = drafter
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            out = greedy_generate(eng, ids, None, None, None, cfg)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    for weights in ("bf16", "int8"):
+        if weights == "int8":
+            eng.quantize_decoder_()
+        _, plain = call(new)
+        ref = plain.sequences[0].cpu().numpy()
+        arms = {"prefill": lambda: call(1), "plain": lambda: call(new)}
+        for k in ks:
+            arms[f"oracle_k{k}"] = lambda k=k: call(new, k, _ScriptDrafter(ref, prompt, k, True, eng.vocab))
+            arms[f"never_k{k}"] = lambda k=k: call(new, k, _ScriptDrafter(ref, prompt, k, False, eng.vocab))
+            arms[f"real_k{k}"] = lambda k=k: call(new, k)
+        ts, stats = {a: [] for a in arms}, {}
+        for a, f in arms.items():                                      # one untimed repetition of every arm
+            _, out = f()
+            if a != "prefill":
+                assert torch.equal(out.sequences, plain.sequences), a
+            stats[a] = getattr(out, "lookup_stats", None)
+        for _ in range(reps):
+            for a, f in arms.items():
+                ts[a].append(f()[0])
+        pre = float(np.median(ts["prefill"]))
+        per_tok = {a: [(v - pre) / (new - 1) for v in ts[a]] for a in arms if a != "prefill"}
+        med = {a: float(np.median(v)) for a, v in per_tok.items()}
+        spread = max(per_tok["plain"]) - min(per_tok["plain"])
+        rec = dict(geo=geo, mode="lookup_e2e", weights=weights, B=1, prompt=prompt, new_tokens=new, reps=reps, prefill_ms=round(pre, 2),
+                   plain_ms_per_token=round(med["plain"], 3), plain_ms_all=[round(v, 3) for v in per_tok["plain"]],
+                   plain_spread_ms=round(spread, 3), arms={}, kernel_src=_src_hash())
+        for k in ks:
+            o, n, r = med[f"oracle_k{k}"], med[f"never_k{k}"], med[f"real_k{k}"]
+            rec["arms"][f"k{k}"] = dict(
+                oracle_ms_per_token=round(o, 3), oracle_ms_all=[round(v, 3) for v in per_tok[f"oracle_k{k}"]], oracle_stats=stats[f"oracle_k{k}"],
+                oracle_speedup=round(med["plain"] / o, 3), oracle_faster_by_more_than_plain_spread=bool(med["plain"] - o > spread),
+                never_ms_per_token=round(n, 3), never_ms_all=[round(v, 3) for v in per_tok[f"never_k{k}"]], never_stats=stats[f"never_k{k}"],
+                wasted_step_cost_vs_plain=round(n / med["plain"], 3),
+                # a step that accepts a drafts emits a + 1 tokens for the never-right step's time: even at a + 1 = never / plain
+                break_even_accepted_per_step=round(max(n / med["plain"] - 1.0, 0.0), 3),
+                break_even_acceptance_rate=round(max(n / med["plain"] - 1.0, 0.0) / k, 4),
+                real_drafter_random_weights_ms_per_token=round(r, 3), real_drafter_random_weights_stats=stats[f"real_k{k}"])
+        recs.append(rec)
+    return recs
+
+
+def lookup_kernel_ab(geo, reps=40, rounds=3):
+    """(b) of --lookup: the verify kernel against the beam kernel on the same rows, one sequence."""
+    l = GEOMETRIES[geo]["lm"]
+    H, Hkv = l["heads"], l.get("kv_heads", l["heads"])
+    hd = l["d"] // H
+    kvd = Hkv * hd
+    recs = []
+    for L in (704, 7603):
+        L_max = L + 32
+        cache = (torch.randn(1, L_max, 2 * kvd, device="cuda", dtype=torch.float32) * 0.5).to(torch.bfloat16)
+        for R in (4, 8, 16, 32):
+            q = torch.randn(R, H * hd, device="cuda", dtype=torch.bfloat16)
+            kv0 = torch.tensor([L], dtype=torch.int32, device="cuda")
+            kv_len = (L + torch.arange(R, device="cuda")).to(torch.int32)
+            zero = torch.zeros(R, dtype=torch.int32, device="cuda")
+            plen = torch.full((R,), L_max, dtype=torch.int32, device="cuda")
+            fns = {"verify": lambda: ops.attn_decode_verify(q, cache, kv0, R, H, Hkv, hd, kvd),
+                   "beam": lambda: ops.attn_decode_beam(q, cache, kv_len, zero, plen, None, H, Hkv, hd, kvd)}
+            assert torch.equal(fns["verify"](), fns["beam"]())
+            meds = {k: [] for k in fns}
+            for _ in range(rounds):
+                ts = {k: [] for k in fns}
+                for _ in range(reps):
+                    for k, f in fns.items():
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        f()
+                        e1.record()
+                        e1.synchronize()
+                        ts[k].append(e0.elapsed_time(e1) * 1e3)
+                for k in fns:
+                    meds[k].append(float(np.median(ts[k])))
+            v, b = float(np.median(meds["verify"])), float(np.median(meds["beam"]))
+            spread = max(meds["beam"]) - min(meds["beam"])
+            recs.append(dict(geo=geo, mode="lookup_kernel_ab", R=R, H=H, Hkv=Hkv, hd=hd, kv_len0=L, L_max=L_max, reps=reps, rounds=rounds,
+                             verify_us=round(v, 2), beam_us=round(b, 2), verify_us_all=[round(x, 2) for x in meds["verify"]],
+                             beam_us_all=[round(x, 2) for x in meds["beam"]], beam_spread_us=round(spread, 2), ratio=round(v / b, 3),
+                             verify_slower_by_more_than_beam_spread=bool(v - b > spread), kernel_src=_src_hash()))
+    return recs
+
+
 def processors_ab(geo, B, prompt, new, reps=3):
     from radvlm_amd.generation import LogitsProcessors, parse_generate_kwargs
     eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
@@ -750,6 +875,8 @@ def main():
     ap.add_argument("--w8-quality", action="store_true")
     ap.add_argument("--sample", action="store_true")
     ap.add_argument("--beams", action="store_true")
+    ap.add_argument("--lookup", action="store_true")
+    ap.add_argument("--lookup-kernel-ab", action="store_true")
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -770,6 +897,10 @@ def main():
     elif a.beams:
         new = a.new if a.new != ap.get_default("new") else 48
         recs = [r for g in a.geos.split(",") for r in beams_kernel_ab(g, a.prompt, new) + beams_step_ab(g, a.prompt, new, reps=min(a.reps, 3))]
+    elif a.lookup_kernel_ab:
+        recs = [r for g in a.geos.split(",") for r in lookup_kernel_ab(g)]
+    elif a.lookup:
+        recs = [r for g in a.geos.split(",") for r in lookup_kernel_ab(g) + lookup_e2e(g, a.prompt, a.new, reps=min(a.reps, 3))]
     elif a.batch_eval:
         recs = [r for g in a.geos.split(",") for r in batch_eval(g, n=a.requests, prompt=a.prompt, reps=min(a.reps, 3))]
     elif a.batch_kernel_ab:
