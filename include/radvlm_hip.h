@@ -488,6 +488,35 @@ int rv_attn_decode_verify_bf16(const void* q, int64_t ld_q, const void* cache, i
                                int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int R, int H, int Hkv, int hd,
                                int chunk, float scale, void* stream);
 
+/* ---- int8 KV cache (generate(kv_cache_dtype="int8"), radvlm_amd/csrc/kvq.hip) --------------------------------------------------------
+ * The reference has no quantised cache (HF's QuantizedCache is the nearest relative); the rule is rv_quantize_rows_w8_bf16's, per group.
+ * One group = the hd values of one kv head of K, or of V, at one cached position:
+ *     amax = max |x|    s = amax / 127 (1 for an all-zero group)    q = clamp(rint(float(x) / s), -127, 127)    x^ = bf16_rne(float(q) * s)
+ * IEEE fp32 division, round half to even; non-finite inputs are outside the contract.  Per decoder layer the cache is two tensors of
+ * flat rows (flat row = b * L_max + position, consecutive): q8 int8 rows of ld_q bytes with the columns of the bf16 cache (K of kv
+ * head g at g*hd, V at Hkv*hd + g*hd), and s fp32 rows of ld_s floats (column g: K head g; column Hkv + g: V head g). */
+/* Quantises M source rows of 2*Hkv*hd bf16 values (rows of ld_src elements: the k|v columns of a q|k|v product) into the flat cache rows
+ * rows[0 .. M) (int64, device); a row outside [0, cache_rows) is skipped.  xhat (optional, NULL to skip): a bf16 cache of the bf16 layout
+ * (rows of ld_x) that receives x^ in the same flat rows.  q8 and s are given together or both NULL (then xhat alone is written).
+ * hd 64 or 128; ld_src, ld_q, ld_x multiples of 8 and >= 2*Hkv*hd, ld_s >= 2*Hkv (RV_ERR_ARG otherwise).  No atomics: a group is
+ * reduced by an xor butterfly inside one wave (max is order-free).  Two source rows naming one cache row race. */
+int rv_kv_quantize_rows_bf16(const void* src, int64_t ld_src, void* q8, int64_t ld_q, float* s, int64_t ld_s, void* xhat, int64_t ld_x,
+                             const int64_t* rows, int64_t cache_rows, int M, int Hkv, int hd, void* stream);
+/* The same arithmetic addressed like rv_kv_append_bf16: source row b goes to flat row b * L_max + pos[b] (pos int32 [B], device); a
+ * position outside [0, L_max) is skipped. */
+int rv_kv_append_q8_bf16(const void* src, int64_t ld_src, void* q8, int64_t ld_q, float* s, int64_t ld_s, void* xhat, int64_t ld_x,
+                         const int32_t* pos, int L_max, int B, int Hkv, int hd, void* stream);
+/* rv_attn_decode_bf16 over the int8 cache: cache_q8 int8 [B][L_max][ld_c] (sequence stride bs_c, V at column v_off + g*hd), cache_s
+ * fp32 [B][L_max][ld_s] (sequence stride bs_s, V scales at column vs_off + g).  A lane loads 8 bytes and its group's scale and rebuilds
+ * bf16_rne(float(q) * s) in registers; the assignment of (key row, 8-element slice) to (wave, lane), each lane's key order, the xor
+ * butterflies, the wave-order sum, `part` and the combine are rv_attn_decode_bf16's, so out is BIT-IDENTICAL to rv_attn_decode_bf16 on
+ * the dequantised cache at the same `chunk`, for every kv_len.  Keys at or past kv_len[b] are never loaded: bytes and scales there may
+ * hold anything (-128, NaN).  Same limits and refusals: hd 64 or 128, H / Hkv <= 8, chunk <= 512 and a multiple of 16 (hd 128) or 32
+ * (hd 64), part of B * H * ceil(L_max / chunk) * (hd + 2) floats, ld_q / ld_o >= H*hd. */
+int rv_attn_decode_kv8_bf16(const void* q, int64_t ld_q, const void* cache_q8, int64_t ld_c, int64_t bs_c, int v_off, const float* cache_s,
+                            int64_t ld_s, int64_t bs_s, int vs_off, const int32_t* kv_len, int L_max, void* out, int64_t ld_o, void* part,
+                            int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk, float scale, void* stream);
+
 /* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
  * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any
  * grid and any placement of W.  W: bf16 rows of ldw elements (a row slice of a fused q|k|v or gate|up store is fine), 16-byte aligned,

@@ -884,21 +884,62 @@ class LlavaEngine:
             raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
                                       "model.merge_and_unload() (the reference merges adapters before evaluation)")
 
-    def kv_cache_bytes(self, B, L_max):
-        """Bytes of a KVCache of B sequences x L_max positions (bf16 K|V rows of every layer)."""
-        return self.l["layers"] * int(B) * int(L_max) * 2 * self.kvd * 2
+    # An int8-dtype KVCache is stored as (int8, fp32 scale) tensors and read by rv_attn_decode_kv8_bf16; False keeps it as bf16 tensors
+    # that hold the dequantised values (written by the same quantise kernels) and reads it with rv_attn_decode_bf16.  The two are
+    # bit-identical, so this switch changes time and memory only: it is the A/B arm of tools/decode_bench.py --kv8.
+    kv8_decode = True
+
+    @staticmethod
+    def _kv_dtype(dtype):
+        if dtype in (None, "bf16"):
+            return "bf16"
+        if dtype == "int8":
+            return "int8"
+        raise ValueError(f"kv cache dtype must be None, 'bf16' or 'int8', got {dtype!r}")
+
+    def kv_cache_bytes(self, B, L_max, dtype="bf16"):
+        """Bytes of a KVCache of B sequences x L_max positions: bf16 K|V rows of every layer (2 * 2*kvd per position and layer), or for
+        dtype "int8" their int8 bytes and one fp32 scale per (kv head, K / V) group (2*kvd + 8*Hkv).  What new_kv_cache(B, L_max, dtype)
+        .nbytes() reports: with kv8_decode False an int8-dtype cache is stored dequantised and costs the bf16 bytes."""
+        per = 2 * self.kvd * 2
+        if self._kv_dtype(dtype) == "int8" and self.kv8_decode:
+            per = 2 * self.kvd + 8 * self.Hkv
+        return self.l["layers"] * int(B) * int(L_max) * per
 
     def free_device_bytes(self):
         """Device memory a new allocation can take: free HBM plus what torch's caching allocator holds unused."""
         free, _ = torch.cuda.mem_get_info(self.device)
         return int(free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device))
 
-    def new_kv_cache(self, B, L_max):
-        """An empty KVCache of B sequences (every length 0) x L_max positions, to be filled by prefill(..., cache=, slots=)."""
-        L = self.l["layers"]
-        return KVCache([torch.zeros(B, L_max, 2 * self.kvd, dtype=BF16, device=self.device) for _ in range(L)], np.zeros(B, np.int64), L_max)
+    def _kv_layers(self, B, L_max, dtype):
+        """The per-layer tensors of an empty cache: (layers, scales or None)."""
+        L, dev = self.l["layers"], self.device
+        if dtype == "int8" and self.kv8_decode:
+            return ([torch.zeros(B, L_max, 2 * self.kvd, dtype=torch.int8, device=dev) for _ in range(L)],
+                    [torch.ones(B, L_max, 2 * self.Hkv, dtype=torch.float32, device=dev) for _ in range(L)])
+        return [torch.zeros(B, L_max, 2 * self.kvd, dtype=BF16, device=dev) for _ in range(L)], None
 
-    def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0, cache=None, slots=None):
+    def new_kv_cache(self, B, L_max, dtype="bf16"):
+        """An empty KVCache of B sequences (every length 0) x L_max positions, to be filled by prefill(..., cache=, slots=).  dtype "int8":
+        K|V rows are quantised per (position, kv head, K / V) group as they are written (KVCache)."""
+        dtype = self._kv_dtype(dtype)
+        layers, scales = self._kv_layers(B, L_max, dtype)
+        return KVCache(layers, np.zeros(B, np.int64), L_max, dtype=dtype, scales=scales)
+
+    def _kv_write_rows(self, cache_layer, scale_layer, src, rows):
+        """An int8-dtype cache's prefill write: quantise the K|V rows src into flat cache rows `rows` (either storage)."""
+        if scale_layer is not None:
+            ops.kv_quantize_rows(src, rows, self.Hkv, self.hd, cache=(cache_layer, scale_layer))
+        else:
+            ops.kv_quantize_rows(src, rows, self.Hkv, self.hd, xhat=cache_layer)
+
+    @staticmethod
+    def _refuse_int8(cache, what):
+        if cache is not None and getattr(cache, "dtype", "bf16") == "int8":
+            raise NotImplementedError(f"{what} on an int8 KV cache: only prefill() and the plain decode_step() read it; "
+                                      "use a bf16 cache (kv_cache_dtype=None)")
+
+    def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0, cache=None, slots=None, kv_dtype=None):
         """The prompt pass of generation: multimodal splice (plan / encode_images, as in forward) and every decoder layer in the packed
         varlen layout, sequence b at cache rows and positions 0 .. len_b - 1 whatever the padding side.  Each layer's post-RoPE K|V rows go
         into a KVCache of len_b + max_new_tokens slots per sequence; the activations are dropped.  No loss, no saved context (self.ctx and
@@ -906,10 +947,18 @@ class LlavaEngine:
         cache / slots (generate_batch): sequence b's K|V rows go instead into slot slots[b] of the existing KVCache `cache` (positions
         0 .. len_b - 1; the slot's later positions are left as they are) and cache.lens[slots[b]] = len_b; the arithmetic is the same, so
         the logits and K|V rows are the bits prefill() gives the same group on a cache of cache.L_max positions.  Other slots are untouched.
+        kv_dtype ("bf16" / "int8"; None: the passed cache's, else "bf16"): with "int8" each layer's K|V rows are quantised on their way
+        into the cache (ops.kv_quantize_rows); the prompt's own attention still runs on the unquantised activations, so the returned
+        logits are those of a bf16 cache.
         Returns (cache, fp32 logits [B, vocab] of every sequence's last prompt row)."""
         self._check_generation()
         dev, l = self.device, self.l
         d, L, kvd = l["d"], l["layers"], self.kvd
+        if cache is not None:
+            if kv_dtype is not None and self._kv_dtype(kv_dtype) != cache.dtype:
+                raise ValueError(f"kv_dtype {kv_dtype!r} does not match the passed cache's dtype {cache.dtype!r}")
+            kv_dtype = cache.dtype
+        kv_dtype = self._kv_dtype(kv_dtype)
         from .splice import IMAGE_TOKEN_INDEX
         ids = np.asarray(input_ids)
         B = int(ids.shape[0])
@@ -942,6 +991,8 @@ class LlavaEngine:
         x = ops.gather_rows(self._dev(plan["idx"][valid].astype(np.int32)), d, self.W("model.embed_tokens.weight"), table)
         rows = self._dev(np.concatenate([seq[b] * L_max + np.arange(n) for b, n in enumerate(lens)]).astype(np.int64))   # cache rows
         layers = []
+        if cache is None and kv_dtype == "int8":
+            cache = self.new_kv_cache(B, L_max, kv_dtype)           # seq = 0 .. B - 1: filled like a passed cache's slots
         for i in range(L):
             x, acts = self._layer_forward(i, x, geom)
             if cache is None:
@@ -949,7 +1000,10 @@ class LlavaEngine:
                 layers.append(kv)
             else:
                 kv = cache.layers[i]
-            kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:])
+            if kv_dtype == "int8":
+                self._kv_write_rows(kv, cache.scales[i] if cache.scales is not None else None, acts["qkv"][:, d:], rows)
+            else:
+                kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:])
             del acts
         last = self._dev((cu[1:] - 1).astype(np.int32))
         hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
@@ -967,12 +1021,18 @@ class LlavaEngine:
         .tail_cols] device, or None).  Row r still appends its K|V at position cache.lens[r] of its OWN row, but reads key position j
         from row prefix_row[r] while j < prefix_len[r] and from row tail_src[r, j - prefix_len[r]] after it (rv_attn_decode_beam_bf16,
         bit-identical to the plain kernel on the gathered cache), so beams share their prompt's rows and their ancestors' tokens and
-        nothing in the cache moves.  Without it every call is what it was."""
+        nothing in the cache moves.  Without it every call is what it was.
+        An int8-dtype cache (KVCache.dtype): the K|V row is quantised by the append (ops.kv_append_q8) and attention reads the int8
+        rows (ops.attn_decode_kv8), bit-identical to this step on a bf16 cache holding the dequantised values (kv8_decode False runs
+        exactly that).  beams= with such a cache raises NotImplementedError."""
         self._check_generation()
         l = self.l
         d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
         hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
         B = cache.B
+        kv8 = getattr(cache, "dtype", "bf16") == "int8"
+        if kv8 and beams is not None:
+            self._refuse_int8(cache, "decode_step(beams=...)")
         if (cache.lens >= cache.L_max).any():
             raise ValueError(f"the KV cache is full ({cache.L_max} slots per sequence)")
         tok = tokens.to(self.device, torch.int32) if torch.is_tensor(tokens) else self._dev(np.asarray(tokens, dtype=np.int32))
@@ -986,10 +1046,18 @@ class LlavaEngine:
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
             qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), w8=q8.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
-            ops.kv_append(qkv[:, d:], cache.layers[i], pos)
-            if beams is None:
+            if kv8 and cache.scales is not None:
+                kvq = (cache.layers[i], cache.scales[i])
+                ops.kv_append_q8(qkv[:, d:], pos, Hkv, hd, cache=kvq)
+                attn = ops.attn_decode_kv8(qkv[:, :d], kvq, kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            elif kv8:       # the reference arm: the dequantised values as bf16, read by the bf16 kernel
+                ops.kv_append_q8(qkv[:, d:], pos, Hkv, hd, xhat=cache.layers[i])
+                attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            elif beams is None:
+                ops.kv_append(qkv[:, d:], cache.layers[i], pos)
                 attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
             else:
+                ops.kv_append(qkv[:, d:], cache.layers[i], pos)
                 attn = ops.attn_decode_beam(qkv[:, :d], cache.layers[i], kv_len, beams.prefix_row, beams.prefix_len, beams.tail_src, H, Hkv,
                                             hd, kvd, tail_cols=beams.tail_cols, chunk=cache.chunk)
             x_mid = self._decode_linear(attn, lv["o"], residual=x, w8=q8.get("o"))
@@ -1029,6 +1097,7 @@ class LlavaEngine:
         depend on M there), the lm_head included whatever its height.  cache.lens is NOT advanced: the caller adds the number of
         tokens it emits; the K|V rows of rejected drafts stay past lens as stale rows, which every kernel ignores."""
         self._check_generation()
+        self._refuse_int8(cache, "verify_step()")
         l = self.l
         d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
         hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
@@ -1082,6 +1151,7 @@ class LlavaEngine:
         The vision tower runs only when an image feature row (image_newline aside) is among the new rows.  The cache grows (one copy of
         the kept rows) when len_b + max_new_tokens exceeds its slots.  Every reuse[b] == 0 (or no cache): prefill(), bit for bit.
         plan: this prompt's self.plan(...), when the caller has it already.  Returns (cache, fp32 logits [B, vocab])."""
+        self._refuse_int8(cache, "extend()")
         if cache is None or reuse is None or not np.any(reuse):
             return self.prefill(input_ids, attention_mask, images, image_sizes, max_new_tokens=max_new_tokens)
         self._check_generation()
@@ -1561,11 +1631,17 @@ class LlavaEngine:
 
 class KVCache:
     """Keys and values of one generate() call: per decoder layer a bf16 [B, L_max, 2 * kvd] tensor holding each position's post-RoPE
-    K | V row as it sits in the q|k|v product (sequence b at rows 0 .. lens[b] - 1), and the host-side lengths.  Freed with the object."""
+    K | V row as it sits in the q|k|v product (sequence b at rows 0 .. lens[b] - 1), and the host-side lengths.  Freed with the object.
+    dtype "int8": every (position, kv head, K / V) group of hd values is stored as s = max|x| / 127 (1 for a zero group) and
+    q = clamp(rint(x / s), -127, 127): layers[i] is int8 [B, L_max, 2 * kvd] with the bf16 cache's columns and scales[i] is fp32
+    [B, L_max, 2 * Hkv] (column g: K head g; column Hkv + g: V head g); the value read back is bf16(float(q) * s).  With
+    LlavaEngine.kv8_decode False the same values are kept dequantised instead: layers[i] bf16, scales None."""
     chunk = 128           # keys per decode-attention workgroup: fixed, so a sequence's result never depends on the batch around it
 
-    def __init__(self, layers, lens, L_max):
+    def __init__(self, layers, lens, L_max, dtype="bf16", scales=None):
         self.layers = layers
+        self.scales = scales
+        self.dtype = dtype
         self.lens = np.asarray(lens, dtype=np.int64).copy()
         self.L_max = int(L_max)
 
@@ -1576,11 +1652,12 @@ class KVCache:
     def grow(self, L_new, keep):
         """Reallocate every layer to L_new slots per sequence, copying the first `keep` rows of each sequence (what is still valid)."""
         assert L_new >= self.L_max and 0 <= keep <= self.L_max
-        for i, t in enumerate(self.layers):
-            nt = torch.zeros(t.shape[0], L_new, t.shape[2], dtype=t.dtype, device=t.device)
-            nt[:, :keep].copy_(t[:, :keep])
-            self.layers[i] = nt
+        for group in (self.layers, self.scales or []):
+            for i, t in enumerate(group):
+                nt = torch.zeros(t.shape[0], L_new, t.shape[2], dtype=t.dtype, device=t.device)
+                nt[:, :keep].copy_(t[:, :keep])
+                group[i] = nt
         self.L_max = int(L_new)
 
     def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in self.layers)
+        return sum(t.numel() * t.element_size() for t in list(self.layers) + list(self.scales or []))

@@ -25,7 +25,7 @@ _PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "bad_words_ids", "m
                "begin_suppress_tokens")
 _ACCEPTED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "attention_mask", "stopping_criteria", "use_cache", "do_sample",
              "num_beams", "streamer", "output_scores", "output_logits", "return_dict_in_generate", "num_return_sequences", "position_ids",
-             "inputs_embeds", "past_key_values", "seed") + _PROCESSORS + _IGNORED_WHEN_GREEDY
+             "inputs_embeds", "past_key_values", "seed", "kv_cache_dtype") + _PROCESSORS + _IGNORED_WHEN_GREEDY
 # prompt-lookup decoding (HF's names): generate() alone takes them, generate_batch() and generate_beams() reject them as unknown
 _LOOKUP = ("prompt_lookup_num_tokens", "max_matching_ngram_size")
 LOOKUP_MAX_TOKENS = 31        # k drafted tokens are verified as k + 1 rows, and the skinny GEMM takes ops.GEMV_MAX_M = 32
@@ -42,8 +42,9 @@ class GenerateDecoderOnlyOutput(SimpleNamespace):
 def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, lookup=False):
     """Validate generate() keyword arguments; returns a namespace with the normalised settings (.sampling: None for greedy, else the
     warper settings and the seed as given; sampling_seeds() resolves it per row).  Raises NotImplementedError for what this build does
-    not do (do_sample=True without seed=, beam search, streamers, caller-supplied inputs_embeds, LoRA engines) and TypeError for unknown
-    names.  lookup: also take prompt_lookup_num_tokens / max_matching_ngram_size (.lookup: None, or .k and .max_ngram; .drafter: None,
+    not do (do_sample=True without seed=, beam search, streamers, caller-supplied inputs_embeds, LoRA engines, kv_cache_dtype="int8"
+    together with past_key_values or prompt_lookup_num_tokens), ValueError for a kv_cache_dtype other than None / "bf16" / "int8"
+    (.kv_cache_dtype: "bf16" or "int8") and TypeError for unknown names.  lookup: also take prompt_lookup_num_tokens / max_matching_ngram_size (.lookup: None, or .k and .max_ngram; .drafter: None,
     greedy_generate then builds a PromptLookupDrafter; a test or a benchmark may set another object with propose(seq))."""
     unknown = sorted(k for k in kwargs if k not in _ACCEPTED and not (lookup and k in _LOOKUP))
     if unknown:
@@ -69,6 +70,12 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     if lora:
         raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
                                   "model.merge_and_unload() (the reference merges adapters before evaluation)")
+    kv_dtype = parse_kv_cache_dtype(kwargs.get("kv_cache_dtype"))
+    if kv_dtype == "int8" and pkv is not None:
+        raise NotImplementedError("kv_cache_dtype='int8' with past_key_values: a GenerationCache is extended by the extend-attention "
+                                  "kernel, which reads a bf16 cache only")
+    if kv_dtype == "int8" and kwargs.get("prompt_lookup_num_tokens") is not None:
+        raise NotImplementedError("kv_cache_dtype='int8' with prompt_lookup_num_tokens: the verify-attention kernel reads a bf16 cache only")
     eos = kwargs.get("eos_token_id", config_eos)
     eos = [] if eos is None else ([int(eos)] if isinstance(eos, (int, np.integer)) else [int(e) for e in eos])
     pad = kwargs.get("pad_token_id", config_pad)
@@ -87,7 +94,18 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
                            past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
+                           kv_cache_dtype=kv_dtype,
                            **_parse_processors(kwargs, eos))
+
+
+def parse_kv_cache_dtype(v):
+    """kv_cache_dtype: None or "bf16" (the bf16 cache, returned as "bf16") or "int8" (K|V rows quantised per position, kv head and K / V
+    as they enter the cache: LlavaEngine / KVCache); ValueError for anything else."""
+    if v is None or v == "bf16":
+        return "bf16"
+    if v == "int8":
+        return "int8"
+    raise ValueError(f"`kv_cache_dtype` has to be None, 'bf16' or 'int8', but is {v!r}")
 
 
 def _parse_lookup(kwargs):
@@ -589,7 +607,9 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     GenerationCache) the prompt pass reuses what the cache holds (LlavaEngine.extend; an empty cache: prefill as without one) and the
     cache keeps the prompt and every generated token but the last.  With cfg.sampling each step's token is drawn by ops.sample_rows
     from the processed scores (row b with seed_b at step t) instead of their argmax; output_scores and the stopping criteria then get
-    the warped scores, output_logits the raw ones as before."""
+    the warped scores, output_logits the raw ones as before.  cfg.kv_cache_dtype "int8": the cache holds int8 K|V rows with one fp32
+    scale per (position, kv head, K / V) group; the first token comes from the unquantised prompt pass, every later one reads the
+    quantised rows."""
     from . import ops
     ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids)
     if ids.ndim == 1:
@@ -628,7 +648,13 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
         hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active and not lookup else None      # the accept loop keeps its own
         sm_ws = ops.sample_rows_workspace(B, dev) if sm is not None else None      # the sampler's scratch, once per call
         if gc is None:
-            cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T)
+            if getattr(cfg, "kv_cache_dtype", "bf16") == "int8":
+                if lookup:
+                    raise NotImplementedError("kv_cache_dtype='int8' with prompt-lookup decoding: the verify-attention kernel reads a bf16 "
+                                              "cache only")
+                cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, kv_dtype="int8")
+            else:
+                cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T)
         else:
             imgs = list(images) if images is not None else []
             plan = engine.plan(ids, am, None, imgs, image_sizes)
@@ -842,7 +868,8 @@ class BatchScheduler:
     stopping criterion (called as generate() calls it at B = 1: the request's tokens [1, t] and its processed scores [1, vocab]), and
     frees its slot.  With cfg.sampling request i carries its own seed (sampling_seeds: an int s gives s + i) and the picker is called with
     seed=, the seeds of the rows' requests (0 for an idle slot), next to each row's step t: what a request draws depends on neither the
-    slot nor the schedule.  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t)."""
+    slot nor the schedule.  cfg.kv_cache_dtype "int8": the memory check and the cache are sized for the int8 cache (the dtype is passed to
+    kv_cache_bytes and new_kv_cache; the default dtype keeps their two-argument calls).  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t)."""
 
     def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None):
         if not _is_int(max_batch_size) or max_batch_size < 1:
@@ -874,14 +901,16 @@ class BatchScheduler:
 
     def _run(self):
         eng, S = self.engine, self.slots
-        need = eng.kv_cache_bytes(S, self.L_max)
+        kvd = getattr(self.cfg, "kv_cache_dtype", "bf16")
+        kv_args = () if kvd == "bf16" else (kvd,)             # the default dtype keeps the two-argument calls
+        need = eng.kv_cache_bytes(S, self.L_max, *kv_args)
         free = eng.free_device_bytes()
         if free is not None and need > free:
             raise ValueError(f"generate_batch: the KV cache of {S} slots x {self.L_max} positions needs {need} bytes, but only {free} bytes "
                              f"of device memory are free: lower max_batch_size or the token budgets")
         if self.picker is None:
             self.picker = DevicePicker(eng, self.cfg, S, self.max_budget, self.logprobs, any(self.min_new[i] > 0 for i in self.runs))
-        self.cache = eng.new_kv_cache(S, self.L_max)
+        self.cache = eng.new_kv_cache(S, self.L_max, *kv_args)
         self.owner = np.full(S, -1, dtype=np.int64)           # request in each slot, -1: idle
         self.t = np.zeros(S, dtype=np.int64)                  # tokens the slot's request has generated
         self.mn = np.zeros(S, dtype=np.int64)                 # its EOS minimum
@@ -994,7 +1023,8 @@ def beams_to_keep(num_beams, n_eos):
 def parse_beam_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
     """Validate generate_beams() keyword arguments: generate()'s, plus length_penalty (float, default 1.0), early_stopping (False, True
     or "never") and num_return_sequences <= num_beams.  ValueError for num_beams outside [1, 16] or K = max(2, 1 + n_eos) * num_beams
-    above 64; NotImplementedError for do_sample=True (beam sampling), past_key_values, streamer, inputs_embeds and LoRA engines;
+    above 64; NotImplementedError for do_sample=True (beam sampling), past_key_values, streamer, inputs_embeds, LoRA engines and
+    kv_cache_dtype="int8" (None and "bf16" are accepted and change nothing);
     TypeError for unknown names.  The sampling knobs HF ignores when greedy stay ignored."""
     unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _BEAM_ONLY)
     if unknown:
@@ -1003,6 +1033,8 @@ def parse_beam_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
         raise NotImplementedError("do_sample=True with beams: beam sampling is not implemented")
     if kwargs.get("past_key_values") is not None:
         raise NotImplementedError("past_key_values: a GenerationCache across generate_beams() calls is not implemented")
+    if parse_kv_cache_dtype(kwargs.get("kv_cache_dtype")) == "int8":
+        raise NotImplementedError("kv_cache_dtype='int8' with beams: the beam-attention kernel reads a bf16 cache only")
     nb = kwargs.get("num_beams")
     nb = 1 if nb is None else nb
     if not _is_int(nb) or not 1 <= nb <= BEAM_MAX:

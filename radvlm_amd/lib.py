@@ -116,6 +116,11 @@ _SIGS = {
                                  _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
     "rv_attn_decode_verify_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32,
                                    _i32, _i32, _i32, _i32, _f32, _c_void_p],
+    "rv_kv_quantize_rows_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32,
+                                 _c_void_p],
+    "rv_kv_append_q8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p],
+    "rv_attn_decode_kv8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _i64, _i64, _i32, _c_void_p, _i32, _c_void_p, _i64,
+                                _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
     "rv_log_softmax_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p],
     "rv_beam_topk_f32": [_c_void_p, _i64, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p],
     "rv_lora_merge_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],

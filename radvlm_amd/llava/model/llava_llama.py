@@ -294,6 +294,11 @@ class LlavaLlamaForCausalLM:
         only (ValueError otherwise, HF's assisted generation is batch-size-1 too); with do_sample=True NotImplementedError; k outside
         1 .. 31 or a non-int ValueError.  Every other greedy keyword keeps its meaning; stopping criteria are called once per emitted
         token, in order, with that token's own score row.
+        kv_cache_dtype: None or "bf16" (today's cache) or "int8": each cached position's K and V are stored per kv head as int8 with
+        one fp32 scale (s = max|x| / 127), 0.516x the cache bytes, read by an int8 decode-attention kernel.  The first token still
+        comes from the unquantised prompt pass; later tokens see the rounded keys and values, so they may differ from the bf16
+        cache's.  It composes with the logits processors, sampling, output_scores / output_logits and load_8bit models; it does
+        NOT compose with past_key_values or prompt_lookup_num_tokens (NotImplementedError), and another value is a ValueError.
         The training state (weights, optimizer, RNG counters) is not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
@@ -317,7 +322,10 @@ class LlavaLlamaForCausalLM:
         the slot and the schedule (up to the rounding of the scores themselves).
         Returns {"req_0": GenerationOutput, ...} in input order: .generated_tokens are what generate() returns for the request alone,
         ending at its EOS token or where a stopping criterion returned True; .logprobs (return_logprobs) the log-softmax of each step's
-        processed scores at the emitted token (when sampling: log q of the drawn token, q the softmax over what the warpers kept).  The training state is not touched."""
+        processed scores at the emitted token (when sampling: log q of the drawn token, q the softmax over what the warpers kept).
+        kv_cache_dtype="int8" (None / "bf16": today's cache): the slots' cache holds int8 K|V rows as in generate(), so the memory
+        check admits about twice the slots or positions; a request's tokens are those of generate(kv_cache_dtype="int8") on it alone.
+        The training state is not touched."""
         from ...generation import generate_batch, parse_batch_kwargs
         inputs = list(inputs)
         cfg = parse_batch_kwargs(kwargs, len(inputs), lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
@@ -337,7 +345,8 @@ class LlavaLlamaForCausalLM:
         "never").  Ties between equal scores go to the lower beam * vocab + token (HF leaves them open).  The KV cache holds B *
         num_beams rows; the prompt is prefilled once per prompt and never copied, and no cache row is reordered (the engine's decode
         attention follows each beam's ancestry instead).  do_sample=True (beam sampling), past_key_values, streamers, inputs_embeds
-        and LoRA models raise NotImplementedError.  The training state is not touched."""
+        and LoRA models raise NotImplementedError, and so does kv_cache_dtype="int8" (the beam-attention kernel reads a bf16 cache;
+        None and "bf16" are accepted and change nothing).  The training state is not touched."""
         from ...generation import beam_generate, parse_beam_kwargs
         cfg = parse_beam_kwargs(dict(kwargs, num_beams=num_beams), lora=bool(self.engine.lora),
                                 config_eos=getattr(self.config, "eos_token_id", None), config_pad=getattr(self.config, "pad_token_id", None))

@@ -672,6 +672,68 @@ def kv_append(src, cache, pos):
     return cache
 
 
+def _kvq_targets(src, cache, xhat, Hkv, hd):
+    """Checks shared by kv_quantize_rows and kv_append_q8: cache is (q8 int8 [B, L_max, 2*kvd], s fp32 [B, L_max, 2*Hkv]) or None,
+    xhat a bf16 [B, L_max, 2*kvd] cache or None.  Returns (q8, ld_q, s, ld_s, xhat, ld_x, B, L_max)."""
+    width = 2 * Hkv * hd
+    _chk(src)
+    assert src.dim() == 2 and src.shape[1] == width and src.stride(1) == 1
+    assert cache is not None or xhat is not None, "nothing to write: pass the int8 cache, the bf16 output or both"
+    q8 = s = None
+    shape = None
+    if cache is not None:
+        q8, s = cache
+        _chk(q8, torch.int8), _chk(s, torch.float32)
+        assert q8.dim() == 3 and q8.shape[2] == width and q8.is_contiguous()
+        assert s.shape == (q8.shape[0], q8.shape[1], 2 * Hkv) and s.is_contiguous()
+        shape = q8.shape[:2]
+    if xhat is not None:
+        _chk(xhat)
+        assert xhat.dim() == 3 and xhat.shape[2] == width and xhat.is_contiguous() and (shape is None or xhat.shape[:2] == shape)
+        shape = xhat.shape[:2]
+    return q8, width, s, 2 * Hkv, xhat, width, int(shape[0]), int(shape[1])
+
+
+def kv_quantize_rows(src, rows, Hkv, hd, cache=None, xhat=None):
+    """Quantises the bf16 K|V rows src [M, 2*Hkv*hd] (a column view of the q|k|v product is fine) per (row, kv head, K / V) group --
+    s = max|x| / 127 (1 for a zero group), q = clamp(rint(x / s), -127, 127) -- into the flat cache rows `rows` (int64 [M] device,
+    b * L_max + position; rows outside the cache are skipped) of cache = (q8 int8 [B, L_max, 2*kvd], s fp32 [B, L_max, 2*Hkv]), and /
+    or writes the dequantised bf16(float(q) * s) to the same rows of the bf16 cache `xhat` (rv_kv_quantize_rows_bf16)."""
+    q8, ld_q, s, ld_s, xh, ld_x, B, L_max = _kvq_targets(src, cache, xhat, Hkv, hd)
+    _chk(rows, torch.int64)
+    M = src.shape[0]
+    assert rows.numel() == M and rows.is_contiguous()
+    lib.call("rv_kv_quantize_rows_bf16", src, src.stride(0), q8, ld_q, s, ld_s, xh, ld_x, rows, B * L_max, M, Hkv, hd)
+
+
+def kv_append_q8(src, pos, Hkv, hd, cache=None, xhat=None):
+    """kv_quantize_rows addressed like kv_append: row b of src [B, 2*Hkv*hd] goes to position pos[b] (int32 [B] device) of sequence b;
+    a position outside the cache is skipped (rv_kv_append_q8_bf16)."""
+    q8, ld_q, s, ld_s, xh, ld_x, B, L_max = _kvq_targets(src, cache, xhat, Hkv, hd)
+    _chk(pos, torch.int32)
+    assert src.shape[0] == B and pos.numel() == B and pos.is_contiguous()
+    lib.call("rv_kv_append_q8_bf16", src, src.stride(0), q8, ld_q, s, ld_s, xh, ld_x, pos, L_max, B, Hkv, hd)
+
+
+def attn_decode_kv8(q, cache, kv_len, H, Hkv, hd, v_off, out=None, chunk=128, scale=None):
+    """attn_decode() over an int8 cache = (q8 int8 [B, L_max, width], s fp32 [B, L_max, 2*Hkv]): rv_attn_decode_kv8_bf16, bit-identical
+    to attn_decode on (q8.float() * s.repeat_interleave(hd, -1)).to(bfloat16) at the same chunk.  K of kv head g at columns g*hd of q8
+    and column g of s, V at v_off + g*hd and Hkv + g."""
+    q8, s = cache
+    _chk(q), _chk(q8, torch.int8), _chk(s, torch.float32), _chk(kv_len, torch.int32)
+    B, L_max, width = q8.shape
+    assert q.shape == (B, H * hd) and q.stride(1) == 1 and q8.is_contiguous() and kv_len.numel() == B and kv_len.is_contiguous()
+    assert s.shape == (B, L_max, 2 * Hkv) and s.is_contiguous()
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if out is None:
+        out = torch.empty(B, H * hd, dtype=BF16, device=q.device)
+    nch = (L_max + chunk - 1) // chunk
+    part = torch.empty(B * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    lib.call("rv_attn_decode_kv8_bf16", q, q.stride(0), q8, width, L_max * width, v_off, s, 2 * Hkv, L_max * 2 * Hkv, Hkv, kv_len, L_max,
+             out, out.stride(0), part, part.numel() * 4, B, H, Hkv, hd, chunk, float(scale))
+    return out
+
+
 def argmax_rows(x, n, out=None):
     """int64 [rows]: torch.argmax of each fp32 row over its first n columns (lowest index on ties)."""
     _chk(x, torch.float32)

@@ -28,6 +28,17 @@
         # rv_gemv_w8_bf16, the 7B Llama and Qwen2-7B decoder shapes, M = 1, 4, 8, 16, 32, cold weights, interleaved
   python tools/decode_bench.py --w8-quality   # the toy goldens' models: logits distance and greedy-token agreement, int8 vs unquantised
   python tools/decode_bench.py --w8-trace [--geos llava15_7b]   # a B = 1 int8 decode run: the workload of `rocprofv3 --kernel-trace --stats`
+  python tools/decode_bench.py --kv8 [--geos ..] [--batches 1,8,32] [--out FILE]
+        # int8 KV cache: one engine per geometry, the decode loop on an int8-dtype cache with engine.kv8_decode False / True interleaved
+        # three times after one untimed repetition of both (rv_attn_decode_bf16 on the dequantised bf16 rows vs rv_attn_decode_kv8_bf16
+        # on the int8 rows: same output bits), then the same after quantize_decoder_(); medians per arm, the reference arm's spread and
+        # the KV bytes per step of both arms
+  python tools/decode_bench.py --kv8-shapes [--out FILE]   # kernel A/B of the two attention entries: the 7B and Qwen2-7B head shapes,
+        # 704 and 7,603 keys, B = 1, 8, 32, cold cache, interleaved; torch.equal is asserted before timing
+  python tools/decode_bench.py --kv8-quality   # the toy goldens' models: next-step logits distance and greedy-token agreement, int8
+        # cache vs bf16 cache (measured and recorded, never gated)
+  python tools/decode_bench.py --kv8-trace [--geos llava15_7b] [--batches 32]   # an int8-cache decode run: the workload of
+        # `rocprofv3 --kernel-trace --stats`
   python tools/decode_bench.py --sample [--geos ..] [--batches 1,8,32] [--out FILE]
         # seeded sampling: (1) rv_sample_rows_f32 (the chat default T=0.2 top_k=50 top_p=0.7, and every warper on) vs
         # rv_logits_process_argmax_rows_f32 with logprobs (one read of the row) at 1 and 32 rows x 32,000 and 152,064, device time,
@@ -278,12 +289,13 @@ def w8_trace(geo, prompt, new):
                  kernel_src=_src_hash())]
 
 
-def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None):
+def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None):
     """Median decode step (decode_step + token choice) in ms; with `lp` (generation.LogitsProcessors) the token comes from
     rv_logits_process_argmax_f32 and is recorded in the device history, as greedy_generate does; with `sm` (the sampling settings of
-    parse_generate_kwargs) it is drawn by rv_sample_rows_f32, row b with seed sm.seed + b, as greedy_generate does."""
+    parse_generate_kwargs) it is drawn by rv_sample_rows_f32, row b with seed sm.seed + b, as greedy_generate does.  kv_dtype: the
+    cache's dtype (prefill's kv_dtype)."""
     B = ids.shape[0]
-    cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new)
+    cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new, **({} if kv_dtype is None else dict(kv_dtype=kv_dtype)))
     hist = torch.zeros(B, new, dtype=torch.int32, device=logits.device) if lp is not None else None
     if sm is not None:
         seeds = torch.tensor([sm.seed + b for b in range(B)], dtype=torch.int64, device=logits.device)
@@ -310,6 +322,122 @@ def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None):
         times.append((time.perf_counter() - t0) * 1e3)
     del cache
     return times[warm:]
+
+
+def kv8_ab(geo, batches, prompt, new, reps=3):
+    """The decode step on an int8-dtype cache, reference arm (dequantised bf16 rows, rv_attn_decode_bf16) vs int8 arm, bf16 weights and
+    then int8 weights, on one engine."""
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    recs = []
+    for weights in ("bf16", "int8"):
+        if weights == "int8":
+            eng.quantize_decoder_()
+        for B in batches:
+            ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+            ts = {False: [], True: []}
+            for flag in (False, True):                                 # warm-up: one untimed repetition of both arms
+                eng.kv8_decode = flag
+                _decode_loop(eng, ids, new, kv_dtype="int8")
+            for _ in range(reps):
+                for flag in (False, True):
+                    eng.kv8_decode = flag
+                    ts[flag].append(float(np.median(_decode_loop(eng, ids, new, kv_dtype="int8"))))
+            eng.kv8_decode = True
+            b, q = float(np.median(ts[False])), float(np.median(ts[True]))
+            keys = (prompt + new // 2) * B * eng.l["layers"]
+            kv16, kv8 = int(keys * 4 * eng.kvd), int(keys * (2 * eng.kvd + 8 * eng.Hkv))
+            wb = w8_weight_bytes(eng) if weights == "int8" else weight_bytes(eng)
+            recs.append(dict(geo=geo, mode="kv8_ab", weights=weights, B=B, prompt=prompt, new_tokens=new, reps=reps, ref_ms_per_step=round(b, 3),
+                             kv8_ms_per_step=round(q, 3), ref_ms_all=[round(x, 3) for x in ts[False]], kv8_ms_all=[round(x, 3) for x in ts[True]],
+                             ref_spread_ms=round(max(ts[False]) - min(ts[False]), 3), delta_ms=round(b - q, 3), speedup=round(b / q, 3),
+                             kv8_faster_by_more_than_ref_spread=bool(b - q > max(ts[False]) - min(ts[False])),
+                             ref_tokens_per_s=round(B * 1e3 / b, 1), kv8_tokens_per_s=round(B * 1e3 / q, 1), weight_bytes=wb,
+                             ref_kv_bytes_per_step=kv16, kv8_kv_bytes_per_step=kv8, kv_bytes_ratio=round(kv8 / kv16, 3),
+                             ref_implied_TBps=round((wb + kv16) / (b * 1e-3) / 1e12, 3), kv8_implied_TBps=round((wb + kv8) / (q * 1e-3) / 1e12, 3),
+                             kernel_src=_src_hash()))
+    return recs
+
+
+def kv8_shapes(reps=20, keys=(704, 7603), batches=(1, 8, 32)):
+    """rv_attn_decode_bf16 on the dequantised cache vs rv_attn_decode_kv8_bf16 on the int8 cache per head shape, interleaved, cold cache."""
+    out = []
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
+    for geo in ("llava15_7b", "llava_ov_qwen2_7b"):
+        l = GEOMETRIES[geo]["lm"]
+        H, hd = l["heads"], l["d"] // l["heads"]
+        Hkv = l.get("kv_heads", H)
+        kvd = Hkv * hd
+        for n in keys:
+            for B in batches:
+                src = torch.randn(B * n, 2 * kvd, device="cuda", dtype=torch.bfloat16)
+                q8 = torch.zeros(B, n, 2 * kvd, dtype=torch.int8, device="cuda")
+                s = torch.ones(B, n, 2 * Hkv, dtype=torch.float32, device="cuda")
+                deq = torch.zeros(B, n, 2 * kvd, dtype=torch.bfloat16, device="cuda")
+                ops.kv_quantize_rows(src, torch.arange(B * n, dtype=torch.int64, device="cuda"), Hkv, hd, cache=(q8, s), xhat=deq)
+                del src
+                q = torch.randn(B, H * hd, device="cuda", dtype=torch.bfloat16)
+                kv_len = torch.full((B,), n, dtype=torch.int32, device="cuda")
+                fns = {"bf16": lambda: ops.attn_decode(q, deq, kv_len, H, Hkv, hd, kvd), "kv8": lambda: ops.attn_decode_kv8(q, (q8, s), kv_len, H, Hkv, hd, kvd)}
+                assert torch.equal(fns["bf16"](), fns["kv8"]())
+                ts = {k: [] for k in fns}
+                for _ in range(reps):
+                    for k, f in fns.items():
+                        flush.zero_()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        f()
+                        e1.record()
+                        e1.synchronize()
+                        ts[k].append(e0.elapsed_time(e1) * 1e3)
+                b, k8 = float(np.median(ts["bf16"])), float(np.median(ts["kv8"]))
+                by16, by8 = B * n * 4 * kvd, B * n * (2 * kvd + 8 * Hkv)
+                out.append(dict(mode="kv8_kernel_ab", geo=geo, H=H, Hkv=Hkv, hd=hd, keys=n, B=B, bf16_us=round(b, 2), kv8_us=round(k8, 2),
+                                speedup=round(b / k8, 3), bf16_TBps=round(by16 / (b * 1e-6) / 1e12, 3), kv8_TBps=round(by8 / (k8 * 1e-6) / 1e12, 3),
+                                chunk=128, kernel_src=_src_hash()))
+                del q8, s, deq
+    return out
+
+
+def kv8_quality_toy(new=32):
+    """How far an int8 KV cache moves the toy goldens' models: relative L2 of the logits of the step after the last prompt row (the first
+    that reads quantised rows; the prompt pass itself is unquantised) and the share of greedy tokens that agree with the bf16 cache.
+    Reported, never gated."""
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    recs = []
+    for geo, golden in (("toy", "toy_e2e"), ("toy_qwen", "toy_qwen_e2e")):
+        g = np.load(os.path.join(root, golden + ".npz"))
+        n = len([k for k in g.files if k.startswith("image") and k[5:].isdigit()])
+        images = [torch.from_numpy(g[f"image{i}"]) for i in range(n)]
+        sizes = [tuple(x) for x in g["image_sizes"].tolist()]
+        eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="portable", seed=0)
+
+        def run(kv_dtype):
+            out = []
+            for b in range(n):
+                p = g["input_ids"][b][g["attention_mask"][b].astype(bool)].astype(np.int64)
+                cache, logits = eng.prefill(p[None], None, [images[b]], [sizes[b]], max_new_tokens=new, kv_dtype=kv_dtype)
+                toks, nxt = [ops.argmax_rows(logits, eng.vocab)], None
+                for _ in range(new - 1):
+                    logits = eng.decode_step(cache, toks[-1].to(torch.int32))
+                    nxt = logits[0].clone() if nxt is None else nxt
+                    toks.append(ops.argmax_rows(logits, eng.vocab))
+                out.append((nxt, torch.cat(toks).cpu().numpy()))
+            return out
+
+        a, b = run("bf16"), run("int8")
+        recs.append(dict(geo=geo, mode="kv8_quality_toy", prompts=n, new_tokens=new,
+                         next_step_logits_rel_l2=[round(float((y[0] - x[0]).norm() / x[0].norm()), 5) for x, y in zip(a, b)],
+                         greedy_tokens_agree=[round(float((x[1] == y[1]).mean()), 4) for x, y in zip(a, b)]))
+    return recs
+
+
+def kv8_trace(geo, B, prompt, new):
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+    ts = _decode_loop(eng, ids, new, kv_dtype="int8")
+    torch.cuda.synchronize()
+    return [dict(geo=geo, mode="kv8_trace", B=B, prompt=prompt, new_tokens=new, kv8_ms_per_step_under_trace=round(float(np.median(ts)), 3),
+                 kernel_src=_src_hash())]
 
 
 def _beam_loop(eng, ids, nb, new, warm=8):
@@ -873,6 +1001,10 @@ def main():
     ap.add_argument("--w8-shapes", action="store_true")
     ap.add_argument("--w8-trace", action="store_true")
     ap.add_argument("--w8-quality", action="store_true")
+    ap.add_argument("--kv8", action="store_true")
+    ap.add_argument("--kv8-shapes", action="store_true")
+    ap.add_argument("--kv8-quality", action="store_true")
+    ap.add_argument("--kv8-trace", action="store_true")
     ap.add_argument("--sample", action="store_true")
     ap.add_argument("--beams", action="store_true")
     ap.add_argument("--lookup", action="store_true")
@@ -892,6 +1024,14 @@ def main():
         recs = w8_quality_toy()
     elif a.w8_trace:
         recs = [r for g in a.geos.split(",") for r in w8_trace(g, a.prompt, a.new)]
+    elif a.kv8_shapes:
+        recs = kv8_shapes()
+    elif a.kv8:
+        recs = [r for g in a.geos.split(",") for r in kv8_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new)]
+    elif a.kv8_quality:
+        recs = kv8_quality_toy()
+    elif a.kv8_trace:
+        recs = [r for g in a.geos.split(",") for r in kv8_trace(g, int(a.batches.split(",")[-1]), a.prompt, a.new)]
     elif a.sample:
         recs = sample_kernel_ab() + [r for g in a.geos.split(",") for r in sample_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new)]
     elif a.beams:
