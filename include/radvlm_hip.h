@@ -471,6 +471,27 @@ int rv_beam_topk_f32(const float* x, int64_t ld, int groups, int nb, int n, cons
 /* Host function: the bytes of scratch rv_beam_topk_f32 needs. */
 int64_t rv_beam_topk_ws_bytes(int groups, int nb, int n, int K);
 
+/* ---- classifier-free guidance (generate(guidance_scale=), radvlm_amd/csrc/cfg.hip) ---------------------------------------------------
+ * HF reaches it through generate(guidance_scale=g, negative_prompt_ids=...) (HF:generation/logits_process.py
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor.__call__), with a second forward pass per token for the unconditional logits.  Here
+ * the unconditional sequence is one more row of the same decode step, and this kernel combines the two raw fp32 logits rows. */
+/* For each of `rows` row pairs and every column j < n (n <= 262144): with lc / lu the bits rv_log_softmax_rows_f32 gives row r of c / u,
+ *     c[r][j] <- fl(fl(g * fl(lc - lu)) + lu)
+ * three separately rounded fp32 operations in torch's order (no fma contraction).  c: raw conditional logits, rows of ld_c floats,
+ * overwritten; u: raw unconditional logits, rows of ld_u floats, never written; the two must not overlap.  Columns >= n of both are
+ * never touched.  No atomics and a fixed reduction order: a row's bits depend on that row pair and on g alone, not on `rows`, the launch
+ * structure or the other rows.  Non-finite logits are outside the contract.
+ * ws NULL: one launch, one workgroup per pair.  ws given (device scratch of ws_bytes >= rv_cfg_guide_ws_bytes(rows), 4-byte aligned,
+ * contents arbitrary, not to be shared by launches that can overlap): the row statistics by one launch, the elementwise part by a
+ * second one that spreads every row over many workgroups -- the same bits, faster on few long rows.
+ * |result - exact| <= (1 + 2^-20) (|g| E(lc) + |1 - g| E(lu) + |fl32(g) - g| |lc - lu| + 2^-24 (2 |g| |lc - lu| + |exact|)) with
+ * E(l) = 2^-24 (2 |l| + 4 ln n + 3), against exact arithmetic on the fp32 inputs and the real g (csrc/cfg.hip derives it).
+ * n < 1, rows < 1, ld_c < n, ld_u < n, a null c or u, a short or misaligned ws are refused (RV_ERR_ARG). */
+int rv_cfg_guide_rows_f32(float* c, int64_t ld_c, const float* u, int64_t ld_u, int rows, int n, float g, void* ws, int64_t ws_bytes,
+                          void* stream);
+/* Host function: the bytes of scratch the two-launch form of rv_cfg_guide_rows_f32 needs. */
+int64_t rv_cfg_guide_ws_bytes(int rows);
+
 /* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens=), radvlm_amd/csrc/lookup.hip) ----------------------------------------
  * The reference reaches it through HF generate(prompt_lookup_num_tokens=k) (HF:generation/candidate_generator.py
  * PromptLookupCandidateGenerator -> _assisted_decoding): k tokens drafted from n-gram repeats of the sequence are verified by one

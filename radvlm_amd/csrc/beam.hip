@@ -4,6 +4,7 @@
 // atomics: a row's (a prompt's) result is bit-identical whatever else shares the launch.
 // Reference call sites are listed per entry point in include/radvlm_hip.h.
 #include "common.h"
+#include "log_softmax.h"
 #include "radvlm_hip.h"
 
 #include <math.h>
@@ -189,61 +190,15 @@ __global__ __launch_bounds__(HD) void attn_decode_beam_combine_kernel(const floa
 //   the last subtraction rounds once more: u |out_i|; and |d_i| <= |out_i| because L >= 0.
 // Together |out_i - exact_i| <= u (2 |out_i| + 4 ln n + 3): 3.2e-6 + 1.2e-7 |out_i| at n = 262144.  It stays under the 1e-5 the
 // logprobs of generate_batch are tested to while |out_i| <= 57; a log-prob further down than that is resolved to 2 ulp of itself.
-constexpr int LS_U = 8;
-
-DEVINL double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
+// The statistics (m, L) are the device functions of log_softmax.h, which rv_cfg_guide_rows_f32 (cfg.hip) shares to get the same bits.
 __global__ __launch_bounds__(256) void log_softmax_rows_kernel(float* __restrict__ x, long ld, int n) {
     __shared__ float redm[4];
     __shared__ double reds[4];
     __shared__ float bc[2];
     float* row = x + (long)blockIdx.x * ld;
     const int tid = threadIdx.x;
-    float m = -INFINITY;
-    for (int j0 = tid; j0 < n; j0 += 256 * LS_U) {
-        float vs[LS_U];
-#pragma unroll
-        for (int u = 0; u < LS_U; ++u) {
-            const int j = j0 + u * 256;
-            vs[u] = j < n ? row[j] : -INFINITY;
-        }
-#pragma unroll
-        for (int u = 0; u < LS_U; ++u) m = fmaxf(m, vs[u]);
-    }
-    m = wave_max(m);
-    if (lane_id() == 0) redm[wave_id()] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));
-    double s = 0.0;
-    for (int j0 = tid; j0 < n; j0 += 256 * LS_U) {
-        float vs[LS_U];
-#pragma unroll
-        for (int u = 0; u < LS_U; ++u) {
-            const int j = j0 + u * 256;
-            vs[u] = j < n ? row[j] : -INFINITY;
-        }
-#pragma unroll
-        for (int u = 0; u < LS_U; ++u) {
-            const int j = j0 + u * 256;
-            if (j < n) s += (double)__expf(vs[u] - m);
-        }
-    }
-    s = wave_sum_f64(s);
-    if (lane_id() == 0) reds[wave_id()] = s;
-    __syncthreads();
-    if (tid == 0) {
-        double t = reds[0];
-        t += reds[1];
-        t += reds[2];
-        t += reds[3];
-        bc[0] = (float)log(t);
-    }
-    __syncthreads();
-    const float L = bc[0];
+    const float m = ls_row_max(row, n, redm);
+    const float L = ls_block_logsum(ls_thread_sum(row, n, m), reds, bc);
     for (int j0 = tid; j0 < n; j0 += 256 * LS_U) {
         float vs[LS_U];
 #pragma unroll

@@ -28,6 +28,8 @@ _ACCEPTED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "at
              "inputs_embeds", "past_key_values", "seed", "kv_cache_dtype") + _PROCESSORS + _IGNORED_WHEN_GREEDY
 # prompt-lookup decoding (HF's names): generate() alone takes them, generate_batch() and generate_beams() reject them as unknown
 _LOOKUP = ("prompt_lookup_num_tokens", "max_matching_ngram_size")
+# classifier-free guidance (HF's names; negative_images / negative_image_sizes are ours: HF's negative prompt cannot carry an image)
+_GUIDANCE = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "negative_images", "negative_image_sizes")
 LOOKUP_MAX_TOKENS = 31        # k drafted tokens are verified as k + 1 rows, and the skinny GEMM takes ops.GEMV_MAX_M = 32
 
 
@@ -45,10 +47,13 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     not do (do_sample=True without seed=, beam search, streamers, caller-supplied inputs_embeds, LoRA engines, kv_cache_dtype="int8"
     together with past_key_values or prompt_lookup_num_tokens), ValueError for a kv_cache_dtype other than None / "bf16" / "int8"
     (.kv_cache_dtype: "bf16" or "int8") and TypeError for unknown names.  lookup: also take prompt_lookup_num_tokens / max_matching_ngram_size (.lookup: None, or .k and .max_ngram; .drafter: None,
-    greedy_generate then builds a PromptLookupDrafter; a test or a benchmark may set another object with propose(seq))."""
-    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and not (lookup and k in _LOOKUP))
+    greedy_generate then builds a PromptLookupDrafter; a test or a benchmark may set another object with propose(seq)).
+    Classifier-free guidance (.guidance: None when off, else .scale and the negative prompt as given, _parse_guidance): with
+    past_key_values or prompt_lookup_num_tokens NotImplementedError."""
+    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and not (lookup and k in _LOOKUP))
     if unknown:
         raise TypeError(f"generate() got unexpected keyword arguments {unknown}")
+    guidance = _parse_guidance(kwargs)
     if kwargs.get("inputs_embeds") is not None:
         raise NotImplementedError("`inputs_embeds` is not supported")      # the reference's generate() raises the same
     if kwargs.get("do_sample") and kwargs.get("seed") is None:
@@ -70,6 +75,11 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     if lora:
         raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
                                   "model.merge_and_unload() (the reference merges adapters before evaluation)")
+    if guidance is not None and pkv is not None:
+        raise NotImplementedError("guidance_scale with past_key_values: a guided call fills one cache with both branches and keeps none "
+                                  "of it across calls")
+    if guidance is not None and kwargs.get("prompt_lookup_num_tokens") is not None:
+        raise NotImplementedError("guidance_scale with prompt_lookup_num_tokens: verifying drafts on two branches is not implemented")
     kv_dtype = parse_kv_cache_dtype(kwargs.get("kv_cache_dtype"))
     if kv_dtype == "int8" and pkv is not None:
         raise NotImplementedError("kv_cache_dtype='int8' with past_key_values: a GenerationCache is extended by the extend-attention "
@@ -94,8 +104,96 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
                            past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
-                           kv_cache_dtype=kv_dtype,
+                           kv_cache_dtype=kv_dtype, guidance=guidance,
                            **_parse_processors(kwargs, eos))
+
+
+def _parse_guidance(kwargs):
+    """Classifier-free guidance settings; None when it is off.  guidance_scale: None or 1 is off (HF adds no processor then, and the call
+    is today's call); any other finite real -- 0, negatives and values below 1 included, as in HF -- turns it on.  ValueError for a bool,
+    a non-number, a value that is not finite as fp32 (the kernel's scale), and for any negative_* argument while guidance is off.  The
+    negative prompt is kept as given; resolve_negative_prompts() checks it against the prompt."""
+    g = kwargs.get("guidance_scale")
+    if g is not None:
+        ok = not isinstance(g, bool) and isinstance(g, (int, float, np.floating, np.integer))
+        if ok:
+            with np.errstate(all="ignore"):
+                ok = bool(np.isfinite(np.float32(min(max(g, -1e39), 1e39))))
+        if not ok:
+            raise ValueError(f"`guidance_scale` has to be a finite number, but is {g!r}")
+    neg = {k: kwargs.get(k) for k in _GUIDANCE[1:]}
+    if g is None or g == 1:
+        given = sorted(k for k, v in neg.items() if v is not None)
+        if given:
+            raise ValueError(f"{given} given without a guidance_scale other than 1: a negative prompt has no effect without guidance")
+        return None
+    return SimpleNamespace(scale=float(g), negative_prompt_ids=neg["negative_prompt_ids"],
+                           negative_prompt_attention_mask=neg["negative_prompt_attention_mask"], negative_images=neg["negative_images"],
+                           negative_image_sizes=neg["negative_image_sizes"])
+
+
+def _check_negative_images(what, ids, images):
+    """The image rule of a negative prompt: images are required when it holds placeholders and refused when it holds none."""
+    from .splice import IMAGE_TOKEN_INDEX
+    k = int((np.asarray(ids) == IMAGE_TOKEN_INDEX).sum())
+    n = len(images)
+    if k and not n:
+        raise ValueError(f"{what}: the negative prompt holds {k} image tokens but no negative_images were passed")
+    if n and not k:
+        raise ValueError(f"{what}: negative_images were passed but the negative prompt holds no image token")
+    if k != n:
+        raise ValueError(f"{what}: the negative prompt holds {k} image tokens but {n} negative_images were passed")
+
+
+def resolve_negative_prompts(guidance, ids, am):
+    """The unconditional rows of a guided generate() call: (ids int64 [B, Ln], mask bool [B, Ln], images list, image_sizes or None).
+    Without negative_prompt_ids each row's negative prompt is its last real prompt token (HF: input_ids[:, -1:] on the first pass).
+    ValueError for a row count other than B, a mask of another shape, a row that is empty after masking, and images that do not match
+    the placeholders (_check_negative_images)."""
+    ids = np.asarray(ids)
+    B = ids.shape[0]
+    nid, nam = guidance.negative_prompt_ids, guidance.negative_prompt_attention_mask
+    to_np = lambda v: np.asarray(v.detach().cpu() if torch.is_tensor(v) else v)
+    if nid is None:
+        if nam is not None:
+            raise ValueError("negative_prompt_attention_mask given without negative_prompt_ids")
+        if am is None:
+            nid = ids[:, -1:]
+        else:
+            m = np.asarray(am).reshape(B, -1).astype(bool)
+            if not m.any(1).all():
+                raise ValueError("the default negative prompt is each row's last prompt token, but a row has none")
+            last = m.shape[1] - 1 - np.argmax(m[:, ::-1], axis=1)
+            nid = ids[np.arange(B), last][:, None]
+        nid = np.ascontiguousarray(nid, dtype=np.int64)
+        nam = np.ones(nid.shape, dtype=bool)
+    else:
+        nid = to_np(nid)
+        if nid.ndim == 1:
+            nid = nid[None]
+        if nid.ndim != 2 or not np.issubdtype(nid.dtype, np.integer):
+            raise ValueError(f"`negative_prompt_ids` has to hold token ids [B, Ln], got shape {nid.shape}, dtype {nid.dtype}")
+        if nid.shape[0] != B:
+            raise ValueError(f"`negative_prompt_ids` holds {nid.shape[0]} rows for {B} prompt rows")
+        nid = nid.astype(np.int64)
+        if nam is None:
+            nam = np.ones(nid.shape, dtype=bool)
+        else:
+            nam = to_np(nam)
+            if nam.ndim == 1:
+                nam = nam[None]
+            if nam.shape != nid.shape:
+                raise ValueError(f"`negative_prompt_attention_mask` has shape {nam.shape}, `negative_prompt_ids` {nid.shape}")
+            nam = nam.astype(bool)
+        if nid.shape[1] == 0 or not nam.any(1).all():
+            raise ValueError("every row of the negative prompt needs at least one token after masking")
+    imgs = guidance.negative_images
+    imgs = [] if imgs is None else ([im for im in imgs] if torch.is_tensor(imgs) else list(imgs))
+    sizes = guidance.negative_image_sizes
+    if sizes is not None and not imgs:
+        raise ValueError("negative_image_sizes given without negative_images")
+    _check_negative_images("generate()", nid[nam], imgs)
+    return nid, nam, imgs, sizes
 
 
 def parse_kv_cache_dtype(v):
@@ -602,6 +700,79 @@ def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
         fed = True
 
 
+def _guided_generate(engine, ids, am, images, image_sizes, cfg):
+    """greedy_generate with classifier-free guidance (cfg.guidance): one KVCache of 2 * B rows, rows 0 .. B - 1 prefilled with the
+    prompts and rows B .. 2B - 1 with the negative prompts (resolve_negative_prompts), L_max = the longer spliced length + the budget.
+    Every decode step runs all 2 * B rows and feeds the emitted token (the pad of a finished row) to both halves, which is what HF's
+    processor does with input_ids[:, -1:].  Per step: output_logits clones the raw conditional rows; ops.cfg_guide_rows turns
+    (conditional, unconditional) into the guided rows in place; then the processors, the argmax or the seeded sampler, output_scores
+    and the stopping criteria run on the guided rows exactly as greedy_generate runs them on the raw ones (CFG is HF's first
+    processor).  min_length / max_length count the conditional prompt."""
+    from . import ops
+    gd = cfg.guidance
+    B, dev, V = ids.shape[0], engine.device, engine.vocab
+    if getattr(cfg, "lookup", None) is not None or getattr(cfg, "drafter", None) is not None:
+        raise NotImplementedError("guidance_scale with prompt_lookup_num_tokens: verifying drafts on two branches is not implemented")
+    nids, nam, nimgs, nsizes = resolve_negative_prompts(gd, ids, am)
+    imgs = list(images) if images is not None else []
+    plan = engine.plan(ids, am, None, imgs, image_sizes)
+    nplan = engine.plan(nids, nam, None, nimgs, nsizes)
+    S = int(plan["S"])
+    T = new_token_budget(cfg, S)
+    lp = LogitsProcessors(cfg, V, S)
+    st = GreedyState(B, cfg)
+    scores, raw = [], []
+    sm = cfg.sampling
+    if sm is not None:
+        seeds = sampling_seeds(sm, B)
+    if T > 0:
+        kvd = getattr(cfg, "kv_cache_dtype", "bf16")
+        kv_args = () if kvd == "bf16" else (kvd,)
+        L_max = max(int(plan["lens"].max()), int(nplan["lens"].max())) + T
+        need, free = engine.kv_cache_bytes(2 * B, L_max, *kv_args), engine.free_device_bytes()
+        if free is not None and need > free:
+            raise ValueError(f"guided generate(): the KV cache of 2 x {B} rows x {L_max} positions needs {need} bytes, but only {free} "
+                             f"bytes of device memory are free: lower the batch or the token budget")
+        cache = engine.new_kv_cache(2 * B, L_max, *kv_args)
+        _, c = engine.prefill(ids, am, images, image_sizes, cache=cache, slots=np.arange(B))
+        _, u = engine.prefill(nids, nam, nimgs or None, nsizes, cache=cache, slots=B + np.arange(B))
+        if sm is not None:
+            sm_seed = torch.tensor(seeds, dtype=torch.int64, device=dev)
+            sm_t = torch.arange(T, dtype=torch.int32, device=dev)[:, None].expand(T, B).contiguous()
+            sm_write = cfg.output_scores or bool(cfg.stopping_criteria)
+            sm_ws = ops.sample_rows_workspace(B, dev)
+        hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active else None
+        gws = ops.cfg_guide_workspace(B, dev)
+        for t in range(T):
+            if cfg.output_logits:
+                raw.append(c.clone())
+            logits = ops.cfg_guide_rows(c, u, V, gd.scale, ws=gws)         # in place: the conditional rows become the guided scores
+            if lp.active:
+                nxt = ops.logits_process_argmax(logits, V, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
+            elif sm is None:
+                nxt = ops.argmax_rows(logits, V)
+            if sm is not None:
+                nxt = ops.sample_rows(logits, V, sm_seed, sm_t[t], sm.temperature, sm.top_k, sm.top_p, sm.min_p, write_scores=sm_write,
+                                      ws=sm_ws)
+                nxt = nxt.cpu().numpy()
+                _check_sampled(nxt, np.flatnonzero(st.unfinished))
+            if cfg.output_scores:
+                scores.append(logits.clone())
+            tok = st.step(nxt, logits, device=dev)
+            if hist is not None:
+                hist[:, t] = torch.from_numpy(tok.astype(np.int32)).to(dev)
+            if st.all_done or t == T - 1:
+                break
+            both = engine.decode_step(cache, torch.from_numpy(np.concatenate([tok, tok])))
+            c, u = both[:B], both[B:]
+        del cache
+    seq = torch.from_numpy(st.sequences()).to(dev)
+    if cfg.return_dict:
+        return GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
+                                         logits=tuple(raw) if cfg.output_logits else None, past_key_values=None)
+    return seq
+
+
 def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg):
     """prefill once, then decode_step per token until every row has finished or the budget is spent.  With cfg.past_key_values (a
     GenerationCache) the prompt pass reuses what the cache holds (LlavaEngine.extend; an empty cache: prefill as without one) and the
@@ -617,6 +788,8 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     am = cfg.attention_mask
     am = None if am is None else np.asarray(am.cpu() if torch.is_tensor(am) else am)
     B = ids.shape[0]
+    if getattr(cfg, "guidance", None) is not None:
+        return _guided_generate(engine, ids, am, images, image_sizes, cfg)
     gc = cfg.past_key_values
     if gc is not None:
         gc._bind(engine, B)
@@ -728,6 +901,9 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
     given = sorted(k for k in _NO_PER_REQUEST if kwargs.get(k) is not None and kwargs.get(k) is not False)
     if given:
         raise TypeError(f"generate_batch() got arguments without a per-request meaning: {given}")
+    if kwargs.get("negative_prompt_attention_mask") is not None:
+        raise TypeError("generate_batch() takes unpadded negative prompts (negative_prompt_ids: a list of 1-D id sequences); "
+                        "negative_prompt_attention_mask has no per-request meaning")
     kw = {k: v for k, v in kwargs.items() if k not in _NO_PER_REQUEST}
     budgets = None
     mnt = kw.get("max_new_tokens")
@@ -742,6 +918,9 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
         del kw["max_new_tokens"]
     cfg = parse_generate_kwargs(kw, lora=lora, config_eos=config_eos, config_pad=config_pad)
     cfg.budgets = budgets
+    if cfg.guidance is not None:
+        for k in ("negative_prompt_ids", "negative_images", "negative_image_sizes"):
+            _per_request(k, getattr(cfg.guidance, k), n)      # a list of another length: ValueError here, before anything runs
     if cfg.sampling is not None:
         sampling_seeds(cfg.sampling, n)                       # a list of another length: ValueError here, before anything runs
     return cfg
@@ -766,9 +945,12 @@ def _size_list(v):
     return [tuple(int(x) for x in s) for s in v]
 
 
-def batch_requests(inputs, images=None, image_sizes=None):
+def batch_requests(inputs, images=None, image_sizes=None, guidance=None):
     """The requests of generate_batch(), normalised: ids (int64 numpy, as given), images (the request's tensors in image-token order)
-    and sizes (one (h, w) per image, or None).  ValueError for a list of the wrong length or images that do not match the image tokens."""
+    and sizes (one (h, w) per image, or None).  ValueError for a list of the wrong length or images that do not match the image tokens.
+    guidance (cfg.guidance of a guided call): every request also gets neg_ids (its entry of negative_prompt_ids, a non-empty 1-D id
+    sequence; without one, the request's last prompt token, HF's rule), neg_images and neg_sizes (its entries of negative_images /
+    negative_image_sizes: required when neg_ids holds image tokens, refused when it holds none)."""
     from .splice import IMAGE_TOKEN_INDEX
     inputs = list(inputs)
     n = len(inputs)
@@ -791,6 +973,27 @@ def batch_requests(inputs, images=None, image_sizes=None):
     with_img = [r for r in reqs if r.images]
     if any(r.sizes is None for r in with_img) and any(r.sizes is not None for r in with_img):
         raise ValueError("image_sizes: give the sizes of every request's images or of none")
+    if guidance is not None:
+        nids = _per_request("negative_prompt_ids", guidance.negative_prompt_ids, n)
+        nims = _per_request("negative_images", guidance.negative_images, n)
+        nszs = _per_request("negative_image_sizes", guidance.negative_image_sizes, n)
+        for i, r in enumerate(reqs):
+            if nids[i] is None:
+                neg = r.ids[-1:]
+            else:
+                neg = np.asarray(nids[i].detach().cpu() if torch.is_tensor(nids[i]) else nids[i])
+                if neg.ndim != 1 or neg.size == 0 or not np.issubdtype(neg.dtype, np.integer):
+                    raise ValueError(f"request {i}: a negative prompt is a non-empty 1-D sequence of token ids, got shape {neg.shape}, "
+                                     f"dtype {neg.dtype}")
+            im = [] if nims[i] is None else ([nims[i]] if torch.is_tensor(nims[i]) else list(nims[i]))
+            sz = _size_list(nszs[i])
+            _check_negative_images(f"request {i}", neg, im)
+            if sz is not None and len(sz) != len(im):
+                raise ValueError(f"request {i}: {len(sz)} negative image sizes for {len(im)} negative images")
+            r.neg_ids, r.neg_images, r.neg_sizes = neg.astype(np.int64), im, sz
+        with_img = [r for r in reqs if r.neg_images]
+        if any(r.neg_sizes is None for r in with_img) and any(r.neg_sizes is not None for r in with_img):
+            raise ValueError("negative_image_sizes: give the sizes of every request's negative images or of none")
     return reqs
 
 
@@ -869,9 +1072,16 @@ class BatchScheduler:
     frees its slot.  With cfg.sampling request i carries its own seed (sampling_seeds: an int s gives s + i) and the picker is called with
     seed=, the seeds of the rows' requests (0 for an idle slot), next to each row's step t: what a request draws depends on neither the
     slot nor the schedule.  cfg.kv_cache_dtype "int8": the memory check and the cache are sized for the int8 cache (the dtype is passed to
-    kv_cache_bytes and new_kv_cache; the default dtype keeps their two-argument calls).  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t)."""
+    kv_cache_bytes and new_kv_cache; the default dtype keeps their two-argument calls).
+    cfg.guidance (classifier-free guidance; the requests then carry neg_ids / neg_images / neg_sizes, batch_requests): the cache has
+    2 * slots rows, slot s holding the request's prompt and row slots + s its negative prompt; the memory check counts both halves and
+    L_max covers the longer of the two prompts plus the budget; an admitted group is two prefills (the negative group ordered by the
+    same image-first rule); a decode step runs all 2 * slots rows, feeding a request's token to both of its rows (an idle slot's two
+    rows: token 0 at length 0); `guide(cond, uncond)` -- default ops.cfg_guide_rows with the call's scale -- then turns the first
+    `slots` rows into the guided scores in place and the picker runs on them as it does without guidance.  A finished request frees
+    both rows.  Without cfg.guidance nothing here changes.  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t)."""
 
-    def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None):
+    def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None, guide=None):
         if not _is_int(max_batch_size) or max_batch_size < 1:
             raise ValueError(f"max_batch_size must be an int >= 1, got {max_batch_size!r}")
         self.engine, self.reqs, self.cfg = engine, reqs, cfg
@@ -884,6 +1094,10 @@ class BatchScheduler:
         self.runs = [i for i in range(n) if self.budget[i] > 0]
         self.slots = min(int(max_batch_size), len(self.runs))
         self.L_max = max([self.spliced[i] + self.budget[i] for i in self.runs], default=0)
+        self.guidance, self.guide = getattr(cfg, "guidance", None), guide
+        if self.guidance is not None:
+            self.neg_spliced = [int(engine.plan(r.neg_ids[None], None, None, r.neg_images, r.neg_sizes)["lens"][0]) for r in reqs]
+            self.L_max = max([max(self.spliced[i], self.neg_spliced[i]) + self.budget[i] for i in self.runs], default=0)
         self.max_budget = max([self.budget[i] for i in self.runs], default=0)
         self.admit_free = max(1, min(ADMIT_FREE_SLOTS if admit_free is None else int(admit_free), self.slots))
         self.picker = picker
@@ -903,14 +1117,19 @@ class BatchScheduler:
         eng, S = self.engine, self.slots
         kvd = getattr(self.cfg, "kv_cache_dtype", "bf16")
         kv_args = () if kvd == "bf16" else (kvd,)             # the default dtype keeps the two-argument calls
-        need = eng.kv_cache_bytes(S, self.L_max, *kv_args)
+        rows = 2 * S if self.guidance is not None else S      # guidance: row S + s is slot s's unconditional sequence
+        need = eng.kv_cache_bytes(rows, self.L_max, *kv_args)
         free = eng.free_device_bytes()
         if free is not None and need > free:
-            raise ValueError(f"generate_batch: the KV cache of {S} slots x {self.L_max} positions needs {need} bytes, but only {free} bytes "
+            raise ValueError(f"generate_batch: the KV cache of {rows} rows x {self.L_max} positions needs {need} bytes, but only {free} bytes "
                              f"of device memory are free: lower max_batch_size or the token budgets")
         if self.picker is None:
             self.picker = DevicePicker(eng, self.cfg, S, self.max_budget, self.logprobs, any(self.min_new[i] > 0 for i in self.runs))
-        self.cache = eng.new_kv_cache(S, self.L_max, *kv_args)
+        self.cache = eng.new_kv_cache(rows, self.L_max, *kv_args)
+        if self.guidance is not None and self.guide is None:
+            from . import ops
+            gws, g, V = ops.cfg_guide_workspace(S, eng.device), self.guidance.scale, eng.vocab
+            self.guide = lambda c, u: ops.cfg_guide_rows(c, u, V, g, ws=gws)
         self.owner = np.full(S, -1, dtype=np.int64)           # request in each slot, -1: idle
         self.t = np.zeros(S, dtype=np.int64)                  # tokens the slot's request has generated
         self.mn = np.zeros(S, dtype=np.int64)                 # its EOS minimum
@@ -944,11 +1163,40 @@ class BatchScheduler:
         imgs = [im for r in rq for im in r.images]
         sizes = [s for r in rq for s in (r.sizes or [])] if any(r.sizes is not None for r in rq) else None
         _, logits = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs)
+        if self.guidance is not None:
+            logits = self._admit_negative(logits, rq, rs)
         self._step(logits, rs)
+
+    def _admit_negative(self, logits, rq, rs):
+        """Prefill the negative prompts of the admitted requests rq (slots rs) into rows slots + s and guide the group's logits."""
+        order = sorted(range(len(rq)), key=lambda j: not rq[j].neg_images)     # the image-first rule, among the negative prompts
+        nq = [rq[j] for j in order]
+        T = max(r.neg_ids.size for r in nq)
+        ids = np.zeros((len(nq), T), dtype=np.int64)
+        am = np.zeros((len(nq), T), dtype=bool)
+        for b, r in enumerate(nq):
+            ids[b, :r.neg_ids.size], am[b, :r.neg_ids.size] = r.neg_ids, True
+        imgs = [im for r in nq for im in r.neg_images]
+        sizes = [s for r in nq for s in (r.neg_sizes or [])] if any(r.neg_sizes is not None for r in nq) else None
+        _, un = self.engine.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=[self.slots + rs[j] for j in order])
+        back = np.argsort(np.asarray(order))                                    # row j of the group is row back[j] of `un`
+        if not np.array_equal(back, np.arange(len(order))):
+            un = un[torch.as_tensor(back, device=un.device)]
+        self.guide(logits, un)
+        return logits
 
     def _decode(self):
         idle = self.owner < 0
         self.events.append(("decode", tuple(int(s) for s in np.flatnonzero(~idle))))
+        if self.guidance is not None:
+            idle2 = np.concatenate([idle, idle])
+            self.cache.lens[idle2] = 0
+            feed = np.where(idle, 0, self.pending)
+            logits = self.engine.decode_step(self.cache, np.concatenate([feed, feed]))
+            self.cache.lens[idle2] = 0
+            self.guide(logits[:self.slots], logits[self.slots:])
+            self._step(logits[:self.slots], list(range(self.slots)))
+            return
         self.cache.lens[idle] = 0
         logits = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending))
         self.cache.lens[idle] = 0
@@ -992,7 +1240,8 @@ class BatchScheduler:
 def generate_batch(engine, inputs, images, image_sizes, cfg, max_batch_size=32, return_logprobs=False):
     """Continuous batching over many prompts (LlavaLlamaForCausalLM.generate_batch); cfg from parse_batch_kwargs.  Each request's
     generated tokens are what generate() returns for it alone (B = 1, the same settings), up to rounding."""
-    return BatchScheduler(engine, batch_requests(inputs, images, image_sizes), cfg, max_batch_size, return_logprobs).run()
+    return BatchScheduler(engine, batch_requests(inputs, images, image_sizes, getattr(cfg, "guidance", None)), cfg, max_batch_size,
+                          return_logprobs).run()
 
 
 # ------------------------------------------------------------------------------------------------ beam search: generate_beams
@@ -1024,11 +1273,16 @@ def parse_beam_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
     """Validate generate_beams() keyword arguments: generate()'s, plus length_penalty (float, default 1.0), early_stopping (False, True
     or "never") and num_return_sequences <= num_beams.  ValueError for num_beams outside [1, 16] or K = max(2, 1 + n_eos) * num_beams
     above 64; NotImplementedError for do_sample=True (beam sampling), past_key_values, streamer, inputs_embeds, LoRA engines and
-    kv_cache_dtype="int8" (None and "bf16" are accepted and change nothing);
+    kv_cache_dtype="int8" (None and "bf16" are accepted and change nothing), and for classifier-free guidance (guidance_scale or any
+    negative_* argument given);
     TypeError for unknown names.  The sampling knobs HF ignores when greedy stay ignored."""
-    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _BEAM_ONLY)
+    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _BEAM_ONLY and k not in _GUIDANCE)
     if unknown:
         raise TypeError(f"generate_beams() got unexpected keyword arguments {unknown}")
+    given = sorted(k for k in _GUIDANCE if kwargs.get(k) is not None)
+    if given:
+        raise NotImplementedError(f"classifier-free guidance with beams is not implemented (guidance_scale and its negative prompt: "
+                                  f"got {given}); generate() and generate_batch() take them")
     if kwargs.get("do_sample"):
         raise NotImplementedError("do_sample=True with beams: beam sampling is not implemented")
     if kwargs.get("past_key_values") is not None:

@@ -299,6 +299,17 @@ class LlavaLlamaForCausalLM:
         comes from the unquantised prompt pass; later tokens see the rounded keys and values, so they may differ from the bf16
         cache's.  It composes with the logits processors, sampling, output_scores / output_logits and load_8bit models; it does
         NOT compose with past_key_values or prompt_lookup_num_tokens (NotImplementedError), and another value is a ValueError.
+        Classifier-free guidance: guidance_scale=g (a finite number; None or 1: off, and the call is bit for bit the call without
+        it) with HF's negative_prompt_ids [B, Ln] / negative_prompt_attention_mask, plus negative_images / negative_image_sizes
+        (required when the negative prompt holds image placeholders, refused when it holds none); without a negative prompt each
+        row's is its last real prompt token (HF).  Each step's scores become log_softmax(uncond) + g * (log_softmax(cond) -
+        log_softmax(uncond)) (HF's UnbatchedClassifierFreeGuidanceLogitsProcessor, rounded as HF rounds it) before the processors and
+        warpers above; the unconditional sequence -- the negative prompt, then the same generated tokens -- is one more row of the
+        same decode step in a cache of 2 * B rows.  output_logits returns the raw conditional logits, output_scores and the stopping
+        criteria the guided, processed scores; min_length / max_length count the conditional prompt.  It composes with sampling,
+        kv_cache_dtype="int8" and load_8bit models; with past_key_values or prompt_lookup_num_tokens NotImplementedError; a bad
+        scale, a negative prompt of another row count or with an empty row, images that do not match its placeholders, or any
+        negative_* argument while guidance is off: ValueError.
         The training state (weights, optimizer, RNG counters) is not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
@@ -325,6 +336,10 @@ class LlavaLlamaForCausalLM:
         processed scores at the emitted token (when sampling: log q of the drawn token, q the softmax over what the warpers kept).
         kv_cache_dtype="int8" (None / "bf16": today's cache): the slots' cache holds int8 K|V rows as in generate(), so the memory
         check admits about twice the slots or positions; a request's tokens are those of generate(kv_cache_dtype="int8") on it alone.
+        guidance_scale=g (one value for the call) with negative_prompt_ids (a list of N unpadded 1-D id sequences, an entry None: the
+        request's last prompt token) and negative_images / negative_image_sizes (per request, as images): classifier-free guidance
+        as in generate().  max_batch_size keeps counting requests; the cache holds two rows per slot (the memory check counts both)
+        and a request's tokens are those of generate() on it alone with the same guidance.  negative_prompt_attention_mask: TypeError.
         The training state is not touched."""
         from ...generation import generate_batch, parse_batch_kwargs
         inputs = list(inputs)
@@ -346,7 +361,8 @@ class LlavaLlamaForCausalLM:
         num_beams rows; the prompt is prefilled once per prompt and never copied, and no cache row is reordered (the engine's decode
         attention follows each beam's ancestry instead).  do_sample=True (beam sampling), past_key_values, streamers, inputs_embeds
         and LoRA models raise NotImplementedError, and so does kv_cache_dtype="int8" (the beam-attention kernel reads a bf16 cache;
-        None and "bf16" are accepted and change nothing).  The training state is not touched."""
+        None and "bf16" are accepted and change nothing), and so does classifier-free guidance (guidance_scale or any negative_*
+        argument).  The training state is not touched."""
         from ...generation import beam_generate, parse_beam_kwargs
         cfg = parse_beam_kwargs(dict(kwargs, num_beams=num_beams), lora=bool(self.engine.lora),
                                 config_eos=getattr(self.config, "eos_token_id", None), config_pad=getattr(self.config, "pad_token_id", None))

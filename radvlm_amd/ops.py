@@ -897,6 +897,38 @@ def log_softmax_rows(x, n):
     return x
 
 
+# rv_cfg_guide_rows_f32's launch structure: "split" (row statistics, then an elementwise launch over many workgroups) or "pair" (one
+# launch, one workgroup per row pair).  The two give the same bits; DESIGN.md 5b "Classifier-free guidance" holds their A/B.
+CFG_GUIDE_ROUTE = "split"
+
+
+def cfg_guide_workspace(rows, device):
+    """Scratch for cfg_guide_rows' two-launch form at up to `rows` rows (fp32, never zeroed); calls that share it run on one stream."""
+    return torch.empty(max(lib.load().rv_cfg_guide_ws_bytes(int(rows)) // 4, 1), dtype=torch.float32, device=device)
+
+
+def cfg_guide_rows(c, u, n, g, ws=None, route=None):
+    """Classifier-free guidance in place (rv_cfg_guide_rows_f32): c[r, :n] <- g * (log_softmax(c[r, :n]) - log_softmax(u[r, :n])) +
+    log_softmax(u[r, :n]) for every fp32 row pair, the log-softmax values being log_softmax_rows' bits and the three operations rounded
+    separately in that order (HF's expression).  u is only read; columns >= n of both are not touched; c and u must not overlap.
+    route: None (CFG_GUIDE_ROUTE), "split" or "pair"; ws: cfg_guide_workspace(>= rows) for "split" (allocated when missing).  Returns c."""
+    _chk(c, torch.float32), _chk(u, torch.float32)
+    rows = c.shape[0]
+    assert c.dim() == 2 and u.dim() == 2 and u.shape[0] == rows and rows >= 1 and c.stride(1) == 1 and u.stride(1) == 1
+    assert 0 < n <= min(c.shape[1], u.shape[1], LOGITS_PROCESS_MAX_N)
+    route = CFG_GUIDE_ROUTE if route is None else route
+    assert route in ("split", "pair")
+    if route == "pair":
+        ws, ws_bytes = None, 0
+    else:
+        ws = cfg_guide_workspace(rows, c.device) if ws is None else ws
+        _chk(ws, torch.float32)
+        assert ws.is_contiguous() and ws.numel() * 4 >= lib.load().rv_cfg_guide_ws_bytes(rows)
+        ws_bytes = ws.numel() * 4
+    lib.call("rv_cfg_guide_rows_f32", c, c.stride(0), u, u.stride(0), rows, int(n), float(g), ws, ws_bytes)
+    return c
+
+
 BEAM_MAX = 16             # beams per prompt (rv_beam_topk_f32)
 BEAM_TOPK_MAX = 64        # candidates kept per prompt and step
 

@@ -62,6 +62,16 @@
         # rv_attn_decode_beam_bf16 (prefix_row 0, prefix_len L_max: the same bits) for R = 4, 8, 16, 32 at 704 and 7603 keys, device
         # time, interleaved, three medians per arm
   python tools/decode_bench.py --lookup-kernel-ab [--geos ..]   # (b) alone
+  python tools/decode_bench.py --cfg [--geos ..] [--batches 1,8,16] [--prompt 704] [--new 128] [--out FILE]
+        # classifier-free guidance: (1) rv_cfg_guide_rows_f32's two launch structures (pair: one workgroup per row pair; split: row
+        # statistics, then an elementwise launch over many workgroups) and the unfused baseline (rv_log_softmax_rows_f32 twice, then
+        # three torch elementwise kernels) at 32,000 and 152,064 columns, 1 and 16 rows, device time, median of 50, interleaved, on
+        # rows just written (warm) and after a 1 GiB fill has evicted them (cold); (2) the decode step (decode_step + guide + argmax)
+        # of a guided run of B requests -- 2 * B cache rows -- with a full-length and with a 1-token negative prompt, beside the plain
+        # step at B and at 2 * B rows, on one engine: one untimed pass of every arm, then the arms alternated three times; median ms
+        # per step per arm, the spread of the three medians, guided / plain(B), guided / plain(2B) and whether the guided step lies
+        # below 2 x plain(B) -- HF's two forward passes -- by more than the plain arm's spread; the guide launch's share of the step
+  python tools/decode_bench.py --cfg-kernel-ab   # (1) alone
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -650,6 +660,133 @@ def lookup_kernel_ab(geo, reps=40, rounds=3):
     return recs
 
 
+def cfg_kernel_ab(reps=50):
+    """rv_cfg_guide_rows_f32 as one launch per row pair ("pair"), as statistics + elementwise launch ("split"), and the unfused
+    baseline: two rv_log_softmax_rows_f32 calls and torch's three elementwise kernels.  Device time per call (events around it, so a
+    gap between an arm's launches counts), median of `reps`, arms interleaved; every call starts from freshly copied raw rows, either
+    still in the caches ("warm": what a decode step leaves) or evicted by a 1 GiB fill ("cold").  The three arms are checked to give
+    the same bits before anything is timed."""
+    recs = []
+    g = 1.5
+    flush = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
+    for n in (32000, 152064):
+        for rows in (1, 16):
+            rng = np.random.default_rng(n + rows)
+            c0 = torch.from_numpy((rng.standard_normal((rows, n)) * 4).astype(np.float32)).cuda()
+            u0 = torch.from_numpy((rng.standard_normal((rows, n)) * 4).astype(np.float32)).cuda()
+            c, u = c0.clone(), u0.clone()
+            ws = ops.cfg_guide_workspace(rows, "cuda")
+
+            def unfused():
+                ops.log_softmax_rows(c, n)
+                ops.log_softmax_rows(u, n)
+                c.sub_(u).mul_(g).add_(u)
+
+            fns = {"pair": lambda: ops.cfg_guide_rows(c, u, n, g, route="pair"), "split": lambda: ops.cfg_guide_rows(c, u, n, g, ws=ws, route="split"),
+                   "unfused": unfused}
+            outs = {}
+            for k, f in fns.items():
+                c.copy_(c0), u.copy_(u0)
+                f()
+                outs[k] = c.clone()
+            assert torch.equal(outs["pair"], outs["split"]) and torch.equal(outs["pair"], outs["unfused"])
+            rec = dict(mode="cfg_kernel_ab", rows=rows, vocab=n, reps=reps, g=g)
+            for temp in ("warm", "cold"):
+                ts = {k: [] for k in fns}
+                for _ in range(reps):
+                    for k, f in fns.items():
+                        c.copy_(c0), u.copy_(u0)
+                        if temp == "cold":
+                            flush.fill_(0.0)
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        f()
+                        e1.record()
+                        e1.synchronize()
+                        ts[k].append(e0.elapsed_time(e1) * 1e3)
+                med = {k: float(np.median(v)) for k, v in ts.items()}
+                rec.update({f"{k}_{temp}_us": round(v, 2) for k, v in med.items()})
+                rec.update({f"{k}_{temp}_p10_p90_us": [round(float(np.percentile(ts[k], 10)), 2), round(float(np.percentile(ts[k], 90)), 2)] for k in fns})
+                rec[f"split_over_pair_{temp}"] = round(med["split"] / med["pair"], 3)
+                rec[f"unfused_over_split_{temp}"] = round(med["unfused"] / med["split"], 3)
+            recs.append(rec)
+    return recs
+
+
+def _guided_loop(eng, ids, nids, new, warm=8):
+    """The decode step of guided generation as generation._guided_generate runs it: one cache of 2 * B rows, two prefills, then per
+    step decode_step over all rows + ops.cfg_guide_rows + argmax.  Returns (step times in ms after warm-up, the guide launch's median
+    device time in us on the last step's rows)."""
+    B, V = ids.shape[0], eng.vocab
+    L_max = max(ids.shape[1], nids.shape[1]) + new
+    cache = eng.new_kv_cache(2 * B, L_max)
+    _, c = eng.prefill(ids, None, None, None, cache=cache, slots=np.arange(B))
+    _, u = eng.prefill(nids, None, None, None, cache=cache, slots=B + np.arange(B))
+    ws = ops.cfg_guide_workspace(B, c.device)
+    tok = ops.argmax_rows(ops.cfg_guide_rows(c, u, V, 1.5, ws=ws), V)
+    times = []
+    for _ in range(1, new):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        both = eng.decode_step(cache, torch.cat([tok, tok]).to(torch.int32))
+        tok = ops.argmax_rows(ops.cfg_guide_rows(both[:B], both[B:], V, 1.5, ws=ws), V)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    raw = both.clone()
+    gus = []
+    for _ in range(50):
+        both.copy_(raw)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ops.cfg_guide_rows(both[:B], both[B:], V, 1.5, ws=ws)
+        e1.record()
+        e1.synchronize()
+        gus.append(e0.elapsed_time(e1) * 1e3)
+    del cache
+    return times[warm:], float(np.median(gus))
+
+
+def cfg_ab(geo, batches, prompt, new, reps=3):
+    """Guided decode at B requests (full-length and 1-token negative prompts) beside the plain decode step at B and at 2 * B rows."""
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    recs = []
+    for B in batches:
+        rng = np.random.default_rng(0)
+        ids, ids2 = rng.integers(0, eng.vocab, (B, prompt)), rng.integers(0, eng.vocab, (2 * B, prompt))
+        neg_full, neg_one = rng.integers(0, eng.vocab, (B, prompt)), ids[:, -1:]
+        guide_us = {}
+
+        def guided(name, nids):
+            ts, gu = _guided_loop(eng, ids, nids, new)
+            guide_us.setdefault(name, []).append(gu)
+            return ts
+
+        arms = {"plain_B": lambda: _decode_loop(eng, ids, new), "plain_2B": lambda: _decode_loop(eng, ids2, new),
+                "guided_full": lambda: guided("guided_full", neg_full), "guided_one": lambda: guided("guided_one", neg_one)}
+        for f in arms.values():                                         # one untimed pass of every arm
+            f()
+        guide_us.clear()
+        ts = {k: [] for k in arms}
+        for _ in range(reps):
+            for k, f in arms.items():
+                ts[k].append(float(np.median(f())))
+        med = {k: float(np.median(v)) for k, v in ts.items()}
+        spread = {k: max(v) - min(v) for k, v in ts.items()}
+        rec = dict(geo=geo, mode="cfg_ab", B=B, prompt=prompt, new_tokens=new, reps=reps, vocab=eng.vocab, guide_route=ops.CFG_GUIDE_ROUTE)
+        for k in arms:
+            rec[f"{k}_ms_per_step"], rec[f"{k}_ms_all"], rec[f"{k}_spread_ms"] = round(med[k], 3), [round(x, 3) for x in ts[k]], round(spread[k], 3)
+        for k in ("guided_full", "guided_one"):
+            gu = float(np.median(guide_us[k]))
+            rec[f"{k}_over_plain_B"] = round(med[k] / med["plain_B"], 3)
+            rec[f"{k}_over_plain_2B"] = round(med[k] / med["plain_2B"], 3)
+            rec[f"{k}_minus_plain_2B_ms"] = round(med[k] - med["plain_2B"], 3)
+            rec[f"{k}_below_2x_plain_B_by_more_than_spread"] = bool(2 * med["plain_B"] - med[k] > spread["plain_B"])
+            rec[f"{k}_guide_us"], rec[f"{k}_guide_share_of_step"] = round(gu, 2), round(gu * 1e-3 / med[k], 4)
+        rec["two_forwards_ms"] = round(2 * med["plain_B"], 3)
+        recs.append(rec)
+    return recs
+
+
 def processors_ab(geo, B, prompt, new, reps=3):
     from radvlm_amd.generation import LogitsProcessors, parse_generate_kwargs
     eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
@@ -1009,6 +1146,8 @@ def main():
     ap.add_argument("--beams", action="store_true")
     ap.add_argument("--lookup", action="store_true")
     ap.add_argument("--lookup-kernel-ab", action="store_true")
+    ap.add_argument("--cfg", action="store_true")
+    ap.add_argument("--cfg-kernel-ab", action="store_true")
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -1041,6 +1180,11 @@ def main():
         recs = [r for g in a.geos.split(",") for r in lookup_kernel_ab(g)]
     elif a.lookup:
         recs = [r for g in a.geos.split(",") for r in lookup_kernel_ab(g) + lookup_e2e(g, a.prompt, a.new, reps=min(a.reps, 3))]
+    elif a.cfg_kernel_ab:
+        recs = cfg_kernel_ab()
+    elif a.cfg:
+        batches = a.batches if a.batches != ap.get_default("batches") else "1,8,16"
+        recs = cfg_kernel_ab() + [r for g in a.geos.split(",") for r in cfg_ab(g, list(map(int, batches.split(","))), a.prompt, a.new)]
     elif a.batch_eval:
         recs = [r for g in a.geos.split(",") for r in batch_eval(g, n=a.requests, prompt=a.prompt, reps=min(a.reps, 3))]
     elif a.batch_kernel_ab:
