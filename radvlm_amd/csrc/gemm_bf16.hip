@@ -1302,19 +1302,83 @@ static bool buf_extents2(GemmParams& P, int trans_a, int trans_b) {
     P.bytesA2 = (unsigned)ea; P.bytesB2 = (unsigned)eb;
     return true;
 }
+// The launch shape of one rv_gemm_bf16_ex call, decided on the host from the sizes, the layouts and the process-wide configuration above
+// (gemm_plan below; rv_gemm_plan reports it, so a test can prove which form it exercised).
+struct GemmPlan {
+    int use256;    // 256x256 kernel (else the 128x128 one: plain NT whole tiles only)
+    int mode;      // MODE of gemm_kernel_256: 0 whole tiles, 1 second operand pair, 2 split-K, 3 tail split
+    int splits;    // K-slices per tile (MODE 2) / per tail tile (MODE 3); 1 otherwise
+    int n_full;    // MODE 3: tiles computed whole; 0 otherwise
+    int grid;      // blocks of the GEMM kernel
+    int pgrid;     // GemmParams::pgrid of that launch
+    int buf;       // buffer-addressed staging
+};
+static void force_from_env() {
+    static bool done = false;
+    if (done) return;
+    const char* e = getenv("RV_GEMM_KERNEL");
+    if (e) g_force_kernel = atoi(e);
+    done = true;
+}
+// K2 = 0: no second operand pair; workspace_bytes = 0: no workspace; dropping: the dropout epilogue is on.
+static GemmPlan gemm_plan(int M, int N, int K, int trans_a, int trans_b, int64_t lda, int64_t ldb, int K2, int64_t lda2, int64_t ldb2,
+                          int64_t workspace_bytes, bool dropping) {
+    force_from_env();
+    GemmPlan pl = {1, K2 > 0 ? 1 : 0, 1, 0, 0, 0, 0};
+    const long tiles256 = (long)((M + BM2 - 1) / BM2) * ((N + BN2 - 1) / BN2);
+    const int nt = (K + BK - 1) / BK;
+    const int force = g_force_kernel;
+    const int cus = cu_budget();            // 256 on an idle MI355X; fewer when collectives are planned to run beside the GEMMs
+    if (dropping) workspace_bytes = 0;           // no K-split shapes: their reduce kernels do not carry the mask
+    const bool ws = workspace_bytes > 0;
+    // split-K: few output tiles but a long contraction (LoRA / bias-like gradients): spread K over the idle CUs
+    if (pl.mode == 0 && ws && tiles256 <= cus / 4 && nt >= 16) {
+        int sp = (int)(cus / tiles256);
+        if (sp > nt / 4) sp = nt / 4;
+        if (sp > 32) sp = 32;
+        if (sp >= 2 && (int64_t)sp * M * N * 4 <= workspace_bytes) { pl.mode = 2; pl.splits = sp; }
+    }
+    // tail split: when the last round of `cus` blocks is at most half full, its tiles are cut into 2-4 K-slices so that the
+    // round costs 1/2 - 1/4 of a full one (e.g. 1408 tiles on 256 CUs: 6 rounds -> 5.5)
+    if (pl.mode == 0 && ws && g_tail_split && tiles256 > cus) {
+        const int rem = (int)(tiles256 % cus);
+        if (rem > 0 && rem <= cus / 2 && nt >= 32) {
+            int sp = cus / rem;
+            if (sp > 4) sp = 4;
+            if ((int64_t)rem * sp * BM2 * BN2 * 4 <= workspace_bytes) { pl.mode = 3; pl.splits = sp; pl.n_full = (int)(tiles256 - rem); }
+        }
+    }
+    // the 128x128 kernel only exists for the plain NT form
+    // tile-shape choice for the plain NT form: whole rounds of `cus` blocks (256^2 tiles, 1 block/CU) against double-rounds of
+    // 2 x cus blocks (128^2 tiles, 2 blocks/CU, ~15 % less efficient per flop but finer grained); measured crossover on
+    // MI355X (tools/ab_kernel12.py): 292 / 352 tiles -> 128^2 wins by 8-27 %, >= 876 tiles -> 256^2 wins by 3-7 %.
+    const long tiles128 = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+    const double cost256 = 4.0 * (double)((tiles256 + cus - 1) / cus);
+    const double cost128 = 2.0 * 1.15 * (double)((tiles128 + 2 * cus - 1) / (2 * cus));
+    pl.use256 = (trans_a || trans_b || pl.mode || dropping) ? 1 : (force ? (force == 2) : (cost256 <= cost128));
+    if (!pl.use256) { pl.grid = pl.pgrid = (int)tiles128; return pl; }
+    // staging: buffer-addressed when every operand the mode reads qualifies (MODE 1: both pairs)
+    GemmParams Q = {};
+    Q.M = M; Q.N = N; Q.K = K; Q.K2 = K2; Q.lda = lda; Q.ldb = ldb; Q.lda2 = lda2; Q.ldb2 = ldb2;
+    pl.buf = buf_extents(Q, trans_a, trans_b) && (pl.mode != 1 || buf_extents2(Q, trans_a, trans_b));
+    const int nwg = (int)tiles256;
+    const int blocks = pl.mode == 2 ? nwg * pl.splits : (pl.mode == 3 ? pl.n_full + (nwg - pl.n_full) * pl.splits : nwg);
+    pl.grid = blocks;
+    pl.pgrid = pl.mode == 3 ? pl.n_full : blocks;
+    // persistent form: one block per CU walks the whole tiles (MODE 3: + the K-slice blocks of the tail tiles behind them)
+    if (g_persist && pl.buf && (pl.mode == 0 || pl.mode == 1) && blocks > cus) { pl.grid = cus; pl.pgrid = cus; }
+    if (g_persist && pl.buf && pl.mode == 3 && pl.n_full > cus) { pl.pgrid = cus; pl.grid = cus + (nwg - pl.n_full) * pl.splits; }
+    return pl;
+}
+
 template <bool TA, bool TB, int MODE, bool BUF = false>
-static void launch256m(const GemmParams& P, hipStream_t st) {
+static void launch256m(const GemmParams& P, const GemmPlan& pl, hipStream_t st) {
     static bool set = false;
     if (!set) { (void)hipFuncSetAttribute((const void*)gemm_kernel_256<TA, TB, MODE, EPI_NONE, BUF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES2); set = true; }
     const int nwg = P.tiles_m * P.tiles_n;
-    const int blocks = MODE == 2 ? nwg * P.splits : (MODE == 3 ? P.n_full + (nwg - P.n_full) * P.splits : nwg);
-    int grid = blocks;
     GemmParams Q = P;
-    Q.pgrid = MODE == 3 ? P.n_full : blocks;
-    // persistent form: one block per CU walks the whole tiles (MODE 3: + the K-slice blocks of the tail tiles behind them)
-    if (g_persist && BUF && (MODE == 0 || MODE == 1) && blocks > cu_budget()) { grid = cu_budget(); Q.pgrid = grid; }
-    if (g_persist && BUF && MODE == 3 && P.n_full > cu_budget()) { Q.pgrid = cu_budget(); grid = Q.pgrid + (nwg - P.n_full) * P.splits; }
-    hipLaunchKernelGGL((gemm_kernel_256<TA, TB, MODE, EPI_NONE, BUF>), dim3(grid), dim3(512), LDS_BYTES2, st, Q);
+    Q.pgrid = pl.pgrid;
+    hipLaunchKernelGGL((gemm_kernel_256<TA, TB, MODE, EPI_NONE, BUF>), dim3(pl.grid), dim3(512), LDS_BYTES2, st, Q);
     if (MODE == 3) hipLaunchKernelGGL(tail_reduce_kernel, dim3((nwg - P.n_full) * 32), dim3(256), 0, st, P);
     if (MODE == 2) {
         const long total = (long)P.M * P.N;
@@ -1322,12 +1386,16 @@ static void launch256m(const GemmParams& P, hipStream_t st) {
     }
 }
 template <bool TA, bool TB>
-static void launch256(GemmParams& P, int mode, hipStream_t st) {
-    if (mode == 1) { if (buf_extents(P, TA, TB) && buf_extents2(P, TA, TB)) launch256m<TA, TB, 1, true>(P, st); else launch256m<TA, TB, 1>(P, st); }
-    else if (mode == 2) { if (buf_extents(P, TA, TB)) launch256m<TA, TB, 2, true>(P, st); else launch256m<TA, TB, 2>(P, st); }
-    else if (buf_extents(P, TA, TB)) { if (mode == 3) launch256m<TA, TB, 3, true>(P, st); else launch256m<TA, TB, 0, true>(P, st); }
-    else if (mode == 3) launch256m<TA, TB, 3>(P, st);
-    else launch256m<TA, TB, 0>(P, st);
+static void launch256(GemmParams& P, const GemmPlan& pl, hipStream_t st) {
+    if (pl.buf) {       // the operand extents of the buffer resources
+        buf_extents(P, TA, TB);
+        if (pl.mode == 1) buf_extents2(P, TA, TB);
+    }
+    if (pl.mode == 1) { if (pl.buf) launch256m<TA, TB, 1, true>(P, pl, st); else launch256m<TA, TB, 1>(P, pl, st); }
+    else if (pl.mode == 2) { if (pl.buf) launch256m<TA, TB, 2, true>(P, pl, st); else launch256m<TA, TB, 2>(P, pl, st); }
+    else if (pl.buf) { if (pl.mode == 3) launch256m<TA, TB, 3, true>(P, pl, st); else launch256m<TA, TB, 0, true>(P, pl, st); }
+    else if (pl.mode == 3) launch256m<TA, TB, 3>(P, pl, st);
+    else launch256m<TA, TB, 0>(P, pl, st);
 }
 
 static int gemm_ex_impl(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* bias,
@@ -1352,53 +1420,21 @@ static int gemm_ex_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)gemm_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_BYTES);
-        const char* e = getenv("RV_GEMM_KERNEL");
-        if (e) g_force_kernel = atoi(e);
         attr_set = true;
     }
-    const long tiles256 = (long)((M + BM2 - 1) / BM2) * ((N + BN2 - 1) / BN2);
-    const int nt = (K + BK - 1) / BK;
-    const int force = g_force_kernel;
-    const int cus = cu_budget();            // 256 on an idle MI355X; fewer when collectives are planned to run beside the GEMMs
-    // split-K: few output tiles but a long contraction (LoRA / bias-like gradients): spread K over the idle CUs
-    int mode = ext ? 1 : 0;
-    if (dropping) workspace = nullptr;           // no K-split shapes: their reduce kernels do not carry the mask
-    if (!ext && workspace && tiles256 <= cus / 4 && nt >= 16) {
-        int sp = (int)(cus / tiles256);
-        if (sp > nt / 4) sp = nt / 4;
-        if (sp > 32) sp = 32;
-        if (sp >= 2 && (int64_t)sp * M * N * 4 <= workspace_bytes) { mode = 2; P.splits = sp; }
-    }
-    // tail split: when the last round of `cus` blocks is at most half full, its tiles are cut into 2-4 K-slices so that the
-    // round costs 1/2 - 1/4 of a full one (e.g. 1408 tiles on 256 CUs: 6 rounds -> 5.5)
-    P.n_full = 0;
-    if (mode == 0 && workspace && g_tail_split && tiles256 > cus) {
-        const int rem = (int)(tiles256 % cus);
-        if (rem > 0 && rem <= cus / 2 && nt >= 32) {
-            int sp = cus / rem;
-            if (sp > 4) sp = 4;
-            if ((int64_t)rem * sp * BM2 * BN2 * 4 <= workspace_bytes) { mode = 3; P.splits = sp; P.n_full = (int)(tiles256 - rem); }
-        }
-    }
-    // the 128x128 kernel only exists for the plain NT form
-    // tile-shape choice for the plain NT form: whole rounds of `cus` blocks (256^2 tiles, 1 block/CU) against double-rounds of
-    // 2 x cus blocks (128^2 tiles, 2 blocks/CU, ~15 % less efficient per flop but finer grained); measured crossover on
-    // MI355X (tools/ab_kernel12.py): 292 / 352 tiles -> 128^2 wins by 8-27 %, >= 876 tiles -> 256^2 wins by 3-7 %.
-    const long tiles128 = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    const double cost256 = 4.0 * (double)((tiles256 + cus - 1) / cus);
-    const double cost128 = 2.0 * 1.15 * (double)((tiles128 + 2 * cus - 1) / (2 * cus));
-    const bool use256 = (trans_a || trans_b || mode || dropping) ? true : (force ? (force == 2) : (cost256 <= cost128));
+    const GemmPlan pl = gemm_plan(M, N, K, trans_a, trans_b, lda, ldb, P.K2, lda2, ldb2, workspace ? workspace_bytes : 0, dropping);
+    P.splits = pl.splits; P.n_full = pl.n_full;
     hipStream_t st = (hipStream_t)stream;
-    if (use256) {
+    if (pl.use256) {
 #ifdef RV_STAMPS
-        if (mode == 0) P.ws = (float*)g_stamp_host;
+        if (pl.mode == 0) P.ws = (float*)g_stamp_host;
 #endif
         P.tiles_m = (M + BM2 - 1) / BM2; P.tiles_n = (N + BN2 - 1) / BN2;
-        if (trans_a) { if (trans_b) launch256<true, true>(P, mode, st); else launch256<true, false>(P, mode, st); }
-        else { if (trans_b) launch256<false, true>(P, mode, st); else launch256<false, false>(P, mode, st); }
+        if (trans_a) { if (trans_b) launch256<true, true>(P, pl, st); else launch256<true, false>(P, pl, st); }
+        else { if (trans_b) launch256<false, true>(P, pl, st); else launch256<false, false>(P, pl, st); }
     } else {
         P.tiles_m = (M + BM - 1) / BM; P.tiles_n = (N + BN - 1) / BN;
-        hipLaunchKernelGGL(gemm_nt_kernel, dim3(P.tiles_m * P.tiles_n), dim3(256), NSTAGE * STAGE_BYTES, st, P);
+        hipLaunchKernelGGL(gemm_nt_kernel, dim3(pl.grid), dim3(256), NSTAGE * STAGE_BYTES, st, P);
     }
     return rv_check_launch();
 }
@@ -1409,6 +1445,21 @@ extern "C" int rv_gemm_bf16_ex(const void* A, int64_t lda, const void* B, int64_
                                int K2, void* workspace, int64_t workspace_bytes, const void* zeros16, void* stream) {
     return gemm_ex_impl(A, lda, B, ldb, C, ldc, bias, residual, ldr, M, N, K, trans_a, trans_b, alpha, act, out_f32, res_f32, A2, lda2, B2, ldb2, K2,
                         workspace, workspace_bytes, zeros16, stream, 0.f, 0);
+}
+
+// The launch shape rv_gemm_bf16_ex takes for these sizes, layouts and workspace under the current configuration (rv_gemm_set_cu_budget,
+// rv_gemm_select_kernel); launches nothing.  K2 = 0: no second operand pair; workspace_bytes = 0: no workspace; dropping != 0: the call is
+// rv_gemm_dropout_add_bf16 with p > 0.  out[6] = {kernel (1 = 128x128, 2 = 256x256), MODE, K-slices, n_full, blocks of the GEMM kernel,
+// buffer-addressed staging}; the launch is persistent when it has fewer blocks than whole tiles + K-slice blocks.
+extern "C" int rv_gemm_plan(int M, int N, int K, int trans_a, int trans_b, int64_t lda, int64_t ldb, int K2, int64_t lda2, int64_t ldb2,
+                            int64_t workspace_bytes, int dropping, int32_t* out) {
+    if (!out || M <= 0 || N <= 0 || K <= 0 || K2 < 0 || workspace_bytes < 0) return RV_ERR_ARG;
+    if ((lda & 7) || (ldb & 7)) return RV_ERR_ARG;
+    if ((!trans_a && (K & 7)) || (trans_a && (M & 7)) || (!trans_b && (K & 7)) || (trans_b && (N & 7))) return RV_ERR_ARG;
+    if (K2 > 0 && ((lda2 & 7) || (ldb2 & 7) || (!trans_a && (K2 & 7)) || (!trans_b && (K2 & 7)))) return RV_ERR_ARG;
+    const GemmPlan pl = gemm_plan(M, N, K, trans_a, trans_b, lda, ldb, K2, lda2, ldb2, workspace_bytes, dropping != 0);
+    out[0] = pl.use256 ? 2 : 1; out[1] = pl.mode; out[2] = pl.splits; out[3] = pl.n_full; out[4] = pl.grid; out[5] = pl.buf;
+    return RV_OK;
 }
 
 // C[M, N] (+)= dropout_p(alpha * A[M, K] op(B)) with the mask of rv_dropout_bf16 over the M * N elements of the product: the adapter branch of

@@ -26,6 +26,7 @@ _SIGS = {
                      _f32, _i32, _i32, _i32, _c_void_p, _c_void_p],
     "rv_gemm_bf16_ex": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32,
                         _f32, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
+    "rv_gemm_plan": [_i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _i64, _i64, _i64, _i32, ctypes.POINTER(ctypes.c_int32)],
     "rv_gemm_rope_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _i32,
                           _c_void_p, _i64, _c_void_p, _c_void_p],
     "rv_gemm_swiglu_fwd_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _c_void_p, _i64, _c_void_p,
