@@ -92,16 +92,21 @@ int rv_gemm_select_kernel(int which);
  * round, split-K of small outputs).  total_cus <= 0: the current device's multiProcessorCount (256 on MI355X); reserved_cus:
  * units left to concurrently running work -- the bucketed RCCL all-reduce that overlaps backward in data-parallel runs
  * (what DDP's NCCL kernels take on the reference's GPUs).  Default without a call: all units, or
- * RV_GEMM_RESERVED_CUS from the environment.  Returns the resulting budget (>= 8) or a negative error code.  Process-wide. */
+ * RV_GEMM_RESERVED_CUS from the environment.  Returns the resulting budget (>= 8) or a negative error code.  Process-wide.
+ * An explicit total (total_cus > 0) needs no device; without a budget and without a device every GEMM entry point (and rv_gemm_plan)
+ * returns RV_ERR_LAUNCH. */
 int rv_gemm_set_cu_budget(int total_cus, int reserved_cus);
-/* The launch shape rv_gemm_bf16_ex takes for these sizes, layouts and workspace under the current rv_gemm_set_cu_budget /
- * rv_gemm_select_kernel configuration; launches nothing (the planner rv_gemm_bf16_ex itself calls).  K2 = 0: no second operand pair;
- * workspace_bytes = 0: no workspace; dropping != 0: the call is rv_gemm_dropout_add_bf16 with p > 0.
+/* The launch shape a GEMM call takes for these sizes, layouts and workspace under the current rv_gemm_set_cu_budget /
+ * rv_gemm_select_kernel configuration; launches nothing and needs no device once a budget is set (the planner every entry point itself
+ * calls: plain integer arithmetic, radvlm_amd/csrc/gemm_plan.h).  K2 = 0: no second operand pair; workspace_bytes = 0: no workspace.
+ * kind: 0 = rv_gemm_bf16_ex; 1 = rv_gemm_dropout_add_bf16 with p > 0; 2 = a fused-epilogue entry point (rv_gemm_rope_bf16,
+ * rv_gemm_swiglu_fwd_bf16 with N = 2F, rv_gemm_swiglu_bwd_bf16 with trans_b = 1; trans_a = 0, no second pair, no workspace), for which
+ * kernel 1 means that the entry point runs its unfused sequence.
  * out[6] = { kernel (1 = 128x128 tiles, 2 = 256x256 tiles), MODE (0 whole tiles, 1 second pair, 2 split-K, 3 tail split), K-slices,
  * n_full (MODE 3: tiles computed whole), blocks of the GEMM kernel, buffer-addressed staging (0 / 1) }.  A launch is persistent when it has
  * fewer blocks than tiles (MODE 0 / 1) or than n_full + (tiles - n_full) * K-slices (MODE 3).  Tests use it to prove which form they ran. */
 int rv_gemm_plan(int M, int N, int K, int trans_a, int trans_b, int64_t lda, int64_t ldb, int K2, int64_t lda2, int64_t ldb2,
-                 int64_t workspace_bytes, int dropping, int32_t* out);
+                 int64_t workspace_bytes, int kind, int32_t* out);
 
 /* Batched strided transpose of bf16 matrices: out[bz][c][r] = in[bz][r][c], r < R, c < C; columns r in [R, R_pad)
  * of every output row are written as zero.  bz = b0 * nb1 + b1; offsets in elements.

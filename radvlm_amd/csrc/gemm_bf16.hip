@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "common.h"
 #include "radvlm_hip.h"
+#include "gemm_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -1234,206 +1235,112 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(GemmParams P) {
 }  // namespace
 
 // ---- process-wide launch configuration (the ONLY state this file keeps; one process drives one GPU) ----------
-//   g_tail_split / g_force_kernel : measurement hooks (rv_gemm_select_kernel; RV_GEMM_KERNEL at first use)
-//   g_persist                     : persistent blocks on (single GPU) / off (collectives share the CUs), rv_gemm_select_kernel(41 / 40)
-//   g_cus                         : compute units the tile-round heuristics plan for = the device's multiProcessorCount minus the
-//                                   units reserved for concurrently running collectives (rv_gemm_set_cu_budget / RV_GEMM_RESERVED_CUS);
-//                                   queried once per process on first use
-//   per-instantiation `attr` flags: hipFuncSetAttribute(MaxDynamicSharedMemorySize) is issued once per kernel instantiation
-// None of it depends on the arguments of a call; results never depend on it (only which launch shape computes them).
-static int g_tail_split = 1;   // rv_gemm_select_kernel(20) disables the tail split (A/B), (21) enables
-static int g_force_kernel = 0;  // 0 auto, 1 = 128x128 kernel, 2 = 256x256 kernel (RV_GEMM_KERNEL or rv_gemm_select_kernel)
-static int g_cus = 0;           // 0 = not yet queried
-static int g_cus_device = -1;   // the device g_cus was derived for: a process that switches devices re-queries (one process normally drives one GPU)
+//   g_cfg (GemmConfig, gemm_plan.h): the CU budget and the rv_gemm_select_kernel switches; RV_GEMM_KERNEL is read at first use
+//   g_cus_device / g_reserved_cus  : which device the budget was derived for, and the units reserved on it
+//   per-instantiation `attr` flags : hipFuncSetAttribute(MaxDynamicSharedMemorySize) is issued once per kernel instantiation
+static_assert(PLAN_TILE128 == BM && PLAN_TILE128 == BN && PLAN_TILE256 == BM2 && PLAN_TILE256 == BN2 && PLAN_BK == BK, "gemm_plan.h plans for these tiles");
+static GemmConfig g_cfg;
+static int g_cus_device = -1;   // the device g_cfg.cus was derived for: a process that switches devices re-queries (one process normally drives one GPU)
 static int g_reserved_cus = -1; // -1 = take RV_GEMM_RESERVED_CUS (default 0) at first use
-static int g_no_buf = 0;         // rv_gemm_select_kernel(30 / 31): buffer-addressed staging off / on (A/B measurement)
-static int g_persist = 1;        // rv_gemm_select_kernel(40 / 41): persistent tile-walking blocks off / on.  OFF when collectives share the GPU
-                                 // (the engine does that for world size > 1): a persistent block that cannot start because an RCCL kernel holds
-                                 // its CU delays its whole share of the tiles (up to 2x for the launch); one-tile blocks only lose part of a round
 extern "C" int rv_gemm_select_kernel(int which) {
-    if (which >= 40) { g_persist = which == 41; return RV_OK; }
-    if (which >= 30) { g_no_buf = which == 30; return RV_OK; }
-    if (which >= 20) { g_tail_split = which - 20; return RV_OK; }
-    g_force_kernel = which;
+    if (which >= 40) g_cfg.persist = which == 41;
+    else if (which >= 30) g_cfg.flat = which == 30;
+    else if (which >= 20) g_cfg.tail_split = which - 20;
+    else g_cfg.force_kernel = which;
     return RV_OK;
 }
-// Number of compute units the GEMM's round / tail-split / split-K heuristics plan for.  total_cus <= 0: ask the device
-// (hipDeviceProp_t::multiProcessorCount of the current device); reserved_cus: units left to other streams (an RCCL all-reduce
-// overlapped with backward occupies a few dozen), subtracted from the total.  Returns the resulting budget.
+// radvlm_hip.h.  total_cus <= 0 asks the current device; an explicit total needs no device (g_cus_device = -1 without one).
 extern "C" int rv_gemm_set_cu_budget(int total_cus, int reserved_cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return RV_ERR_LAUNCH;
-    if (total_cus <= 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return RV_ERR_LAUNCH;
-        total_cus = n;
-    }
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    if (total_cus <= 0 && (dev < 0 || hipDeviceGetAttribute(&total_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)) return RV_ERR_LAUNCH;
     g_cus_device = dev;
-    if (reserved_cus < 0) reserved_cus = 0;
-    g_reserved_cus = reserved_cus;
-    g_cus = total_cus - reserved_cus;
-    if (g_cus < 8) g_cus = 8;
-    return g_cus;
+    g_reserved_cus = reserved_cus < 0 ? 0 : reserved_cus;
+    g_cfg.cus = total_cus - g_reserved_cus < 8 ? 8 : total_cus - g_reserved_cus;
+    return g_cfg.cus;
 }
-static int cu_budget() {
+// The configuration every entry point plans with; an error code when no budget can be established (no device and no explicit total).
+static int gemm_config(GemmConfig& cfg) {
+    static bool env_read = false;
+    if (const char* e = env_read ? nullptr : getenv("RV_GEMM_KERNEL")) g_cfg.force_kernel = atoi(e);
+    env_read = true;
     int dev = 0;
-    if (g_cus != 0 && hipGetDevice(&dev) == hipSuccess && dev != g_cus_device) g_cus = 0;     // another device became current: plan for ITS units
-    if (g_cus == 0) {
+    if (g_cfg.cus != 0 && hipGetDevice(&dev) == hipSuccess && dev != g_cus_device) g_cfg.cus = 0;     // another device became current: plan for ITS units
+    if (g_cfg.cus == 0) {
         const char* e = getenv("RV_GEMM_RESERVED_CUS");
-        rv_gemm_set_cu_budget(0, g_reserved_cus >= 0 ? g_reserved_cus : (e ? atoi(e) : 0));
+        const int rc = rv_gemm_set_cu_budget(0, g_reserved_cus >= 0 ? g_reserved_cus : (e ? atoi(e) : 0));
+        if (rc < 0) return rc;
     }
-    return g_cus;
+    cfg = g_cfg;
+    return RV_OK;
 }
 
-// Operand extents for the buffer-addressed kernels; false when a shape does not qualify (K tail inside a row, >= 2 GiB operand).
-static bool buf_extents(GemmParams& P, int trans_a, int trans_b) {
-    // a K tail is a resource boundary only for contraction-major operands (whole rows past the end read as zero); inside the rows of a
-    // row-major operand it is not -- e.g. the weight gradients of a 14998-token batch (both operands contraction-major) qualify
-    if ((P.K % BK) && !(trans_a && trans_b)) return false;
-    const long ea = (trans_a ? (long)P.K : (long)P.M) * P.lda * 2, eb = (trans_b ? (long)P.K : (long)P.N) * P.ldb * 2;
-    if (ea >= (1L << 31) || eb >= (1L << 31) || g_no_buf) return false;
-    P.bytesA = (unsigned)ea; P.bytesB = (unsigned)eb;
-    return true;
+// Operands, leading dimensions, sizes and epilogue scalars of a launch; everything else zero (no second pair, no workspace, no fused
+// epilogue, no dropout) for the entry point to set.  The launch-shape fields come from the plan (launch256).
+static GemmParams gemm_params(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* bias, const void* residual,
+                              int64_t ldr, const void* zeros16, int M, int N, int K, float alpha, int act = RV_ACT_NONE, int out_f32 = 0, int res_f32 = 0) {
+    GemmParams P = {};
+    P.A = (const bf16*)A; P.B = (const bf16*)B; P.C = C; P.bias = (const bf16*)bias; P.R = residual; P.zeros = (const bf16*)zeros16;
+    P.lda = lda; P.ldb = ldb; P.ldc = ldc; P.ldr = ldr;
+    P.M = M; P.N = N; P.K = K; P.act = act; P.out_f32 = out_f32; P.res_f32 = res_f32; P.alpha = alpha; P.splits = 1;
+    return P;
 }
-static bool buf_extents2(GemmParams& P, int trans_a, int trans_b) {
-    if ((P.K2 % BK) && !(trans_a && trans_b)) return false;
-    const long ea = (trans_a ? (long)P.K2 : (long)P.M) * P.lda2 * 2, eb = (trans_b ? (long)P.K2 : (long)P.N) * P.ldb2 * 2;
-    if (ea >= (1L << 31) || eb >= (1L << 31)) return false;
-    P.bytesA2 = (unsigned)ea; P.bytesB2 = (unsigned)eb;
-    return true;
+static void launch_splitk_reduce(const GemmParams& P, hipStream_t st) {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)P.M * P.N + 255) / 256)), dim3(256), 0, st, P);
 }
-// The launch shape of one rv_gemm_bf16_ex call, decided on the host from the sizes, the layouts and the process-wide configuration above
-// (gemm_plan below; rv_gemm_plan reports it, so a test can prove which form it exercised).
-struct GemmPlan {
-    int use256;    // 256x256 kernel (else the 128x128 one: plain NT whole tiles only)
-    int mode;      // MODE of gemm_kernel_256: 0 whole tiles, 1 second operand pair, 2 split-K, 3 tail split
-    int splits;    // K-slices per tile (MODE 2) / per tail tile (MODE 3); 1 otherwise
-    int n_full;    // MODE 3: tiles computed whole; 0 otherwise
-    int grid;      // blocks of the GEMM kernel
-    int pgrid;     // GemmParams::pgrid of that launch
-    int buf;       // buffer-addressed staging
-};
-static void force_from_env() {
-    static bool done = false;
-    if (done) return;
-    const char* e = getenv("RV_GEMM_KERNEL");
-    if (e) g_force_kernel = atoi(e);
-    done = true;
+// The one launcher of gemm_kernel_256: the launch-shape fields of the parameters are the plan's; the reduce kernel of a K-split follows.
+template <bool TA, bool TB, int MODE, int EPI, bool BUF>
+static void launch256(GemmParams P, const GemmPlan& pl, hipStream_t st) {
+    static bool attr = false;      // once per instantiation (see the launch-configuration note above)
+    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_kernel_256<TA, TB, MODE, EPI, BUF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES2); attr = true; }
+    P.tiles_m = pl.tiles_m; P.tiles_n = pl.tiles_n; P.splits = pl.splits; P.n_full = pl.n_full; P.pgrid = pl.pgrid;
+    P.bytesA = pl.bytesA; P.bytesB = pl.bytesB; P.bytesA2 = pl.bytesA2; P.bytesB2 = pl.bytesB2;
+    hipLaunchKernelGGL((gemm_kernel_256<TA, TB, MODE, EPI, BUF>), dim3(pl.grid), dim3(512), LDS_BYTES2, st, P);
+    if (MODE == 3) hipLaunchKernelGGL(tail_reduce_kernel, dim3((pl.tiles_m * pl.tiles_n - pl.n_full) * 32), dim3(256), 0, st, P);
+    if (MODE == 2) launch_splitk_reduce(P, st);
 }
-// K2 = 0: no second operand pair; workspace_bytes = 0: no workspace; dropping: the dropout epilogue is on.
-static GemmPlan gemm_plan(int M, int N, int K, int trans_a, int trans_b, int64_t lda, int64_t ldb, int K2, int64_t lda2, int64_t ldb2,
-                          int64_t workspace_bytes, bool dropping) {
-    force_from_env();
-    GemmPlan pl = {1, K2 > 0 ? 1 : 0, 1, 0, 0, 0, 0};
-    const long tiles256 = (long)((M + BM2 - 1) / BM2) * ((N + BN2 - 1) / BN2);
-    const int nt = (K + BK - 1) / BK;
-    const int force = g_force_kernel;
-    const int cus = cu_budget();            // 256 on an idle MI355X; fewer when collectives are planned to run beside the GEMMs
-    if (dropping) workspace_bytes = 0;           // no K-split shapes: their reduce kernels do not carry the mask
-    const bool ws = workspace_bytes > 0;
-    // split-K: few output tiles but a long contraction (LoRA / bias-like gradients): spread K over the idle CUs
-    if (pl.mode == 0 && ws && tiles256 <= cus / 4 && nt >= 16) {
-        int sp = (int)(cus / tiles256);
-        if (sp > nt / 4) sp = nt / 4;
-        if (sp > 32) sp = 32;
-        if (sp >= 2 && (int64_t)sp * M * N * 4 <= workspace_bytes) { pl.mode = 2; pl.splits = sp; }
-    }
-    // tail split: when the last round of `cus` blocks is at most half full, its tiles are cut into 2-4 K-slices so that the
-    // round costs 1/2 - 1/4 of a full one (e.g. 1408 tiles on 256 CUs: 6 rounds -> 5.5)
-    if (pl.mode == 0 && ws && g_tail_split && tiles256 > cus) {
-        const int rem = (int)(tiles256 % cus);
-        if (rem > 0 && rem <= cus / 2 && nt >= 32) {
-            int sp = cus / rem;
-            if (sp > 4) sp = 4;
-            if ((int64_t)rem * sp * BM2 * BN2 * 4 <= workspace_bytes) { pl.mode = 3; pl.splits = sp; pl.n_full = (int)(tiles256 - rem); }
+// Run-time values to template arguments, for every instantiation without a fused epilogue: 4 layouts x 4 modes x 2 staging forms.
+template <class F>
+static void with_bool(bool v, F f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+static void launch256_plain(const GemmParams& P, const GemmPlan& pl, bool trans_a, bool trans_b, hipStream_t st) {
+    with_bool(trans_a, [&](auto ta) { with_bool(trans_b, [&](auto tb) { with_bool(pl.buf != 0, [&](auto buf) {
+        constexpr bool TA = decltype(ta)::value, TB = decltype(tb)::value, BUF = decltype(buf)::value;
+        switch (pl.mode) {
+            case 1: launch256<TA, TB, 1, EPI_NONE, BUF>(P, pl, st); break;
+            case 2: launch256<TA, TB, 2, EPI_NONE, BUF>(P, pl, st); break;
+            case 3: launch256<TA, TB, 3, EPI_NONE, BUF>(P, pl, st); break;
+            default: launch256<TA, TB, 0, EPI_NONE, BUF>(P, pl, st);
         }
-    }
-    // the 128x128 kernel only exists for the plain NT form
-    // tile-shape choice for the plain NT form: whole rounds of `cus` blocks (256^2 tiles, 1 block/CU) against double-rounds of
-    // 2 x cus blocks (128^2 tiles, 2 blocks/CU, ~15 % less efficient per flop but finer grained); measured crossover on
-    // MI355X (tools/ab_kernel12.py): 292 / 352 tiles -> 128^2 wins by 8-27 %, >= 876 tiles -> 256^2 wins by 3-7 %.
-    const long tiles128 = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    const double cost256 = 4.0 * (double)((tiles256 + cus - 1) / cus);
-    const double cost128 = 2.0 * 1.15 * (double)((tiles128 + 2 * cus - 1) / (2 * cus));
-    pl.use256 = (trans_a || trans_b || pl.mode || dropping) ? 1 : (force ? (force == 2) : (cost256 <= cost128));
-    if (!pl.use256) { pl.grid = pl.pgrid = (int)tiles128; return pl; }
-    // staging: buffer-addressed when every operand the mode reads qualifies (MODE 1: both pairs)
-    GemmParams Q = {};
-    Q.M = M; Q.N = N; Q.K = K; Q.K2 = K2; Q.lda = lda; Q.ldb = ldb; Q.lda2 = lda2; Q.ldb2 = ldb2;
-    pl.buf = buf_extents(Q, trans_a, trans_b) && (pl.mode != 1 || buf_extents2(Q, trans_a, trans_b));
-    const int nwg = (int)tiles256;
-    const int blocks = pl.mode == 2 ? nwg * pl.splits : (pl.mode == 3 ? pl.n_full + (nwg - pl.n_full) * pl.splits : nwg);
-    pl.grid = blocks;
-    pl.pgrid = pl.mode == 3 ? pl.n_full : blocks;
-    // persistent form: one block per CU walks the whole tiles (MODE 3: + the K-slice blocks of the tail tiles behind them)
-    if (g_persist && pl.buf && (pl.mode == 0 || pl.mode == 1) && blocks > cus) { pl.grid = cus; pl.pgrid = cus; }
-    if (g_persist && pl.buf && pl.mode == 3 && pl.n_full > cus) { pl.pgrid = cus; pl.grid = cus + (nwg - pl.n_full) * pl.splits; }
-    return pl;
-}
-
-template <bool TA, bool TB, int MODE, bool BUF = false>
-static void launch256m(const GemmParams& P, const GemmPlan& pl, hipStream_t st) {
-    static bool set = false;
-    if (!set) { (void)hipFuncSetAttribute((const void*)gemm_kernel_256<TA, TB, MODE, EPI_NONE, BUF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES2); set = true; }
-    const int nwg = P.tiles_m * P.tiles_n;
-    GemmParams Q = P;
-    Q.pgrid = pl.pgrid;
-    hipLaunchKernelGGL((gemm_kernel_256<TA, TB, MODE, EPI_NONE, BUF>), dim3(pl.grid), dim3(512), LDS_BYTES2, st, Q);
-    if (MODE == 3) hipLaunchKernelGGL(tail_reduce_kernel, dim3((nwg - P.n_full) * 32), dim3(256), 0, st, P);
-    if (MODE == 2) {
-        const long total = (long)P.M * P.N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P);
-    }
-}
-template <bool TA, bool TB>
-static void launch256(GemmParams& P, const GemmPlan& pl, hipStream_t st) {
-    if (pl.buf) {       // the operand extents of the buffer resources
-        buf_extents(P, TA, TB);
-        if (pl.mode == 1) buf_extents2(P, TA, TB);
-    }
-    if (pl.mode == 1) { if (pl.buf) launch256m<TA, TB, 1, true>(P, pl, st); else launch256m<TA, TB, 1>(P, pl, st); }
-    else if (pl.mode == 2) { if (pl.buf) launch256m<TA, TB, 2, true>(P, pl, st); else launch256m<TA, TB, 2>(P, pl, st); }
-    else if (pl.buf) { if (pl.mode == 3) launch256m<TA, TB, 3, true>(P, pl, st); else launch256m<TA, TB, 0, true>(P, pl, st); }
-    else if (pl.mode == 3) launch256m<TA, TB, 3>(P, pl, st);
-    else launch256m<TA, TB, 0>(P, pl, st);
+    }); }); });
 }
 
 static int gemm_ex_impl(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* bias,
                         const void* residual, int64_t ldr, int M, int N, int K, int trans_a, int trans_b, float alpha,
                         int act, int out_f32, int res_f32, const void* A2, int64_t lda2, const void* B2, int64_t ldb2,
                         int K2, void* workspace, int64_t workspace_bytes, const void* zeros16, void* stream, float drop_p, uint64_t drop_seed) {
-    if (!A || !B || !C || !zeros16 || M <= 0 || N <= 0 || K <= 0) return RV_ERR_ARG;
-    if ((lda & 7) || (ldb & 7)) return RV_ERR_ARG;
-    if ((!trans_a && (K & 7)) || (trans_a && (M & 7)) || (!trans_b && (K & 7)) || (trans_b && (N & 7))) return RV_ERR_ARG;
-    if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)zeros16) & 15) return RV_ERR_ARG;
     const bool ext = A2 && B2 && K2 > 0;
-    if (ext && ((lda2 & 7) || (ldb2 & 7) || (!trans_a && (K2 & 7)) || (!trans_b && (K2 & 7)) || (((uintptr_t)A2 | (uintptr_t)B2) & 15))) return RV_ERR_ARG;
-    GemmParams P;
-    P.A = (const bf16*)A; P.B = (const bf16*)B; P.C = C; P.bias = (const bf16*)bias; P.R = residual;
-    P.zeros = (const bf16*)zeros16;
-    P.lda = lda; P.ldb = ldb; P.ldc = ldc; P.ldr = ldr;
-    P.M = M; P.N = N; P.K = K; P.act = act; P.out_f32 = out_f32; P.res_f32 = res_f32; P.alpha = alpha;
-    P.A2 = (const bf16*)A2; P.B2 = (const bf16*)B2; P.lda2 = lda2; P.ldb2 = ldb2; P.K2 = ext ? K2 : 0;
-    P.ws = (float*)workspace; P.splits = 1;
-    P.drop_thr = drop_p > 0.f ? rv_dropout_thr16(drop_p) : 0u; P.drop_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; P.drop_seed = drop_seed;
-    const bool dropping = P.drop_thr != 0;       // lives in the general epilogue of the 256x256 whole-tile kernel only
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_BYTES);
-        attr_set = true;
-    }
-    const GemmPlan pl = gemm_plan(M, N, K, trans_a, trans_b, lda, ldb, P.K2, lda2, ldb2, workspace ? workspace_bytes : 0, dropping);
-    P.splits = pl.splits; P.n_full = pl.n_full;
+    const unsigned drop_thr = drop_p > 0.f ? rv_dropout_thr16(drop_p) : 0u;
+    const GemmRequest rq = {M, N, K, trans_a, trans_b, lda, ldb, ext ? K2 : 0, lda2, ldb2, workspace && workspace_bytes > 0 ? workspace_bytes : 0,
+                            drop_thr ? GEMM_DROPOUT : GEMM_PLAIN};      // the mask lives in the general epilogue of the 256x256 whole-tile kernel only
+    if (!A || !B || !C || !zeros16 || !gemm_args_ok(rq)) return RV_ERR_ARG;
+    if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)zeros16) & 15) return RV_ERR_ARG;
+    if (ext && (((uintptr_t)A2 | (uintptr_t)B2) & 15)) return RV_ERR_ARG;
+    GemmConfig cfg;
+    if (const int rc = gemm_config(cfg)) return rc;
+    GemmParams P = gemm_params(A, lda, B, ldb, C, ldc, bias, residual, ldr, zeros16, M, N, K, alpha, act, out_f32, res_f32);
+    P.A2 = (const bf16*)A2; P.B2 = (const bf16*)B2; P.lda2 = lda2; P.ldb2 = ldb2; P.K2 = rq.K2; P.ws = (float*)workspace;
+    P.drop_thr = drop_thr; P.drop_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; P.drop_seed = drop_seed;
+    const GemmPlan pl = gemm_plan(rq, cfg);
     hipStream_t st = (hipStream_t)stream;
     if (pl.use256) {
 #ifdef RV_STAMPS
         if (pl.mode == 0) P.ws = (float*)g_stamp_host;
 #endif
-        P.tiles_m = (M + BM2 - 1) / BM2; P.tiles_n = (N + BN2 - 1) / BN2;
-        if (trans_a) { if (trans_b) launch256<true, true>(P, pl, st); else launch256<true, false>(P, pl, st); }
-        else { if (trans_b) launch256<false, true>(P, pl, st); else launch256<false, false>(P, pl, st); }
+        launch256_plain(P, pl, trans_a, trans_b, st);
     } else {
-        P.tiles_m = (M + BM - 1) / BM; P.tiles_n = (N + BN - 1) / BN;
+        static bool attr = false;
+        if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_BYTES); attr = true; }
+        P.tiles_m = pl.tiles_m; P.tiles_n = pl.tiles_n;
         hipLaunchKernelGGL(gemm_nt_kernel, dim3(pl.grid), dim3(256), NSTAGE * STAGE_BYTES, st, P);
     }
     return rv_check_launch();
@@ -1447,17 +1354,14 @@ extern "C" int rv_gemm_bf16_ex(const void* A, int64_t lda, const void* B, int64_
                         workspace, workspace_bytes, zeros16, stream, 0.f, 0);
 }
 
-// The launch shape rv_gemm_bf16_ex takes for these sizes, layouts and workspace under the current configuration (rv_gemm_set_cu_budget,
-// rv_gemm_select_kernel); launches nothing.  K2 = 0: no second operand pair; workspace_bytes = 0: no workspace; dropping != 0: the call is
-// rv_gemm_dropout_add_bf16 with p > 0.  out[6] = {kernel (1 = 128x128, 2 = 256x256), MODE, K-slices, n_full, blocks of the GEMM kernel,
-// buffer-addressed staging}; the launch is persistent when it has fewer blocks than whole tiles + K-slice blocks.
+// radvlm_hip.h: the plan of a call of `kind` (GemmKind) under the current configuration, through the checks and the planner every launch uses.
 extern "C" int rv_gemm_plan(int M, int N, int K, int trans_a, int trans_b, int64_t lda, int64_t ldb, int K2, int64_t lda2, int64_t ldb2,
-                            int64_t workspace_bytes, int dropping, int32_t* out) {
-    if (!out || M <= 0 || N <= 0 || K <= 0 || K2 < 0 || workspace_bytes < 0) return RV_ERR_ARG;
-    if ((lda & 7) || (ldb & 7)) return RV_ERR_ARG;
-    if ((!trans_a && (K & 7)) || (trans_a && (M & 7)) || (!trans_b && (K & 7)) || (trans_b && (N & 7))) return RV_ERR_ARG;
-    if (K2 > 0 && ((lda2 & 7) || (ldb2 & 7) || (!trans_a && (K2 & 7)) || (!trans_b && (K2 & 7)))) return RV_ERR_ARG;
-    const GemmPlan pl = gemm_plan(M, N, K, trans_a, trans_b, lda, ldb, K2, lda2, ldb2, workspace_bytes, dropping != 0);
+                            int64_t workspace_bytes, int kind, int32_t* out) {
+    const GemmRequest rq = {M, N, K, trans_a, trans_b, lda, ldb, K2, lda2, ldb2, workspace_bytes, kind};
+    if (!out || !gemm_args_ok(rq)) return RV_ERR_ARG;
+    GemmConfig cfg;
+    if (const int rc = gemm_config(cfg)) return rc;
+    const GemmPlan pl = gemm_plan(rq, cfg);
     out[0] = pl.use256 ? 2 : 1; out[1] = pl.mode; out[2] = pl.splits; out[3] = pl.n_full; out[4] = pl.grid; out[5] = pl.buf;
     return RV_OK;
 }
@@ -1490,29 +1394,21 @@ extern "C" int rv_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_
 // Fused-epilogue entry points (256x256 kernel, plain tiles).  Each falls back to the unfused sequence (GEMM, then the elementwise
 // kernel of ops.hip) when the output has too few 256x256 tiles for that kernel to be the right choice, or when a shape constraint of
 // the fused form does not hold -- results are bit-identical either way (the fused epilogues keep the unfused rounding points).
-template <int EPI, bool TB, bool BUF>
-static void launch_fused1(const GemmParams& P, hipStream_t st) {
-    static bool attr = false;      // once per instantiation (see the launch-configuration note above)
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_kernel_256<false, TB, 0, EPI, BUF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES2); attr = true; }
-    int grid = P.tiles_m * P.tiles_n;
-    if (g_persist && BUF && grid > cu_budget()) grid = cu_budget();
-    hipLaunchKernelGGL((gemm_kernel_256<false, TB, 0, EPI, BUF>), dim3(grid), dim3(512), LDS_BYTES2, st, P);
+// The plan of a fused call (row-major A); use256 = 0 also where the ABI's preconditions fail: the unfused sequence reports those.
+static int fused_plan(int M, int N, int K, int trans_b, int64_t lda, int64_t ldb, GemmPlan& pl) {
+    const GemmRequest rq = {M, N, K, 0, trans_b, lda, ldb, 0, 0, 0, 0, GEMM_FUSED};
+    GemmConfig cfg;
+    if (const int rc = gemm_config(cfg)) return rc;
+    pl = gemm_plan(rq, cfg);
+    if (!gemm_args_ok(rq)) pl.use256 = 0;
+    return RV_OK;
 }
 template <int EPI, bool TB>
-static int launch_fused(GemmParams& P, int tiles_m, int tiles_n, hipStream_t st) {
-    P.tiles_m = tiles_m; P.tiles_n = tiles_n; P.n_full = 0; P.splits = 1; P.ws = nullptr;
-    P.A2 = nullptr; P.B2 = nullptr; P.K2 = 0; P.lda2 = P.ldb2 = 0;
-    if (buf_extents(P, 0, TB)) launch_fused1<EPI, TB, true>(P, st);
-    else launch_fused1<EPI, TB, false>(P, st);
+static int launch_fused(const GemmParams& P, const GemmPlan& pl, void* stream) {
+    if (((uintptr_t)P.A | (uintptr_t)P.B | (uintptr_t)P.zeros) & 15) return RV_ERR_ARG;
+    if (pl.buf) launch256<false, TB, 0, EPI, true>(P, pl, (hipStream_t)stream);
+    else launch256<false, TB, 0, EPI, false>(P, pl, (hipStream_t)stream);
     return rv_check_launch();
-}
-static bool big_enough_for_256(int M, int N) {
-    const int cus = cu_budget();
-    const long tiles256 = (long)((M + BM2 - 1) / BM2) * ((N + BN2 - 1) / BN2);
-    const long tiles128 = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    const int force = g_force_kernel;
-    if (force) return force == 2;
-    return 4.0 * (double)((tiles256 + cus - 1) / cus) <= 2.0 * 1.15 * (double)((tiles128 + 2 * cus - 1) / (2 * cus));
 }
 
 extern "C" int rv_gemm_rope_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* bias,
@@ -1520,8 +1416,10 @@ extern "C" int rv_gemm_rope_bf16(const void* A, int64_t lda, const void* B, int6
                                  void* workspace, int64_t workspace_bytes, const void* zeros16, void* stream) {
     if (!A || !B || !C || !cos_sin || !zeros16 || M <= 0 || N <= 0 || K <= 0 || rope_heads <= 0 || (long)rope_heads * hd > N) return RV_ERR_ARG;
     if ((hd & 15) || (!positions && S <= 0)) return RV_ERR_ARG;
-    const bool fused = (hd == 128 || hd == 64) && (N % 8 == 0) && (ldc % 8 == 0) && (N % hd == 0) && big_enough_for_256(M, N) &&
-                       ((((uintptr_t)C) | ((uintptr_t)bias) | ((uintptr_t)cos_sin)) & 15) == 0 && !(lda & 7) && !(ldb & 7) && !(K & 7);
+    GemmPlan pl;
+    if (const int rc = fused_plan(M, N, K, 0, lda, ldb, pl)) return rc;
+    const bool fused = pl.use256 && (hd == 128 || hd == 64) && (N % 8 == 0) && (ldc % 8 == 0) && (N % hd == 0) &&
+                       ((((uintptr_t)C) | ((uintptr_t)bias) | ((uintptr_t)cos_sin)) & 15) == 0;
     if (!fused) {
         int rc = rv_gemm_bf16_ex(A, lda, B, ldb, C, ldc, bias, nullptr, 0, M, N, K, 0, 0, 1.f, RV_ACT_NONE, 0, 0, nullptr, 0, nullptr, 0, 0,
                                  workspace, workspace_bytes, zeros16, stream);
@@ -1529,51 +1427,44 @@ extern "C" int rv_gemm_rope_bf16(const void* A, int64_t lda, const void* B, int6
         return positions ? rv_rope_inplace_pos(C, ldc, cos_sin, positions, M, rope_heads, hd, 1, 1, stream)
                          : rv_rope_inplace(C, ldc, cos_sin, M, S, rope_heads, hd, 1, 1, stream);
     }
-    if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)zeros16) & 15) return RV_ERR_ARG;
-    GemmParams P = {};
-    P.A = (const bf16*)A; P.B = (const bf16*)B; P.C = C; P.bias = (const bf16*)bias; P.zeros = (const bf16*)zeros16;
-    P.lda = lda; P.ldb = ldb; P.ldc = ldc; P.M = M; P.N = N; P.K = K; P.alpha = 1.f;
+    GemmParams P = gemm_params(A, lda, B, ldb, C, ldc, bias, nullptr, 0, zeros16, M, N, K, 1.f);
     P.rope_cs = cos_sin; P.rope_pos = positions; P.rope_S = S > 0 ? S : 1; P.rope_cols = rope_heads * hd; P.rope_hd = hd;
-    return launch_fused<EPI_ROPE, false>(P, (M + BM2 - 1) / BM2, (N + BN2 - 1) / BN2, (hipStream_t)stream);
+    return launch_fused<EPI_ROPE, false>(P, pl, stream);
 }
 
 extern "C" int rv_gemm_swiglu_fwd_bf16(const void* A, int64_t lda, const void* Wgu, int64_t ldb, void* GU, int64_t ldgu, void* ACT,
                                        int64_t ldact, int M, int F, int K, void* workspace, int64_t workspace_bytes, const void* zeros16,
                                        void* stream) {
     if (!A || !Wgu || !GU || !ACT || !zeros16 || M <= 0 || F <= 0 || K <= 0 || (F & 7) || (ldgu & 7) || (ldact & 7)) return RV_ERR_ARG;
-    const bool fused = big_enough_for_256(M, 2 * F) && ((((uintptr_t)GU) | ((uintptr_t)ACT)) & 15) == 0 && !(lda & 7) && !(ldb & 7) && !(K & 7);
-    if (!fused) {
+    GemmPlan pl;
+    if (const int rc = fused_plan(M, 2 * F, K, 0, lda, ldb, pl)) return rc;
+    if (!pl.use256 || ((((uintptr_t)GU) | ((uintptr_t)ACT)) & 15)) {
         int rc = rv_gemm_bf16_ex(A, lda, Wgu, ldb, GU, ldgu, nullptr, nullptr, 0, M, 2 * F, K, 0, 0, 1.f, RV_ACT_NONE, 0, 0, nullptr, 0, nullptr,
                                  0, 0, workspace, workspace_bytes, zeros16, stream);
         if (rc != RV_OK) return rc;
         return rv_swiglu_fwd(GU, ldgu, ACT, ldact, M, F, stream);
     }
-    if (((uintptr_t)A | (uintptr_t)Wgu | (uintptr_t)zeros16) & 15) return RV_ERR_ARG;
-    GemmParams P = {};
-    P.A = (const bf16*)A; P.B = (const bf16*)Wgu; P.C = GU; P.zeros = (const bf16*)zeros16;
-    P.lda = lda; P.ldb = ldb; P.ldc = ldgu; P.M = M; P.N = 2 * F; P.K = K; P.alpha = 1.f;
+    GemmParams P = gemm_params(A, lda, Wgu, ldb, GU, ldgu, nullptr, nullptr, 0, zeros16, M, 2 * F, K, 1.f);
     P.F = F; P.C2 = (bf16*)ACT; P.ldc2 = ldact;
-    return launch_fused<EPI_SWIGLU_FWD, false>(P, (M + BM2 - 1) / BM2, (F + 127) / 128, (hipStream_t)stream);
+    return launch_fused<EPI_SWIGLU_FWD, false>(P, pl, stream);
 }
 
 extern "C" int rv_gemm_swiglu_bwd_bf16(const void* dY, int64_t ldy, const void* Wd, int64_t ldw, const void* GU, int64_t ldgu, void* dGU,
                                        int64_t lddgu, void* dact_scratch, int64_t ld_dact, int M, int F, int K, void* workspace,
                                        int64_t workspace_bytes, const void* zeros16, void* stream) {
     if (!dY || !Wd || !GU || !dGU || !zeros16 || M <= 0 || F <= 0 || K <= 0 || (F & 7) || (ldgu & 7) || (lddgu & 7)) return RV_ERR_ARG;
-    const bool fused = big_enough_for_256(M, F) && ((((uintptr_t)GU) | ((uintptr_t)dGU)) & 15) == 0 && !(ldy & 7) && !(ldw & 7) && !(K & 7);
-    if (!fused) {
+    GemmPlan pl;
+    if (const int rc = fused_plan(M, F, K, 1, ldy, ldw, pl)) return rc;
+    if (!pl.use256 || ((((uintptr_t)GU) | ((uintptr_t)dGU)) & 15)) {
         if (!dact_scratch || (ld_dact & 7)) return RV_ERR_ARG;      // the unfused sequence needs d(act) [M, F] as a real tensor
         int rc = rv_gemm_bf16_ex(dY, ldy, Wd, ldw, dact_scratch, ld_dact, nullptr, nullptr, 0, M, F, K, 0, 1, 1.f, RV_ACT_NONE, 0, 0, nullptr, 0,
                                  nullptr, 0, 0, workspace, workspace_bytes, zeros16, stream);
         if (rc != RV_OK) return rc;
         return rv_swiglu_bwd(dact_scratch, ld_dact, GU, ldgu, dGU, lddgu, M, F, stream);
     }
-    if (((uintptr_t)dY | (uintptr_t)Wd | (uintptr_t)zeros16) & 15) return RV_ERR_ARG;
-    GemmParams P = {};
-    P.A = (const bf16*)dY; P.B = (const bf16*)Wd; P.C = dGU; P.zeros = (const bf16*)zeros16;
-    P.lda = ldy; P.ldb = ldw; P.ldc = lddgu; P.M = M; P.N = F; P.K = K; P.alpha = 1.f;
+    GemmParams P = gemm_params(dY, ldy, Wd, ldw, dGU, lddgu, nullptr, nullptr, 0, zeros16, M, F, K, 1.f);
     P.F = F; P.G = (const bf16*)GU; P.ldg = ldgu;
-    return launch_fused<EPI_SWIGLU_BWD, true>(P, (M + BM2 - 1) / BM2, (F + BN2 - 1) / BN2, (hipStream_t)stream);
+    return launch_fused<EPI_SWIGLU_BWD, true>(P, pl, stream);
 }
 
 // gA[R, K] (+)= 1 / (1 - p) * dT[M, R]^T mask_p(X)[M, K] with the mask of rv_dropout_bf16(X viewed as M * K contiguous elements, p, seed): the
@@ -1585,7 +1476,9 @@ extern "C" int rv_lora_a_grad_bf16(const void* dT, int64_t ldt, const void* X, i
     if (R > 64 || (R & 7) || (K & 7) || (ldx & 7) || (ldt & 7) || (p > 0.f && ldx != K)) return RV_ERR_ARG;
     if ((((uintptr_t)X) | ((uintptr_t)dT)) & 15) return RV_ERR_ARG;
     const int ncb = (K + AG_BN - 1) / AG_BN, nst = (M + AG_BM - 1) / AG_BM;
-    int splits = (3 * cu_budget() + ncb - 1) / ncb;          // three blocks per CU are resident (48 KiB of LDS each)
+    GemmConfig cfg;
+    if (const int rc = gemm_config(cfg)) return rc;
+    int splits = (3 * cfg.cus + ncb - 1) / ncb;          // three blocks per CU are resident (48 KiB of LDS each)
     if (splits > nst) splits = nst;
     if (splits > 32) splits = 32;
     const int64_t per = (int64_t)R * K * 4;
@@ -1596,11 +1489,9 @@ extern "C" int rv_lora_a_grad_bf16(const void* dT, int64_t ldt, const void* X, i
     Q.thr = rv_dropout_thr16(p); Q.seed = seed;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(lora_agrad_kernel, dim3((unsigned)(ncb * splits)), dim3(256), 0, st, Q);
-    GemmParams P{};
-    P.M = R; P.N = K; P.splits = splits; P.ws = (float*)workspace; P.alpha = p > 0.f ? 1.f / (1.f - p) : 1.f; P.bias = nullptr; P.act = RV_ACT_NONE;
-    P.R = accumulate ? gA : nullptr; P.ldr = ldg; P.res_f32 = 0; P.C = gA; P.ldc = ldg; P.out_f32 = 0;
-    const long total = (long)R * K;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P);
+    GemmParams P = gemm_params(nullptr, 0, nullptr, 0, gA, ldg, nullptr, accumulate ? gA : nullptr, ldg, nullptr, R, K, 0, p > 0.f ? 1.f / (1.f - p) : 1.f);
+    P.splits = splits; P.ws = (float*)workspace;
+    launch_splitk_reduce(P, st);
     return rv_check_launch();
 }
 

@@ -148,6 +148,18 @@ def workspace_bytes(case, plan):
     return 0
 
 
+BUDGETS = {8: (8, 0), 13: (16, 3)}          # rv_gemm_set_cu_budget(total, reserved) for a row's budget; 0 is the device's own
+PLAIN, DROPOUT, FUSED = 0, 1, 2             # the call kinds of rv_gemm_plan
+
+
+def plan_args(case, ws_bytes=0, kind=PLAIN):
+    """The arguments of rv_gemm_plan before `out` for a case whose operands are embedded by embed_geometry (what the GPU test runs)."""
+    c = case
+    ld = lambda k, rows, tr: embed_geometry(k, rows)[1] if tr else embed_geometry(rows, k)[1]
+    return (c.M, c.N, c.K, int(c.ta), int(c.tb), ld(c.K, c.M, c.ta), ld(c.K, c.N, c.tb), c.K2, ld(c.K2, c.M, c.ta) if c.K2 else 0,
+            ld(c.K2, c.N, c.tb) if c.K2 else 0, ws_bytes, kind)
+
+
 def alpha_of(case):
     return 1.0 if case.epi == "plain" else 0.5
 

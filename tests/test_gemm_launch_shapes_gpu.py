@@ -7,16 +7,18 @@ shape must equal the float64 reference bit for bit over the whole output: a tile
 prefetch racing an epilogue or a wrong buffer extent all show.  Operands and outputs are views inside NaN-filled buffers."""
 import ctypes
 import os
+import subprocess
+import sys
+import textwrap
 
 import pytest
 import torch
 
 import gemm_ref as G
-from gemm_ref import BF16, CASES, COL_OFF, ROW_OFF, Plan
+from gemm_ref import BF16, BUDGETS, CASES, COL_OFF, ROW_OFF, Plan
 
 pytestmark = pytest.mark.gpu
 
-BUDGETS = {8: (8, 0), 13: (16, 3)}          # rv_gemm_set_cu_budget(total, reserved); any other key: the device's own
 WS_GUARD = 4096                             # fp32 sentinels behind an exactly sized workspace
 
 
@@ -56,9 +58,9 @@ class _Config:
             self.L.rv_gemm_select_kernel(code)
         return got
 
-    def plan(self, M, N, K, ta, tb, lda, ldb, K2=0, lda2=0, ldb2=0, ws_bytes=0, dropping=0):
+    def plan(self, M, N, K, ta, tb, lda, ldb, K2=0, lda2=0, ldb2=0, ws_bytes=0, kind=G.PLAIN):
         out = (ctypes.c_int32 * 6)()
-        rc = self.L.rv_gemm_plan(M, N, K, int(ta), int(tb), lda, ldb, K2, lda2, ldb2, ws_bytes, dropping, out)
+        rc = self.L.rv_gemm_plan(M, N, K, int(ta), int(tb), lda, ldb, K2, lda2, ldb2, ws_bytes, kind, out)
         assert rc == 0, rc
         return Plan(*out)
 
@@ -144,10 +146,10 @@ class _Operands:
     def operands_untouched(self):
         return all(_untouched_outside(buf, v.shape[0], v.shape[1]) for buf, v in self.keep)
 
-    def plan(self, cfg, ws_bytes, dropping=0):
-        c = self.case
-        return cfg.plan(c.M, c.N, c.K, c.ta, c.tb, self.a.stride(0), self.b.stride(0), c.K2, self.a2.stride(0) if c.K2 else 0,
-                        self.b2.stride(0) if c.K2 else 0, ws_bytes, dropping)
+    def plan(self, cfg, ws_bytes, kind=G.PLAIN):
+        args = G.plan_args(self.case, ws_bytes, kind)          # the arguments the CPU test of the table plans with ...
+        assert args[5:7] == (self.a.stride(0), self.b.stride(0)) and (not self.case.K2 or args[8:10] == (self.a2.stride(0), self.b2.stride(0)))
+        return cfg.plan(*args)                                  # ... are those of the call run() makes
 
     def run(self, out_dtype, ws, alpha=None, act=0):
         """One rv_gemm_bf16_ex call into a fresh sentinel buffer; returns (buffer, view of C)."""
@@ -189,7 +191,7 @@ def test_launch_shape_is_taken_and_exact(cfg, name):
         assert dev.plan(cfg, need) == plan, (name, budget)
         if need:
             assert dev.plan(cfg, need - 1).mode == 0, (name, budget)
-            assert dev.plan(cfg, need, dropping=1).mode == 0, (name, budget)     # the reduce kernels do not carry the dropout mask
+            assert dev.plan(cfg, need, G.DROPOUT).mode == 0, (name, budget)     # the reduce kernels do not carry the dropout mask
         for dtype in (torch.float32, BF16):
             wsbuf, ws = _workspace(need)
             cbuf, cv = dev.run(dtype, ws)
@@ -258,7 +260,7 @@ def test_dropout_epilogue_under_the_persistent_walk(cfg, K, accumulate):
     outs = []
     for budget, grid in ((8, 8), (0, 9)):
         cfg.set(budget)
-        assert cfg.plan(M, N, K, 0, 1, av.stride(0), bv.stride(0), dropping=1) == Plan(2, 0, 1, 0, grid, 1)
+        assert cfg.plan(M, N, K, 0, 1, av.stride(0), bv.stride(0), kind=G.DROPOUT) == Plan(2, 0, 1, 0, grid, 1)
         ybuf, yv = _embed(M, N, BF16, y0)
         lib.call("rv_gemm_dropout_add_bf16", av, av.stride(0), bv, bv.stride(0), yv, yv.stride(0), M, N, K, 1, alpha, p, seed, int(accumulate),
                  lib.zeros16(yv.device))
@@ -269,9 +271,9 @@ def test_dropout_epilogue_under_the_persistent_walk(cfg, K, accumulate):
 
 
 def _fused_plan(cfg, M, N, K, tb, lda, ldb):
-    """The fused entry points launch gemm_kernel_256 MODE 0 by the two rules rv_gemm_plan reports for the plain call of the same sizes without
-    a workspace: buffer-addressed when the operands qualify, persistent when that holds and there are more tiles than the budget."""
-    return cfg.plan(M, N, K, 0, tb, lda, ldb)
+    """The plan a fused entry point launches by (kernel 1: it runs the unfused sequence): gemm_kernel_256 MODE 0, buffer-addressed when the
+    operands qualify, persistent when that holds and there are more tiles than the budget."""
+    return cfg.plan(M, N, K, 0, tb, lda, ldb, kind=G.FUSED)
 
 
 @pytest.mark.parametrize("K,hd,H,Hkv,explicit_pos", [(192, 128, 4, 1, False), (200, 128, 4, 1, True), (192, 64, 6, 3, True)])
@@ -317,6 +319,73 @@ def test_swiglu_epilogues_under_the_persistent_walk(cfg, K, d):
         buf = int(d % 64 == 0)
         assert _fused_plan(cfg, M, Fb, d, 1, d, Fb) == Plan(2, 0, 1, 0, 8 if buf and budget else 9, buf)
         _assert_exact(ops.gemm_swiglu_bwd(dy, wd, gub, Fb), dgu_ref, f"swiglu bwd d {d} budget {budget}")
+
+
+def _swiglu_bwd_without_scratch(dy, wd, gu, dgu, F):
+    """rv_gemm_swiglu_bwd_bf16 with dact_scratch = NULL: 0 exactly when the fused form runs, RV_ERR_ARG (-1) before any launch otherwise."""
+    lib = _lib()
+    return lib.load().rv_gemm_swiglu_bwd_bf16(dy.data_ptr(), dy.stride(0), wd.data_ptr(), wd.stride(0), gu.data_ptr(), gu.stride(0), dgu.data_ptr(),
+                                              dgu.stride(0), None, 0, dy.shape[0], F, dy.shape[1], None, 0, lib.zeros16(dy.device).data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream)
+
+
+# (budget, M, F) -> the fused plan, or None where the round-cost rule 4 ceil(tiles256 / cus) <= 2.3 ceil(tiles128 / 2 cus) picks the 128x128 kernel
+_FUSED_CELLS = {(8, 1000, 1000): Plan(2, 0, 1, 0, 8, 1),        # 16 tiles: 4 * 2 <= 2.3 * 4, 8 persistent blocks
+                (13, 1000, 1000): None,                         # 4 * 2 > 2.3 * 3
+                (8, 744, 712): None,                            # 9 tiles: 4 * 2 > 2.3 * 3
+                (13, 744, 712): Plan(2, 0, 1, 0, 9, 1)}         # 4 * 1 <= 2.3 * 2, one tile per block
+
+
+@pytest.mark.parametrize("M,F", [(1000, 1000), (744, 712)])
+def test_fused_entry_points_fall_back_by_the_round_cost_rule_whatever_the_layout(cfg, M, F):
+    """Under automatic kernel choice a plain call with a contraction-major operand always takes the 256x256 kernel; the fused entry points
+    do not: rv_gemm_swiglu_bwd_bf16 (B contraction-major) runs fused exactly where the round-cost rule picks that kernel, and refuses a
+    NULL scratch, launching nothing, where it would run the unfused sequence.  rv_gemm_plan(kind 2) says which, for nt and nn alike."""
+    ops = _ops()
+    d = 64
+    dy, wd, gu = _rnd(51, (M, d)).cuda(), _rnd(52, (d, F), 0.1).cuda(), _rnd(53, (M, 2 * F)).cuda()
+    cfg.set(0, kernel=1)
+    ref = ops.gemm_swiglu_bwd(dy, wd, gu, F)
+    for budget in (8, 13):
+        want = _FUSED_CELLS[budget, M, F]
+        cfg.set(budget)
+        unfused = Plan(1, 0, 1, 0, G._tiles(M, F, 128), 0)
+        assert _fused_plan(cfg, M, F, d, 1, d, F) == (want or unfused), (budget, M, F)
+        assert _fused_plan(cfg, M, F, d, 0, d, d) == (want or unfused), (budget, M, F)          # the nn forms: RoPE, SwiGLU forward
+        assert cfg.plan(M, F, d, 0, 1, d, F).kernel == 2                                        # the plain nt call: always the 256x256 kernel
+        dgu = _sentinel((M, 2 * F), BF16)
+        rc = _swiglu_bwd_without_scratch(dy, wd, gu, dgu, F)
+        if want:
+            assert rc == 0, (budget, M, F, rc)
+            _assert_exact(dgu, ref, f"swiglu bwd fused {M}x{F} budget {budget}")
+        else:
+            assert rc == -1, (budget, M, F, rc)
+            assert bool((dgu.view(torch.int16) == 0x7fc5).all()), (budget, M, F)
+
+
+def test_kernel_choice_from_the_environment_holds_from_the_first_call():
+    """RV_GEMM_KERNEL=2 in a fresh process whose FIRST GEMM call is a fused entry point: 744 x 712 at budget 8, which the round-cost rule
+    would send to the unfused sequence, runs fused (a NULL scratch is accepted)."""
+    _ops()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = textwrap.dedent(f"""
+        import sys
+        sys.path.insert(0, {root!r})
+        import torch
+        from radvlm_amd import lib
+        L = lib.load()
+        assert L.rv_gemm_set_cu_budget(8, 0) == 8
+        M, F, d = 744, 712, 64
+        dy, wd = torch.ones(M, d, dtype=torch.bfloat16, device="cuda"), torch.ones(d, F, dtype=torch.bfloat16, device="cuda")
+        gu, dgu = torch.ones(M, 2 * F, dtype=torch.bfloat16, device="cuda"), torch.empty(M, 2 * F, dtype=torch.bfloat16, device="cuda")
+        rc = L.rv_gemm_swiglu_bwd_bf16(dy.data_ptr(), d, wd.data_ptr(), F, gu.data_ptr(), 2 * F, dgu.data_ptr(), 2 * F, None, 0, M, F, d, None, 0,
+                                       lib.zeros16(dy.device).data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        print("RESULT", rc)
+    """)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, RV_GEMM_KERNEL="2"))
+    assert p.returncode == 0, (p.returncode, p.stderr[-800:])
+    assert p.stdout.split("RESULT")[1].split() == ["0"], p.stdout
 
 
 def test_plan_refuses_what_the_gemm_refuses(cfg):

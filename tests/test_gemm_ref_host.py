@@ -1,6 +1,13 @@
 """CPU checks of tests/gemm_ref.py: the operands, the float64 reference and the case table alone meet the conditions under which
 tests/test_gemm_launch_shapes_gpu.py may demand bit-exact results of every launch shape of rv_gemm_bf16_ex, so a failure there points at
-a kernel or at the planner."""
+a kernel or at the planner -- and the planner itself, through the real library: rv_gemm_plan is integer arithmetic over sizes and
+switches, so with an explicit budget (rv_gemm_set_cu_budget(total > 0, ...)) the whole case table is checked here, without a device."""
+import ctypes
+import os
+import subprocess
+import sys
+import textwrap
+
 import numpy as np
 import torch
 
@@ -106,3 +113,62 @@ def test_plans_are_consistent_and_cover_every_launch_shape():
     for mode in (2, 3):
         assert any(((c.K + BK - 1) // BK) % p.splits for c in CASES for p in c.budgets.values() if p.mode == mode)
     assert TILE == 256
+
+
+DEVICE_BUDGETS = (64, 96, 256, 304)         # a row's budget 0 is "the device's own": its plan holds from 64 compute units on
+
+
+def _plan(L, case, ws_bytes, kind=G.PLAIN):
+    out = (ctypes.c_int32 * 6)()
+    rc = L.rv_gemm_plan(*G.plan_args(case, ws_bytes, kind), out)
+    assert rc == 0, (case.name, rc)
+    return G.Plan(*out)
+
+
+def test_the_library_plans_every_row_of_the_table_without_a_device():
+    """Every row at every budget of the row (0: at 64, 96, 256 and 304 units), under the row's forced kernel and switches: rv_gemm_plan
+    gives the row's plan with the workspace gemm_ref.workspace_bytes names; one byte less, or the dropout kind, and a K-split row plans
+    MODE 0."""
+    from radvlm_amd import lib
+    L = lib.load()
+    checked = 0
+    try:
+        for c in CASES:
+            for budget, plan in c.budgets.items():
+                for total, reserved in ([G.BUDGETS[budget]] if budget else [(n, 0) for n in DEVICE_BUDGETS]):
+                    assert L.rv_gemm_set_cu_budget(total, reserved) == total - reserved
+                    for code in (21, 31, 41, plan.kernel) + c.switches:
+                        L.rv_gemm_select_kernel(code)
+                    need = G.workspace_bytes(c, plan)
+                    assert _plan(L, c, need) == plan, (c.name, budget, total)
+                    if need:
+                        assert _plan(L, c, need - 1).mode == 0, (c.name, budget, total)
+                        assert _plan(L, c, need, G.DROPOUT).mode == 0, (c.name, budget, total)
+                    checked += 1
+    finally:
+        for code in (0, 21, 31, 41):
+            L.rv_gemm_select_kernel(code)
+        L.rv_gemm_set_cu_budget(0, int(os.environ.get("RV_GEMM_RESERVED_CUS", "0")))      # the device's own again, where there is a device
+    assert checked == sum(1 if b else len(DEVICE_BUDGETS) for c in CASES for b in c.budgets)
+
+
+def test_planning_without_a_budget_or_a_device_is_an_error_not_a_crash():
+    """A fresh process whose first GEMM call is rv_gemm_plan, no budget set: where there is no device the call returns the error code
+    of the failed device query and the process goes on (it used to divide by the missing budget); with a device it plans."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = textwrap.dedent(f"""
+        import ctypes, sys
+        sys.path.insert(0, {root!r})
+        from radvlm_amd import lib
+        L = lib.load()
+        out = (ctypes.c_int32 * 6)()
+        rc = L.rv_gemm_plan(744, 712, 128, 0, 0, 128, 128, 0, 0, 0, 0, 0, out)
+        print("RESULT", rc, L.rv_gemm_set_cu_budget(0, 0), L.rv_gemm_set_cu_budget(8, 0),
+              L.rv_gemm_plan(744, 712, 128, 0, 0, 128, 128, 0, 0, 0, 0, 0, out), *out)
+    """)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert p.returncode == 0, (p.returncode, p.stderr[-800:])
+    rc, device_budget, budget, rc2, *plan = (int(v) for v in p.stdout.split("RESULT")[1].split())
+    assert rc == (0 if device_budget > 0 else device_budget) and (device_budget > 0 or device_budget == -2), (rc, device_budget)
+    # an explicit total needs no device; 9 tiles on 8 units: 4 * 2 > 2.3 * ceil(36 / 16), the 128x128 kernel's 6 x 6 tiles
+    assert budget == 8 and rc2 == 0 and G.Plan(*plan) == G.Plan(1, 0, 1, 0, 36, 0), (budget, rc2, plan)
