@@ -358,6 +358,28 @@ int64_t rv_w8_row_bytes(int K);
 int rv_gemv_w8_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp, const float* scale, void* Y, int64_t ldy,
                     const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
                     int64_t ws_bytes, void* stream);
+/* Weight-only MXFP4 decoding (reference: load_pretrained_model(load_4bit=True), model/builder.py; here OCP Microscaling FP4, E2M1
+ * elements with one E8M0 scale per block of 32 consecutive k, radvlm_amd/csrc/mxfp4.hip).  For each block of a bf16 row (the last
+ * block is shorter when K % 32 != 0; only its existing entries count):
+ *     amax = max |w|    e = floor(log2(amax)) - 2 (0 for an all-zero block)    a = |w| / 2^e
+ *     code = nearest of {0, .5, 1, 1.5, 2, 3, 4, 6} (codes 0..7), ties to the even code, a > 6 saturates to code 7
+ *     W^ = sign(w) * value[code] * 2^e (exactly a bf16 number; code 0 gives +0.0)    nibble = sign << 3 | code (0 for code 0)
+ * One pass over W[N, K] (rows of ldw elements; a row slice of the fused q|k|v or gate|up store is fine) writes W^ over W, the nibbles to
+ * packed[N][ldp] (ldp = rv_w4_row_bytes(K)) and the scale bytes e + 127 to scales[N][lds] (uint8, lds = rv_w4_scale_row_bytes(K)).
+ * The layout is private to this entry and rv_gemv_w4_bf16: 64 bytes per four 32-deep K steps, the 8 weights of each of the four steps
+ * that one MFMA lane group reads side by side; padding past K is nibble 0 and scale byte 127.  Lossy (about 12 % relative Frobenius
+ * error on Gaussian rows); block maxima outside [2^-120, 2^120] and non-finite weights are outside the contract.  K % 8 == 0,
+ * ldw % 8 == 0. */
+int rv_quantize_rows_mxfp4_bf16(void* W, int64_t ldw, void* packed, int64_t ldp, void* scales, int64_t lds, int N, int K, void* stream);
+/* Bytes of one packed nibble row / of one scale row for K input features (host functions, no launch). */
+int64_t rv_w4_row_bytes(int K);
+int64_t rv_w4_scale_row_bytes(int K);
+/* rv_gemv_bf16 with the weight given as (packed, scales) of rv_quantize_rows_mxfp4_bf16: the bf16 operand W^ is rebuilt in registers,
+ * the K split, the k-to-lane assignment and the accumulation order are rv_gemv_bf16's, so Y is bit-identical to rv_gemv_bf16 on W^ for
+ * every M <= 32.  0.27x the weight bytes per call.  Same workspace rule; ldp and lds must be the layout's. */
+int rv_gemv_w4_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp, const void* scales, int64_t lds, void* Y, int64_t ldy,
+                    const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
+                    int64_t ws_bytes, void* stream);
 /* Decode attention (flash-decoding): for every sequence b and q head h, softmax(scale * q[b,h] K^T) V over the cached keys
  * [0, kv_len[b]) of kv head h / (H / Hkv), hd in {64, 128}, up to 8 q heads per kv head (GQA), fp32 softmax and accumulation.
  * cache: bf16 [B][L_max][ld_c] (sequence stride bs_c), K of kv head g at columns g*hd, V at v_off + g*hd.  q: [B, H*hd] rows (ld_q);

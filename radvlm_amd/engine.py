@@ -38,6 +38,7 @@ class LlavaEngine:
                  padding_side="right", force_grad_sync=False, recompute=False):
         self.geo = geo
         self.weights_version = 0              # bumped by every write to the weights (weights_changed): a GenerationCache of an older one is stale
+        self.w4 = None                        # per layer {name: (packed nibbles, E8M0 scale bytes)} after quantize_decoder_("mxfp4"); likewise
         self.w8 = None                        # per layer {name: (packed int8, fp32 scale)} after quantize_decoder_(); dropped by weights_changed
         assert recompute in (False, True, "auto")
         self.recompute = recompute            # activation recompute policy of the decoder layers (_recompute_layers)
@@ -260,6 +261,7 @@ class LlavaEngine:
         copies of tower weights (padded patch / attention projections) when the tower may have changed, and bumps weights_version."""
         self.weights_version += 1
         self.w8 = None           # the int8 copies describe the weights they were made from: a changed engine is a plain bf16 engine again
+        self.w4 = None           # the MXFP4 copies likewise
         if tower:
             self._patch_w = None
             self._vis_pad = {}
@@ -833,28 +835,49 @@ class LlavaEngine:
     # On a quantised engine (quantize_decoder_) the skinny route reads the int8 copy; False forces the bf16 kernel on the same
     # (dequantised) weights.  The two are bit-identical, so this switch changes time only: it is the A/B arm of tools/decode_bench.py --w8.
     w8_decode = True
+    # The same switch for the MXFP4 copy (quantize_decoder_("mxfp4")): the A/B arm of tools/decode_bench.py --w4.
+    w4_decode = True
 
     def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16, w8=None, skinny=False):
         """skinny: the skinny kernel whatever the row count (<= ops.GEMV_MAX_M) and the weight's height -- verify_step, whose rows must
         carry the bits of the one-row decode step, which always takes that kernel."""
         max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
         if skinny or x.shape[0] <= min(max_m, ops.GEMV_MAX_M):
-            if w8 is not None:
+            if w8 is not None:                                      # the layer's quantised copy: (packed, scale), int8 or MXFP4 by its dtype
+                if w8[0].dtype == torch.uint8:
+                    if self._w4_cell_takes_bf16(w.shape[0], w.shape[1], x.shape[0]):
+                        return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
+                    return ops.gemv_w4(x, w8[0], w8[1], w.shape[1], bias=bias, residual=residual, out_dtype=out_dtype)
                 return ops.gemv_w8(x, w8[0], w8[1], w.shape[1], bias=bias, residual=residual, out_dtype=out_dtype)
             return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
         return ops.gemm_nt(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
 
+    # (N, K) -> the measured row counts at which rv_gemv_w4_bf16 did NOT beat rv_gemv_bf16 on the same weight by more than the bf16 arm's
+    # own spread (max - min of its 20 samples); those launches go back to the bf16 kernel, which gives the same bits.  A launch of M rows
+    # reads the cell of the next measured M (1, 4, 8, 16, 32) at or above its own.  Record: profiles/decode_ab_gemv.jsonl, mode w4,
+    # build "default", field w4_faster_by_more_than_bf16_spread (tests/test_w4_host.py holds this table to that record).  The Qwen2
+    # q|k|v and o_proj cells are 1.02x - 1.11x on the medians, inside the spread; the three 7B cells are 1.3x - 1.8x on the medians and
+    # fail the bar on one slow bf16 sample each.  Every cell that stays with the 4-bit kernel is 1.23x - 2.28x faster on that record.
+    W4_BF16_CELLS = {(12288, 4096): (1,), (4096, 4096): (4, 16), (4608, 3584): (1, 4, 8, 16, 32), (3584, 3584): (1, 4, 8, 16, 32)}
+
+    def _w4_cell_takes_bf16(self, N, K, M):
+        cells = self.W4_BF16_CELLS.get((N, K))
+        return bool(cells) and next(m for m in (1, 4, 8, 16, 32) if M <= m) in cells
+
     def _layer_w8(self, i):
+        """The quantised copies the decode GEMMs of layer i read: the int8 pairs, the MXFP4 pairs, or none (bf16 on the same weights)."""
+        if self.w4 is not None:
+            return self.w4[i] if self.w4_decode else {}
         return self.w8[i] if (self.w8 is not None and self.w8_decode) else {}
 
     @property
     def is_quantized(self):
-        return self.w8 is not None
+        return self.w8 is not None or self.w4 is not None
 
     W8_MATRICES = ("qkv", "o", "gu", "down")
 
-    def quantize_decoder_(self):
-        """Weight-only int8 for decoding (the reference's load_8bit): every layer's fused q|k|v, o_proj, fused gate|up and down_proj are
+    def quantize_decoder_(self, fmt="int8"):
+        """fmt="int8" (the default).  Weight-only int8 for decoding (the reference's load_8bit): every layer's fused q|k|v, o_proj, fused gate|up and down_proj are
         quantised row-wise (s = max|row| / 127, q = clamp(rint(w / s), -127, 127)) and the bf16 weight is OVERWRITTEN with the
         dequantised bf16(float(q) * s), which is the model's weight from then on: prefill, extend, forward and state_dict() read it
         through the unchanged bf16 code, and decode steps read (q, s) through rv_gemv_w8_bf16, which rebuilds the same bits -- one
@@ -863,16 +886,29 @@ class LlavaEngine:
         call raises (quantising the dequantised weight would round again), and any later write to the weights (load_state_dict,
         optimizer_step, merge_lora_, resize_token_embeddings) drops the int8 copies.  When optimizer state exists, the fp32 master copy
         of the quantised matrices is rewritten from the dequantised weights (as merge_lora_ does), so a later optimizer_step starts from
-        them instead of restoring the unquantised values.  Non-finite weights are outside the contract."""
+        them instead of restoring the unquantised values.  Non-finite weights are outside the contract.
+
+        fmt="mxfp4".  The same act with OCP Microscaling FP4 (the 4-bit mode): E2M1 elements, one power-of-two scale per block of 32
+        consecutive input features (e = floor(log2 max|block|) - 2, nearest value with ties to the even code, saturating).  The
+        quantised weight is exactly a bf16 number and replaces the bf16 weight; the copies go to `w4` ({name: (packed nibbles, scale
+        bytes)} per layer, 4.25 bits per weight, about 1.27x the memory of these matrices with the bf16 copy kept) and decode steps
+        read them through rv_gemv_w4_bf16, bit-identical to the bf16 kernel on the same weights.  Everything else is as for int8.
+        This format is lossy: about 12 % relative Frobenius error per matrix against about 1 % for int8."""
+        if fmt not in ("int8", "mxfp4"):
+            raise ValueError(f"quantize_decoder_(fmt={fmt!r}): expected 'int8' or 'mxfp4'")
         self._check_generation()
-        if self.w8 is not None:
+        if self.is_quantized:
             raise RuntimeError("quantize_decoder_(): the decoder is already quantised; a second pass would round the weights again")
-        w8 = []
+        quantize = ops.quantize_rows_w8 if fmt == "int8" else ops.quantize_rows_mxfp4
+        copies = []
         for i in range(self.l["layers"]):
             lv = self._layer_views(i)
-            w8.append({n: ops.quantize_rows_w8(lv[n]) for n in self.W8_MATRICES})
+            copies.append({n: quantize(lv[n]) for n in self.W8_MATRICES})
         self.weights_changed(tower=False)
-        self.w8 = w8
+        if fmt == "int8":
+            self.w8 = copies
+        else:
+            self.w4 = copies
         if self.master is not None and self.base is None:
             for i in range(self.l["layers"]):
                 for t, _, _ in LORA_TARGETS:

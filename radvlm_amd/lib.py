@@ -100,6 +100,9 @@ _SIGS = {
     "rv_quantize_rows_w8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p],
     "rv_gemv_w8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _i32,
                         _c_void_p, _i64, _c_void_p],
+    "rv_quantize_rows_mxfp4_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _c_void_p],
+    "rv_gemv_w4_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _i32,
+                        _c_void_p, _i64, _c_void_p],
     "rv_attn_decode_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32,
                             _i32, _i32, _f32, _c_void_p],
     "rv_attn_extend_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
@@ -129,7 +132,7 @@ _SIGS = {
 }
 
 EXPORTED_SYMBOLS = ["rv_version", "rv_gemm_select_kernel", "rv_gemm_set_cu_budget", "rv_attn_fwd_nat_pairs", "rv_gemv_split",
-                    "rv_w8_row_bytes", "rv_sample_uniform24", "rv_sample_ws_bytes", "rv_beam_topk_ws_bytes", "rv_cfg_guide_ws_bytes"] + sorted(_SIGS)
+                    "rv_w8_row_bytes", "rv_w4_row_bytes", "rv_w4_scale_row_bytes", "rv_sample_uniform24", "rv_sample_ws_bytes", "rv_beam_topk_ws_bytes", "rv_cfg_guide_ws_bytes"] + sorted(_SIGS)
 
 _lib = None
 
@@ -150,6 +153,9 @@ def load():
         lib.rv_version.restype = ctypes.c_char_p
         lib.rv_w8_row_bytes.argtypes = [_i32]
         lib.rv_w8_row_bytes.restype = _i64
+        for fn in (lib.rv_w4_row_bytes, lib.rv_w4_scale_row_bytes):
+            fn.argtypes = [_i32]
+            fn.restype = _i64
         lib.rv_sample_uniform24.argtypes = [ctypes.c_uint64, ctypes.c_int32]
         lib.rv_sample_uniform24.restype = ctypes.c_uint32
         lib.rv_sample_ws_bytes.argtypes = [ctypes.c_int]

@@ -37,7 +37,7 @@ def _load_into(model, sd, what):
         raise KeyError(f"{what}: tensors the model does not have: {unexpected[:4]}")
 
 
-def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bit=False, device="cuda", **ignored):
+def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bit=False, device="cuda", quantization=None, **ignored):
     """Returns (tokenizer or None, model, image_processor or None, context_len).
       * adapter_config.json in model_path (LoRA run): the model is built from model_base (or the adapter config's
         base_model_name_or_path when that is a local directory), non_lora_trainables.bin is loaded over it and the adapters are merged
@@ -45,10 +45,18 @@ def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bi
       * model_base given and no adapters (projector-only run): model_base's weights, then mm_projector.bin from model_path;
       * otherwise model_path is a full checkpoint.
     load_8bit=True (builder.py:27-31): after loading (and merging adapters, if any) the decoder's matrices are quantised to row-wise
-    int8 for decoding, model.quantize_decoder_(); lm_head stays bf16 as in the reference.  load_4bit is accepted and ignored.
+    int8 for decoding, model.quantize_decoder_(); lm_head stays bf16 as in the reference.  quantization="int8" is the same thing;
+    quantization="mxfp4" is the 4-bit mode, model.quantize_decoder_("mxfp4") (lossy: about 12 % relative error per matrix).  Any other
+    string, or load_8bit=True together with "mxfp4", is a ValueError.  load_4bit is accepted and ignored.
     Geometry and mm_* / image_* settings come from model_path's config.json in every case.  The tokenizer comes from
     transformers.AutoTokenizer only when its files are in model_base or model_path."""
     from ... import lora_io
+    if quantization not in (None, "int8", "mxfp4"):
+        raise ValueError(f"quantization={quantization!r}: expected None, 'int8' or 'mxfp4'")
+    if load_8bit and quantization == "mxfp4":
+        raise ValueError("load_8bit=True and quantization='mxfp4' name two different formats: pass one of them")
+    if load_8bit:
+        quantization = "int8"
     if os.path.exists(os.path.join(model_path, "adapter_config.json")):
         acfg = lora_io.read_adapter_config(model_path)
         if model_base is None:
@@ -70,8 +78,8 @@ def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bi
         _load_into(model, lora_io.read_projector(model_path), "mm_projector.bin")
     else:
         model = _build_model(model_path, model_path, device)
-    if load_8bit:
-        model.quantize_decoder_()
+    if quantization is not None:
+        model.quantize_decoder_(quantization)
     model.eval()
     tokenizer = None
     tok_dir = next((p for p in (model_base, model_path) if p and any(os.path.exists(os.path.join(p, f)) for f in _TOKENIZER_FILES)), None)

@@ -625,6 +625,60 @@ def gemv_w8(x, packed, scale, K, out=None, bias=None, residual=None, out_dtype=B
     return out
 
 
+def w4_row_bytes(K):
+    """Bytes of one packed MXFP4 nibble row for K input features: 64 per four 32-deep K steps (a function of K alone, no library call)."""
+    return ((int(K) + 31) // 32 + 3) // 4 * 64
+
+
+def w4_scale_row_bytes(K):
+    """Bytes of one MXFP4 scale row for K input features: one E8M0 byte per 32-deep K step, padded to whole quads of steps."""
+    return ((int(K) + 31) // 32 + 3) // 4 * 4
+
+
+def quantize_rows_mxfp4(w):
+    """MXFP4 quantisation of a bf16 [N, K] weight IN PLACE (rv_quantize_rows_mxfp4_bf16): per block of 32 consecutive k one power-of-two
+    scale 2^e, e = floor(log2(max|block|)) - 2, and per weight the nearest E2M1 value of |w| / 2^e (ties to the even code, saturating);
+    w <- sign * value * 2^e, exactly a bf16 number.  w may be a row-major view with a row stride (the fused q|k|v and gate|up views).
+    Returns (packed uint8 [N, w4_row_bytes(K)] in gemv_w4's private layout, scales uint8 [N, w4_scale_row_bytes(K)]).  Lossy (about
+    12 % relative Frobenius error on Gaussian rows).  Block maxima outside [2^-120, 2^120] and non-finite weights are outside the
+    contract."""
+    _chk(w)
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    assert K % 8 == 0 and w.stride(0) % 8 == 0
+    packed = torch.empty(N, w4_row_bytes(K), dtype=torch.uint8, device=w.device)
+    scales = torch.empty(N, w4_scale_row_bytes(K), dtype=torch.uint8, device=w.device)
+    lib.call("rv_quantize_rows_mxfp4_bf16", w, w.stride(0), packed, packed.stride(0), scales, scales.stride(0), N, K)
+    return packed, scales
+
+
+def gemv_w4(x, packed, scales, K, out=None, bias=None, residual=None, out_dtype=BF16, workspace=None):
+    """gemv() with the weight given as quantize_rows_mxfp4's (packed, scales) of a [N, K] weight: rv_gemv_w4_bf16, 0.27x the weight
+    bytes, bit-identical to gemv(x, w) on the quantised weight quantize_rows_mxfp4 left in place."""
+    _chk(x), _chk(packed, torch.uint8), _chk(scales, torch.uint8)
+    M = x.shape[0]
+    N = packed.shape[0]
+    assert 1 <= M <= GEMV_MAX_M and x.shape[1] == K and x.stride(1) == 1
+    assert packed.is_contiguous() and packed.shape[1] == w4_row_bytes(K)
+    assert scales.is_contiguous() and scales.shape == (N, w4_scale_row_bytes(K))
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype in (BF16, torch.float32)
+    if bias is not None:
+        _chk(bias)
+        assert bias.numel() == N and bias.is_contiguous()
+    ldr = 0
+    if residual is not None:
+        _chk(residual)
+        assert residual.shape == (M, N) and residual.stride(1) == 1
+        ldr = residual.stride(0)
+    if workspace is None:
+        workspace = default_workspace(x.device)
+    lib.call("rv_gemv_w4_bf16", x, x.stride(0), packed, packed.stride(0), scales, scales.stride(0), out, out.stride(0), bias, residual, ldr,
+             M, N, K, int(out.dtype == torch.float32), workspace, workspace.numel() * workspace.element_size())
+    return out
+
+
 def attn_decode(q, cache, kv_len, H, Hkv, hd, v_off, out=None, chunk=128, scale=None):
     """One query row per (sequence, q head) against the cached keys [0, kv_len[b]): q [B, H*hd] rows; cache bf16 [B, L_max, width]
     with K of kv head g at columns g*hd and V at v_off + g*hd; kv_len int32 [B] (device).  Returns bf16 [B, H*hd]."""

@@ -27,6 +27,8 @@
   python tools/decode_bench.py --w8-shapes [--out FILE]   # per-shape kernel A/B: rv_gemv_bf16 on the dequantised weight vs
         # rv_gemv_w8_bf16, the 7B Llama and Qwen2-7B decoder shapes, M = 1, 4, 8, 16, 32, cold weights, interleaved
   python tools/decode_bench.py --w8-quality   # the toy goldens' models: logits distance and greedy-token agreement, int8 vs unquantised
+  python tools/decode_bench.py --w4 | --w4-shapes | --w4-quality   # the same three for MXFP4 decoder weights (quantize_decoder_("mxfp4"),
+        # rv_gemv_w4_bf16, engine.w4_decode); the int8 kernel / an int8 engine is timed in the same rounds, for information
   python tools/decode_bench.py --w8-trace [--geos llava15_7b]   # a B = 1 int8 decode run: the workload of `rocprofv3 --kernel-trace --stats`
   python tools/decode_bench.py --kv8 [--geos ..] [--batches 1,8,32] [--out FILE]
         # int8 KV cache: one engine per geometry, the decode loop on an int8-dtype cache with engine.kv8_decode False / True interleaved
@@ -257,8 +259,8 @@ def w8_ab(geo, batches, prompt, new, reps=3):
     return recs
 
 
-def w8_quality_toy(new=32):
-    """How far int8 decoder weights move the toy goldens' models (portable-init weights, the golden prompts with their images): relative
+def w8_quality_toy(new=32, fmt="int8"):
+    """How far int8 (or, fmt="mxfp4", 4-bit) decoder weights move the toy goldens' models (portable-init weights, the golden prompts with their images): relative
     L2 of the last prompt row's logits and the share of greedy tokens that agree with the unquantised model.  Reported, never gated."""
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
     recs = []
@@ -281,11 +283,124 @@ def w8_quality_toy(new=32):
             return out
 
         a = run()
-        eng.quantize_decoder_()
+        eng.quantize_decoder_(fmt)
         b = run()
-        recs.append(dict(geo=geo, mode="w8_quality_toy", prompts=n, new_tokens=new,
+        recs.append(dict(geo=geo, mode="w8_quality_toy" if fmt == "int8" else "w4_quality_toy", prompts=n, new_tokens=new,
                          logits_rel_l2=[round(float((y[0] - x[0]).norm() / x[0].norm()), 5) for x, y in zip(a, b)],
                          greedy_tokens_agree=[round(float((x[1] == y[1]).mean()), 4) for x, y in zip(a, b)]))
+    return recs
+
+
+def _timed_interleaved(fns, flush, reps):
+    """Every function of `fns` timed `reps` times in turn (A, B, C, A, B, C ...) on cold weights; microseconds per call."""
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, f in fns.items():
+            flush.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            ts[k].append(e0.elapsed_time(e1) * 1e3)
+    return ts
+
+
+def w4_shapes(reps=20):
+    """rv_gemv_bf16 on the MXFP4-quantised weight vs rv_gemv_w4_bf16 per decoder shape (the same output bits), interleaved, cold weights,
+    as w8_shapes(); the int8 kernel on an int8 copy of the same weight is timed in the same rounds, for information."""
+    out = []
+    for geo in ("llava15_7b", "llava_ov_qwen2_7b"):
+        l = GEOMETRIES[geo]["lm"]
+        d, F = l["d"], l["ffn"]
+        kvd = l.get("kv_heads", l["heads"]) * (d // l["heads"])
+        for name, N, K in [("qkv", d + 2 * kvd, d), ("o", d, d), ("gu", 2 * F, d), ("down", d, F)]:
+            w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02
+            packed, scales = ops.quantize_rows_mxfp4(w)
+            p8, s8 = ops.quantize_rows_w8(w.clone())
+            flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
+            for M in (1, 4, 8, 16, 32):
+                x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+                fns = {"bf16": lambda: ops.gemv(x, w), "w4": lambda: ops.gemv_w4(x, packed, scales, K), "w8": lambda: ops.gemv_w8(x, p8, s8, K)}
+                assert torch.equal(fns["bf16"](), fns["w4"]())
+                fns["w8"]()
+                ts = _timed_interleaved(fns, flush, reps)
+                b, q, q8 = (float(np.median(ts[k])) for k in ("bf16", "w4", "w8"))
+                spread = float(np.percentile(ts["bf16"], 75) - np.percentile(ts["bf16"], 25))
+                out.append(dict(mode="w4", geo=geo, shape=name, N=N, K=K, M=M, bf16_us=round(b, 2), w4_us=round(q, 2), w8_us=round(q8, 2),
+                                speedup=round(b / q, 3), speedup_vs_w8=round(q8 / q, 3), bf16_iqr_us=round(spread, 2),
+                                bf16_min_us=round(min(ts["bf16"]), 2), bf16_max_us=round(max(ts["bf16"]), 2),
+                                w4_faster_by_more_than_bf16_spread=bool(b - q > max(ts["bf16"]) - min(ts["bf16"])),
+                                bf16_TBps=round(2 * N * K / (b * 1e-6) / 1e12, 3),
+                                w4_TBps=round(N * (packed.shape[1] + scales.shape[1]) / (q * 1e-6) / 1e12, 3),
+                                split=ops.gemv_split(N, K), layout="16-byte interleaved step quads + E8M0 bytes",
+                                build=os.path.basename(os.environ.get("RADVLM_HIP_LIB", "default")), kernel_src=_src_hash()))
+            del w, packed, scales, p8, s8, flush
+    return out
+
+
+def w4_weight_bytes(eng):
+    """Weight bytes a decode step reads on the 4-bit route: nibble rows + scale bytes of the four decoder matrices, bf16 lm_head."""
+    l = eng.l
+    q = sum(p.numel() + s.numel() for layer in eng.w4 for p, s in layer.values())
+    return int(q + 2 * l["vocab"] * l["d"])
+
+
+def w4_ab(geo, batches, prompt, new, reps=3):
+    """The --w8 protocol for MXFP4: the decode step with engine.w4_decode False / True, interleaved `reps` times; a second engine with
+    int8 weights is timed in the same rounds (the int8 figure of the same box)."""
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    eng8 = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    ids1 = np.random.default_rng(0).integers(0, eng.vocab, (1, prompt))
+
+    def greedy(e, n):
+        cache, logits = e.prefill(ids1, None, None, None, max_new_tokens=n)
+        first = logits[0].clone()
+        toks = [ops.argmax_rows(logits, e.vocab)]
+        for _ in range(n - 1):
+            toks.append(ops.argmax_rows(e.decode_step(cache, toks[-1].to(torch.int32)), e.vocab))
+        return first, torch.cat(toks).cpu().numpy()
+
+    lg0, tk0 = greedy(eng, 64)                                        # the unquantised model on the prompt of the timed runs
+    eng.quantize_decoder_("mxfp4")
+    eng8.quantize_decoder_("int8")
+    quality = {}
+    for name, e in (("mxfp4", eng), ("int8", eng8)):
+        lg1, tk1 = greedy(e, 64)
+        quality[name] = dict(logits_rel_l2=round(float((lg1 - lg0).norm() / lg0.norm()), 5),
+                             greedy_tokens_agree=round(float((tk0 == tk1).mean()), 4),
+                             first_disagreement=int(np.argmax(tk0 != tk1)) if (tk0 != tk1).any() else None, tokens=64)
+    arms = {"bf16": (eng, False), "w4": (eng, True), "w8": (eng8, True)}
+    recs = []
+    for B in batches:
+        ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+        ts = {k: [] for k in arms}
+
+        def run(k):
+            e, flag = arms[k]
+            e.w4_decode = flag
+            try:
+                return float(np.median(_decode_loop(e, ids, new)))
+            finally:
+                e.w4_decode = True
+
+        for k in arms:                                                 # warm-up: one untimed repetition of every arm
+            run(k)
+        for _ in range(reps):
+            for k in arms:
+                ts[k].append(run(k))
+        b, q, q8 = (float(np.median(ts[k])) for k in ("bf16", "w4", "w8"))
+        kv = int(2 * eng.l["layers"] * 2 * eng.kvd * (prompt + new // 2) * B)
+        wb, w4b, w8b = weight_bytes(eng), w4_weight_bytes(eng), w8_weight_bytes(eng8)
+        recs.append(dict(geo=geo, mode="w4_ab", B=B, prompt=prompt, new_tokens=new, reps=reps, bf16_ms_per_step=round(b, 3),
+                         w4_ms_per_step=round(q, 3), w8_ms_per_step=round(q8, 3), bf16_ms_all=[round(x, 3) for x in ts["bf16"]],
+                         w4_ms_all=[round(x, 3) for x in ts["w4"]], w8_ms_all=[round(x, 3) for x in ts["w8"]],
+                         bf16_spread_ms=round(max(ts["bf16"]) - min(ts["bf16"]), 3), delta_ms=round(b - q, 3), speedup=round(b / q, 3),
+                         w4_faster_by_more_than_bf16_spread=bool(b - q > max(ts["bf16"]) - min(ts["bf16"])),
+                         bf16_tokens_per_s=round(B * 1e3 / b, 1), w4_tokens_per_s=round(B * 1e3 / q, 1), w8_tokens_per_s=round(B * 1e3 / q8, 1),
+                         bf16_weight_bytes=wb, w4_weight_bytes=w4b, w8_weight_bytes=w8b, weight_bytes_ratio=round(w4b / wb, 3),
+                         kv_bytes_per_step=kv, bf16_implied_TBps=round((wb + kv) / (b * 1e-3) / 1e12, 3),
+                         w4_implied_TBps=round((w4b + kv) / (q * 1e-3) / 1e12, 3), quality_vs_unquantised=quality, kernel_src=_src_hash()))
     return recs
 
 
@@ -1138,6 +1253,9 @@ def main():
     ap.add_argument("--w8-shapes", action="store_true")
     ap.add_argument("--w8-trace", action="store_true")
     ap.add_argument("--w8-quality", action="store_true")
+    ap.add_argument("--w4", action="store_true")
+    ap.add_argument("--w4-shapes", action="store_true")
+    ap.add_argument("--w4-quality", action="store_true")
     ap.add_argument("--kv8", action="store_true")
     ap.add_argument("--kv8-shapes", action="store_true")
     ap.add_argument("--kv8-quality", action="store_true")
@@ -1163,6 +1281,12 @@ def main():
         recs = w8_quality_toy()
     elif a.w8_trace:
         recs = [r for g in a.geos.split(",") for r in w8_trace(g, a.prompt, a.new)]
+    elif a.w4_shapes:
+        recs = w4_shapes()
+    elif a.w4:
+        recs = [r for g in a.geos.split(",") for r in w4_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new)]
+    elif a.w4_quality:
+        recs = w8_quality_toy(fmt="mxfp4")
     elif a.kv8_shapes:
         recs = kv8_shapes()
     elif a.kv8:
