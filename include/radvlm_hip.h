@@ -329,12 +329,12 @@ int rv_cast_bf16_to_f32(const void* in, float* out, int64_t n, void* stream);
 /* y[i] = a[i] + b[i] (bf16). */
 int rv_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream);
 
-/* ---- decode (generate(): one new token per sequence, radvlm_amd/csrc/decode.hip) ---------------------------------------------
+/* ---- decode (generate(): one new token per sequence, radvlm_amd/csrc/gemv.hip and decode.hip) ----------------------------
  * The reference decodes through HF generate on inputs_embeds (llava_llama.py generate() -> HF:generation/utils.py greedy search with
  * a DynamicCache); these entry points are its per-token arithmetic: the projections at M = batch rows, attention of one query row
  * against the cache, the cache update, the greedy logits processors and the greedy argmax. */
-/* Skinny NT GEMM: Y[M,N] = X[M,K] W[N,K]^T (+ bias[N]) (+ residual[M,N]) for 1 <= M <= 32 (fp32 accumulation; bf16 Y, or fp32 Y with
- * out_f32 for the lm_head scores).  Weights are streamed once (16-byte nontemporal loads); the K range is split over workgroups when
+/* Skinny NT GEMM (gemv.hip, with its two quantised forms below): Y[M,N] = X[M,K] W[N,K]^T (+ bias[N]) (+ residual[M,N]) for
+ * 1 <= M <= 32 (fp32 accumulation; bf16 Y, or fp32 Y with out_f32 for the lm_head scores).  Weights are streamed once (16-byte nontemporal loads); the K range is split over workgroups when
  * N alone gives too few of them (rv_gemv_split(N, K) slices, combined in slice order by a second launch through `workspace`, which
  * needs split * M * N * 4 bytes when split > 1).  The reduction order is a function of (N, K): row r's result is bit-identical for
  * every M.  K % 8 == 0, ldx % 8 == 0, ldw % 8 == 0. */
@@ -359,7 +359,7 @@ int rv_gemv_w8_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp,
                     const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
                     int64_t ws_bytes, void* stream);
 /* Weight-only MXFP4 decoding (reference: load_pretrained_model(load_4bit=True), model/builder.py; here OCP Microscaling FP4, E2M1
- * elements with one E8M0 scale per block of 32 consecutive k, radvlm_amd/csrc/mxfp4.hip).  For each block of a bf16 row (the last
+ * elements with one E8M0 scale per block of 32 consecutive k).  For each block of a bf16 row (the last
  * block is shorter when K % 32 != 0; only its existing entries count):
  *     amax = max |w|    e = floor(log2(amax)) - 2 (0 for an all-zero block)    a = |w| / 2^e
  *     code = nearest of {0, .5, 1, 1.5, 2, 3, 4, 6} (codes 0..7), ties to the even code, a > 6 saturates to code 7
@@ -380,7 +380,7 @@ int64_t rv_w4_scale_row_bytes(int K);
 int rv_gemv_w4_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp, const void* scales, int64_t lds, void* Y, int64_t ldy,
                     const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
                     int64_t ws_bytes, void* stream);
-/* Decode attention (flash-decoding): for every sequence b and q head h, softmax(scale * q[b,h] K^T) V over the cached keys
+/* Decode attention (flash-decoding, decode.hip): for every sequence b and q head h, softmax(scale * q[b,h] K^T) V over the cached keys
  * [0, kv_len[b]) of kv head h / (H / Hkv), hd in {64, 128}, up to 8 q heads per kv head (GQA), fp32 softmax and accumulation.
  * cache: bf16 [B][L_max][ld_c] (sequence stride bs_c), K of kv head g at columns g*hd, V at v_off + g*hd.  q: [B, H*hd] rows (ld_q);
  * out: bf16 [B, H*hd] rows (ld_o).  Keys are split into chunks of `chunk` rows (a multiple of 16 for hd 128, of 32 for hd 64,

@@ -11,15 +11,6 @@
 
 namespace {
 
-#define ST ((hipStream_t)stream)
-
-DEVINL bf16x8 zero8() {
-    bf16x8 z;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = (bf16)0.f;
-    return z;
-}
-
 // ------------------------------------------------------------------------------------------------ beam decode attention
 // decode.hip's attn_decode_kernel with one change: key position j of query row b is read from cache row src(b, j) instead of row b,
 //   src(b, j) = j < prefix_len[b] ? prefix_row[b] : tail_src[b][j - prefix_len[b]],   clamped into [0, cache_rows).
@@ -315,8 +306,6 @@ __global__ __launch_bounds__(256) void beam_topk_merge_kernel(const float* __res
         pi = bi;
     }
 }
-
-inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace
 

@@ -38,8 +38,6 @@
 
 namespace {
 
-#define ST ((hipStream_t)stream)
-
 constexpr int CG_EW_U = 4;                   // elements per thread of the elementwise launch
 constexpr int CG_EW = 256 * CG_EW_U;         // columns per workgroup
 

@@ -23,6 +23,19 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 DEVINL float bf2f(bf16 x) { return (float)x; }
 DEVINL bf16 f2bf(float x) { return (bf16)x; }
 
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+
+DEVINL bf16x8 zero8() {
+    bf16x8 z;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z[i] = (bf16)0.f;
+    return z;
+}
+
+// weights are read once per token by exactly one CU: nontemporal (MI355X_MICROARCH "nt-weights")
+DEVINL bf16x8 ld_nt(const bf16* p) { return __builtin_nontemporal_load((const bf16x8*)p); }
+
 DEVINL f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 DEVINL int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
@@ -86,5 +99,9 @@ DEVINL unsigned rv_keep8(unsigned long long seed, unsigned long long e0, unsigne
     return m;
 }
 static inline unsigned rv_dropout_thr16(float p) { return (unsigned)((double)p * 65536.0 + 0.5); }
+
+// host side of every entry point: its `void* stream` argument as a HIP stream, and the block count of a grid
+#define ST ((hipStream_t)stream)
+static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
 static inline int rv_check_launch() { return hipGetLastError() == hipSuccess ? RV_OK : RV_ERR_LAUNCH; }

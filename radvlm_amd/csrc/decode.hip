@@ -1,7 +1,7 @@
-// Decode-time kernels for gfx950: the skinny NT GEMM of one generated token per sequence (M = batch, 1..32 rows), flash-decoding
-// attention of one query row per (sequence, q head) against a KV cache, the cache append and the row argmax of greedy decoding.
-// Reductions use a fixed order that depends on the problem shape only (N, K; a sequence's own kv_len) -- never on M, on other rows or
-// on timing -- and no atomics: a row's result is bit-identical whatever else shares its launch.
+// Decode-time kernels for gfx950: flash-decoding attention of one query row per (sequence, q head) against a KV cache, the cache
+// append, and the row argmax of greedy decoding with its logits processors.
+// Reductions use a fixed order that depends on the problem shape only (a sequence's own kv_len) -- never on other rows or on
+// timing -- and no float atomics: a row's result is bit-identical whatever else shares its launch.
 // Reference call sites are listed per entry point in include/radvlm_hip.h.
 #include "common.h"
 #include "radvlm_hip.h"
@@ -9,266 +9,6 @@
 #include <math.h>
 
 namespace {
-
-#define ST ((hipStream_t)stream)
-
-DEVINL bf16x8 zero8() {
-    bf16x8 z;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = (bf16)0.f;
-    return z;
-}
-
-// weights are read once per token by exactly one CU: nontemporal (MI355X_MICROARCH "nt-weights")
-DEVINL bf16x8 ld_nt(const bf16* p) { return __builtin_nontemporal_load((const bf16x8*)p); }
-
-// ------------------------------------------------------------------------------------------------ skinny NT GEMM
-// Y[M,N] = X[M,K] W[N,K]^T (+ bias) (+ residual), M <= 32.  Block: 4 waves, 64 output columns (four 16-column MFMA tiles); the K steps
-// (32 deep) of the block's K range are split into 4 contiguous runs, one per wave.  Weights go straight from HBM to VGPRs (dwordx4, nt),
-// U steps in flight per wave; the X rows (<= 64 KB, L2-resident) are loaded beside them.  MT = row tiles of 16 (rows >= M read zeros).
-// MFMA 16x16x32: A = X rows (lane l: row l&15, k 8*(l>>4)..+7), B = W rows (lane l: column l&15, same k) -> D[row][col].
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-constexpr int GV_COLS = 64;
-constexpr int GV_U = 4;
-
-// W8: the weight operand is int8 with one fp32 scale per row (rv_quantize_rows_w8_bf16's packed rows) and the bf16 fragment
-// bf16_rne(float(q) * s) is rebuilt in registers.  Same K steps per wave, same k-to-lane assignment per MFMA and every accumulator
-// takes its steps in ascending order, so the result is bit-identical to the bf16 kernel on the dequantised weight.  Packed row:
-// 64 bytes per PAIR of K steps; lane group kg's 16 bytes hold its 8 weights of step 2j, then its 8 of step 2j + 1 (one dwordx4 nt
-// load feeds two MFMA steps); a trailing odd step and ragged K are zero-padded in the packed row.
-// Step pairs in flight per wave.  2 (the bf16 kernel's four K steps per iteration at half its bytes) against 4 (its bytes in flight at twice
-// the K per iteration) were both built and timed per decoder shape on one box (DESIGN.md 5b "8-bit decoder weights"; the records of both
-// builds are in profiles/decode_ab_gemv.jsonl, mode w8, field `build`).  2 is the default: it needs fewer registers than the bf16 kernel
-// (96 / 128 against 112 / 146, VGPR + AGPR), 4 needs 144 / 192 and leaves 3 / 2 waves per SIMD.  build.sh out.so -DRV_GV8_P=4 rebuilds
-// the other.
-#ifndef RV_GV8_P
-#define RV_GV8_P 2
-#endif
-constexpr int GV8_P = RV_GV8_P;
-
-DEVINL bf16x8 dq8(unsigned lo, unsigned hi, float s) {
-    bf16x8 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        r[i] = f2bf((float)(int)(signed char)(lo >> (8 * i)) * s);
-        r[4 + i] = f2bf((float)(int)(signed char)(hi >> (8 * i)) * s);
-    }
-    return r;
-}
-
-// The scale pointer is a trailing parameter pack, empty for bf16.  It exists for one reason: the bf16 instantiation keeps the parent
-// kernel's exact parameter list, and with it the parent's device code instruction for instruction (an extra pointer, or the body moved
-// into an inlined helper, changed its register allocation).  W8 = "a scale was passed".
-DEVINL const float* gv_scale() { return nullptr; }
-DEVINL const float* gv_scale(const float* p) { return p; }
-
-template <int MT, typename... S>
-__global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W, long ldw, int M, int N,
-                                                   int K, int split, float* __restrict__ part, void* __restrict__ Y, long ldy,
-                                                   const bf16* __restrict__ bias, const bf16* __restrict__ R, long ldr, int out_f32,
-                                                   S... scale_arg) {
-    constexpr bool W8 = sizeof...(S) == 1;
-    __shared__ float red[4][MT * 16][GV_COLS];
-    const int lane = lane_id(), w = wave_id();
-    const int c = lane & 15, kg = lane >> 4;
-    const int n0 = blockIdx.x * GV_COLS;
-    const int sidx = blockIdx.y;
-    const int ks = (K + 31) / 32;
-    const int unit = sidx * 4 + w, units = split * 4;
-    const int s0 = (int)((long)ks * unit / units), s1 = (int)((long)ks * (unit + 1) / units);
-    const bf16* wp[4];
-    bool n_ok[4];
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-        const int n = n0 + ct * 16 + c;
-        n_ok[ct] = n < N;
-        if constexpr (W8)                                           // packed rows of ldw bytes, 16 bytes per lane group and step pair
-            wp[ct] = (const bf16*)((const char*)W + (long)(n_ok[ct] ? n : 0) * ldw + kg * 16);
-        else
-            wp[ct] = W + (long)(n_ok[ct] ? n : 0) * ldw + kg * 8;
-    }
-    const bf16* xp[MT];
-    bool m_ok[MT];
-#pragma unroll
-    for (int rt = 0; rt < MT; ++rt) {
-        const int m = rt * 16 + c;
-        m_ok[rt] = m < M;
-        xp[rt] = X + (long)(m_ok[rt] ? m : 0) * ldx + kg * 8;
-    }
-    f32x4 acc[MT][4];
-#pragma unroll
-    for (int rt = 0; rt < MT; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (W8) {
-        const float* __restrict__ wscale = gv_scale(scale_arg...);
-        float sc[4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) sc[ct] = n_ok[ct] ? wscale[n0 + ct * 16 + c] : 0.f;
-        int st = s0;
-        if ((st & 1) && st < s1) {                                  // the wave's range starts inside a pair: its second half alone
-            const int k = st * 32;
-            const bool kin = k + kg * 8 < K;
-            u32x2 wq[4];
-            bf16x8 xf[MT];
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct)
-                wq[ct] = (kin && n_ok[ct]) ? __builtin_nontemporal_load((const u32x2*)((const char*)wp[ct] + (long)(st >> 1) * 64 + 8))
-                                           : u32x2{0u, 0u};
-#pragma unroll
-            for (int rt = 0; rt < MT; ++rt) xf[rt] = (kin && m_ok[rt]) ? *(const bf16x8*)(xp[rt] + k) : zero8();
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                const bf16x8 wf = dq8(wq[ct].x, wq[ct].y, sc[ct]);
-#pragma unroll
-                for (int rt = 0; rt < MT; ++rt) acc[rt][ct] = mfma16(xf[rt], wf, acc[rt][ct]);
-            }
-            ++st;
-        }
-        for (; st < s1; st += 2 * GV8_P) {
-            u32x4 wq[GV8_P][4];
-            bf16x8 xf[2 * GV8_P][MT];
-#pragma unroll
-            for (int p = 0; p < GV8_P; ++p) {
-                const bool pin = st + 2 * p < s1;                   // a pair's 64 bytes exist whenever its first step does
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct)
-                    wq[p][ct] = (pin && n_ok[ct])
-                                    ? __builtin_nontemporal_load((const u32x4*)((const char*)wp[ct] + (long)((st >> 1) + p) * 64))
-                                    : u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int k = (st + 2 * p + h) * 32;
-                    const bool kin = (st + 2 * p + h) < s1 && k + kg * 8 < K;
-#pragma unroll
-                    for (int rt = 0; rt < MT; ++rt) xf[2 * p + h][rt] = (kin && m_ok[rt]) ? *(const bf16x8*)(xp[rt] + k) : zero8();
-                }
-            }
-#pragma unroll
-            for (int p = 0; p < GV8_P; ++p) {
-                const bool hin = st + 2 * p + 1 < s1;               // the pair's second step may belong to the next wave: zeros then
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    const bf16x8 w0 = dq8(wq[p][ct].x, wq[p][ct].y, sc[ct]);
-#pragma unroll
-                    for (int rt = 0; rt < MT; ++rt) acc[rt][ct] = mfma16(xf[2 * p][rt], w0, acc[rt][ct]);
-                }
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    const bf16x8 w1 = dq8(hin ? wq[p][ct].z : 0u, hin ? wq[p][ct].w : 0u, sc[ct]);
-#pragma unroll
-                    for (int rt = 0; rt < MT; ++rt) acc[rt][ct] = mfma16(xf[2 * p + 1][rt], w1, acc[rt][ct]);
-                }
-            }
-        }
-    } else {
-        for (int st = s0; st < s1; st += GV_U) {
-            bf16x8 wf[GV_U][4], xf[GV_U][MT];
-#pragma unroll
-            for (int u = 0; u < GV_U; ++u) {
-                const int k = (st + u) * 32;
-                const bool kin = (st + u) < s1 && k + kg * 8 < K;       // K % 8 == 0: a lane's 8 elements are all in or all out
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) wf[u][ct] = (kin && n_ok[ct]) ? ld_nt(wp[ct] + k) : zero8();
-#pragma unroll
-                for (int rt = 0; rt < MT; ++rt) xf[u][rt] = (kin && m_ok[rt]) ? *(const bf16x8*)(xp[rt] + k) : zero8();
-            }
-#pragma unroll
-            for (int u = 0; u < GV_U; ++u)
-#pragma unroll
-                for (int rt = 0; rt < MT; ++rt)
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = mfma16(xf[u][rt], wf[u][ct], acc[rt][ct]);
-        }
-    }
-#pragma unroll
-    for (int rt = 0; rt < MT; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[w][rt * 16 + 4 * kg + r][ct * 16 + c] = acc[rt][ct][r];
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < MT * 16 * GV_COLS; idx += 256) {
-        const int m = idx / GV_COLS, col = idx % GV_COLS, n = n0 + col;
-        if (m >= M || n >= N) continue;
-        float v = red[0][m][col];
-        v += red[1][m][col];
-        v += red[2][m][col];
-        v += red[3][m][col];
-        if (split > 1) {
-            part[((long)sidx * M + m) * N + n] = v;
-            continue;
-        }
-        if (bias) v += bf2f(bias[n]);
-        if (R) v += bf2f(R[(long)m * ldr + n]);
-        if (out_f32)
-            ((float*)Y)[(long)m * ldy + n] = v;
-        else
-            ((bf16*)Y)[(long)m * ldy + n] = f2bf(v);
-    }
-}
-
-// split-K combine: the K-slices summed in slice order, then bias / residual / store (same epilogue as above)
-__global__ void gemv_combine_kernel(const float* __restrict__ part, int split, int M, int N, void* __restrict__ Y, long ldy,
-                                    const bf16* __restrict__ bias, const bf16* __restrict__ R, long ldr, int out_f32) {
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= (long)M * N) return;
-    const int m = (int)(tid / N), n = (int)(tid % N);
-    float v = part[tid];
-    for (int s = 1; s < split; ++s) v += part[(long)s * M * N + tid];
-    if (bias) v += bf2f(bias[n]);
-    if (R) v += bf2f(R[(long)m * ldr + n]);
-    if (out_f32)
-        ((float*)Y)[(long)m * ldy + n] = v;
-    else
-        ((bf16*)Y)[(long)m * ldy + n] = f2bf(v);
-}
-
-// ------------------------------------------------------------------------------------------------ int8 row quantisation
-// One workgroup per weight row: absmax, s = amax / 127 (1 for a zero row), q = clamp(rint(w / s)), W <- bf16_rne(float(q) * s) in place,
-// q into the packed row gemv_kernel's int8 instantiation reads.  IEEE division and rint (round half to even); max is order-free, no
-// atomics.  The in-place write is race-free because (a) every load of pass 1 is consumed before the __syncthreads() after the wave
-// reduction, which all threads pass before any thread writes, and (b) in pass 2 the map g -> k is a bijection onto the row's 8-element
-// groups, so each group is read and written by one thread only (not the thread that read it in pass 1: the barrier orders those).
-__global__ __launch_bounds__(256) void quantize_rows_w8_kernel(bf16* __restrict__ W, long ldw, signed char* __restrict__ Q, long ldq,
-                                                               float* __restrict__ scale, int K) {
-    __shared__ float red[4];
-    bf16* row = W + (long)blockIdx.x * ldw;
-    signed char* qrow = Q + (long)blockIdx.x * ldq;
-    float amax = 0.f;
-    for (int k = threadIdx.x * 8; k < K; k += 256 * 8) {
-        const bf16x8 t = *(const bf16x8*)(row + k);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(bf2f(t[i])));
-    }
-    amax = wave_max(amax);
-    if (lane_id() == 0) red[wave_id()] = amax;
-    __syncthreads();
-    amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float s = amax > 0.f ? amax / 127.f : 1.f;
-    if (threadIdx.x == 0) scale[blockIdx.x] = s;
-    // packed group g (8 bytes): pair g / 8, lane group (g % 8) / 2, half g % 2 -> k = (2 * pair + half) * 32 + 8 * group
-    for (int g = threadIdx.x; g < ldq / 8; g += 256) {
-        const int k = (2 * (g >> 3) + (g & 1)) * 32 + ((g & 7) >> 1) * 8;
-        unsigned lo = 0u, hi = 0u;
-        if (k < K) {
-            const bf16x8 t = *(const bf16x8*)(row + k);
-            bf16x8 o;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float q = fminf(fmaxf(rintf(bf2f(t[i]) / s), -127.f), 127.f);
-                o[i] = f2bf(q * s);
-                const unsigned b = (unsigned)(int)q & 0xffu;
-                if (i < 4) lo |= b << (8 * i);
-                else hi |= b << (8 * (i - 4));
-            }
-            *(bf16x8*)(row + k) = o;
-        }
-        *(u32x2*)(qrow + (long)g * 8) = u32x2{lo, hi};
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ decode attention
 // Block (chunk c, kv head kh, sequence b): keys [c*chunk, min((c+1)*chunk, kv_len[b])) for the G = H / Hkv query heads of kv head kh,
@@ -659,75 +399,7 @@ __global__ __launch_bounds__(256) void logits_process_argmax_rows_kernel(
     }
 }
 
-inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
-
 }  // namespace
-
-extern "C" int rv_gemv_split(int N, int K) {
-    // K slices per column block: enough blocks for >= 2 per CU on 256 CUs, every wave keeps >= 2 of its 32-deep K steps.  A function of
-    // (N, K) only, so a row's reduction order never depends on M.
-    const long nb = (N + GV_COLS - 1) / GV_COLS, ks = (K + 31) / 32;
-    int split = 1;
-    while (nb * split < 512 && split < 16 && ks >= (long)split * 2 * 4 * 2) split *= 2;
-    return split;
-}
-
-extern "C" int rv_gemv_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, void* Y, int64_t ldy, const void* bias, const void* residual,
-                            int64_t ldr, int M, int N, int K, int out_f32, void* workspace, int64_t ws_bytes, void* stream) {
-    if (!X || !W || !Y || M < 1 || M > 32 || N <= 0 || K <= 0 || (K & 7) || (ldx & 7) || (ldw & 7) || ldx < K || ldw < K || ldy < N ||
-        (residual && ldr < N))
-        return RV_ERR_ARG;
-    const int split = rv_gemv_split(N, K);
-    float* part = nullptr;
-    if (split > 1) {
-        if (!workspace || ws_bytes < (int64_t)split * M * N * 4) return RV_ERR_ARG;
-        part = (float*)workspace;
-    }
-    const dim3 grid(cdiv(N, GV_COLS), split);
-    if (M <= 16)
-        hipLaunchKernelGGL(gemv_kernel<1>, grid, dim3(256), 0, ST, (const bf16*)X, (long)ldx, (const bf16*)W, (long)ldw, M, N, K, split, part, Y,
-                           (long)ldy, (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32);
-    else
-        hipLaunchKernelGGL(gemv_kernel<2>, grid, dim3(256), 0, ST, (const bf16*)X, (long)ldx, (const bf16*)W, (long)ldw, M, N, K, split, part, Y,
-                           (long)ldy, (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32);
-    if (split > 1)
-        hipLaunchKernelGGL(gemv_combine_kernel, dim3(cdiv((long)M * N, 256)), dim3(256), 0, ST, (const float*)part, split, M, N, Y, (long)ldy,
-                           (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32);
-    return rv_check_launch();
-}
-
-extern "C" int64_t rv_w8_row_bytes(int K) { return (((int64_t)K + 31) / 32 + 1) / 2 * 64; }
-
-extern "C" int rv_quantize_rows_w8_bf16(void* W, int64_t ldw, void* packed, int64_t ldp, float* scale, int N, int K, void* stream) {
-    if (!W || !packed || !scale || N <= 0 || K <= 0 || (K & 7) || (ldw & 7) || ldw < K || ldp != rv_w8_row_bytes(K)) return RV_ERR_ARG;
-    hipLaunchKernelGGL(quantize_rows_w8_kernel, dim3(N), dim3(256), 0, ST, (bf16*)W, (long)ldw, (signed char*)packed, (long)ldp, scale, K);
-    return rv_check_launch();
-}
-
-extern "C" int rv_gemv_w8_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp, const float* scale, void* Y, int64_t ldy,
-                               const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
-                               int64_t ws_bytes, void* stream) {
-    if (!X || !packed || !scale || !Y || M < 1 || M > 32 || N <= 0 || K <= 0 || (K & 7) || (ldx & 7) || ldx < K || ldp != rv_w8_row_bytes(K) ||
-        ldy < N || (residual && ldr < N))
-        return RV_ERR_ARG;
-    const int split = rv_gemv_split(N, K);
-    float* part = nullptr;
-    if (split > 1) {
-        if (!workspace || ws_bytes < (int64_t)split * M * N * 4) return RV_ERR_ARG;
-        part = (float*)workspace;
-    }
-    const dim3 grid(cdiv(N, GV_COLS), split);
-    if (M <= 16)
-        hipLaunchKernelGGL((gemv_kernel<1, const float*>), grid, dim3(256), 0, ST, (const bf16*)X, (long)ldx, (const bf16*)packed, (long)ldp, M, N, K,
-                           split, part, Y, (long)ldy, (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32, scale);
-    else
-        hipLaunchKernelGGL((gemv_kernel<2, const float*>), grid, dim3(256), 0, ST, (const bf16*)X, (long)ldx, (const bf16*)packed, (long)ldp, M, N, K,
-                           split, part, Y, (long)ldy, (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32, scale);
-    if (split > 1)
-        hipLaunchKernelGGL(gemv_combine_kernel, dim3(cdiv((long)M * N, 256)), dim3(256), 0, ST, (const float*)part, split, M, N, Y, (long)ldy,
-                           (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32);
-    return rv_check_launch();
-}
 
 extern "C" int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
                                    int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk,

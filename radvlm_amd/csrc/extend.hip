@@ -15,19 +15,10 @@
 
 namespace {
 
-#define ST ((hipStream_t)stream)
-
 constexpr int XT_KT = 64;        // keys per LDS stage
 constexpr int XT_GMAX = 8;       // query heads per kv head
 constexpr int XT_MAXRT = 2;      // 16-row MFMA row tiles per wave (row tiles per block <= 8, 4 waves)
 constexpr int XT_KPAD = 8;       // LDS row padding (bf16 elements)
-
-DEVINL bf16x8 xt_zero8() {
-    bf16x8 z;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = (bf16)0.f;
-    return z;
-}
 
 // query sub-tiles of 16 rows per block: enough (query, head) row tiles for the 4 waves, at most 8 (a function of G alone)
 DEVINL __host__ int xt_qs(int G) { return G >= 4 ? 1 : 4 / G; }
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(const bf16* __restrict
         const bool ok = rt < R && i < n_b;
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk)
-            qf[k][kk] = ok ? *(const bf16x8*)(q + (long)(q_beg + i) * ld_q + (kh * G + g) * HD + kk * 32 + lh * 8) : xt_zero8();
+            qf[k][kk] = ok ? *(const bf16x8*)(q + (long)(q_beg + i) * ld_q + (kh * G + g) * HD + kk * 32 + lh * 8) : zero8();
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) o[k][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -83,7 +74,7 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(const bf16* __restrict
         for (int e = threadIdx.x; e < XT_KT * HD / 8; e += 256) {
             const int key = e / (HD / 8), d8 = (e % (HD / 8)) * 8;
             const int j = kb + key;
-            bf16x8 kv = xt_zero8(), vv = xt_zero8();
+            bf16x8 kv = zero8(), vv = zero8();
             if (j < j1) {
                 kv = *(const bf16x8*)(cb + (long)j * ld_c + d8);
                 vv = *(const bf16x8*)(cb + (long)j * ld_c + v_off + d8);

@@ -12,10 +12,6 @@
 
 namespace {
 
-#define ST ((hipStream_t)stream)
-
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
 // ------------------------------------------------------------------------------------------------ quantising cache write
 // Block (x: 256-lane slice of a row, y: source row m).  A lane owns 8 consecutive values; the HD / 8 lanes of a group sit side by side in
 // one wave (HD / 8 divides 64), so the group maximum is an xor butterfly over them -- max is order-free and there is nothing to add.
@@ -241,8 +237,6 @@ __global__ __launch_bounds__(HD) void attn_decode_kv8_combine_kernel(const float
     }
     out[(long)b * ld_o + h * HD + dd] = f2bf(nc > 0 ? o / L : 0.f);
 }
-
-inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
 int kv_quantize_launch(const void* src, int64_t ld_src, void* q8, int64_t ld_q, float* s, int64_t ld_s, void* xhat, int64_t ld_x,
                        const int64_t* rows, const int32_t* pos, int L_max, int64_t cache_rows, int M, int Hkv, int hd, void* stream) {

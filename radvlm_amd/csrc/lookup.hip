@@ -10,15 +10,6 @@
 
 namespace {
 
-#define ST ((hipStream_t)stream)
-
-DEVINL bf16x8 zero8() {
-    bf16x8 z;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = (bf16)0.f;
-    return z;
-}
-
 // ------------------------------------------------------------------------------------------------ verify decode attention
 // decode.hip's attn_decode_kernel for a staircase of rows.  Block (chunk c, kv head kh, sequence b x row group): a "query" is one
 // (row, q head of kv head kh) pair, up to AV_NQ = 16 of them per block (rows per group = 16 / G: 16 rows of an MHA model, 2 of a G = 7

@@ -10,19 +10,10 @@
 
 namespace {
 
-#define ST ((hipStream_t)stream)
-
 constexpr int LM_COLS = 64;             // W columns per block: four 16-column MFMA tiles
 constexpr int LM_ROWS = 64;             // W rows per row tile: one 16-row MFMA tile per wave
 constexpr int LM_RED_LD = LM_COLS + 4;  // fp32 product tile row stride (floats)
 constexpr int LM_BLOCKS = 2048;         // target grid size (row tiles per block grow beyond it)
-
-DEVINL bf16x8 zero8() {
-    bf16x8 z;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = (bf16)0.f;
-    return z;
-}
 
 // Block: W columns [k0, k0 + 64) x row tiles [rt0, rt1) of 64 rows.  The A strip A[:, k0:k0+64] is staged once, transposed (at[col][j]),
 // so each lane's MFMA B operand (A[j = 8(l>>4) .. +7][col l&15]) is one 16-byte LDS read.  Per row tile: wave w computes rows 16w .. +15
@@ -100,8 +91,6 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(bf16* __restrict__ W, l
         }
     }
 }
-
-inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace
 

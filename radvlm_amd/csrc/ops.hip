@@ -787,8 +787,6 @@ inline bool fits_one_dispatch(long work_items) { return work_items < (1L << 32);
 
 }  // namespace
 
-#define ST ((hipStream_t)stream)
-
 extern "C" const char* rv_version(void) { return "radvlm_hip 0.1 gfx950"; }
 
 extern "C" int rv_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int rows, int d, float eps, void* stream) {

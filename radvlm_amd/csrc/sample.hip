@@ -31,8 +31,6 @@
 
 #include <math.h>
 
-#define ST ((hipStream_t)stream)
-
 typedef unsigned long long u64;
 
 namespace {

@@ -838,19 +838,20 @@ class LlavaEngine:
     # The same switch for the MXFP4 copy (quantize_decoder_("mxfp4")): the A/B arm of tools/decode_bench.py --w4.
     w4_decode = True
 
-    def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16, w8=None, skinny=False):
-        """skinny: the skinny kernel whatever the row count (<= ops.GEMV_MAX_M) and the weight's height -- verify_step, whose rows must
+    def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16, wq=None, skinny=False):
+        """wq: the weight's quantised copy (packed, scales) from _layer_wq, int8 or MXFP4 by its dtype, or None.
+        skinny: the skinny kernel whatever the row count (<= ops.GEMV_MAX_M) and the weight's height -- verify_step, whose rows must
         carry the bits of the one-row decode step, which always takes that kernel."""
         max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
-        if skinny or x.shape[0] <= min(max_m, ops.GEMV_MAX_M):
-            if w8 is not None:                                      # the layer's quantised copy: (packed, scale), int8 or MXFP4 by its dtype
-                if w8[0].dtype == torch.uint8:
-                    if self._w4_cell_takes_bf16(w.shape[0], w.shape[1], x.shape[0]):
-                        return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
-                    return ops.gemv_w4(x, w8[0], w8[1], w.shape[1], bias=bias, residual=residual, out_dtype=out_dtype)
-                return ops.gemv_w8(x, w8[0], w8[1], w.shape[1], bias=bias, residual=residual, out_dtype=out_dtype)
+        if not skinny and x.shape[0] > min(max_m, ops.GEMV_MAX_M):
+            return ops.gemm_nt(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
+        if wq is None:
             return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
-        return ops.gemm_nt(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
+        if wq[0].dtype != torch.uint8:
+            return ops.gemv_w8(x, wq[0], wq[1], w.shape[1], bias=bias, residual=residual, out_dtype=out_dtype)
+        if self._w4_cell_takes_bf16(w.shape[0], w.shape[1], x.shape[0]):
+            return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
+        return ops.gemv_w4(x, wq[0], wq[1], w.shape[1], bias=bias, residual=residual, out_dtype=out_dtype)
 
     # (N, K) -> the measured row counts at which rv_gemv_w4_bf16 did NOT beat rv_gemv_bf16 on the same weight by more than the bf16 arm's
     # own spread (max - min of its 20 samples); those launches go back to the bf16 kernel, which gives the same bits.  A launch of M rows
@@ -864,7 +865,7 @@ class LlavaEngine:
         cells = self.W4_BF16_CELLS.get((N, K))
         return bool(cells) and next(m for m in (1, 4, 8, 16, 32) if M <= m) in cells
 
-    def _layer_w8(self, i):
+    def _layer_wq(self, i):
         """The quantised copies the decode GEMMs of layer i read: the int8 pairs, the MXFP4 pairs, or none (bf16 on the same weights)."""
         if self.w4 is not None:
             return self.w4[i] if self.w4_decode else {}
@@ -1078,9 +1079,9 @@ class LlavaEngine:
         cs = self.rope_table(cache.L_max)
         x = ops.gather_rows(tok.contiguous(), d, self.W("model.embed_tokens.weight"))
         for i in range(L):
-            lv, q8 = self._layer_views(i), self._layer_w8(i)
+            lv, wq = self._layer_views(i), self._layer_wq(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), w8=q8.get("qkv"))
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
             if kv8 and cache.scales is not None:
                 kvq = (cache.layers[i], cache.scales[i])
@@ -1096,10 +1097,10 @@ class LlavaEngine:
                 ops.kv_append(qkv[:, d:], cache.layers[i], pos)
                 attn = ops.attn_decode_beam(qkv[:, :d], cache.layers[i], kv_len, beams.prefix_row, beams.prefix_len, beams.tail_src, H, Hkv,
                                             hd, kvd, tail_cols=beams.tail_cols, chunk=cache.chunk)
-            x_mid = self._decode_linear(attn, lv["o"], residual=x, w8=q8.get("o"))
+            x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], w8=q8.get("gu")), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid, w8=q8.get("down"))
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu")), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"))
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
         cache.lens += 1
@@ -1160,9 +1161,9 @@ class LlavaEngine:
         cs = self.rope_table(L_max)
         x = ops.gather_rows(tok.contiguous().view(-1), d, self.W("model.embed_tokens.weight"))
         for i in range(L):
-            lv, q8 = self._layer_views(i), self._layer_w8(i)
+            lv, wq = self._layer_views(i), self._layer_wq(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), w8=q8.get("qkv"), skinny=True)
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"), skinny=True)
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
             kv = cache.layers[i]
             kv.view(L_max, 2 * kvd).index_copy_(0, slots, qkv[:, d:])
@@ -1170,10 +1171,10 @@ class LlavaEngine:
                 attn = ops.attn_decode_beam(qkv[:, :d], kv, kv_len, zero, plen, None, H, Hkv, hd, kvd, chunk=cache.chunk)
             else:
                 attn = ops.attn_decode_verify(qkv[:, :d], kv, kv0, R, H, Hkv, hd, kvd, chunk=cache.chunk)
-            x_mid = self._decode_linear(attn, lv["o"], residual=x, w8=q8.get("o"), skinny=True)
+            x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"), skinny=True)
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], w8=q8.get("gu"), skinny=True), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid, w8=q8.get("down"), skinny=True)
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu"), skinny=True), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"), skinny=True)
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32, skinny=True)
         return logits[:, :self.vocab]
@@ -1232,17 +1233,17 @@ class LlavaEngine:
         cs = self.rope_table(L_max)
         x = ops.gather_rows(self._dev(src), d, self.W("model.embed_tokens.weight"), table)
         for i in range(L):
-            lv, q8 = self._layer_views(i), self._layer_w8(i)
+            lv, wq = self._layer_views(i), self._layer_wq(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), w8=q8.get("qkv"))
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
             kv = cache.layers[i]
             kv.view(B * L_max, 2 * kvd).index_copy_(0, slots, qkv[:, d:])
             attn = ops.attn_extend(qkv[:, :d], kv, cu_d, r_d, H, Hkv, hd, kvd, int(n.max()))
-            x_mid = self._decode_linear(attn, lv["o"], residual=x, w8=q8.get("o"))
+            x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], w8=q8.get("gu")), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid, w8=q8.get("down"))
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu")), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"))
         last = self._dev((cu_q[1:] - 1).astype(np.int32))
         hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)

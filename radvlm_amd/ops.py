@@ -554,13 +554,12 @@ def gemv_split(N, K):
     return int(lib.load().rv_gemv_split(int(N), int(K)))
 
 
-def gemv(x, w, out=None, bias=None, residual=None, out_dtype=BF16, workspace=None):
-    """out[M,N] = x[M,K] @ w[N,K]^T (+ bias) (+ residual) for M <= 32 rows (decode): rv_gemv_bf16, weights streamed once.
-    Row r of the result is bit-identical for every M."""
-    _chk(x), _chk(w)
-    M, K = x.shape
-    N = w.shape[0]
-    assert 1 <= M <= GEMV_MAX_M and w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1
+def _gemv_args(x, N, K, out, bias, residual, out_dtype, workspace):
+    """What gemv, gemv_w8 and gemv_w4 share once each has checked its own [N, K] weight operand: the checks of x, out (allocated when
+    None), bias and residual, and the default workspace.  Returns (M, out, ldr, workspace, its bytes)."""
+    _chk(x)
+    M, Kx = x.shape
+    assert 1 <= M <= GEMV_MAX_M and Kx == K and x.stride(1) == 1
     if out is None:
         out = torch.empty(M, N, dtype=out_dtype, device=x.device)
     assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype in (BF16, torch.float32)
@@ -574,9 +573,28 @@ def gemv(x, w, out=None, bias=None, residual=None, out_dtype=BF16, workspace=Non
         ldr = residual.stride(0)
     if workspace is None:
         workspace = default_workspace(x.device)
+    return M, out, ldr, workspace, workspace.numel() * workspace.element_size()
+
+
+def gemv(x, w, out=None, bias=None, residual=None, out_dtype=BF16, workspace=None):
+    """out[M,N] = x[M,K] @ w[N,K]^T (+ bias) (+ residual) for M <= 32 rows (decode): rv_gemv_bf16, weights streamed once.
+    Row r of the result is bit-identical for every M."""
+    _chk(w)
+    N, K = w.shape
+    assert w.stride(1) == 1
+    M, out, ldr, ws, ws_bytes = _gemv_args(x, N, K, out, bias, residual, out_dtype, workspace)
     lib.call("rv_gemv_bf16", x, x.stride(0), w, w.stride(0), out, out.stride(0), bias, residual, ldr, M, N, K,
-             int(out.dtype == torch.float32), workspace, workspace.numel() * workspace.element_size())
+             int(out.dtype == torch.float32), ws, ws_bytes)
     return out
+
+
+def _quantize_rows_args(w):
+    """The input checks quantize_rows_w8 and quantize_rows_mxfp4 share; returns (N, K)."""
+    _chk(w)
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    assert K % 8 == 0 and w.stride(0) % 8 == 0
+    return N, K
 
 
 def w8_row_bytes(K):
@@ -589,10 +607,7 @@ def quantize_rows_w8(w):
     q = clamp(rint(w / s), -127, 127), w <- bf16(float(q) * s).  w may be a row-major view with a row stride (the fused q|k|v and
     gate|up views).  Returns (packed int8 [N, w8_row_bytes(K)] in gemv_w8's private layout, scale fp32 [N]).  Quantising the result
     again rounds again: call it once per weight.  Non-finite weights are outside the contract."""
-    _chk(w)
-    assert w.dim() == 2 and w.stride(1) == 1
-    N, K = w.shape
-    assert K % 8 == 0 and w.stride(0) % 8 == 0
+    N, K = _quantize_rows_args(w)
     packed = torch.empty(N, w8_row_bytes(K), dtype=torch.int8, device=w.device)
     scale = torch.empty(N, dtype=torch.float32, device=w.device)
     lib.call("rv_quantize_rows_w8_bf16", w, w.stride(0), packed, packed.stride(0), scale, N, K)
@@ -602,26 +617,12 @@ def quantize_rows_w8(w):
 def gemv_w8(x, packed, scale, K, out=None, bias=None, residual=None, out_dtype=BF16, workspace=None):
     """gemv() with the weight given as quantize_rows_w8's (packed, scale) of a [N, K] weight: rv_gemv_w8_bf16, half the weight bytes,
     bit-identical to gemv(x, w) on the dequantised weight quantize_rows_w8 left in place."""
-    _chk(x), _chk(packed, torch.int8), _chk(scale, torch.float32)
-    M = x.shape[0]
+    _chk(packed, torch.int8), _chk(scale, torch.float32)
     N = packed.shape[0]
-    assert 1 <= M <= GEMV_MAX_M and x.shape[1] == K and x.stride(1) == 1
     assert packed.is_contiguous() and packed.shape[1] == w8_row_bytes(K) and scale.numel() == N and scale.is_contiguous()
-    if out is None:
-        out = torch.empty(M, N, dtype=out_dtype, device=x.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype in (BF16, torch.float32)
-    if bias is not None:
-        _chk(bias)
-        assert bias.numel() == N and bias.is_contiguous()
-    ldr = 0
-    if residual is not None:
-        _chk(residual)
-        assert residual.shape == (M, N) and residual.stride(1) == 1
-        ldr = residual.stride(0)
-    if workspace is None:
-        workspace = default_workspace(x.device)
+    M, out, ldr, ws, ws_bytes = _gemv_args(x, N, K, out, bias, residual, out_dtype, workspace)
     lib.call("rv_gemv_w8_bf16", x, x.stride(0), packed, packed.stride(0), scale, out, out.stride(0), bias, residual, ldr, M, N, K,
-             int(out.dtype == torch.float32), workspace, workspace.numel() * workspace.element_size())
+             int(out.dtype == torch.float32), ws, ws_bytes)
     return out
 
 
@@ -642,10 +643,7 @@ def quantize_rows_mxfp4(w):
     Returns (packed uint8 [N, w4_row_bytes(K)] in gemv_w4's private layout, scales uint8 [N, w4_scale_row_bytes(K)]).  Lossy (about
     12 % relative Frobenius error on Gaussian rows).  Block maxima outside [2^-120, 2^120] and non-finite weights are outside the
     contract."""
-    _chk(w)
-    assert w.dim() == 2 and w.stride(1) == 1
-    N, K = w.shape
-    assert K % 8 == 0 and w.stride(0) % 8 == 0
+    N, K = _quantize_rows_args(w)
     packed = torch.empty(N, w4_row_bytes(K), dtype=torch.uint8, device=w.device)
     scales = torch.empty(N, w4_scale_row_bytes(K), dtype=torch.uint8, device=w.device)
     lib.call("rv_quantize_rows_mxfp4_bf16", w, w.stride(0), packed, packed.stride(0), scales, scales.stride(0), N, K)
@@ -655,27 +653,13 @@ def quantize_rows_mxfp4(w):
 def gemv_w4(x, packed, scales, K, out=None, bias=None, residual=None, out_dtype=BF16, workspace=None):
     """gemv() with the weight given as quantize_rows_mxfp4's (packed, scales) of a [N, K] weight: rv_gemv_w4_bf16, 0.27x the weight
     bytes, bit-identical to gemv(x, w) on the quantised weight quantize_rows_mxfp4 left in place."""
-    _chk(x), _chk(packed, torch.uint8), _chk(scales, torch.uint8)
-    M = x.shape[0]
+    _chk(packed, torch.uint8), _chk(scales, torch.uint8)
     N = packed.shape[0]
-    assert 1 <= M <= GEMV_MAX_M and x.shape[1] == K and x.stride(1) == 1
     assert packed.is_contiguous() and packed.shape[1] == w4_row_bytes(K)
     assert scales.is_contiguous() and scales.shape == (N, w4_scale_row_bytes(K))
-    if out is None:
-        out = torch.empty(M, N, dtype=out_dtype, device=x.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype in (BF16, torch.float32)
-    if bias is not None:
-        _chk(bias)
-        assert bias.numel() == N and bias.is_contiguous()
-    ldr = 0
-    if residual is not None:
-        _chk(residual)
-        assert residual.shape == (M, N) and residual.stride(1) == 1
-        ldr = residual.stride(0)
-    if workspace is None:
-        workspace = default_workspace(x.device)
+    M, out, ldr, ws, ws_bytes = _gemv_args(x, N, K, out, bias, residual, out_dtype, workspace)
     lib.call("rv_gemv_w4_bf16", x, x.stride(0), packed, packed.stride(0), scales, scales.stride(0), out, out.stride(0), bias, residual, ldr,
-             M, N, K, int(out.dtype == torch.float32), workspace, workspace.numel() * workspace.element_size())
+             M, N, K, int(out.dtype == torch.float32), ws, ws_bytes)
     return out
 
 

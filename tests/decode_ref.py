@@ -1,4 +1,4 @@
-"""CPU references and input builders for the decode kernels (radvlm_amd/csrc/decode.hip, extend.hip).  Plain torch on the CPU, float64
+"""CPU references and input builders for the decode kernels (radvlm_amd/csrc/gemv.hip, decode.hip, extend.hip).  Plain torch on the CPU, float64
 unless a dtype is asked for; nothing here touches a GPU, so tests/test_decode_ref_host.py can show without one that the constructions
 meet the exact conditions tests/test_decode_edges_gpu.py asserts of the kernels."""
 import math

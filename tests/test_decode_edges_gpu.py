@@ -1,4 +1,4 @@
-"""GPU tests of the decode kernels at the shapes, strides and key counts where they can go wrong (radvlm_amd/csrc/decode.hip, extend.hip):
+"""GPU tests of the decode kernels at the shapes, strides and key counts where they can go wrong (radvlm_amd/csrc/gemv.hip, decode.hip, extend.hip):
 ragged K / N / M of the skinny GEMM and its int8 twin with exact integer products, needle rows that pin every key position of the
 decode attention, leading dimensions other than the packed ones with guard columns, the cache append's skips and widths, the argmax's
 NaN / inf / signed-zero conventions, and the argument checks.  References and input builders: tests/decode_ref.py (its own CPU checks:
@@ -530,8 +530,9 @@ def test_kv_append_refuses_bad_arguments():
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("kernel", ["bf16", "w8"])
+@pytest.mark.parametrize("kernel", ["bf16", "w8", "w4"])
 def test_gemv_refuses_bad_arguments(kernel):
+    """The three entry points share one argument check (gemv.hip's gemv_launch): each refuses the same six bad argument sets."""
     ops = _ops()
     N, K = 64, 2056
     split = ops.gemv_split(N, K)
@@ -539,19 +540,26 @@ def test_gemv_refuses_bad_arguments(kernel):
     x = torch.zeros(40, K + 64, dtype=BF16, device="cuda")
     w = torch.ones(N, K, dtype=BF16, device="cuda")
     y = torch.zeros(40, N + 64, dtype=BF16, device="cuda")
+    res = torch.zeros(40, N + 64, dtype=BF16, device="cuda")
     ws = torch.zeros(split * 40 * N, dtype=torch.float32, device="cuda")
     pk, sc = ops.quantize_rows_w8(w.clone())
+    p4, s4 = ops.quantize_rows_mxfp4(w.clone())
 
-    def run(M=32, K_=K, ldx=K, ldy=N, ws_bytes=None):
+    def run(M=32, K_=K, ldx=K, ldy=N, ws_bytes=None, ldr=None):
         ws_bytes = ops.gemv_split(N, K_) * M * N * 4 if ws_bytes is None else ws_bytes
+        r, ldr = (None, 0) if ldr is None else (res, ldr)
         if kernel == "bf16":
-            _call("rv_gemv_bf16", x, ldx, w, K, y, ldy, None, None, 0, M, N, K_, 0, ws, ws_bytes)
+            _call("rv_gemv_bf16", x, ldx, w, K, y, ldy, None, r, ldr, M, N, K_, 0, ws, ws_bytes)
+        elif kernel == "w8":
+            _call("rv_gemv_w8_bf16", x, ldx, pk, ops.w8_row_bytes(K_), sc, y, ldy, None, r, ldr, M, N, K_, 0, ws, ws_bytes)
         else:
-            _call("rv_gemv_w8_bf16", x, ldx, pk, ops.w8_row_bytes(K_), sc, y, ldy, None, None, 0, M, N, K_, 0, ws, ws_bytes)
+            _call("rv_gemv_w4_bf16", x, ldx, p4, ops.w4_row_bytes(K_), s4, ops.w4_scale_row_bytes(K_), y, ldy, None, r, ldr, M, N, K_, 0, ws,
+                  ws_bytes)
 
     from radvlm_amd.lib import RadvlmHipError
     run()                                                              # accepted, the workspace exactly large enough
-    for kw in (dict(M=33), dict(K_=12), dict(ldx=K - 8), dict(ldy=N - 1), dict(ws_bytes=split * 32 * N * 4 - 4)):
+    run(ldr=N)                                                         # accepted, a residual at the smallest row stride
+    for kw in (dict(M=33), dict(K_=12), dict(ldx=K - 8), dict(ldy=N - 1), dict(ws_bytes=split * 32 * N * 4 - 4), dict(ldr=N - 1)):
         with pytest.raises(RadvlmHipError):
             run(**kw)
     torch.cuda.synchronize()

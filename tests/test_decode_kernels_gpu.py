@@ -1,4 +1,4 @@
-"""GPU tests of the decode kernels (radvlm_amd/csrc/decode.hip): the skinny GEMM, decode attention, the cache append and the row argmax,
+"""GPU tests of the decode kernels (radvlm_amd/csrc/gemv.hip, decode.hip): the skinny GEMM, decode attention, the cache append and the row argmax,
 each against a CPU fp32 reference or the kernel the prefill path uses."""
 import math
 

@@ -94,6 +94,8 @@ def test_entry_points_declared_and_bound():
         decl = re.search(r"int " + name + r"\(([^;]*)\);", hdr).group(1)
         assert len(decl.split(",")) == len(lib._SIGS[name])
     assert "rv_w8_row_bytes" in declared and "rv_w8_row_bytes" in lib.EXPORTED_SYMBOLS
+    build = open(os.path.join(ROOT, "radvlm_amd", "csrc", "build.sh")).read()
+    assert "gemv" in build.split('SRCS="')[1].split('"')[0].split() and "$OBJ/gemv.res" in build
     so = os.path.join(ROOT, "radvlm_amd", "libradvlm_hip.so")
     if os.path.exists(so):
         l = lib.load()
