@@ -449,10 +449,13 @@ __global__ __launch_bounds__(TPB) void cross_entropy_kernel(const bf16* logits, 
 #pragma unroll
         for (int j = 1; j < 8; ++j) vm = fmaxf(vm, v[j]);
         const float mn = fmaxf(m, vm);
+        // Nothing finite seen yet (masked logits: a run of -inf that is this thread's first vector): shift by 0, not by -inf, so that
+        // every term is exp(-inf) = 0 and not exp(-inf - -inf) = NaN, which s would keep once m turns finite.
+        const float sh = mn == -INFINITY ? 0.f : mn;
         float a = 0.f;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a += __expf(v[j] - mn);
-        s = s * __expf(m - mn) + a;
+        for (int j = 0; j < 8; ++j) a += __expf(v[j] - sh);
+        s = s * __expf(m - sh) + a;
         m = mn;
     }
     // block combine of (m, s)
@@ -796,19 +799,19 @@ extern "C" int rv_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd
 }
 extern "C" int rv_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx, int dx_add,
                               float* dw_partial, int nblk, int rows, int d, void* stream) {
-    if (!dy || !x || !w || !rstd || !dx || !dw_partial || nblk <= 0 || rows <= 0 || (d & 7) || d > 8192) return RV_ERR_ARG;
+    if (!dy || !x || !w || !rstd || !dx || !dw_partial || nblk <= 0 || rows <= 0 || d <= 0 || (d & 7) || d > 8192) return RV_ERR_ARG;
     hipLaunchKernelGGL(rmsnorm_bwd_kernel, dim3(nblk), dim3(TPB), 0, ST, (const bf16*)dy, (const bf16*)x, (const bf16*)w, rstd,
                        (bf16*)dx, dx_add, dw_partial, rows, d);
     return rv_check_launch();
 }
 extern "C" int rv_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* stats, int rows, int d, float eps, void* stream) {
-    if (!x || !w || !b || !y || rows <= 0 || (d & 7) || d > 8192) return RV_ERR_ARG;
+    if (!x || !w || !b || !y || rows <= 0 || d <= 0 || (d & 7) || d > 8192) return RV_ERR_ARG;
     hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(rows), dim3(TPB), 0, ST, (const bf16*)x, (const bf16*)w, (const bf16*)b, (bf16*)y, stats, d, eps);
     return rv_check_launch();
 }
 extern "C" int rv_layernorm_bwd(const void* dy, const void* x, const void* w, const float* stats, void* dx, int dx_add,
                                 float* partial, int nblk, int rows, int d, void* stream) {
-    if (!dy || !x || !w || !stats || !dx || !partial || nblk <= 0 || rows <= 0 || (d & 7) || d > 8192) return RV_ERR_ARG;
+    if (!dy || !x || !w || !stats || !dx || !partial || nblk <= 0 || rows <= 0 || d <= 0 || (d & 7) || d > 8192) return RV_ERR_ARG;
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nblk), dim3(TPB), 0, ST, (const bf16*)dy, (const bf16*)x, (const bf16*)w, stats,
                        (bf16*)dx, dx_add, partial, rows, d);
     return rv_check_launch();
