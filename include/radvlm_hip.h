@@ -573,6 +573,27 @@ int rv_attn_decode_kv8_bf16(const void* q, int64_t ld_q, const void* cache_q8, i
                             int64_t ld_s, int64_t bs_s, int vs_off, const int32_t* kv_len, int L_max, void* out, int64_t ld_o, void* part,
                             int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk, float scale, void* stream);
 
+/* ---- shared prompt prefixes (generate_batch(share_prefix=True), radvlm_amd/csrc/prefix.hip) ------------------------------------------
+ * The reference evaluates a split one request at a time (HF generate() per sample), so each question about a radiograph pays for the
+ * image's keys again; HF has no counterpart.  Here the requests of one generate_batch() call that begin with the same prompt records
+ * keep bit-equal K|V at those positions of their own cache rows (copied, LlavaEngine / BatchScheduler), and this entry reads them once. */
+/* rv_attn_decode_bf16 for rows grouped in tiles.  c0: int32 [B] (device), row b's shared chunk count; tile: int32 [B][16] (device),
+ * tile[b][0] == b when row b leads a tile, whose rows are then tile[b][0 .. 16 / (H / Hkv)) up to the first -1; any other row has
+ * tile[b][0] != b.  Workgroup (chunk c, kv head, row b) with c >= c0[b] is rv_attn_decode_bf16's.  With c < c0[b] it returns at once
+ * unless b leads its tile; a leading workgroup loads and converts the chunk's K and V fragments once, from row b, and uses each for up
+ * to 16 (row, q head) queries of its tile, writing every row's partial in the plain `part` layout; one combine per row with the row's
+ * own kv_len.  CONTRACT: when every row of a tile has c0 equal to its leader's, holds at least c0 * chunk keys and holds K|V equal to
+ * the leader's at positions below c0 * chunk, every row of out is BIT-IDENTICAL to rv_attn_decode_bf16 on the same cache at the same
+ * `chunk` (key-to-lane assignment, each lane's summation order, the shuffle trees, the wave 0..3 merge and the combine are that
+ * kernel's; a key a row may not see is skipped, never multiplied by zero).  c0 all zero: rv_attn_decode_bf16 on every row.  The table
+ * is not trusted for bounds: entries outside [0, B) end a tile's list, and a query never sees a position at or past its row's kv_len
+ * or the leader's, so rows past kv_len may hold anything (NaN included); a table that breaks the contract gives wrong values in the
+ * rows it names, never an access outside q / cache / part.  Limits and refusals are rv_attn_decode_bf16's (hd 64 or 128, H / Hkv <= 8,
+ * chunk <= 512 and a multiple of 16 (hd 128) or 32 (hd 64), part of B * H * ceil(L_max / chunk) * (hd + 2) floats).  No atomics. */
+int rv_attn_decode_shared_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
+                               const int32_t* c0, const int32_t* tile, int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes,
+                               int B, int H, int Hkv, int hd, int chunk, float scale, void* stream);
+
 /* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
  * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any
  * grid and any placement of W.  W: bf16 rows of ldw elements (a row slice of a fused q|k|v or gate|up store is fine), 16-byte aligned,

@@ -1050,7 +1050,7 @@ class LlavaEngine:
         cache.lens[seq] = lens
         return cache, logits[:, :self.vocab]
 
-    def decode_step(self, cache, tokens, beams=None):
+    def decode_step(self, cache, tokens, beams=None, shared=None):
         """One generated token per sequence: tokens [B] (int, host or device) at position cache.lens[b] -> fp32 logits [B, vocab].
         Per layer: RMSNorm, q|k|v projection, RoPE at the token's position, cache append, decode attention over the sequence's cached
         keys, o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual; then the final norm and the lm_head (fp32 scores).
@@ -1061,8 +1061,21 @@ class LlavaEngine:
         nothing in the cache moves.  Without it every call is what it was.
         An int8-dtype cache (KVCache.dtype): the K|V row is quantised by the append (ops.kv_append_q8) and attention reads the int8
         rows (ops.attn_decode_kv8), bit-identical to this step on a bf16 cache holding the dequantised values (kv8_decode False runs
-        exactly that).  beams= with such a cache raises NotImplementedError."""
+        exactly that).  beams= with such a cache raises NotImplementedError.
+        shared (generate_batch(share_prefix=True)): a tile table from shared_plan() -- .c0 / .tile, device int32 [B] / [B, 16], uploaded
+        when the active set changes, not per step.  Rows of a tile hold equal K|V at their first c0 * chunk positions, and attention
+        reads those chunks once per tile (rv_attn_decode_shared_bf16), bit-identical to the plain kernel on the same cache;
+        shared_route decides whether it does.  Not combined with beams= or an int8 cache (NotImplementedError).  With shared=None
+        every call is what it was."""
         self._check_generation()
+        if shared is not None:
+            if beams is not None:
+                raise NotImplementedError("decode_step(shared=...) with beams=: one row lookup per call")
+            self._refuse_int8(cache, "decode_step(shared=...)")
+            if shared.c0.numel() != cache.B:
+                raise ValueError(f"the tile table has {shared.c0.numel()} rows, the cache {cache.B}")
+            if not self._use_shared(shared, cache):
+                shared = None
         l = self.l
         d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
         hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
@@ -1090,6 +1103,9 @@ class LlavaEngine:
             elif kv8:       # the reference arm: the dequantised values as bf16, read by the bf16 kernel
                 ops.kv_append_q8(qkv[:, d:], pos, Hkv, hd, xhat=cache.layers[i])
                 attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            elif shared is not None:
+                ops.kv_append(qkv[:, d:], cache.layers[i], pos)
+                attn = ops.attn_decode_shared(qkv[:, :d], cache.layers[i], kv_len, shared.c0, shared.tile, H, Hkv, hd, kvd, chunk=cache.chunk)
             elif beams is None:
                 ops.kv_append(qkv[:, d:], cache.layers[i], pos)
                 attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
@@ -1105,6 +1121,43 @@ class LlavaEngine:
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
         cache.lens += 1
         return logits[:, :self.vocab]
+
+    # decode_step(shared=)'s attention.  rv_attn_decode_shared_bf16 reads a tile's shared chunks once for its 16 / G rows and gives
+    # rv_attn_decode_bf16's bits, so the route changes time only.  shared_route: None = the measured table below; "shared" / "plain"
+    # force one arm ("plain" ignores the table and runs ops.attn_decode: the reference arm and the benchmark's A/B).  Same-box A/B on
+    # the two 7B head shapes at B = 32, rows in groups of 2, 4, 8, 16, 32 holding one prefix of 704 or 7,603 keys (each row 40 keys
+    # of its own), cold cache, interleaved, median of 20 (tools/decode_bench.py --shared-shapes, profiles/decode_bench.jsonl mode
+    # shared_kernel_ab, DESIGN.md 5b "Shared prompt prefixes"); shared / plain:
+    #   one q head per kv head (llava15, 16 rows per tile)   group  2     4     8     16    32
+    #                                          704 keys            1.00  0.80  0.75  0.66  0.67     (plain 145 us, spread 2.5 us)
+    #                                        7,603 keys            0.87  0.60  0.47  0.41  0.41     (plain 1,146 us, spread 6 - 10 us)
+    #   7 q heads per kv head (Qwen2, 2 rows per tile): 1.45 at 704 keys (47 -> 68 us) and 1.21 at 7,603 (318 -> 385 us), every group.
+    # The shared arm is taken only where it was faster by more than the plain arm's own spread (p90 - p10): every llava15 cell but
+    # (group 2, 704 keys), which is a tie.  Between two measured cells the nearer one in log distance decides: groups 2 | 4 -> 3 rows
+    # in the launch's largest tile, keys 704 | 7,603 -> 2,313 shared keys.  Qwen2 loses in every cell (two rows per workgroup do not
+    # pay for the staircase's 16-query structure, as in verify_route) and takes the plain kernel; group sizes that were not measured
+    # (G = 2 .. 6, 8) take it too until a measurement says otherwise.  Those requests still share the prompt pass.
+    shared_route = None
+
+    @property
+    def shared_rows_per_tile(self):
+        """Rows of one tile of rv_attn_decode_shared_bf16: 16 (row, q head) queries per workgroup over G = heads / kv heads."""
+        return ops.SHARED_TILE_COLS // (self.l["heads"] // self.Hkv)
+
+    def shared_plan(self, c0, tile):
+        """The device copy of a tile table (generation.shared_tiles), validated first (ops.shared_tiles_upload): decode_step(shared=)."""
+        return ops.shared_tiles_upload(c0, tile, self.shared_rows_per_tile, self.device)
+
+    def _use_shared(self, plan, cache):
+        if self.shared_route is not None:
+            if self.shared_route not in ("shared", "plain"):
+                raise ValueError(f"shared_route must be None, 'shared' or 'plain', got {self.shared_route!r}")
+            return self.shared_route == "shared"
+        if self.l["heads"] != self.Hkv:
+            return False
+        rows = int((plan.tile_host >= 0).sum(axis=1).max())               # the largest tile
+        keys = int(plan.c0_host.max()) * cache.chunk
+        return rows >= 3 or keys >= 2313
 
     # verify_step's attention.  rv_attn_decode_verify_bf16 reads a chunk once for a group of 16 / G rows; the same rows through
     # rv_attn_decode_beam_bf16 (prefix_row 0, prefix_len L_max) give the same bits from R times as many, smaller workgroups.  Same-box
@@ -1179,7 +1232,7 @@ class LlavaEngine:
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32, skinny=True)
         return logits[:, :self.vocab]
 
-    def extend(self, cache, input_ids, attention_mask=None, images=None, image_sizes=None, reuse=None, max_new_tokens=0, plan=None):
+    def extend(self, cache, input_ids, attention_mask=None, images=None, image_sizes=None, reuse=None, max_new_tokens=0, plan=None, slots=None):
         """The prompt pass of a continued generation over a KV cache of an earlier call on the same weights: sequence b's positions
         0 .. reuse[b] - 1 are kept from `cache` (a KVCache; later positions are dropped), its positions reuse[b] .. len_b - 1 (at least one)
         run through every decoder layer as one packed batch of M = sum(len_b - reuse[b]) rows -- RMSNorm, q|k|v, RoPE at the explicit
@@ -1187,9 +1240,19 @@ class LlavaEngine:
         o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual -- then the final norm and the lm_head on each sequence's last row.
         The vision tower runs only when an image feature row (image_newline aside) is among the new rows.  The cache grows (one copy of
         the kept rows) when len_b + max_new_tokens exceeds its slots.  Every reuse[b] == 0 (or no cache): prefill(), bit for bit.
-        plan: this prompt's self.plan(...), when the caller has it already.  Returns (cache, fp32 logits [B, vocab])."""
+        plan: this prompt's self.plan(...), when the caller has it already.
+        slots (generate_batch(share_prefix=True)): sequence b of the prompt batch lives in row slots[b] of `cache`, which may hold more
+        rows; the other rows and their lengths are untouched, cache.lens[slots] is set, and a need beyond cache.L_max is a ValueError
+        (no growth).  rv_attn_extend_bf16 indexes the cache by sequence number, so it is given all cache.B sequences with no new rows
+        for the ones not extended (its workgroups return, its combine skips them) and the packed rows in slot order; a row's
+        arithmetic is that of extend() on a cache of these sequences alone with the same L_max.
+        Returns (cache, fp32 logits [B, vocab])."""
         self._refuse_int8(cache, "extend()")
+        if slots is not None and cache is None:
+            raise ValueError("extend(slots=) needs the cache the slots index")
         if cache is None or reuse is None or not np.any(reuse):
+            if slots is not None:
+                return self.prefill(input_ids, attention_mask, images, image_sizes, max_new_tokens=max_new_tokens, cache=cache, slots=slots)
             return self.prefill(input_ids, attention_mask, images, image_sizes, max_new_tokens=max_new_tokens)
         self._check_generation()
         from .generation import grown_length
@@ -1203,20 +1266,34 @@ class LlavaEngine:
             plan = self.plan(ids, attention_mask, None, imgs, image_sizes)
         lens = plan["lens"].astype(np.int64)
         r = np.asarray(reuse, dtype=np.int64).reshape(-1)
-        if cache.B != B or r.shape[0] != B:
-            raise ValueError(f"the cache holds {cache.B} sequences, the prompt {B}")
-        if (r < 0).any() or (r > cache.lens).any() or (r >= lens).any():
+        if slots is None:
+            seq = np.arange(B)
+            if cache.B != B or r.shape[0] != B:
+                raise ValueError(f"the cache holds {cache.B} sequences, the prompt {B}")
+        else:
+            seq = np.asarray(slots, dtype=np.int64).reshape(-1)
+            if seq.shape[0] != B or r.shape[0] != B or np.unique(seq).shape[0] != B or (seq < 0).any() or (seq >= cache.B).any():
+                raise ValueError(f"slots must be {B} distinct indices into the cache's {cache.B} sequences, got {seq.tolist()}")
+        if (r < 0).any() or (r > cache.lens[seq]).any() or (r >= lens).any():
             raise ValueError("reuse[b] must lie in [0, min(cached length, prompt length - 1)]")
         n = lens - r
-        L_new = grown_length(cache.L_max, int((lens + int(max_new_tokens)).max()))
-        if L_new > cache.L_max:
-            cache.grow(L_new, int(r.max()))
-        cache.lens = r.copy()
+        need = int((lens + int(max_new_tokens)).max())
+        if slots is None:
+            L_new = grown_length(cache.L_max, need)
+            if L_new > cache.L_max:
+                cache.grow(L_new, int(r.max()))
+            cache.lens = r.copy()
+        else:
+            if need > cache.L_max:
+                raise ValueError(f"the prompts need {need} positions, the cache holds {cache.L_max}")
+            cache.lens[seq] = r
+        CB = cache.B
+        order = np.argsort(seq, kind="stable")                # the packed rows go in cache-row order; without slots: 0 .. B - 1
         L_max = cache.L_max
         valid = plan["attention_mask"].reshape(-1)
         flat = plan["idx"][valid]
         cu_full = np.concatenate([[0], np.cumsum(lens)])
-        src = np.concatenate([flat[cu_full[b] + r[b]:cu_full[b + 1]] for b in range(B)]).astype(np.int32)
+        src = np.concatenate([flat[cu_full[b] + r[b]:cu_full[b + 1]] for b in order]).astype(np.int32)
         nl_code = -int(plan["n_feat_rows"]) - 2
         if ((src <= -2) & (src != nl_code)).any():
             if not imgs:
@@ -1226,10 +1303,12 @@ class LlavaEngine:
             table = (self.W("model.image_newline").reshape(1, d) if self.with_newline else
                      torch.zeros(1, d, dtype=BF16, device=self.device))
             src = np.where(src == nl_code, -2, src).astype(np.int32)
-        pos = np.concatenate([np.arange(r[b], lens[b]) for b in range(B)])
-        cu_q = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
-        slots = self._dev(np.concatenate([b * L_max + np.arange(r[b], lens[b]) for b in range(B)]).astype(np.int64))
-        pos_d, cu_d, r_d = self._dev(pos.astype(np.int32)), self._dev(cu_q), self._dev(r.astype(np.int32))
+        pos = np.concatenate([np.arange(r[b], lens[b]) for b in order])
+        n_all, r_all = np.zeros(CB, dtype=np.int64), np.zeros(CB, dtype=np.int64)
+        n_all[seq], r_all[seq] = n, r
+        cu_q = np.concatenate([[0], np.cumsum(n_all)]).astype(np.int32)
+        rows = self._dev(np.concatenate([seq[b] * L_max + np.arange(r[b], lens[b]) for b in order]).astype(np.int64))
+        pos_d, cu_d, r_d = self._dev(pos.astype(np.int32)), self._dev(cu_q), self._dev(r_all.astype(np.int32))
         cs = self.rope_table(L_max)
         x = ops.gather_rows(self._dev(src), d, self.W("model.embed_tokens.weight"), table)
         for i in range(L):
@@ -1238,16 +1317,19 @@ class LlavaEngine:
             qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
             kv = cache.layers[i]
-            kv.view(B * L_max, 2 * kvd).index_copy_(0, slots, qkv[:, d:])
+            kv.view(CB * L_max, 2 * kvd).index_copy_(0, rows, qkv[:, d:])
             attn = ops.attn_extend(qkv[:, :d], kv, cu_d, r_d, H, Hkv, hd, kvd, int(n.max()))
             x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
             act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu")), F)
             x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"))
-        last = self._dev((cu_q[1:] - 1).astype(np.int32))
+        last = self._dev((cu_q[seq + 1] - 1).astype(np.int32))              # sequence b's last new row, in the prompt batch's order
         hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
-        cache.lens = lens.copy()
+        if slots is None:
+            cache.lens = lens.copy()
+        else:
+            cache.lens[seq] = lens
         return cache, logits[:, :self.vocab]
 
     def _cross_entropy(self, logits, tgt, V, inv, gscale):

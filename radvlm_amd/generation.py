@@ -897,7 +897,9 @@ class GenerationOutput(SimpleNamespace):
 
 def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
     """generate_batch() keywords: generate()'s greedy and sampling settings (seed: an int, or a list of n ints), validated by parse_generate_kwargs and applied per request;
-    max_new_tokens may also be a list of n budgets (cfg.budgets).  TypeError for arguments without a per-request meaning."""
+    max_new_tokens may also be a list of n budgets (cfg.budgets).  TypeError for arguments without a per-request meaning.
+    share_prefix (cfg.share_prefix, default False): a bool, ValueError otherwise; NotImplementedError together with
+    kv_cache_dtype="int8" or guidance_scale."""
     given = sorted(k for k in _NO_PER_REQUEST if kwargs.get(k) is not None and kwargs.get(k) is not False)
     if given:
         raise TypeError(f"generate_batch() got arguments without a per-request meaning: {given}")
@@ -905,6 +907,9 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
         raise TypeError("generate_batch() takes unpadded negative prompts (negative_prompt_ids: a list of 1-D id sequences); "
                         "negative_prompt_attention_mask has no per-request meaning")
     kw = {k: v for k, v in kwargs.items() if k not in _NO_PER_REQUEST}
+    share = kw.pop("share_prefix", False)                     # generate_batch() alone takes it: generate() / generate_beams() reject the name
+    if not isinstance(share, (bool, np.bool_)):
+        raise ValueError(f"share_prefix must be True or False, got {share!r}")
     budgets = None
     mnt = kw.get("max_new_tokens")
     if mnt is not None and not _is_int(mnt):
@@ -918,6 +923,12 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
         del kw["max_new_tokens"]
     cfg = parse_generate_kwargs(kw, lora=lora, config_eos=config_eos, config_pad=config_pad)
     cfg.budgets = budgets
+    cfg.share_prefix = bool(share)
+    if cfg.share_prefix and cfg.kv_cache_dtype == "int8":
+        raise NotImplementedError("share_prefix=True with kv_cache_dtype='int8': the extend-attention and shared decode kernels read a bf16 "
+                                  "cache only")
+    if cfg.share_prefix and cfg.guidance is not None:
+        raise NotImplementedError("share_prefix=True with guidance_scale: sharing across the two branches of a guided call is not implemented")
     if cfg.guidance is not None:
         for k in ("negative_prompt_ids", "negative_images", "negative_image_sizes"):
             _per_request(k, getattr(cfg.guidance, k), n)      # a list of another length: ValueError here, before anything runs
@@ -995,6 +1006,89 @@ def batch_requests(inputs, images=None, image_sizes=None, guidance=None):
         if any(r.neg_sizes is None for r in with_img) and any(r.neg_sizes is not None for r in with_img):
             raise ValueError("negative_image_sizes: give the sizes of every request's negative images or of none")
     return reqs
+
+
+# ------------------------------------------------------------------------------------------------ shared prompt prefixes
+SHARE_MIN_PREFIX = 128        # = KVCache.chunk: below one decode chunk neither the prompt pass nor the decode kernel gains anything
+SHARED_TILE_COLS = 16         # columns of the tile table (rv_attn_decode_shared_bf16 reads 16 // G of them)
+
+
+def common_prefix(a, b):
+    """Length of the longest common prefix of two record arrays."""
+    k = min(len(a), len(b))
+    neq = np.nonzero(np.asarray(a[:k]) != np.asarray(b[:k]))[0]
+    return int(neq[0]) if neq.size else k
+
+
+def best_source(records, sources):
+    """The source of a request among `sources`, (slot, records) pairs: P = the longest common prefix of records, capped at
+    len(records) - 1 (the last prompt position is always computed: its logits start the decoding) and, being a common prefix, at the
+    source's prompt length; the longest P wins, ties go to the lowest slot.  Returns (slot, P), or (-1, 0) when P < SHARE_MIN_PREFIX
+    for every source: the request is then a leader."""
+    best, bp = -1, 0
+    for slot, rec in sorted(sources, key=lambda e: e[0]):
+        p = min(common_prefix(records, rec), len(records) - 1)
+        if p > bp:
+            best, bp = int(slot), p
+    return (best, bp) if bp >= SHARE_MIN_PREFIX else (-1, 0)
+
+
+def shared_tiles(active_slots, lineage, P, rows_per_tile, chunk, S):
+    """The tile table of rv_attn_decode_shared_bf16 for S cache rows.  lineage[s]: the lineage of slot s (any int >= 0: the slots copied,
+    directly or transitively, from one leader prompt, and that leader), -1 for an ungrouped slot; P[s]: the positions slot s holds in
+    common with its lineage (a leader: the largest P a follower took from it).  The active slots of a lineage, sorted by slot, are cut
+    into tiles of rows_per_tile rows; a tile's shared chunk count is min(P over its rows) // chunk.  Returns (c0 int32 [S]: 0 for
+    ungrouped rows, idle rows, tiles of one row and tiles with no whole shared chunk; tile int32 [S, 16]: row s lists its tile's slots
+    when it is the tile's first row, padded with -1, else tile[s, 0] == -1)."""
+    c0 = np.zeros(S, dtype=np.int32)
+    tile = np.full((S, SHARED_TILE_COLS), -1, dtype=np.int32)
+    assert 1 <= rows_per_tile <= SHARED_TILE_COLS and chunk > 0
+    groups = {}
+    for s in sorted(int(v) for v in active_slots):
+        if lineage[s] >= 0:
+            groups.setdefault(int(lineage[s]), []).append(s)
+    for rows in groups.values():
+        for k in range(0, len(rows), rows_per_tile):
+            t = rows[k:k + rows_per_tile]
+            c = min(int(P[s]) for s in t) // chunk
+            if len(t) < 2 or c <= 0:
+                continue
+            c0[t] = c
+            tile[t[0], :len(t)] = t
+    return c0, tile
+
+
+def check_shared_tiles(c0, tile, rows_per_tile):
+    """ValueError unless (c0 [S], tile [S, 16]) is a table shared_tiles could have built: every tile entry in [-1, S); a listed tile
+    names its own row first (the leader), then distinct rows, at most rows_per_tile of them, -1 only as padding; c0 >= 0, equal within a
+    tile; a row with c0 > 0 belongs to exactly one listed tile and a row with c0 == 0 to none."""
+    c0, tile = np.asarray(c0), np.asarray(tile)
+    S = c0.shape[0]
+    if c0.ndim != 1 or tile.shape != (S, SHARED_TILE_COLS):
+        raise ValueError(f"shared tiles: c0 must be [S] and tile [S, {SHARED_TILE_COLS}], got {c0.shape} and {tile.shape}")
+    if not 1 <= rows_per_tile <= SHARED_TILE_COLS:
+        raise ValueError(f"shared tiles: rows_per_tile must lie in [1, {SHARED_TILE_COLS}], got {rows_per_tile}")
+    if (tile < -1).any() or (tile >= S).any():
+        raise ValueError(f"shared tiles: an entry lies outside [-1, {S})")
+    if (c0 < 0).any():
+        raise ValueError("shared tiles: a negative shared chunk count")
+    member = np.zeros(S, dtype=np.int64)
+    for s in range(S):
+        if tile[s, 0] == -1:
+            if (tile[s] != -1).any():
+                raise ValueError(f"shared tiles: row {s} lists rows after a -1")
+            continue
+        if tile[s, 0] != s:
+            raise ValueError(f"shared tiles: row {s} lists a tile that starts with row {int(tile[s, 0])}: the leader comes first")
+        n = int((tile[s] >= 0).sum())
+        rows = tile[s, :n]
+        if (rows < 0).any() or n > rows_per_tile or np.unique(rows).shape[0] != n:
+            raise ValueError(f"shared tiles: row {s}'s tile must be at most {rows_per_tile} distinct rows with -1 only as padding")
+        if c0[s] <= 0 or (c0[rows] != c0[s]).any():
+            raise ValueError(f"shared tiles: the rows of row {s}'s tile must have one shared chunk count > 0, got {c0[rows].tolist()}")
+        member[rows] += 1
+    if (member > 1).any() or ((c0 > 0) != (member == 1)).any():
+        raise ValueError("shared tiles: a row with c0 > 0 must belong to exactly one listed tile and a row with c0 == 0 to none")
 
 
 class DevicePicker:
@@ -1079,7 +1173,16 @@ class BatchScheduler:
     same image-first rule); a decode step runs all 2 * slots rows, feeding a request's token to both of its rows (an idle slot's two
     rows: token 0 at length 0); `guide(cond, uncond)` -- default ops.cfg_guide_rows with the call's scale -- then turns the first
     `slots` rows into the guided scores in place and the picker runs on them as it does without guidance.  A finished request frees
-    both rows.  Without cfg.guidance nothing here changes.  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t)."""
+    both rows.  Without cfg.guidance nothing here changes.  `events` records the schedule: ("admit", requests, slots), ("decode", active slots), ("finish", request, slot, t).
+    cfg.share_prefix (shared prompt prefixes; the engine is then also reached through extend(..., slots=, reuse=), shared_rows_per_tile,
+    shared_plan and decode_step(shared=)): every request's position_records are computed once, image uids by content with one table per
+    call.  Each request of an admitted group, in input order, takes as source the active slot or earlier leader of the same admission
+    with the longest common prefix P (best_source); with P >= SHARE_MIN_PREFIX it is a follower, else a leader.  Leaders are prefilled
+    as ever; then every follower's positions 0 .. P - 1 are copied into its own slot (one copy per layer) and one extend computes all
+    the followers' suffixes; _step runs once per phase and ("share", request, slot, source slot, P) follows the "admit" entry.  A
+    row is self-contained, so a group outlives its leader and no cache bytes are saved.  The decode step's tile table (shared_tiles
+    over the active slots' lineages) is rebuilt when an admission or a finish changes the active set and uploaded when it differs;
+    while no tile shares a chunk decode_step is called without shared=.  Without cfg.share_prefix nothing here changes."""
 
     def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None, guide=None):
         if not _is_int(max_batch_size) or max_batch_size < 1:
@@ -1087,7 +1190,15 @@ class BatchScheduler:
         self.engine, self.reqs, self.cfg = engine, reqs, cfg
         self.logprobs = bool(return_logprobs)
         n = len(reqs)
-        self.spliced = [int(engine.plan(r.ids[None], None, None, r.images, r.sizes)["lens"][0]) for r in reqs]
+        plans = [engine.plan(r.ids[None], None, None, r.images, r.sizes) for r in reqs]
+        self.spliced = [int(pl["lens"][0]) for pl in plans]
+        self.share = bool(getattr(cfg, "share_prefix", False))
+        if self.share:
+            if getattr(cfg, "guidance", None) is not None or getattr(cfg, "kv_cache_dtype", "bf16") == "int8":
+                raise NotImplementedError("share_prefix=True takes a bf16 cache and no guidance_scale")
+            held = []                                         # one uid table per call: (pixels, image_size) of every distinct image
+            self.records = [position_records(pl, self._image_uids(held, r))[0] for pl, r in zip(plans, reqs)]
+        del plans
         self.budget = [cfg.budgets[i] if cfg.budgets is not None else new_token_budget(cfg, self.spliced[i]) for i in range(n)]
         self.min_new = [min_new_length(cfg, self.spliced[i]) for i in range(n)]
         self.seeds = None if getattr(cfg, "sampling", None) is None else sampling_seeds(cfg.sampling, n)
@@ -1104,6 +1215,19 @@ class BatchScheduler:
         self.events = []
         self.tokens = [[] for _ in range(n)]
         self.logps = [[] for _ in range(n)]
+
+    @staticmethod
+    def _image_uids(held, r):
+        """uid of each image of request r by content, as GenerationCache._image_uids: the same bits and image_size, the same uid."""
+        uids = []
+        for i, im in enumerate(r.images):
+            size = None if r.sizes is None else tuple(int(v) for v in r.sizes[i])
+            hit = next((u for u, (px, sz) in enumerate(held) if sz == size and (px is im or _same_pixels(px, im))), None)
+            if hit is None:
+                hit = len(held)
+                held.append((im, size))
+            uids.append(hit)
+        return uids
 
     def run(self):
         """Generate every request; returns {"req_<i>": GenerationOutput} in input order."""
@@ -1135,6 +1259,11 @@ class BatchScheduler:
         self.mn = np.zeros(S, dtype=np.int64)                 # its EOS minimum
         self.pending = np.zeros(S, dtype=np.int64)            # its last token, fed to the next decode step
         self.free = list(range(S))
+        if self.share:
+            self.slot_rec = [None] * S                        # prompt records of the slot's request, None: idle
+            self.lineage = np.full(S, -1, dtype=np.int64)     # the request whose prompt the slot's shared positions come from, -1: none
+            self.P = np.zeros(S, dtype=np.int64)              # positions the slot holds in common with its lineage
+            self.plan, self.plan_key, self.retile = None, None, False
         waiting = list(self.runs)
         while waiting or (self.owner >= 0).any():
             while waiting and (len(self.free) >= self.admit_free or not (self.owner >= 0).any() or len(waiting) <= len(self.free)):
@@ -1151,6 +1280,11 @@ class BatchScheduler:
         self.events.append(("admit", tuple(group), tuple(gslots)))
         for q, s in zip(group, gslots):
             self.owner[s], self.t[s], self.mn[s] = q, 0, self.min_new[q]
+        if self.share:
+            followers = self._match(group, gslots)
+            if followers:
+                self._admit_shared(group, gslots, followers)
+                return
         # image requests first: in a batch the splice gives a text-only prompt a (dummy) image slot, which must not shift later images
         order = sorted(range(len(group)), key=lambda j: not self.reqs[group[j]].images)
         rq = [self.reqs[group[j]] for j in order]
@@ -1166,6 +1300,75 @@ class BatchScheduler:
         if self.guidance is not None:
             logits = self._admit_negative(logits, rq, rs)
         self._step(logits, rs)
+
+    def _match(self, group, gslots):
+        """Sources of an admitted group (share_prefix): for each request in input order, the best source (best_source) among the active
+        slots' prompts -- the group's own slots were free, so they are none of those -- and the earlier leaders of this admission.
+        Books records, lineage and P per slot and the "share" events; returns {index in group: (source slot, P)} of the followers."""
+        taken = set(int(s) for s in gslots)
+        sources = [(s, self.slot_rec[s]) for s in range(self.slots) if self.owner[s] >= 0 and s not in taken]
+        followers = {}
+        for j, (q, s) in enumerate(zip(group, gslots)):
+            rec = self.records[q]
+            src, p = best_source(rec, sources)
+            self.slot_rec[s] = rec
+            if src < 0:
+                self.lineage[s], self.P[s] = -1, 0
+                sources.append((int(s), rec))                 # a leader of this admission: prefilled before any follower is copied
+                continue
+            followers[j] = (src, p)
+            if self.lineage[src] < 0:                         # the source becomes a lineage's leader
+                self.lineage[src] = self.owner[src]
+            if self.lineage[src] == self.owner[src]:          # a leader's own P: the largest P a follower took from it
+                self.P[src] = max(self.P[src], p)
+            # copied from a follower, the row holds the lineage's prompt only as far as that follower does
+            self.lineage[s], self.P[s] = self.lineage[src], min(p, int(self.P[src]))
+            self.events.append(("share", int(q), int(s), int(src), int(p)))
+        self.retile = True
+        return followers
+
+    def _admit_shared(self, group, gslots, followers):
+        """An admission with followers, in two phases: the leaders through prefill as ever; then every follower's shared positions are
+        copied into its slot (one copy per layer) and one extend computes all the followers' suffixes.  _step runs once per phase."""
+        eng = self.engine
+        for part in (False, True):
+            members = [j for j in range(len(group)) if (j in followers) == part]
+            if not members:
+                continue
+            order = sorted(members, key=lambda j: not self.reqs[group[j]].images)      # the image-first rule of _admit
+            rq = [self.reqs[group[j]] for j in order]
+            rs = [gslots[j] for j in order]
+            T = max(r.ids.size for r in rq)
+            ids = np.zeros((len(rq), T), dtype=np.int64)
+            am = np.zeros((len(rq), T), dtype=bool)
+            for b, r in enumerate(rq):
+                ids[b, :r.ids.size], am[b, :r.ids.size] = r.ids, True
+            imgs = [im for r in rq for im in r.images]
+            sizes = [s for r in rq for s in (r.sizes or [])] if any(r.sizes is not None for r in rq) else None
+            if not part:
+                _, logits = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs)
+            else:
+                reuse = np.array([followers[j][1] for j in order], dtype=np.int64)
+                for j in members:                             # input order: a source is an older slot or a leader of phase 1
+                    src, p = followers[j]
+                    for layer in self.cache.layers:
+                        layer[gslots[j], :p] = layer[src, :p]
+                    self.cache.lens[gslots[j]] = p            # the slot holds these positions now: what extend(reuse=) checks
+                _, logits = eng.extend(self.cache, ids, am, imgs or None, sizes, reuse=reuse, slots=rs)
+            self._step(logits, rs)
+
+    def _shared_plan(self):
+        """The decode step's tile table, rebuilt when an admission or a finish changed the active set and uploaded when it differs
+        from the last one; None while no tile shares a chunk."""
+        if self.retile:
+            self.retile = False
+            c0, tile = shared_tiles(np.flatnonzero(self.owner >= 0), self.lineage, self.P, self.engine.shared_rows_per_tile,
+                                    type(self.cache).chunk, self.slots)
+            key = (c0.tobytes(), tile.tobytes())
+            if key != self.plan_key:
+                self.plan_key = key
+                self.plan = self.engine.shared_plan(c0, tile) if c0.any() else None
+        return self.plan
 
     def _admit_negative(self, logits, rq, rs):
         """Prefill the negative prompts of the admitted requests rq (slots rs) into rows slots + s and guide the group's logits."""
@@ -1198,7 +1401,11 @@ class BatchScheduler:
             self._step(logits[:self.slots], list(range(self.slots)))
             return
         self.cache.lens[idle] = 0
-        logits = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending))
+        plan = self._shared_plan() if self.share else None
+        if plan is None:
+            logits = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending))
+        else:
+            logits = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending), shared=plan)
         self.cache.lens[idle] = 0
         self._step(logits, list(range(self.slots)))
 
@@ -1233,6 +1440,8 @@ class BatchScheduler:
                 self.events.append(("finish", q, int(s), n))
                 self.owner[s], self.t[s], self.mn[s] = -1, 0, 0
                 self.free = sorted(self.free + [int(s)])
+                if self.share:                                # the row keeps its bits until the slot is refilled, but it is no source
+                    self.slot_rec[s], self.lineage[s], self.P[s], self.retile = None, -1, 0, True
             else:
                 self.pending[s], self.t[s] = tk, n
 

@@ -125,6 +125,8 @@ _SIGS = {
     "rv_kv_append_q8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p],
     "rv_attn_decode_kv8_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _i64, _i64, _i32, _c_void_p, _i32, _c_void_p, _i64,
                                 _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
+    "rv_attn_decode_shared_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i64,
+                                   _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
     "rv_log_softmax_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p],
     "rv_beam_topk_f32": [_c_void_p, _i64, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p],
     "rv_cfg_guide_rows_f32": [_c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _f32, _c_void_p, _i64, _c_void_p],

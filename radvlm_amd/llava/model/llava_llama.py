@@ -340,6 +340,13 @@ class LlavaLlamaForCausalLM:
         request's last prompt token) and negative_images / negative_image_sizes (per request, as images): classifier-free guidance
         as in generate().  max_batch_size keeps counting requests; the cache holds two rows per slot (the memory check counts both)
         and a request's tokens are those of generate() on it alone with the same guidance.  negative_prompt_attention_mask: TypeError.
+        share_prefix=True (default False: nothing changes): requests that begin with the same spliced positions -- equal token ids
+        and image rows of bit-identical pixels with the same image_size, at least 128 of them -- share them within the call: the
+        first is prefilled, a follower's cache row gets the common positions by a copy and only its suffix runs through the decoder
+        (LlavaEngine.extend(slots=)), so the tower and the prompt pass run once per distinct prefix, and decode attention may read
+        a group's shared keys once per step (rv_attn_decode_shared_bf16, the plain kernel's bits; LlavaEngine.shared_route).  A
+        follower's tokens agree with the unshared call's within rounding; prompts with nothing in common give exactly the call
+        without the keyword.  A non-bool value: ValueError; with kv_cache_dtype="int8" or guidance_scale: NotImplementedError.
         The training state is not touched."""
         from ...generation import generate_batch, parse_batch_kwargs
         inputs = list(inputs)

@@ -4,6 +4,7 @@ Names follow the reference's operators.  No op her
 """
 import math
 
+import numpy as np
 import torch
 
 from . import lib
@@ -924,6 +925,43 @@ def attn_decode_verify(q, cache, kv_len0, R, H, Hkv, hd, v_off, out=None, chunk=
     part = torch.empty(B * R * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
     lib.call("rv_attn_decode_verify_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len0, L_max, out, out.stride(0), part,
              part.numel() * 4, B, R, H, Hkv, hd, chunk, float(scale))
+    return out
+
+
+SHARED_TILE_COLS = 16     # columns of attn_decode_shared's tile table: 16 / G rows of them are read (rv_attn_decode_shared_bf16)
+
+
+def shared_tiles_upload(c0, tile, rows_per_tile, device):
+    """The device copies of a shared-prefix tile table (generation.shared_tiles: c0 int32 [S], tile int32 [S, 16]), validated by
+    generation.check_shared_tiles first (ValueError for a table attn_decode_shared must not see).  Returns a namespace with .c0 / .tile
+    (device int32) and .c0_host / .tile_host: what decode_step(shared=) and attn_decode_shared take, uploaded once per change of the
+    active set, not per step."""
+    from types import SimpleNamespace
+    from .generation import check_shared_tiles
+    c0 = np.ascontiguousarray(c0, dtype=np.int32)
+    tile = np.ascontiguousarray(tile, dtype=np.int32)
+    check_shared_tiles(c0, tile, rows_per_tile)
+    return SimpleNamespace(c0=torch.from_numpy(c0).to(device), tile=torch.from_numpy(tile).to(device), c0_host=c0, tile_host=tile,
+                           rows_per_tile=int(rows_per_tile))
+
+
+def attn_decode_shared(q, cache, kv_len, c0, tile, H, Hkv, hd, v_off, out=None, chunk=128, scale=None):
+    """attn_decode for rows grouped in tiles that hold equal K|V at their first c0 * chunk positions (rv_attn_decode_shared_bf16): c0
+    int32 [B] and tile int32 [B, 16] device tensors from shared_tiles_upload (a table for 16 // (H // Hkv) rows per tile); a tile's
+    shared chunks are read once, from its first row.  Bit-identical to attn_decode on the same cache when the tiles' rows really hold
+    equal K|V there and at least c0 * chunk keys each.  Returns bf16 [B, H*hd]."""
+    _chk(q), _chk(cache), _chk(kv_len, torch.int32), _chk(c0, torch.int32), _chk(tile, torch.int32)
+    B, L_max, width = cache.shape
+    assert q.shape == (B, H * hd) and q.stride(1) == 1 and cache.is_contiguous() and kv_len.numel() == B and kv_len.is_contiguous()
+    assert c0.shape == (B,) and c0.is_contiguous() and tile.shape == (B, SHARED_TILE_COLS) and tile.is_contiguous()
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if out is None:
+        out = torch.empty(B, H * hd, dtype=BF16, device=q.device)
+    assert out.shape == (B, H * hd) and out.stride(1) == 1
+    nch = (L_max + chunk - 1) // chunk
+    part = torch.empty(B * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    lib.call("rv_attn_decode_shared_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len, c0, tile, L_max, out, out.stride(0),
+             part, part.numel() * 4, B, H, Hkv, hd, chunk, float(scale))
     return out
 
 

@@ -74,6 +74,15 @@
         # per step per arm, the spread of the three medians, guided / plain(B), guided / plain(2B) and whether the guided step lies
         # below 2 x plain(B) -- HF's two forward passes -- by more than the plain arm's spread; the guide launch's share of the step
   python tools/decode_bench.py --cfg-kernel-ab   # (1) alone
+  python tools/decode_bench.py --shared-shapes [--out FILE]   # kernel A/B of shared prompt prefixes: rv_attn_decode_bf16 vs
+        # rv_attn_decode_shared_bf16 on one cache, the 7B and Qwen2-7B head shapes, 704 and 7,603 shared keys (each row 40 keys of
+        # its own after them), B = 32 rows in groups of 2, 4, 8, 16, 32 that hold one prefix; the protocol of --kv8-shapes: cold
+        # cache, interleaved, median of 20, torch.equal asserted before timing; the plain arm's p10 / p90 are its spread
+  python tools/decode_bench.py --share-prefix [--geos ..] [--new 32] [--out FILE]
+        # generate_batch end to end: 64 requests = 8 images x 8 questions of 24 - 40 tokens behind a 35-token system prompt and
+        # the image (llava_ov_qwen2_7b: anyres_max_9, 10 tiles, 8 slots), image-major order, 32 slots, EOS disabled; arms: sharing off,
+        # sharing on with shared_route "plain" and with "shared", one untimed pass of each and then interleaved three times; per
+        # arm the median wall time with that run's time inside prefill / extend, tower runs (calls, images) and decode ms / step
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -987,6 +996,145 @@ def sample_ab(geo, batches, prompt, new, reps=3):
     return recs
 
 
+def shared_shapes(reps=20, keys=(704, 7603), groups=(2, 4, 8, 16, 32), B=32, own=40):
+    """rv_attn_decode_bf16 vs rv_attn_decode_shared_bf16 per head shape: B rows in groups that hold one prefix of `keys` positions and
+    `own` positions of their own, interleaved, cold cache."""
+    from radvlm_amd.generation import shared_tiles
+    out = []
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
+    for geo in ("llava15_7b", "llava_ov_qwen2_7b"):
+        l = GEOMETRIES[geo]["lm"]
+        H, hd = l["heads"], l["d"] // l["heads"]
+        Hkv = l.get("kv_heads", H)
+        kvd, rpt = Hkv * hd, ops.SHARED_TILE_COLS // (H // Hkv)
+        for n in keys:
+            L = n + own + 1
+            cache = torch.randn(B, L, 2 * kvd, device="cuda", dtype=torch.bfloat16)
+            q = torch.randn(B, H * hd, device="cuda", dtype=torch.bfloat16)
+            kv_len = torch.full((B,), n + own, dtype=torch.int32, device="cuda")
+            for gs in groups:
+                for s in range(B):
+                    if s % gs:
+                        cache[s, :n] = cache[s - s % gs, :n]
+                c0, tile = shared_tiles(np.arange(B), np.arange(B) // gs, np.full(B, n), rpt, 128, B)
+                plan = ops.shared_tiles_upload(c0, tile, rpt, "cuda")
+                fns = {"plain": lambda: ops.attn_decode(q, cache, kv_len, H, Hkv, hd, kvd),
+                       "shared": lambda: ops.attn_decode_shared(q, cache, kv_len, plan.c0, plan.tile, H, Hkv, hd, kvd)}
+                assert torch.equal(fns["plain"](), fns["shared"]())
+                ts = _timed_interleaved(fns, flush, reps)
+                pl, sh = float(np.median(ts["plain"])), float(np.median(ts["shared"]))
+                p10, p90 = float(np.percentile(ts["plain"], 10)), float(np.percentile(ts["plain"], 90))
+                out.append(dict(mode="shared_kernel_ab", geo=geo, H=H, Hkv=Hkv, hd=hd, shared_keys=n, keys=n + own, B=B, group=gs,
+                                rows_per_tile=rpt, tiles=int((tile[:, 0] >= 0).sum()), c0=int(c0.max()), plain_us=round(pl, 2),
+                                shared_us=round(sh, 2), shared_over_plain=round(sh / pl, 3), plain_p10_us=round(p10, 2),
+                                plain_p90_us=round(p90, 2), shared_p10_us=round(float(np.percentile(ts["shared"], 10)), 2),
+                                shared_p90_us=round(float(np.percentile(ts["shared"], 90)), 2),
+                                shared_faster_by_more_than_plain_spread=bool(pl - sh > p90 - p10), reps=reps, chunk=128,
+                                kernel_src=_src_hash()))
+                print(f"# {geo} keys {n} group {gs}: plain {pl:.1f} us, shared {sh:.1f} us", file=sys.stderr, flush=True)
+            del cache
+    return out
+
+
+class _ShareClock:
+    """Wall time inside the engine's prompt passes (prefill, extend) and decode steps, and the tower's runs, synchronised around each
+    call (the scheduler synchronises every step anyway).  prefill called from extend is not counted twice."""
+
+    def __init__(self, eng):
+        self.eng, self.depth = eng, 0
+        self.reset()
+        for name in ("prefill", "extend", "decode_step", "encode_images"):
+            setattr(eng, name, self._wrap(name, getattr(eng, name)))
+
+    def reset(self):
+        self.prompt_ms, self.prefills, self.extends, self.steps, self.tower_calls, self.tower_images = 0.0, 0, 0, [], 0, 0
+
+    def _wrap(self, name, fn):
+        def timed(*a, **k):
+            if name == "encode_images":
+                self.tower_calls += 1
+                self.tower_images += int(a[0].shape[0])
+                return fn(*a, **k)
+            if self.depth:
+                return fn(*a, **k)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            self.depth += 1
+            try:
+                r = fn(*a, **k)
+            finally:
+                self.depth -= 1
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            if name == "decode_step":
+                self.steps.append(ms)
+            else:
+                self.prompt_ms += ms
+                self.prefills += name == "prefill"
+                self.extends += name == "extend"
+            return r
+        return timed
+
+    def close(self):
+        for name in ("prefill", "extend", "decode_step", "encode_images"):
+            delattr(self.eng, name)
+
+
+def share_prefix_e2e(geo, new=32, reps=3, n_img=8, n_q=8):
+    """--share-prefix: generate_batch over n_img images x n_q questions with sharing off, on (plain kernel) and on (shared kernel).
+    32 slots; 8 for the anyres_max_9 prompts, the largest batch of 7.6k-position prompts the prompt pass has been run at (--continue)."""
+    from radvlm_amd.generation import BatchScheduler, batch_requests, parse_batch_kwargs
+    eng, ids, images, sizes = _conversation(geo, n_img)
+    rng = np.random.default_rng(3)
+    prompts, ims, szs = [], [], []
+    for i in range(n_img):
+        for _ in range(n_q):
+            prompts.append(np.concatenate([ids[0, :36], rng.integers(3, eng.vocab, int(rng.integers(24, 41)))]))   # the system prompt, the image token
+            ims.append(images[i])
+            szs.append(sizes[i])
+    clock = _ShareClock(eng)
+    slots = 8 if eng.aspect.startswith("anyres") else 32
+    arms = {"off": (False, None), "on_plain": (True, "plain"), "on_shared": (True, "shared")}
+
+    def run(arm):
+        share, route = arms[arm]
+        cfg = parse_batch_kwargs(dict(max_new_tokens=new, eos_token_id=None, **(dict(share_prefix=True) if share else {})), len(prompts))
+        clock.reset()
+        eng.shared_route = route
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        try:
+            sch = BatchScheduler(eng, batch_requests(prompts, ims, szs), cfg, slots)
+            out = sch.run()
+        finally:
+            eng.shared_route = None
+        torch.cuda.synchronize()
+        wall = (time.perf_counter() - t0) * 1e3
+        return dict(wall_s=round(wall / 1e3, 3), prompt_pass_s=round(clock.prompt_ms / 1e3, 3), prefills=clock.prefills, extends=clock.extends,
+                    tower_calls=clock.tower_calls, tower_images=clock.tower_images, decode_steps=len(clock.steps),
+                    decode_ms_per_step=round(float(np.median(clock.steps)), 3), shares=sum(e[0] == "share" for e in sch.events),
+                    tokens=sum(len(o.generated_tokens) for o in out.values())), [o.generated_tokens for o in out.values()]
+
+    first = {arm: run(arm) for arm in arms}                           # untimed pass of every arm
+    assert first["on_plain"][1] == first["on_shared"][1]              # the two routes: the same tokens
+    runs = {arm: [] for arm in arms}
+    for _ in range(reps):
+        for arm in arms:
+            runs[arm].append(run(arm)[0])
+            print(f"# {geo} {arm}: {runs[arm][-1]}", file=sys.stderr, flush=True)
+    clock.close()
+    lens = eng.plan(prompts[0][None], None, None, [ims[0]], [szs[0]])["lens"]
+    rec = dict(mode="share_prefix", geo=geo, requests=len(prompts), images=n_img, questions_per_image=n_q, prompt_positions=int(lens[0]),
+               new_tokens=new, max_batch_size=slots, reps=reps, image_aspect_ratio=eng.aspect,
+               tokens_equal_off_vs_on=sum(a == b for a, b in zip(first["off"][1], first["on_shared"][1])), kernel_src=_src_hash())
+    for arm, rs in runs.items():
+        wall = [r["wall_s"] for r in rs]
+        rec[arm] = dict(rs[int(np.argsort(wall)[len(wall) // 2])], wall_s_all=wall)
+    rec["wall_on_shared_over_off"] = round(rec["on_shared"]["wall_s"] / rec["off"]["wall_s"], 3)
+    rec["wall_on_plain_over_off"] = round(rec["on_plain"]["wall_s"] / rec["off"]["wall_s"], 3)
+    return [rec]
+
+
 def _conversation(geo, B, seed=0):
     """Engine + turn-1 batch of the --continue configs: ids as bench.py's synthetic batch (129 ids, the image token at 35)."""
     g = GEOMETRIES[geo]
@@ -1266,6 +1414,8 @@ def main():
     ap.add_argument("--lookup-kernel-ab", action="store_true")
     ap.add_argument("--cfg", action="store_true")
     ap.add_argument("--cfg-kernel-ab", action="store_true")
+    ap.add_argument("--shared-shapes", action="store_true")
+    ap.add_argument("--share-prefix", action="store_true")
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -1306,6 +1456,11 @@ def main():
         recs = [r for g in a.geos.split(",") for r in lookup_kernel_ab(g) + lookup_e2e(g, a.prompt, a.new, reps=min(a.reps, 3))]
     elif a.cfg_kernel_ab:
         recs = cfg_kernel_ab()
+    elif a.shared_shapes:
+        recs = shared_shapes()
+    elif a.share_prefix:
+        new = a.new if a.new != ap.get_default("new") else 32
+        recs = [r for g in a.geos.split(",") for r in share_prefix_e2e(g, new=new, reps=min(a.reps, 3))]
     elif a.cfg:
         batches = a.batches if a.batches != ap.get_default("batches") else "1,8,16"
         recs = cfg_kernel_ab() + [r for g in a.geos.split(",") for r in cfg_ab(g, list(map(int, batches.split(","))), a.prompt, a.new)]
