@@ -594,6 +594,41 @@ int rv_attn_decode_shared_bf16(const void* q, int64_t ld_q, const void* cache, i
                                const int32_t* c0, const int32_t* tile, int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes,
                                int B, int H, int Hkv, int hd, int chunk, float scale, void* stream);
 
+/* ---- scoring candidate answers (model.score(), radvlm_amd/csrc/score.hip) -----------------------------------------------------------
+ * The reference's abnormality_classification task (radvlm/evaluation/evaluate_instructions.py) generates free text per finding and
+ * string-matches it; lm-evaluation-harness's loglikelihood (and HF compute_transition_scores) instead reads log p(answer | prompt) off
+ * one forward per (prompt + answer).  Here a prompt is prefilled once and every candidate answer runs only its own rows, reading the
+ * prompt's keys in place. */
+/* rv_attn_extend_bf16 with two key sources.  Sequence b has n_b = cu_q[b+1] - cu_q[b] >= 0 query rows at positions prefix_len[b] + i,
+ * and query i attends causally to the keys [0, prefix_len[b] + i]: key j < prefix_len[b] is position j of row prefix_row[b] of
+ * `prefix` (bf16 [P_rows][P_max][ld_p], row stride bs_p), key j >= prefix_len[b] is position j - prefix_len[b] of row b of `tail`
+ * (bf16 [B][T_max][ld_t], row stride bs_t; the n_b tail rows are already written).  Both use the KV cache's column layout (K of kv
+ * head g at g*hd, V at v_off + g*hd).  cu_q (B + 1), prefix_row and prefix_len (B) are int32 device arrays; max_q >= every n_b and
+ * max_q <= T_max.  The work split, the 64-key stages, the online softmax, the partials and the combine are rv_attn_extend_bf16's and
+ * the chunk grid is fixed in absolute key positions (only the address a staged key is loaded from is chosen per key): out is
+ * BIT-IDENTICAL to rv_attn_extend_bf16 with r = prefix_len and the same `chunk` on the cache materialised as
+ * prefix[prefix_row[b], :prefix_len[b]] ++ tail[b, :n_b], for hd 64 and 128 and up to 8 q heads per kv head.  Keys past a query's own
+ * position are never loaded: prefix positions >= prefix_len[b] and tail positions >= n_b may hold anything (NaN included).  A sequence
+ * with n_b == 0 writes nothing.  A sequence whose prefix_row[b] is outside [0, P_rows) or whose prefix_len[b] is outside [0, P_max]
+ * is not read at all and its rows of out are zeros.  part: M * H * ceil((P_max + T_max) / chunk) * (hd + 2) floats.  Refusals
+ * (RV_ERR_ARG) as rv_attn_extend_bf16's, and a null prefix_row / prefix_len, P_rows <= 0, P_max <= 0, T_max <= 0, max_q > T_max. */
+int rv_attn_extend_prefix_bf16(const void* q, int64_t ld_q, const void* prefix, int64_t ld_p, int64_t bs_p, int P_rows, int P_max,
+                               const void* tail, int64_t ld_t, int64_t bs_t, int T_max, int v_off, const int32_t* cu_q,
+                               const int32_t* prefix_row, const int32_t* prefix_len, void* out, int64_t ld_o, void* part,
+                               int64_t part_bytes, int B, int M, int max_q, int H, int Hkv, int hd, int chunk, float scale, void* stream);
+/* The log-prob of one given token per row, and the row's argmax: output row r reads row s = src_row ? src_row[r] : r of the fp32
+ * logits x (x_rows rows of ld floats, first n columns, n <= 262144) and gets
+ *     logprob[r] = fl(fl(x[s][target[r]] - m) - L),
+ * (m, L) by the statements rv_log_softmax_rows_f32 runs (csrc/log_softmax.h), so the value is the bits that entry leaves at that
+ * column; x is never written.  target[r] < 0 (an ignored position, e.g. -100): 0.0f.  target[r] >= n: NaN.  s outside [0, x_rows):
+ * NaN, argmax[r] = -1, and no row is read.  A row with a NaN, a +inf or no finite entry gives NaN, as there; a -inf target in a finite
+ * row gives -inf.  argmax (int64 [rows], or NULL to skip) follows rv_argmax_rows_f32's rule (lowest index among equal maxima, NaN
+ * above everything) and is written whatever the target.  src_row (int32 [rows], or NULL) lets several outputs share one row, e.g. the
+ * candidates that continue one prompt.  Columns >= n are never read.  One workgroup per output row, no atomics: a row's bits depend on
+ * neither `rows` nor the other rows. */
+int rv_token_logprob_rows_f32(const float* x, int64_t ld, int x_rows, int n, const int32_t* src_row, const int32_t* target, int rows,
+                              float* logprob, int64_t* argmax, void* stream);
+
 /* LoRA merge (peft merge_and_unload): W[N,K] <- bf16_rne(float(W) + scale * sum_j B[n,j] A[j,k]) in place, 1 <= r <= 256.  The sum runs in
  * fp32 on MFMA in a fixed order (r zero-padded to a multiple of 32) and is rounded once: the same inputs give the same bits for any
  * grid and any placement of W.  W: bf16 rows of ldw elements (a row slice of a fused q|k|v or gate|up store is fine), 16-byte aligned,

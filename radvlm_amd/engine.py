@@ -1332,6 +1332,75 @@ class LlavaEngine:
             cache.lens[seq] = lens
         return cache, logits[:, :self.vocab]
 
+    def score_tails(self, prefix, prefix_row, tails, logits, arrays=None):
+        """Log-probs of given continuations of prefilled prompts (model.score()).  prefix: a bf16 KVCache filled by prefill(), one row
+        per distinct prompt, and `logits` the fp32 last-row logits prefill() returned with it; candidate k continues row prefix_row[k]
+        with the tokens tails[k] (n_k >= 1 ids).  Its tokens t_0 .. t_{n-2} run at positions P .. P + n - 2 (P = prefix.lens[row]) as
+        one packed batch of M = sum(n_k - 1) rows through extend()'s layer sequence -- RMSNorm, q|k|v, RoPE at the explicit positions,
+        the K|V rows written into a tail cache [C, T_max, 2*kvd] per layer, attention over the prompt's keys read in place from
+        `prefix` and then the candidate's own (rv_attn_extend_prefix_bf16: no copy of a prompt, however many candidates share it),
+        o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual -- then the final norm on every row and the lm_head in row slices
+        whose fp32 logits stay under scoring.LOGITS_BYTES_CAP, each slice going straight into rv_token_logprob_rows_f32 with the next
+        token as target.  t_0 is scored from row prefix_row[k] of `logits`; a one-token candidate runs no row.  The quantised decoders
+        work as in extend() (_decode_linear).  prefix is only read; self.ctx and the optimizer state are not touched.
+        arrays: scoring.launch_arrays(prefix_row, prefix.lens[prefix_row], tails), when the caller has it already.
+        Returns (fp32 log-probs, int64 argmax ids), device tensors of sum(n_k) entries: candidate k's tokens in order at
+        arrays.offsets[k] .. offsets[k + 1]."""
+        self._check_generation()
+        self._refuse_int8(prefix, "score_tails()")
+        from . import scoring
+        l = self.l
+        d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
+        hd, Hkv, kvd, V = self.hd, self.Hkv, self.kvd, self.vocab
+        prow = np.asarray(prefix_row, dtype=np.int64).reshape(-1)
+        if prow.shape[0] != len(tails) or (prow < 0).any() or (prow >= prefix.B).any():
+            raise ValueError(f"prefix_row must hold one index into the cache's {prefix.B} rows per candidate")
+        a = arrays if arrays is not None else scoring.launch_arrays(prow, prefix.lens[prow], tails)
+        if a.C != len(tails) or not np.array_equal(a.prefix_row, prow) or not np.array_equal(a.prefix_len, prefix.lens[prow]):
+            raise ValueError("arrays does not describe these candidates on this cache")
+        if logits.dim() != 2 or logits.shape[0] != prefix.B or logits.dtype != torch.float32:
+            raise ValueError(f"logits must be the fp32 [{prefix.B}, vocab] rows prefill() returned with the cache")
+        total = int(a.offsets[-1])
+        lp = torch.empty(total, dtype=torch.float32, device=self.device)
+        am = torch.empty(total, dtype=torch.int64, device=self.device)
+        first_lp, first_am = ops.token_logprob_rows(logits, V, self._dev(a.first_targets), src_row=self._dev(a.src_row))
+        first_out = self._dev(a.first_out)
+        lp.index_copy_(0, first_out, first_lp)
+        am.index_copy_(0, first_out, first_am)
+        if a.M == 0:
+            return lp, am
+        C, T_max = a.C, a.T_max
+        pos_d, cu_d = self._dev(a.positions), self._dev(a.cu_q)
+        prow_d, plen_d, rows = self._dev(a.prefix_row), self._dev(a.prefix_len), self._dev(a.tail_rows)
+        cs = self.rope_table(prefix.L_max + T_max)
+        table = torch.zeros(1, d, dtype=BF16, device=self.device)      # candidates are text: the splice reads token embeddings only
+        x = ops.gather_rows(self._dev(a.tokens), d, self.W("model.embed_tokens.weight"), table)
+        tail = [torch.zeros(C, T_max, 2 * kvd, dtype=BF16, device=self.device) for _ in range(L)]
+        for i in range(L):
+            lv, wq = self._layer_views(i), self._layer_wq(i)
+            h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
+            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"))
+            ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
+            tail[i].view(C * T_max, 2 * kvd).index_copy_(0, rows, qkv[:, d:])
+            attn = ops.attn_extend_prefix(qkv[:, :d], prefix.layers[i], tail[i], cu_d, prow_d, plen_d, H, Hkv, hd, kvd, a.max_q)
+            x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"))
+            h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
+            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu")), F)
+            x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"))
+        del tail
+        hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
+        w_head = self.W("lm_head.weight")
+        step = max(1, scoring.LOGITS_BYTES_CAP // (int(w_head.shape[0]) * 4))
+        tgt, row_out = self._dev(a.targets), self._dev(a.row_out)
+        for m0 in range(0, a.M, step):
+            m1 = min(a.M, m0 + step)
+            sl = self._decode_linear(hN[m0:m1], w_head, out_dtype=torch.float32)
+            s_lp, s_am = ops.token_logprob_rows(sl, V, tgt[m0:m1])
+            lp.index_copy_(0, row_out[m0:m1], s_lp)
+            am.index_copy_(0, row_out[m0:m1], s_am)
+            del sl
+        return lp, am
+
     def _cross_entropy(self, logits, tgt, V, inv, gscale):
         from . import lib
         rows = logits.shape[0]

@@ -130,6 +130,9 @@ _SIGS = {
     "rv_log_softmax_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p],
     "rv_beam_topk_f32": [_c_void_p, _i64, _i32, _i32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p],
     "rv_cfg_guide_rows_f32": [_c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _f32, _c_void_p, _i64, _c_void_p],
+    "rv_attn_extend_prefix_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _c_void_p,
+                                   _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
+    "rv_token_logprob_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p],
     "rv_lora_merge_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
 }
 

@@ -355,6 +355,26 @@ class LlavaLlamaForCausalLM:
         return generate_batch(self.engine, inputs, images, image_sizes, cfg, max_batch_size=max_batch_size, return_logprobs=return_logprobs)
 
     @torch.no_grad()
+    def score(self, inputs, candidates, images=None, image_sizes=None, max_batch_size=32, **kwargs):
+        """Log-likelihoods of given answers (lm-evaluation-harness's `loglikelihood`, HF's compute_transition_scores on a sequence the
+        caller already has): closed-ended VQA and multiple choice (log p("Yes" | image, question) against log p("No" | ...)), per-finding
+        ranking scores, the perplexity of a reference report.
+        inputs / images / image_sizes: generate_batch()'s request format, N unpadded 1-D prompts and per-request images.  candidates: a
+        list of N lists of 1-D token-id sequences (text ids in [0, vocab)).  Each distinct prompt is prefilled once -- the tower and the
+        prompt pass run once per prompt, max_batch_size prompts at a time, equal prompts of a group once -- and every candidate runs
+        only its own tokens, reading the prompt's keys in place (LlavaEngine.score_tails).
+        Returns a scoring.ScoreOutput: .token_logprobs[i][c] fp32 CPU tensor [len(candidate)], log_softmax(raw logits)[token] at every
+        candidate position; .logprobs[i] float64 [C_i], their sums (fp64, token order); .is_greedy[i] bool [C_i], every token its row's
+        argmax; .best(length_normalized=False) the best candidate's index per prompt (ties: the lower index).
+        The raw distribution is the point: no logits processors, no sampling, no kv_cache_dtype (any other keyword: TypeError).
+        ValueError for an empty prompt, candidate or candidate list, candidate ids outside [0, vocab) and lists of different lengths;
+        NotImplementedError for LoRA models (merge_and_unload() first).  int8 / MXFP4 decoders work.  The training state is not touched."""
+        if kwargs:
+            raise TypeError(f"score() got unexpected keyword arguments {sorted(kwargs)}")
+        from ...scoring import score
+        return score(self.engine, list(inputs), candidates, images, image_sizes, max_batch_size=max_batch_size)
+
+    @torch.no_grad()
     def generate_beams(self, inputs=None, images=None, image_sizes=None, num_beams=1, modalities=("image",), **kwargs):
         """Beam search (HF generate(num_beams=...) on the spliced inputs_embeds: transformers 5.x GenerationMixin._beam_search, restated
         in generation.BeamState).  inputs / images / image_sizes as in generate().  Returns the NEW tokens only, LongTensor

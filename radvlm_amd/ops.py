@@ -702,6 +702,51 @@ def attn_extend(q, cache, cu_q, r, H, Hkv, hd, v_off, max_q, out=None, chunk=EXT
     return out
 
 
+def attn_extend_prefix(q, prefix, tail, cu_q, prefix_row, prefix_len, H, Hkv, hd, v_off, max_q, out=None, chunk=EXTEND_CHUNK, scale=None):
+    """attn_extend with two key sources (rv_attn_extend_prefix_bf16): sequence b's query rows cu_q[b] .. cu_q[b+1] - 1 sit at positions
+    prefix_len[b] + i; keys below prefix_len[b] are read in place from row prefix_row[b] of `prefix` (bf16 [P_rows, P_max, width], e.g. a
+    prefilled KV cache shared by many candidates), the rest from row b of `tail` (bf16 [B, T_max, width], the sequence's own rows, already
+    written).  cu_q (B + 1) / prefix_row / prefix_len (B) int32 device arrays, 1 <= max_q <= T_max.  Bit-identical to attn_extend on the
+    materialised cache at the same chunk.  Returns bf16 [M, H*hd]."""
+    _chk(q), _chk(prefix), _chk(tail), _chk(cu_q, torch.int32), _chk(prefix_row, torch.int32), _chk(prefix_len, torch.int32)
+    assert prefix.dim() == 3 and tail.dim() == 3 and prefix.is_contiguous() and tail.is_contiguous()
+    P_rows, P_max, width = prefix.shape
+    B, T_max, tw = tail.shape
+    M = q.shape[0]
+    assert tw == width and q.shape == (M, H * hd) and q.stride(1) == 1 and cu_q.numel() == B + 1
+    assert prefix_row.numel() == B and prefix_len.numel() == B
+    assert cu_q.is_contiguous() and prefix_row.is_contiguous() and prefix_len.is_contiguous() and 1 <= max_q <= M
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if out is None:
+        out = torch.empty(M, H * hd, dtype=BF16, device=q.device)
+    assert out.shape == (M, H * hd) and out.stride(1) == 1
+    nch = (P_max + T_max + chunk - 1) // chunk
+    part = torch.empty(M * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    lib.call("rv_attn_extend_prefix_bf16", q, q.stride(0), prefix, width, P_max * width, P_rows, P_max, tail, width, T_max * width, T_max,
+             v_off, cu_q, prefix_row, prefix_len, out, out.stride(0), part, part.numel() * 4, B, M, int(max_q), H, Hkv, hd, chunk,
+             float(scale))
+    return out
+
+
+def token_logprob_rows(x, n, target, src_row=None, want_argmax=True):
+    """(logprob fp32 [rows], argmax int64 [rows] or None) of rv_token_logprob_rows_f32: output row r reads row src_row[r] (r when
+    src_row is None) of the fp32 logits x, first n columns, and gets log_softmax_rows' bits at column target[r] (int32 [rows] device;
+    negative: 0.0, >= n: NaN) and the row's argmax (argmax_rows' rule).  x is not modified."""
+    _chk(x, torch.float32), _chk(target, torch.int32)
+    assert x.dim() == 2 and x.stride(1) == 1 and 0 < n <= min(x.shape[1], LOGITS_PROCESS_MAX_N)
+    rows = target.numel()
+    assert rows >= 1 and target.is_contiguous()
+    if src_row is not None:
+        _chk(src_row, torch.int32)
+        assert src_row.numel() == rows and src_row.is_contiguous()
+    else:
+        assert rows <= x.shape[0]
+    logprob = torch.empty(rows, dtype=torch.float32, device=x.device)
+    argmax = torch.empty(rows, dtype=torch.int64, device=x.device) if want_argmax else None
+    lib.call("rv_token_logprob_rows_f32", x, x.stride(0), x.shape[0], int(n), src_row, target, rows, logprob, argmax)
+    return logprob, argmax
+
+
 def kv_append(src, cache, pos):
     """cache[b, pos[b], :] = src[b, :] (src [B, width] bf16 rows, e.g. the k|v columns of the qkv product; pos int32 [B] device)."""
     _chk(src), _chk(cache), _chk(pos, torch.int32)

@@ -83,6 +83,17 @@
         # the image (llava_ov_qwen2_7b: anyres_max_9, 10 tiles, 8 slots), image-major order, 32 slots, EOS disabled; arms: sharing off,
         # sharing on with shared_route "plain" and with "shared", one untimed pass of each and then interleaved three times; per
         # arm the median wall time with that run's time inside prefill / extend, tower runs (calls, images) and decode ms / step
+  python tools/decode_bench.py --score-shapes [--out FILE]   # kernel A/B of scoring: rv_attn_extend_bf16 on the materialised cache
+        # (every candidate's row holds a copy of the prompt's keys) vs rv_attn_extend_prefix_bf16 (one prompt row read in place), the 7B
+        # and Qwen2-7B head shapes, a 704-position prompt with 2, 8, 32 candidates of 4 and of 64 tokens (3 / 63 rows each); the
+        # protocol of --kv8-shapes: cold cache, interleaved, median of 20, torch.equal asserted before timing; the extend arm's
+        # p10 / p90 are its spread; plus the bytes per candidate of the copy the prefix kernel avoids, over the layers
+  python tools/decode_bench.py --score [--geos ..] [--reps 3] [--out FILE]
+        # model.score() against the one-by-one route: the training forward on prompt + candidate with the candidate as labels,
+        # reading the loss, once per candidate (the tower and the prompt's rows run every time); one image prompt of 704 spliced
+        # positions (or the shortest the geometry's image allows), C = 2, 8, 32 candidates of 4 and of 64 tokens, one engine per
+        # geometry, one untimed pass of both arms and then the arms alternated --reps times; wall ms per call, medians, the
+        # one-by-one arm's spread (max - min) and whether score() is faster by more than that spread; the decoder rows of both arms
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -1036,6 +1047,107 @@ def shared_shapes(reps=20, keys=(704, 7603), groups=(2, 4, 8, 16, 32), B=32, own
     return out
 
 
+def score_shapes(reps=20, prompt=704, cands=(2, 8, 32), lens=(4, 64)):
+    """rv_attn_extend_bf16 on the materialised cache vs rv_attn_extend_prefix_bf16 per head shape: C candidates of n tokens (n - 1 rows
+    each) after one prompt of `prompt` positions, interleaved, cold cache."""
+    out = []
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
+    for geo in ("llava15_7b", "llava_ov_qwen2_7b"):
+        l = GEOMETRIES[geo]["lm"]
+        H, hd, L = l["heads"], l["d"] // l["heads"], l["layers"]
+        Hkv = l.get("kv_heads", H)
+        kvd = Hkv * hd
+        for n in lens:
+            T = n - 1
+            for C in cands:
+                prefix = torch.randn(1, prompt, 2 * kvd, device="cuda", dtype=torch.bfloat16)
+                tail = torch.randn(C, T, 2 * kvd, device="cuda", dtype=torch.bfloat16)
+                mat = torch.cat([prefix.expand(C, -1, -1), tail], dim=1).contiguous()          # the copy share_prefix would make
+                q = torch.randn(C * T, H * hd, device="cuda", dtype=torch.bfloat16)
+                cu = torch.arange(C + 1, dtype=torch.int32, device="cuda") * T
+                plen = torch.full((C,), prompt, dtype=torch.int32, device="cuda")
+                prow = torch.zeros(C, dtype=torch.int32, device="cuda")
+                fns = {"extend": lambda: ops.attn_extend(q, mat, cu, plen, H, Hkv, hd, kvd, T),
+                       "prefix": lambda: ops.attn_extend_prefix(q, prefix, tail, cu, prow, plen, H, Hkv, hd, kvd, T)}
+                assert torch.equal(fns["extend"](), fns["prefix"]())
+                ts = _timed_interleaved(fns, flush, reps)
+                ex, px = float(np.median(ts["extend"])), float(np.median(ts["prefix"]))
+                p10, p90 = float(np.percentile(ts["extend"], 10)), float(np.percentile(ts["extend"], 90))
+                out.append(dict(mode="score_kernel_ab", geo=geo, H=H, Hkv=Hkv, hd=hd, prompt=prompt, candidates=C, candidate_tokens=n,
+                                rows=C * T, extend_us=round(ex, 2), prefix_us=round(px, 2), prefix_over_extend=round(px / ex, 3),
+                                extend_p10_us=round(p10, 2), extend_p90_us=round(p90, 2),
+                                prefix_p10_us=round(float(np.percentile(ts["prefix"], 10)), 2),
+                                prefix_p90_us=round(float(np.percentile(ts["prefix"], 90)), 2),
+                                prefix_faster_by_more_than_extend_spread=bool(ex - px > p90 - p10),
+                                prefix_slower_by_more_than_extend_spread=bool(px - ex > p90 - p10),
+                                copy_bytes_avoided_per_candidate=prompt * 2 * kvd * 2 * L, reps=reps, chunk=ops.EXTEND_CHUNK,
+                                kernel_src=_src_hash()))
+                print(f"# {geo} C {C} x {n} tokens: extend {ex:.1f} us, prefix {px:.1f} us", file=sys.stderr, flush=True)
+                del prefix, tail, mat, q
+    return out
+
+
+def score_e2e(geo, reps=3, prompt=704, cands=(2, 8, 32), lens=(4, 64)):
+    """--score: scoring.score() vs one training forward per (prompt + candidate), reading the loss."""
+    from radvlm_amd import scoring
+    g = GEOMETRIES[geo]
+    eng = LlavaEngine(g, device="cuda:0", init="fast", seed=0)
+    rng = np.random.default_rng(0)
+    img = g["vision"]["image"]
+    image = torch.randn(3, img, img, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    size = (img, img)
+    probe = np.full(36, 5, dtype=np.int64)
+    probe[35] = -200
+    base = int(eng.plan(probe[None], None, None, [image], [size])["lens"][0])      # 35 tokens, then the image's rows
+    ids = rng.integers(3, eng.vocab, size=36 + max(0, prompt - base), dtype=np.int64)
+    ids[35] = -200
+    P = int(eng.plan(ids[None], None, None, [image], [size])["lens"][0])
+    recs = []
+    for n in lens:
+        for C in cands:
+            cs = [rng.integers(3, eng.vocab, n).astype(np.int64) for _ in range(C)]
+
+            def shared():
+                return scoring.score(eng, [ids], [cs], images=[image], image_sizes=[size])
+
+            def one_by_one():
+                losses = []
+                for c in cs:
+                    full = np.concatenate([ids, c])[None]
+                    labels = np.full(full.shape, -100, dtype=np.int64)
+                    labels[0, ids.size:] = c
+                    losses.append(eng.forward(full, np.ones(full.shape, dtype=bool), labels, [image], image_sizes=[size]))
+                    eng.ctx = None
+                return [float(v) for v in losses]
+
+            def timed(f):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                r = f()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3, r
+
+            with torch.no_grad():
+                _, so = timed(shared)                                           # one untimed pass of both arms
+                _, lo = timed(one_by_one)
+                # the two routes score the same thing: mean token log-prob against the loss, within the bf16-logits CE's rounding
+                gap = max(abs(-float(so.logprobs[0][c]) / n - lo[c]) for c in range(C))
+                ts = {"score": [], "one_by_one": []}
+                for _ in range(reps):
+                    ts["score"].append(timed(shared)[0])
+                    ts["one_by_one"].append(timed(one_by_one)[0])
+            sm, om = float(np.median(ts["score"])), float(np.median(ts["one_by_one"]))
+            spread = max(ts["one_by_one"]) - min(ts["one_by_one"])
+            recs.append(dict(mode="score_e2e", geo=geo, prompt_positions=P, candidates=C, candidate_tokens=n, reps=reps,
+                             score_ms=round(sm, 2), one_by_one_ms=round(om, 2), score_over_one_by_one=round(sm / om, 4),
+                             score_ms_all=[round(v, 2) for v in ts["score"]], one_by_one_ms_all=[round(v, 2) for v in ts["one_by_one"]],
+                             one_by_one_spread_ms=round(spread, 2), score_faster_by_more_than_one_by_one_spread=bool(om - sm > spread),
+                             decoder_rows_score=P + C * (n - 1), decoder_rows_one_by_one=C * (P + n), tower_passes_score=1,
+                             tower_passes_one_by_one=C, max_abs_mean_nll_gap=round(gap, 5), kernel_src=_src_hash()))
+            print(f"# {geo} C {C} x {n} tokens: score {sm:.1f} ms, one by one {om:.1f} ms", file=sys.stderr, flush=True)
+    return recs
+
+
 class _ShareClock:
     """Wall time inside the engine's prompt passes (prefill, extend) and decode steps, and the tower's runs, synchronised around each
     call (the scheduler synchronises every step anyway).  prefill called from extend is not counted twice."""
@@ -1416,6 +1528,8 @@ def main():
     ap.add_argument("--cfg-kernel-ab", action="store_true")
     ap.add_argument("--shared-shapes", action="store_true")
     ap.add_argument("--share-prefix", action="store_true")
+    ap.add_argument("--score", action="store_true")
+    ap.add_argument("--score-shapes", action="store_true")
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -1458,6 +1572,10 @@ def main():
         recs = cfg_kernel_ab()
     elif a.shared_shapes:
         recs = shared_shapes()
+    elif a.score_shapes:
+        recs = score_shapes()
+    elif a.score:
+        recs = [r for g in a.geos.split(",") for r in score_e2e(g, reps=min(a.reps, 3))]
     elif a.share_prefix:
         new = a.new if a.new != ap.get_default("new") else 32
         recs = [r for g in a.geos.split(",") for r in share_prefix_e2e(g, new=new, reps=min(a.reps, 3))]
