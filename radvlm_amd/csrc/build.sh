@@ -2,8 +2,8 @@
 # Build libradvlm_hip.so (gfx950) in-tree. hipcc cross-compiles without a GPU.
 #   build.sh [out.so [flags...]]   variant build: every source again with the extra flags (e.g. -DRV_ATTN_STAMPS), objects in build/<out>/ (lib_S.so: build/lib_S/),
 #                                  library radvlm_amd/<out.so> (load it with RADVLM_HIP_LIB); the default build's objects stay as they are
-# The compiler's per-kernel resource report is kept (build/*.res) and the default build FAILS if a hot kernel (GEMM, attention) touches
-# scratch memory (gemv.hip and decode.hip: the skinny GEMM / decode-attention accumulators too; lora_merge.hip; extend.hip; sample.hip; beam.hip; lookup.hip; kvq.hip; cfg.hip; prefix.hip; score.hip): a rolled epilogue loop once turned the GEMM accumulators into a scratch array and cost 18 % unnoticed.
+# The compiler's per-kernel resource report is kept (build/*.res) and the default build FAILS if a kernel of any source in SRCS touches
+# scratch memory: a rolled epilogue loop once turned the GEMM accumulators into a scratch array and cost 18 % unnoticed.
 set -e
 cd "$(dirname "$0")"
 SRCS="gemm_bf16 attention ops gemv decode lora_merge extend sample beam lookup kvq cfg prefix score"
@@ -23,7 +23,7 @@ for f in $SRCS; do
 done
 for p in "${pids[@]}"; do wait $p; done
 grep -h "error\|warning" $OBJ/*.res | grep -v "Rpass" | head -20 || true
-if grep -h -B8 "ScratchSize \[bytes/lane\]: [1-9]" $OBJ/gemm_bf16.res $OBJ/attention.res $OBJ/gemv.res $OBJ/decode.res $OBJ/lora_merge.res $OBJ/extend.res $OBJ/sample.res $OBJ/beam.res $OBJ/lookup.res $OBJ/kvq.res $OBJ/cfg.res $OBJ/prefix.res $OBJ/score.res | grep "Function Name"; then
+if grep -h -B8 "ScratchSize \[bytes/lane\]: [1-9]" $(printf "$OBJ/%s.res " $SRCS) | grep "Function Name"; then
   # a variant may spill on purpose (the in-kernel cycle stamps of -DRV_STAMPS do): it is only told
   if [ $# -gt 0 ]; then echo "WARNING: the kernels above use scratch memory (see $OBJ/*.res)" >&2
   else echo "ERROR: the kernels above use scratch memory (see $OBJ/*.res)" >&2; exit 1; fi

@@ -202,7 +202,7 @@ def test_entry_points_declared_and_bound():
         decl = re.search(r"int " + name + r"\(([^;]*)\);", hdr).group(1)
         assert len(decl.split(",")) == len(lib._SIGS[name])
     build = open(os.path.join(ROOT, "radvlm_amd", "csrc", "build.sh")).read()
-    assert "kvq" in build.split('SRCS="')[1].split('"')[0].split() and "$OBJ/kvq.res" in build
+    assert "kvq" in build.split('SRCS="')[1].split('"')[0].split() and '$(printf "$OBJ/%s.res " $SRCS)' in build
 
 
 def test_public_surface():

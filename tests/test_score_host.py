@@ -20,7 +20,7 @@ def test_score_symbols_declared_and_bound():
     for s in ("rv_attn_extend_prefix_bf16", "rv_token_logprob_rows_f32"):
         assert s in declared and s in lib.EXPORTED_SYMBOLS and s in lib._SIGS, s
     build = open(os.path.join(ROOT, "radvlm_amd", "csrc", "build.sh")).read()
-    assert re.search(r'SRCS="[^"]*\bscore\b', build) and "$OBJ/score.res" in build          # built, and under the scratch gate
+    assert re.search(r'SRCS="[^"]*\bscore\b', build) and '$(printf "$OBJ/%s.res " $SRCS)' in build          # built, and under the scratch gate
 
 
 def test_candidate_validation():

@@ -135,7 +135,7 @@ def test_entry_points_declared_and_bound():
     for name in ("rv_w4_row_bytes", "rv_w4_scale_row_bytes"):
         assert name in declared and name in lib.EXPORTED_SYMBOLS
     build = open(os.path.join(ROOT, "radvlm_amd", "csrc", "build.sh")).read()
-    assert "gemv" in build.split('SRCS="')[1].split('"')[0].split() and "$OBJ/gemv.res" in build
+    assert "gemv" in build.split('SRCS="')[1].split('"')[0].split() and '$(printf "$OBJ/%s.res " $SRCS)' in build
     so = os.path.join(ROOT, "radvlm_amd", "libradvlm_hip.so")
     if os.path.exists(so):
         l = lib.load()

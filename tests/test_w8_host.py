@@ -95,7 +95,7 @@ def test_entry_points_declared_and_bound():
         assert len(decl.split(",")) == len(lib._SIGS[name])
     assert "rv_w8_row_bytes" in declared and "rv_w8_row_bytes" in lib.EXPORTED_SYMBOLS
     build = open(os.path.join(ROOT, "radvlm_amd", "csrc", "build.sh")).read()
-    assert "gemv" in build.split('SRCS="')[1].split('"')[0].split() and "$OBJ/gemv.res" in build
+    assert "gemv" in build.split('SRCS="')[1].split('"')[0].split() and '$(printf "$OBJ/%s.res " $SRCS)' in build
     so = os.path.join(ROOT, "radvlm_amd", "libradvlm_hip.so")
     if os.path.exists(so):
         l = lib.load()
