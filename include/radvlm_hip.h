@@ -159,7 +159,13 @@ int rv_rope_inplace(void* x, int64_t ld, const float* cos_sin, int rows, int S, 
  * softmax_fp32(scale * Q K^T + causal + key-padding) V: modeling_llama.py:349-368 + :1191-1225,
  * llama_flash_attn_monkey_patch.py:51-69; non-causal for HF:modeling_clip.py:259-277.
  * q/k/out: token-major [(b*S+s)*ld + h*hd + e]; vT: [b,h,hd,S_pad] (zero padded); lse: fp32 [b,h,S_pad];
- * lens (optional int32 [B]): valid keys per sample (right padding).  hd in {64,128}; S_pad % 64 == 0. */
+ * lens (optional int32 [B]): valid keys per sample (right padding).  hd in {64,128}; S_pad % 64 == 0.
+ * Precondition (all attention entry points): 1 <= lens[b] <= S -- it is not checked; a sample without a valid key has no softmax.
+ * Rows at or beyond lens[b] (padded layout): the forward still writes out and lse for every row below S -- such a row attends the
+ * keys below lens[b] (and, causal, not after itself); the values are finite, and they are no contract.  The backward expects dout = 0
+ * in those rows and then writes dq, dk and dv of those rows as exact zeros.  It never lets lse / delta of a row at or beyond lens[b]
+ * (or the sample's length in a packed batch), or of [S, S_pad), reach a gradient: those entries may hold anything, NaN included.
+ * Nothing is written at or beyond row S of a sample's lse / delta, and nothing outside the [rows, H*hd] extent of out / dq / dk / dv. */
 int rv_attn_fwd(const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* vT, void* out, int64_t ld_o,
                 float* lse, const int32_t* lens, int B, int H, int S, int S_pad, int hd, int causal, float scale,
                 const void* zeros16, void* stream);

@@ -741,8 +741,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_nat_kernel(AttnParams 
         }
         dsum += __shfl_xor(dsum, 16, 64);
         dsum += __shfl_xor(dsum, 32, 64);
-        lse2[qs] = P.lse[(long)(b * P.H + h) * P.S_pad + row] * LOG2E;
-        dl[qs] = dsum;
+        // rows at or beyond the sample's length: whatever lse / delta hold there (stale or never written) must not reach dQ: p = exp2(-inf) = 0
+        const bool live = q0 + qs * 16 + c < len;
+        lse2[qs] = live ? P.lse[(long)(b * P.H + h) * P.S_pad + row] * LOG2E : INFINITY;
+        dl[qs] = live ? dsum : 0.f;
         if (g == 0 && q0 + qs * 16 + c < S) P.delta[(long)(b * P.H + h) * P.S_pad + row] = dsum;   // for the dK/dV pass
     }
     const int kv_end = CAUSAL ? min(len, (qblk + 1) * (32 * NW)) : len;
@@ -987,12 +989,15 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_nat_kernel(AttnParams
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float p = fexp2(__builtin_fmaf(s[qq][r], sl2, -ls[r] * LOG2E));
-                        if (EDGE) {
+                        float ds = p * (dp[qq][r] - dl[r]);
+                        if (EDGE) {   // both selected: lse / delta of a masked row may hold anything (0 * NaN would poison the wave's 16 keys)
                             const int qidx = qrow + r;
-                            p = ((kidx < len) && (qidx < q_end) && (!CAUSAL || kidx <= qidx)) ? p : 0.f;
+                            const bool ok = (kidx < len) && (qidx < q_end) && (!CAUSAL || kidx <= qidx);
+                            p = ok ? p : 0.f;
+                            ds = ok ? ds : 0.f;
                         }
                         s[qq][r] = p;
-                        dp[qq][r] = p * (dp[qq][r] - dl[r]);
+                        dp[qq][r] = ds;
                     }
                 }
                 const bf16x8 pf = pack8(s[0], s[1]), dsf = pack8(dp[0], dp[1]);
@@ -1075,8 +1080,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_bwd_dq_kernel(AttnParams
         }
         dsum += __shfl_xor(dsum, 16, 64);
         dsum += __shfl_xor(dsum, 32, 64);
-        lse2[qs] = P.lse[(long)(b * P.H + h) * P.S_pad + row] * LOG2E;
-        dl[qs] = dsum;
+        // rows at or beyond the sample's length: whatever lse / delta hold there (stale or never written) must not reach dQ: p = exp2(-inf) = 0
+        const bool live = q0 + qs * 16 + c < len;
+        lse2[qs] = live ? P.lse[(long)(b * P.H + h) * P.S_pad + row] * LOG2E : INFINITY;
+        dl[qs] = live ? dsum : 0.f;
         if (g == 0 && q0 + qs * 16 + c < S) P.delta[(long)(b * P.H + h) * P.S_pad + row] = dsum;   // for the dK/dV pass
     }
     const int kv_end = CAUSAL ? min(len, (qblk + 1) * (32 * NW)) : len;

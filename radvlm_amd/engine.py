@@ -269,9 +269,13 @@ class LlavaEngine:
     def _stat_buffer(self, key, B, H, s_pad):
         """fp32 [B, H, s_pad] softmax-statistics buffers (lse per layer, delta), allocated once (zeroed) and reused every step: the
         kernels overwrite the entries of valid rows only -- no fill kernel per layer.  With ragged data a later batch of the same padded
-        shape but shorter samples therefore sees STALE lse / delta in rows >= len; that is harmless by construction, not by zeroing:
-        the dK/dV edge tiles select p = 0 for query rows >= q_end before any use of lse / delta, and the dQ pass reads them only for
-        rows < len (tests/test_train_features_gpu.py::test_stale_softmax_statistics_are_masked)."""
+        shape but shorter samples therefore sees STALE lse / delta in rows >= len (padded layout: the forward and the dQ pass rewrite
+        every row below S, so only [S, s_pad) is stale; packed: everything from the sample's length on).  That is harmless by
+        construction, not by zeroing, whatever the stale values are (NaN and Inf included): the dK/dV passes reach such rows only in
+        their edge tiles, where p AND dS are selected to 0 after lse / delta were used (a select, not a product with 0); the dQ passes
+        replace lse by +inf and delta by 0 for rows >= len in their prologue, so p = exp2(-inf) = 0 there
+        (tests/test_train_features_gpu.py::test_stale_softmax_statistics_are_masked on the engine,
+        tests/test_attention_edges_gpu.py::test_stale_softmax_statistics_never_reach_a_gradient on the kernels)."""
         k = (key, B, H, s_pad)
         buf = self._stats.get(k)
         if buf is None:

@@ -373,7 +373,7 @@ def test_stale_softmax_statistics_are_masked(golden_dir, packed):
         return eng.grads.clone()
     a = LlavaEngine(GEOMETRIES["toy"], device="cuda:0", init="portable", seed=0, packed=packed)
     run(a, am_full, lab)                                  # fills lse / delta for all rows
-    # plant large (finite: stale values are old statistics) numbers where a later, shorter batch must not look
+    # plant large finite numbers (stale values are old statistics) where a later, shorter batch must not look
     assert a._stats
     for k, buf in a._stats.items():
         buf[-1, :, :] = torch.where(buf[-1] != 0, torch.full_like(buf[-1], 1e30), buf[-1])     # the last sample's rows: all stale now
@@ -381,6 +381,12 @@ def test_stale_softmax_statistics_are_masked(golden_dir, packed):
     b = LlavaEngine(GEOMETRIES["toy"], device="cuda:0", init="portable", seed=0, packed=packed)
     gb = run(b, am_short, lab_short)
     assert torch.isfinite(ga.float()).all() and torch.equal(ga, gb)
+    # and NaN: after one diverged step the cached buffers hold NaN for every later step, and 0 * NaN is not 0 -- a masked row's statistics
+    # must be dropped by a select, never by a product (tests/test_attention_edges_gpu.py pins the same at kernel level)
+    for k, buf in a._stats.items():
+        buf[-1, :, :] = torch.where(buf[-1] != 0, torch.full_like(buf[-1], float("nan")), buf[-1])
+    gn = run(a, am_short, lab_short)
+    assert torch.isfinite(gn.float()).all() and torch.equal(gn, gb)
 
 
 def test_images_already_on_the_device(golden_dir):
