@@ -533,6 +533,35 @@ int rv_cfg_guide_rows_f32(float* c, int64_t ld_c, const float* u, int64_t ld_u, 
 /* Host function: the bytes of scratch the two-launch form of rv_cfg_guide_rows_f32 needs. */
 int64_t rv_cfg_guide_ws_bytes(int rows);
 
+/* ---- DoLa, decoding by contrasting layers (generate(dola_layers=), radvlm_amd/csrc/dola.hip) -----------------------------------------
+ * HF reaches it through generate(dola_layers=...) (transformers 4.43 - 4.5x: _dola_decoding, _dola_select_contrast,
+ * _relative_top_filter).  Here the candidate layers' hidden states of the current token go through lm_head as further rows of the
+ * decode step, and this kernel turns the 1 + n_layers raw fp32 logits rows of a sequence into the contrasted score row. */
+/* For each of `rows` rows: f's row r (rows of ld_f floats, the last layer's raw logits, overwritten) against the n_layers candidate
+ * rows c + k * stride_c_layer + r * ld_c (0 <= k < n_layers <= 16, never written, not overlapping f), first n columns (n <= 262144).
+ * With lf / lq_k the bits rv_log_softmax_rows_f32 gives the rows:
+ *   n_layers > 1: J_k = 0.5 * mean_v M ((log M - lf) + (log M - lq_k)), M = (exp(lf) + exp(lq_k)) / 2 (the Jensen-Shannon divergence;
+ *   fp32 terms with the fast exp / log, a term with M < FLT_MIN counting as 0, summed in fp64 in a fixed order), and
+ *   chosen[r] = argmax_k J_k, an exact tie going to the lower k; n_layers == 1: chosen[r] = 0 and no divergence is computed.
+ *   f[r][v] <- -inf where lf_v < fl(max(lf) + log_rt), else fl(lf_v - lb_v), lb the chosen row's log-softmax: one fp32 rounding on
+ *   the log-softmax kernel's bits, so given chosen[r] the row is bit for bit what torch computes from rv_log_softmax_rows_f32's rows.
+ * log_rt: fl32(ln relative_top), from the host.  chosen: int32 [rows].  jsd: fp32 [rows][n_layers] receiving J (0 for n_layers == 1),
+ * or NULL.  Columns >= n are never touched.  No atomics and a fixed reduction order: a row's f, chosen and jsd bits depend on that
+ * row's 1 + n_layers rows alone, not on `rows`, the grid or the other rows.  Non-finite logits are outside the contract but cannot
+ * fault (chosen stays below n_layers).  ws: device scratch of ws_bytes >= rv_dola_ws_bytes(rows, n_layers), 8-byte aligned, contents
+ * arbitrary, not to be shared by launches that can overlap.
+ * With u = 2^-24, E(l) = u (2 |l| + 4 ln n + 3), X(l) = u (|l| + 2), A = 2 log M - lf - lq, Ab = |log M - lf| + |log M - lq|, T = M A:
+ *   |J^_k - J_k| <= (1 + 2^-10) (0.5 / n) sum_v B_v + u |J_k| + 2^-100,
+ *   B_v = |p A / 2 + (p - q) / 2| E(lf) + |q A / 2 + (q - p) / 2| E(lq) + (|A| + 2) ((p X(lf) + q X(lq)) / 2 + u M) + 8 u M |log M|
+ *         + 2 u M Ab + u |T|
+ * against exact arithmetic on the fp32 inputs (csrc/dola.hip derives it).
+ * A null f, c, chosen or ws, rows < 1, n_layers < 1 or > 16, n < 1 or > 262144, ld_f < n, ld_c < n, a short or misaligned ws are
+ * refused (RV_ERR_ARG). */
+int rv_dola_contrast_rows_f32(float* f, int64_t ld_f, const float* c, int64_t ld_c, int64_t stride_c_layer, int rows, int n_layers, int n,
+                              float log_rt, int32_t* chosen, float* jsd, void* ws, int64_t ws_bytes, void* stream);
+/* Host function: the bytes of scratch rv_dola_contrast_rows_f32 needs. */
+int64_t rv_dola_ws_bytes(int rows, int n_layers);
+
 /* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens=), radvlm_amd/csrc/lookup.hip) ----------------------------------------
  * The reference reaches it through HF generate(prompt_lookup_num_tokens=k) (HF:generation/candidate_generator.py
  * PromptLookupCandidateGenerator -> _assisted_decoding): k tokens drafted from n-gram repeats of the sequence are verified by one

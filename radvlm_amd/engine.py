@@ -980,7 +980,8 @@ class LlavaEngine:
             raise NotImplementedError(f"{what} on an int8 KV cache: only prefill() and the plain decode_step() read it; "
                                       "use a bf16 cache (kv_cache_dtype=None)")
 
-    def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0, cache=None, slots=None, kv_dtype=None):
+    def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0, cache=None, slots=None, kv_dtype=None,
+                tap_layers=None):
         """The prompt pass of generation: multimodal splice (plan / encode_images, as in forward) and every decoder layer in the packed
         varlen layout, sequence b at cache rows and positions 0 .. len_b - 1 whatever the padding side.  Each layer's post-RoPE K|V rows go
         into a KVCache of len_b + max_new_tokens slots per sequence; the activations are dropped.  No loss, no saved context (self.ctx and
@@ -991,10 +992,15 @@ class LlavaEngine:
         kv_dtype ("bf16" / "int8"; None: the passed cache's, else "bf16"): with "int8" each layer's K|V rows are quantised on their way
         into the cache (ops.kv_quantize_rows); the prompt's own attention still runs on the unquantised activations, so the returned
         logits are those of a bf16 cache.
+        tap_layers (DoLa, generate(dola_layers=)): a tuple of n distinct layer numbers c in [0, layers); the call then returns a third
+        value, fp32 [n, B, vocab]: lm_head of every sequence's last prompt row as it ENTERS decoder layer c (c = 0: the spliced
+        embedding row; c = k: the residual stream after layer k), without the final norm, in tap_layers' order (_tap_logits).  Only
+        those rows are kept, never whole activations; the cache and the mature logits are bit for bit those of the call without it.
         Returns (cache, fp32 logits [B, vocab] of every sequence's last prompt row)."""
         self._check_generation()
         dev, l = self.device, self.l
         d, L, kvd = l["d"], l["layers"], self.kvd
+        taps = self._check_taps(tap_layers)
         if cache is not None:
             if kv_dtype is not None and self._kv_dtype(kv_dtype) != cache.dtype:
                 raise ValueError(f"kv_dtype {kv_dtype!r} does not match the passed cache's dtype {cache.dtype!r}")
@@ -1034,7 +1040,11 @@ class LlavaEngine:
         layers = []
         if cache is None and kv_dtype == "int8":
             cache = self.new_kv_cache(B, L_max, kv_dtype)           # seq = 0 .. B - 1: filled like a passed cache's slots
+        if taps is not None:
+            tap_rows, tapped = self._dev((cu[1:] - 1).astype(np.int32)), {}
         for i in range(L):
+            if taps is not None and i in taps:
+                tapped[i] = ops.gather_rows(tap_rows, d, x)
             x, acts = self._layer_forward(i, x, geom)
             if cache is None:
                 kv = torch.zeros(B, L_max, 2 * kvd, dtype=BF16, device=dev)
@@ -1048,13 +1058,52 @@ class LlavaEngine:
             del acts
         last = self._dev((cu[1:] - 1).astype(np.int32))
         hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
-        logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
+        if taps is None:
+            logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
+        else:
+            logits, cand = self._tap_logits(hN, [tapped[c] for c in taps])
         if cache is None:
-            return KVCache(layers, lens, L_max), logits[:, :self.vocab]
-        cache.lens[seq] = lens
+            cache = KVCache(layers, lens, L_max)
+        else:
+            cache.lens[seq] = lens
+        if taps is not None:
+            return cache, logits[:, :self.vocab], cand
         return cache, logits[:, :self.vocab]
 
-    def decode_step(self, cache, tokens, beams=None, shared=None):
+    # lm_head of a tapped step: "stacked" puts [mature; candidates] into one skinny launch (skinny=True: a row's bits do not depend on
+    # the row count) where that keeps the mature rows' bits, i.e. where the mature rows alone take the skinny kernel today and
+    # (1 + n) * B <= ops.GEMV_MAX_M, and is "second" elsewhere; "second" keeps the mature rows' launch as it is and runs the candidates'
+    # rows in a second one.  Both give the same bits.  Measured (tools/decode_bench.py --dola, profiles/decode_bench.jsonl mode dola_ab,
+    # DESIGN.md 5b "DoLa"; dola_layers="high", B = 1, the only measured batch at which stacking applies): added ms per step over the
+    # plain step, second -> stacked: llava15_7b 0.103 -> 0.033, Qwen2-7B 0.400 -> 0.094, each faster by more than the second arm's
+    # spread (0.007 / 0.006 ms), so stacking is the default.
+    tap_lm_head = "stacked"
+
+    def _check_taps(self, tap_layers):
+        if tap_layers is None:
+            return None
+        taps = tuple(tap_layers)
+        L = self.l["layers"]
+        if not 1 <= len(taps) <= ops.DOLA_MAX_LAYERS or len(set(taps)) != len(taps) or any(
+                isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < L for c in taps):
+            raise ValueError(f"tap_layers must be 1 .. {ops.DOLA_MAX_LAYERS} distinct ints in [0, {L}), got {tap_layers!r}")
+        return tuple(int(c) for c in taps)
+
+    def _tap_logits(self, hN, hs):
+        """(mature fp32 logits [B, ld], candidate fp32 logits [n, B, vocab]) from the normed last rows hN and the n tapped bf16 rows
+        hs (each [B, d], no norm): the candidates are _decode_linear(cat(hs), lm_head, out_dtype=fp32) -- row k * B + b is candidate k
+        of sequence b -- and the mature rows carry the bits of the call without taps (tap_lm_head)."""
+        w = self.W("lm_head.weight")
+        B, n = hN.shape[0], len(hs)
+        max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
+        if self.tap_lm_head == "stacked" and B <= min(max_m, ops.GEMV_MAX_M) and (1 + n) * B <= ops.GEMV_MAX_M:
+            both = self._decode_linear(torch.cat([hN] + list(hs), 0), w, out_dtype=torch.float32, skinny=True)
+            return both[:B], both[B:].view(n, B, -1)[:, :, :self.vocab]
+        logits = self._decode_linear(hN, w, out_dtype=torch.float32)
+        cand = self._decode_linear(torch.cat(list(hs), 0), w, out_dtype=torch.float32)
+        return logits, cand.view(n, B, -1)[:, :, :self.vocab]
+
+    def decode_step(self, cache, tokens, beams=None, shared=None, tap_layers=None):
         """One generated token per sequence: tokens [B] (int, host or device) at position cache.lens[b] -> fp32 logits [B, vocab].
         Per layer: RMSNorm, q|k|v projection, RoPE at the token's position, cache append, decode attention over the sequence's cached
         keys, o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual; then the final norm and the lm_head (fp32 scores).
@@ -1070,8 +1119,15 @@ class LlavaEngine:
         when the active set changes, not per step.  Rows of a tile hold equal K|V at their first c0 * chunk positions, and attention
         reads those chunks once per tile (rv_attn_decode_shared_bf16), bit-identical to the plain kernel on the same cache;
         shared_route decides whether it does.  Not combined with beams= or an int8 cache (NotImplementedError).  With shared=None
-        every call is what it was."""
+        every call is what it was.
+        tap_layers (DoLa): as in prefill -- a tuple of n distinct layer numbers c in [0, layers); the call then returns (logits, fp32
+        [n, B, vocab]): lm_head of the token's row as it enters layer c, no final norm, in tap_layers' order.  The logits and the
+        cache are bit for bit those of the call without it; it works with quantised decoders and an int8 cache (lm_head stays bf16,
+        the attention branch is not touched) and is not combined with beams= or shared= (NotImplementedError)."""
         self._check_generation()
+        taps = self._check_taps(tap_layers)
+        if taps is not None and (beams is not None or shared is not None):
+            raise NotImplementedError("decode_step(tap_layers=...) with beams= or shared=: DoLa runs on the plain decode step")
         if shared is not None:
             if beams is not None:
                 raise NotImplementedError("decode_step(shared=...) with beams=: one row lookup per call")
@@ -1095,7 +1151,10 @@ class LlavaEngine:
         kv_len = self._dev((cache.lens + 1).astype(np.int32))
         cs = self.rope_table(cache.L_max)
         x = ops.gather_rows(tok.contiguous(), d, self.W("model.embed_tokens.weight"))
+        tapped = {}
         for i in range(L):
+            if taps is not None and i in taps:
+                tapped[i] = x                      # every statement below makes a new x: the row stays as it is
             lv, wq = self._layer_views(i), self._layer_wq(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
             qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"))
@@ -1122,6 +1181,10 @@ class LlavaEngine:
             act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu")), F)
             x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"))
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
+        if taps is not None:
+            logits, cand = self._tap_logits(hN, [tapped[c] for c in taps])
+            cache.lens += 1
+            return logits[:, :self.vocab], cand
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
         cache.lens += 1
         return logits[:, :self.vocab]

@@ -30,6 +30,9 @@ _ACCEPTED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "at
 _LOOKUP = ("prompt_lookup_num_tokens", "max_matching_ngram_size")
 # classifier-free guidance (HF's names; negative_images / negative_image_sizes are ours: HF's negative prompt cannot carry an image)
 _GUIDANCE = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "negative_images", "negative_image_sizes")
+# DoLa, decoding by contrasting layers (HF's name); _parse_dola / resolve_dola_layers
+_DOLA = ("dola_layers",)
+DOLA_MAX_LAYERS = 16          # candidate layers per call (rv_dola_contrast_rows_f32)
 LOOKUP_MAX_TOKENS = 31        # k drafted tokens are verified as k + 1 rows, and the skinny GEMM takes ops.GEMV_MAX_M = 32
 
 
@@ -49,11 +52,14 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     (.kv_cache_dtype: "bf16" or "int8") and TypeError for unknown names.  lookup: also take prompt_lookup_num_tokens / max_matching_ngram_size (.lookup: None, or .k and .max_ngram; .drafter: None,
     greedy_generate then builds a PromptLookupDrafter; a test or a benchmark may set another object with propose(seq)).
     Classifier-free guidance (.guidance: None when off, else .scale and the negative prompt as given, _parse_guidance): with
-    past_key_values or prompt_lookup_num_tokens NotImplementedError."""
-    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and not (lookup and k in _LOOKUP))
+    past_key_values or prompt_lookup_num_tokens NotImplementedError.
+    DoLa (.dola: None when off, else the validated dola_layers spec, _parse_dola; resolve_dola_layers turns it into layer numbers
+    once the call knows the engine's depth): with guidance_scale, past_key_values or prompt_lookup_num_tokens NotImplementedError."""
+    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and k not in _DOLA and not (lookup and k in _LOOKUP))
     if unknown:
         raise TypeError(f"generate() got unexpected keyword arguments {unknown}")
     guidance = _parse_guidance(kwargs)
+    dola = _parse_dola(kwargs)
     if kwargs.get("inputs_embeds") is not None:
         raise NotImplementedError("`inputs_embeds` is not supported")      # the reference's generate() raises the same
     if kwargs.get("do_sample") and kwargs.get("seed") is None:
@@ -80,6 +86,12 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
                                   "of it across calls")
     if guidance is not None and kwargs.get("prompt_lookup_num_tokens") is not None:
         raise NotImplementedError("guidance_scale with prompt_lookup_num_tokens: verifying drafts on two branches is not implemented")
+    if dola is not None and guidance is not None:
+        raise NotImplementedError("dola_layers with guidance_scale: contrasting layers on top of the guided scores is not implemented")
+    if dola is not None and pkv is not None:
+        raise NotImplementedError("dola_layers with past_key_values: the extend pass hands out no intermediate hidden states")
+    if dola is not None and kwargs.get("prompt_lookup_num_tokens") is not None:
+        raise NotImplementedError("dola_layers with prompt_lookup_num_tokens: the verify step hands out no intermediate hidden states")
     kv_dtype = parse_kv_cache_dtype(kwargs.get("kv_cache_dtype"))
     if kv_dtype == "int8" and pkv is not None:
         raise NotImplementedError("kv_cache_dtype='int8' with past_key_values: a GenerationCache is extended by the extend-attention "
@@ -104,8 +116,60 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
                            past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
-                           kv_cache_dtype=kv_dtype, guidance=guidance,
+                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola,
                            **_parse_processors(kwargs, eos))
+
+
+def _parse_dola(kwargs):
+    """The dola_layers keyword, validated as far as it can be without the model's depth: None (off), "low", "high", or a tuple of
+    distinct non-negative ints (a list or tuple, in the given order).  ValueError for any other string or type, an empty list, a bool,
+    a non-int, a negative value, a duplicate, and more than DOLA_MAX_LAYERS values."""
+    v = kwargs.get("dola_layers")
+    if v is None:
+        return None
+    if isinstance(v, str):
+        if v not in ("low", "high"):
+            raise ValueError(f"`dola_layers` has to be 'low', 'high' or a list of layer numbers, but is {v!r}")
+        return v
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"`dola_layers` has to be 'low', 'high' or a list of layer numbers, but is {v!r}")
+    if any(isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) for c in v):
+        raise ValueError(f"`dola_layers` has to hold ints, but is {v!r}")
+    layers = tuple(int(c) for c in v)
+    if not layers:
+        raise ValueError("`dola_layers` is an empty list: there is no layer to contrast with")
+    if min(layers) < 0:
+        raise ValueError(f"`dola_layers` holds a negative layer number: {list(layers)}")
+    if len(set(layers)) != len(layers):
+        raise ValueError(f"`dola_layers` holds a layer twice: {list(layers)}")
+    if len(layers) > DOLA_MAX_LAYERS:
+        raise ValueError(f"`dola_layers` holds {len(layers)} layers; at most {DOLA_MAX_LAYERS} candidates are contrasted")
+    return layers
+
+
+def resolve_dola_layers(spec, L, tied=False):
+    """The candidate layer numbers of a DoLa call on a decoder of L layers (HF: _dola_decoding), in contrast order: "low" is
+    range(start, L // 2, 2) for L <= 40, else range(start, 20, 2); "high" is range(L // 2, L, 2) for L <= 40, else range(L - 20, L,
+    2); a tuple is taken as given.  start = 0 for untied output embeddings (every geometry here); tied: HF's 2 if L > 2, 1 if L == 2,
+    else 0.  Layer c is the hidden state that enters decoder layer c (0: the embeddings).  ValueError for an empty result, a value
+    outside [0, L) -- HF drops those silently -- and more than DOLA_MAX_LAYERS candidates."""
+    L = int(L)
+    start = (2 if L > 2 else (1 if L == 2 else 0)) if tied else 0
+    if spec == "low":
+        layers = tuple(range(start, L // 2, 2)) if L <= 40 else tuple(range(start, 20, 2))
+    elif spec == "high":
+        layers = tuple(range(L // 2, L, 2)) if L <= 40 else tuple(range(L - 20, L, 2))
+    else:
+        layers = _parse_dola(dict(dola_layers=spec))
+        if layers is None or isinstance(layers, str):
+            raise ValueError(f"`dola_layers` has to be 'low', 'high' or a list of layer numbers, but is {spec!r}")
+    if not layers:
+        raise ValueError(f"dola_layers={spec!r} names no layer of a {L}-layer decoder")
+    if any(not 0 <= c < L for c in layers):
+        raise ValueError(f"dola_layers={list(layers)}: every candidate has to lie in [0, {L}) (0: the embeddings, k: after layer k)")
+    if len(layers) > DOLA_MAX_LAYERS:
+        raise ValueError(f"dola_layers={spec!r} gives {len(layers)} layers; at most {DOLA_MAX_LAYERS} candidates are contrasted")
+    return layers
 
 
 def _parse_guidance(kwargs):
@@ -780,7 +844,12 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     from the processed scores (row b with seed_b at step t) instead of their argmax; output_scores and the stopping criteria then get
     the warped scores, output_logits the raw ones as before.  cfg.kv_cache_dtype "int8": the cache holds int8 K|V rows with one fp32
     scale per (position, kv head, K / V) group; the first token comes from the unquantised prompt pass, every later one reads the
-    quantised rows."""
+    quantised rows.
+    cfg.dola (DoLa): the spec is resolved against the engine's depth once; prefill and every decode_step are asked for the candidate
+    layers' logits (tap_layers=) and ops.dola_contrast_rows turns each step's raw rows into the contrasted rows in place, after
+    output_logits has cloned the raw ones and before the processors, the argmax or the sampler, output_scores and the stopping
+    criteria, which all see the contrasted rows (the place guidance puts the guided rows).  The dict output then carries
+    dola_premature_layers, int64 [B, steps]: the layer each row chose, -1 at steps after the row has finished."""
     from . import ops
     ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids)
     if ids.ndim == 1:
@@ -802,6 +871,13 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     st = GreedyState(B, cfg)
     scores = []
     dev = engine.device
+    dola = getattr(cfg, "dola", None)
+    tap, picks = {}, []
+    if dola is not None:
+        if gc is not None or lookup:
+            raise NotImplementedError("dola_layers with past_key_values or prompt_lookup_num_tokens is not implemented")
+        dola = resolve_dola_layers(dola, engine.l["layers"])
+        tap = dict(tap_layers=dola)
     # prompt length in HF's sense: the spliced inputs_embeds width (the longest spliced prompt of the batch)
     plan_len = None
     if (cfg.max_new_tokens is None and cfg.max_length is not None) or min_needs_prompt_len(cfg):
@@ -825,9 +901,11 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                 if lookup:
                     raise NotImplementedError("kv_cache_dtype='int8' with prompt-lookup decoding: the verify-attention kernel reads a bf16 "
                                               "cache only")
-                cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, kv_dtype="int8")
+                cache, logits, *cand = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, kv_dtype="int8", **tap)
             else:
-                cache, logits = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T)
+                cache, logits, *cand = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **tap)
+            if dola is not None:
+                dws = ops.dola_workspace(B, len(dola), dev)
         else:
             imgs = list(images) if images is not None else []
             plan = engine.plan(ids, am, None, imgs, image_sizes)
@@ -848,6 +926,8 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
         for t in range(plain_steps):
             if cfg.output_logits:
                 raw.append(logits.clone())
+            if dola is not None:          # in place: the raw mature rows become the contrasted rows
+                picks.append((ops.dola_contrast_rows(logits, cand[0], engine.vocab, ws=dws)[1], st.unfinished.copy()))
             if lp.active:                 # in place: logits become HF's processed scores
                 nxt = ops.logits_process_argmax(logits, engine.vocab, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
             elif sm is None:
@@ -864,7 +944,10 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                 hist[:, t] = torch.from_numpy(tok.astype(np.int32)).to(dev)
             if st.all_done or t == T - 1:
                 break
-            logits = engine.decode_step(cache, torch.from_numpy(tok))
+            if dola is None:
+                logits = engine.decode_step(cache, torch.from_numpy(tok))
+            else:
+                logits, *cand = engine.decode_step(cache, torch.from_numpy(tok), **tap)
         if gc is not None:          # the prompt and the tokens fed to decode_step (every emitted one but the last; pads of finished rows)
             fed = st.sequences()[:, :int(cache.lens[0] - plan["lens"][0])]
             gc._store(cache, [np.concatenate([recs[b], fed[b]]) for b in range(B)], imgs, image_sizes, uids, engine)
@@ -875,6 +958,13 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                                         logits=tuple(raw) if cfg.output_logits else None, past_key_values=cfg.past_key_values)
         if lookup:
             out.lookup_stats = lookup_stats
+        if dola is not None:
+            lay = np.full((B, len(picks)), -1, dtype=np.int64)
+            if picks:
+                ch = torch.stack([c for c, _ in picks], 1).cpu().numpy()           # one copy: [B, steps] indices into `dola`
+                live = np.stack([u for _, u in picks], 1)
+                lay[live] = np.asarray(dola, dtype=np.int64)[ch[live]]
+            out.dola_premature_layers = torch.from_numpy(lay).to(dev)
         return out
     return seq
 
@@ -899,7 +989,7 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
     """generate_batch() keywords: generate()'s greedy and sampling settings (seed: an int, or a list of n ints), validated by parse_generate_kwargs and applied per request;
     max_new_tokens may also be a list of n budgets (cfg.budgets).  TypeError for arguments without a per-request meaning.
     share_prefix (cfg.share_prefix, default False): a bool, ValueError otherwise; NotImplementedError together with
-    kv_cache_dtype="int8" or guidance_scale."""
+    kv_cache_dtype="int8", guidance_scale or dola_layers."""
     given = sorted(k for k in _NO_PER_REQUEST if kwargs.get(k) is not None and kwargs.get(k) is not False)
     if given:
         raise TypeError(f"generate_batch() got arguments without a per-request meaning: {given}")
@@ -929,6 +1019,9 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
                                   "cache only")
     if cfg.share_prefix and cfg.guidance is not None:
         raise NotImplementedError("share_prefix=True with guidance_scale: sharing across the two branches of a guided call is not implemented")
+    if cfg.share_prefix and cfg.dola is not None:
+        raise NotImplementedError("share_prefix=True with dola_layers: the extend pass and the shared decode step hand out no intermediate "
+                                  "hidden states")
     if cfg.guidance is not None:
         for k in ("negative_prompt_ids", "negative_images", "negative_image_sizes"):
             _per_request(k, getattr(cfg.guidance, k), n)      # a list of another length: ValueError here, before anything runs
@@ -1182,7 +1275,11 @@ class BatchScheduler:
     the followers' suffixes; _step runs once per phase and ("share", request, slot, source slot, P) follows the "admit" entry.  A
     row is self-contained, so a group outlives its leader and no cache bytes are saved.  The decode step's tile table (shared_tiles
     over the active slots' lineages) is rebuilt when an admission or a finish changes the active set and uploaded when it differs;
-    while no tile shares a chunk decode_step is called without shared=.  Without cfg.share_prefix nothing here changes."""
+    while no tile shares a chunk decode_step is called without shared=.  Without cfg.share_prefix nothing here changes.
+    cfg.dola (DoLa): the spec is resolved against the engine's depth once per call; admissions and decode steps ask the engine for the
+    candidate layers' logits (tap_layers=) and `contrast(logits, candidates)` -- default ops.dola_contrast_rows -- turns the rows into
+    the contrasted rows in place where `guide` runs in a guided call, before the picker.  Every row chooses its own layer, so an idle
+    slot's garbage row touches no other row.  Not combined with guidance or share_prefix.  Without cfg.dola nothing here changes."""
 
     def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None, guide=None):
         if not _is_int(max_batch_size) or max_batch_size < 1:
@@ -1206,6 +1303,11 @@ class BatchScheduler:
         self.slots = min(int(max_batch_size), len(self.runs))
         self.L_max = max([self.spliced[i] + self.budget[i] for i in self.runs], default=0)
         self.guidance, self.guide = getattr(cfg, "guidance", None), guide
+        self.dola, self.contrast = getattr(cfg, "dola", None), None
+        if self.dola is not None:
+            if self.guidance is not None or self.share:
+                raise NotImplementedError("dola_layers with guidance_scale or share_prefix=True is not implemented")
+            self.dola = resolve_dola_layers(self.dola, engine.l["layers"])
         if self.guidance is not None:
             self.neg_spliced = [int(engine.plan(r.neg_ids[None], None, None, r.neg_images, r.neg_sizes)["lens"][0]) for r in reqs]
             self.L_max = max([max(self.spliced[i], self.neg_spliced[i]) + self.budget[i] for i in self.runs], default=0)
@@ -1254,6 +1356,10 @@ class BatchScheduler:
             from . import ops
             gws, g, V = ops.cfg_guide_workspace(S, eng.device), self.guidance.scale, eng.vocab
             self.guide = lambda c, u: ops.cfg_guide_rows(c, u, V, g, ws=gws)
+        if self.dola is not None:
+            from . import ops
+            dws, V = ops.dola_workspace(S, len(self.dola), eng.device), eng.vocab
+            self.contrast = lambda f, c: ops.dola_contrast_rows(f, c, V, ws=dws)
         self.owner = np.full(S, -1, dtype=np.int64)           # request in each slot, -1: idle
         self.t = np.zeros(S, dtype=np.int64)                  # tokens the slot's request has generated
         self.mn = np.zeros(S, dtype=np.int64)                 # its EOS minimum
@@ -1296,6 +1402,11 @@ class BatchScheduler:
             ids[b, :r.ids.size], am[b, :r.ids.size] = r.ids, True
         imgs = [im for r in rq for im in r.images]
         sizes = [s for r in rq for s in (r.sizes or [])] if any(r.sizes is not None for r in rq) else None
+        if self.dola is not None:
+            _, logits, cand = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs, tap_layers=self.dola)
+            self.contrast(logits, cand)
+            self._step(logits, rs)
+            return
         _, logits = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs)
         if self.guidance is not None:
             logits = self._admit_negative(logits, rq, rs)
@@ -1401,6 +1512,12 @@ class BatchScheduler:
             self._step(logits[:self.slots], list(range(self.slots)))
             return
         self.cache.lens[idle] = 0
+        if self.dola is not None:
+            logits, cand = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending), tap_layers=self.dola)
+            self.cache.lens[idle] = 0
+            self.contrast(logits, cand)
+            self._step(logits, list(range(self.slots)))
+            return
         plan = self._shared_plan() if self.share else None
         if plan is None:
             logits = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending))
@@ -1482,12 +1599,15 @@ def parse_beam_kwargs(kwargs, lora=False, config_eos=None, config_pad=None):
     """Validate generate_beams() keyword arguments: generate()'s, plus length_penalty (float, default 1.0), early_stopping (False, True
     or "never") and num_return_sequences <= num_beams.  ValueError for num_beams outside [1, 16] or K = max(2, 1 + n_eos) * num_beams
     above 64; NotImplementedError for do_sample=True (beam sampling), past_key_values, streamer, inputs_embeds, LoRA engines and
-    kv_cache_dtype="int8" (None and "bf16" are accepted and change nothing), and for classifier-free guidance (guidance_scale or any
-    negative_* argument given);
+    kv_cache_dtype="int8" (None and "bf16" are accepted and change nothing), for dola_layers, and for classifier-free guidance
+    (guidance_scale or any negative_* argument given);
     TypeError for unknown names.  The sampling knobs HF ignores when greedy stay ignored."""
-    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _BEAM_ONLY and k not in _GUIDANCE)
+    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _BEAM_ONLY and k not in _GUIDANCE and k not in _DOLA)
     if unknown:
         raise TypeError(f"generate_beams() got unexpected keyword arguments {unknown}")
+    if kwargs.get("dola_layers") is not None:
+        raise NotImplementedError("dola_layers with beams: contrasting layers per beam is not implemented; generate() and generate_batch() "
+                                  "take it")
     given = sorted(k for k in _GUIDANCE if kwargs.get(k) is not None)
     if given:
         raise NotImplementedError(f"classifier-free guidance with beams is not implemented (guidance_scale and its negative prompt: "

@@ -310,6 +310,19 @@ class LlavaLlamaForCausalLM:
         kv_cache_dtype="int8" and load_8bit models; with past_key_values or prompt_lookup_num_tokens NotImplementedError; a bad
         scale, a negative prompt of another row count or with an empty row, images that do not match its placeholders, or any
         negative_* argument while guidance is off: ValueError.
+        DoLa, decoding by contrasting layers: dola_layers="low", "high" or a list of layer numbers (HF's keyword; None: off, and the
+        call is bit for bit the call without it).  Layer c is the hidden state entering decoder layer c (0: the embeddings), sent
+        through lm_head without the final norm; "low" / "high" are HF's buckets (every second layer of the lower / upper half, of
+        the first / last 20 for more than 40 layers).  Per step and per row the candidate whose next-token distribution has the
+        largest Jensen-Shannon divergence from the last layer's is chosen (HF averages it over the batch; here every row chooses,
+        which is HF at B = 1), and the scores become log_softmax(last) - log_softmax(chosen) where log_softmax(last) >= its maximum
+        + ln 0.1 and -inf elsewhere (HF's relative_top = 0.1), before the processors and warpers above.  No second sequence and no
+        extra cache row: the candidates' hidden rows are further rows of the step's lm_head.  output_logits returns the raw last-layer
+        logits, output_scores and the stopping criteria the contrasted, processed scores; with return_dict_in_generate the output
+        gains .dola_premature_layers, int64 [B, steps], the layer each row chose (-1 after the row's EOS).  It composes with
+        sampling, kv_cache_dtype="int8" and quantised decoders; with guidance_scale, past_key_values or prompt_lookup_num_tokens
+        NotImplementedError; another string, an empty list, a duplicate, a non-int, a bool, a layer outside [0, layers) (HF drops
+        those silently) or more than 16 candidates: ValueError.
         The training state (weights, optimizer, RNG counters) is not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
@@ -346,7 +359,10 @@ class LlavaLlamaForCausalLM:
         (LlavaEngine.extend(slots=)), so the tower and the prompt pass run once per distinct prefix, and decode attention may read
         a group's shared keys once per step (rv_attn_decode_shared_bf16, the plain kernel's bits; LlavaEngine.shared_route).  A
         follower's tokens agree with the unshared call's within rounding; prompts with nothing in common give exactly the call
-        without the keyword.  A non-bool value: ValueError; with kv_cache_dtype="int8" or guidance_scale: NotImplementedError.
+        without the keyword.  A non-bool value: ValueError; with kv_cache_dtype="int8", guidance_scale or dola_layers:
+        NotImplementedError.
+        dola_layers (one value for the call): DoLa as in generate().  Every request chooses its own layer at every step, so a
+        request's tokens are those of generate(dola_layers=...) on it alone; the cache keeps one row per slot.
         The training state is not touched."""
         from ...generation import generate_batch, parse_batch_kwargs
         inputs = list(inputs)
@@ -388,8 +404,8 @@ class LlavaLlamaForCausalLM:
         num_beams rows; the prompt is prefilled once per prompt and never copied, and no cache row is reordered (the engine's decode
         attention follows each beam's ancestry instead).  do_sample=True (beam sampling), past_key_values, streamers, inputs_embeds
         and LoRA models raise NotImplementedError, and so does kv_cache_dtype="int8" (the beam-attention kernel reads a bf16 cache;
-        None and "bf16" are accepted and change nothing), and so does classifier-free guidance (guidance_scale or any negative_*
-        argument).  The training state is not touched."""
+        None and "bf16" are accepted and change nothing), and so do classifier-free guidance (guidance_scale or any negative_*
+        argument) and dola_layers.  The training state is not touched."""
         from ...generation import beam_generate, parse_beam_kwargs
         cfg = parse_beam_kwargs(dict(kwargs, num_beams=num_beams), lora=bool(self.engine.lora),
                                 config_eos=getattr(self.config, "eos_token_id", None), config_pad=getattr(self.config, "pad_token_id", None))

@@ -1050,6 +1050,40 @@ def cfg_guide_rows(c, u, n, g, ws=None, route=None):
     return c
 
 
+DOLA_MAX_LAYERS = 16      # candidate layers per call (rv_dola_contrast_rows_f32)
+DOLA_RELATIVE_TOP = 0.1   # HF's relative_top, fixed
+DOLA_LOG_RT = float(np.float32(math.log(DOLA_RELATIVE_TOP)))        # fl32(ln relative_top): the float64 logarithm, rounded once
+
+
+def dola_workspace(rows, n_layers, device):
+    """Scratch for dola_contrast_rows at up to `rows` rows and `n_layers` candidates (fp64, never zeroed); calls that share it run on one
+    stream."""
+    return torch.empty(max(lib.load().rv_dola_ws_bytes(int(rows), int(n_layers)) // 8, 1), dtype=torch.float64, device=device)
+
+
+def dola_contrast_rows(f, c, n, ws=None, want_jsd=False):
+    """DoLa's layer choice, relative-top filter and contrast in place (rv_dola_contrast_rows_f32).  f: fp32 [rows, >= n], the last
+    layer's raw logits; c: fp32 [n_layers, rows, >= n], the candidate layers' raw logits (only read, not overlapping f).  Per row the
+    candidate with the largest Jensen-Shannon divergence from f's distribution is chosen (ties: the lower index; n_layers == 1: that
+    one, no divergence computed) and f[r, :n] <- log_softmax(f) - log_softmax(c[chosen]) where log_softmax(f) >= max + ln 0.1, -inf
+    elsewhere, on log_softmax_rows' bits with one rounding.  Columns >= n are not touched.  ws: dola_workspace(>= rows, n_layers)
+    (allocated when missing).  Returns (f, chosen int32 [rows]) and with want_jsd also the divergences fp32 [rows, n_layers]."""
+    _chk(f, torch.float32), _chk(c, torch.float32)
+    assert f.dim() == 2 and c.dim() == 3 and f.stride(1) == 1 and c.stride(2) == 1
+    rows, nl = f.shape[0], c.shape[0]
+    assert rows >= 1 and c.shape[1] == rows and 1 <= nl <= DOLA_MAX_LAYERS
+    assert 0 < n <= min(f.shape[1], c.shape[2], LOGITS_PROCESS_MAX_N)
+    need = lib.load().rv_dola_ws_bytes(rows, nl)
+    ws = dola_workspace(rows, nl, f.device) if ws is None else ws
+    _chk(ws, torch.float64)
+    assert ws.is_contiguous() and ws.numel() * 8 >= need
+    chosen = torch.empty(rows, dtype=torch.int32, device=f.device)
+    jsd = torch.empty(rows, nl, dtype=torch.float32, device=f.device) if want_jsd else None
+    lib.call("rv_dola_contrast_rows_f32", f, f.stride(0), c, c.stride(1), c.stride(0), rows, nl, int(n), DOLA_LOG_RT, chosen, jsd, ws,
+             ws.numel() * 8)
+    return (f, chosen, jsd) if want_jsd else (f, chosen)
+
+
 BEAM_MAX = 16             # beams per prompt (rv_beam_topk_f32)
 BEAM_TOPK_MAX = 64        # candidates kept per prompt and step
 

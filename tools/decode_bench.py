@@ -94,6 +94,15 @@
         # positions (or the shortest the geometry's image allows), C = 2, 8, 32 candidates of 4 and of 64 tokens, one engine per
         # geometry, one untimed pass of both arms and then the arms alternated --reps times; wall ms per call, medians, the
         # one-by-one arm's spread (max - min) and whether score() is faster by more than that spread; the decoder rows of both arms
+  python tools/decode_bench.py --dola-shapes [--out FILE]   # DoLa's kernel alone: rv_dola_contrast_rows_f32 against the unfused
+        # composition (rv_log_softmax_rows_f32 twice, torch's exp / log / products, sum, argmax, masked subtraction) on the same rows,
+        # 32,000 columns with 8 candidates and 152,064 with 7, rows 1, 8, 32; torch.equal asserted before timing; device time,
+        # interleaved, median of 20, warm and after a 1 GiB fill; the unfused arm's p10 / p90 are its spread
+  python tools/decode_bench.py --dola [--geos ..] [--batches 1,8,32] [--prompt 704] [--new 128] [--out FILE]
+        # the decode step (decode_step + contrast + argmax) with dola_layers="high" beside the plain step on one engine: one untimed
+        # pass of every arm, then the arms alternated three times; median ms per step per arm, the spread of the three medians, the
+        # added ms per step, and the candidates' lm_head rows in a second launch against stacked with the mature rows into one
+        # skinny launch where that keeps the mature rows' bits (LlavaEngine.tap_lm_head)
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -922,6 +931,151 @@ def cfg_ab(geo, batches, prompt, new, reps=3):
     return recs
 
 
+def _dola_inputs(n, nl, rows, seed=0):
+    """The kernel tests' rows: f = 4 randn, candidate k = f + 0.25 * 2^(k/2) randn in a shuffled order."""
+    g = torch.Generator().manual_seed(seed + n + 31 * nl + rows)
+    f = 4 * torch.randn(rows, n, generator=g)
+    order = torch.randperm(nl, generator=g).tolist()
+    c = torch.stack([f + 0.25 * 2 ** (order[k] / 2) * torch.randn(rows, n, generator=g) for k in range(nl)])
+    return f.cuda(), c.cuda()
+
+
+def dola_shapes(reps=20):
+    """rv_dola_contrast_rows_f32 (four launches: statistics, divergence pieces, select, contrast) against the unfused composition on
+    the same rows: two rv_log_softmax_rows_f32 calls, then torch's exp / log / products, the sum, argmax and the masked subtraction.
+    n = 32000 with 8 candidates and n = 152064 with 7, rows 1, 8, 32.  Device time per call (events around it), median of `reps`, arms
+    interleaved, every call from freshly copied raw rows, warm and after a 1 GiB fill ("cold").  torch.equal of the contrasted rows is
+    asserted before anything is timed.  The kernel has one launch structure, so there is no second arm of its own."""
+    recs = []
+    flush = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
+    log_rt = torch.tensor(ops.DOLA_LOG_RT, dtype=torch.float32, device="cuda")
+    for n, nl in ((32000, 8), (152064, 7)):
+        for rows in (1, 8, 32):
+            f0, c0 = _dola_inputs(n, nl, rows)
+            f, c = f0.clone(), c0.clone()
+            ws = ops.dola_workspace(rows, nl, "cuda")
+            ar = torch.arange(rows, device="cuda")
+
+            def unfused():
+                lf = ops.log_softmax_rows(f, n)
+                lq = ops.log_softmax_rows(c.view(nl * rows, n), n).view(nl, rows, n)
+                M = 0.5 * (lf.exp() + lq.exp())
+                lm = M.log()
+                J = torch.where(M > 0, M * ((lm - lf) + (lm - lq)), M).double().sum(-1)
+                lb = lq[J.argmax(0), ar]
+                thresh = lf.max(1, keepdim=True).values + log_rt
+                f.copy_(torch.where(lf < thresh, torch.full_like(lf, float("-inf")), lf - lb))
+
+            fns = {"fused": lambda: ops.dola_contrast_rows(f, c, n, ws=ws), "unfused": unfused}
+            outs = {}
+            for k, fn in fns.items():
+                f.copy_(f0), c.copy_(c0)
+                fn()
+                outs[k] = f.clone()
+            assert torch.equal(outs["fused"], outs["unfused"])
+            rec = dict(mode="dola_kernel_ab", rows=rows, vocab=n, n_layers=nl, reps=reps)
+            for temp in ("warm", "cold"):
+                ts = {k: [] for k in fns}
+                for _ in range(reps):
+                    for k, fn in fns.items():
+                        f.copy_(f0), c.copy_(c0)
+                        if temp == "cold":
+                            flush.fill_(0.0)
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        fn()
+                        e1.record()
+                        e1.synchronize()
+                        ts[k].append(e0.elapsed_time(e1) * 1e3)
+                med = {k: float(np.median(v)) for k, v in ts.items()}
+                rec.update({f"{k}_{temp}_us": round(v, 2) for k, v in med.items()})
+                rec.update({f"{k}_{temp}_p10_p90_us": [round(float(np.percentile(ts[k], 10)), 2), round(float(np.percentile(ts[k], 90)), 2)] for k in fns})
+                rec[f"unfused_over_fused_{temp}"] = round(med["unfused"] / med["fused"], 3)
+                spread = float(np.percentile(ts["unfused"], 90) - np.percentile(ts["unfused"], 10))
+                rec[f"fused_faster_by_more_than_unfused_spread_{temp}"] = bool(med["unfused"] - med["fused"] > spread)
+            recs.append(rec)
+    return recs
+
+
+def _dola_loop(eng, ids, new, layers, warm=8):
+    """The decode step of generate(dola_layers=) as greedy_generate runs it: decode_step(tap_layers=) + ops.dola_contrast_rows + argmax.
+    Returns (step times in ms after warm-up, the contrast call's median device time in us on the last step's rows)."""
+    B, V = ids.shape[0], eng.vocab
+    cache, f, c = eng.prefill(ids, None, None, None, max_new_tokens=new, tap_layers=layers)
+    ws = ops.dola_workspace(B, len(layers), f.device)
+    tok = ops.argmax_rows(ops.dola_contrast_rows(f, c, V, ws=ws)[0], V)
+    times = []
+    for _ in range(1, new):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f, c = eng.decode_step(cache, tok.to(torch.int32), tap_layers=layers)
+        tok = ops.argmax_rows(ops.dola_contrast_rows(f, c, V, ws=ws)[0], V)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    raw, us = f.clone(), []
+    for _ in range(20):
+        f.copy_(raw)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ops.dola_contrast_rows(f, c, V, ws=ws)
+        e1.record()
+        e1.synchronize()
+        us.append(e0.elapsed_time(e1) * 1e3)
+    del cache
+    return times[warm:], float(np.median(us))
+
+
+def dola_ab(geo, batches, prompt, new, reps=3):
+    """The decode step with dola_layers="high" beside the plain decode step, interleaved `reps` times as --kv8 does; the candidates'
+    lm_head rows in a second launch ("second") and, where it keeps the mature rows' bits, stacked with them into one skinny launch
+    ("stacked", LlavaEngine.tap_lm_head)."""
+    from radvlm_amd.generation import resolve_dola_layers
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    layers = resolve_dola_layers("high", eng.l["layers"])
+    recs = []
+    for B in batches:
+        ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+        head = eng.W("lm_head.weight")
+        max_m = eng.gemv_max_m_wide if head.shape[0] >= 65536 else eng.gemv_max_m
+        stackable = B <= min(max_m, ops.GEMV_MAX_M) and (1 + len(layers)) * B <= ops.GEMV_MAX_M
+        contrast_us = {}
+
+        def dola(route):
+            eng.tap_lm_head = route
+            try:
+                ts, us = _dola_loop(eng, ids, new, layers)
+            finally:
+                del eng.tap_lm_head
+            contrast_us.setdefault(route, []).append(us)
+            return ts
+
+        arms = {"plain": lambda: _decode_loop(eng, ids, new), "dola_second": lambda: dola("second")}
+        if stackable:
+            arms["dola_stacked"] = lambda: dola("stacked")
+        for fn in arms.values():                                        # one untimed pass of every arm
+            fn()
+        contrast_us.clear()
+        ts = {k: [] for k in arms}
+        for _ in range(reps):
+            for k, fn in arms.items():
+                ts[k].append(float(np.median(fn())))
+        med = {k: float(np.median(v)) for k, v in ts.items()}
+        rec = dict(geo=geo, mode="dola_ab", B=B, prompt=prompt, new_tokens=new, reps=reps, vocab=eng.vocab, dola_layers=list(layers),
+                   stacked_applies=bool(stackable))
+        for k in arms:
+            rec[f"{k}_ms_per_step"], rec[f"{k}_ms_all"], rec[f"{k}_spread_ms"] = round(med[k], 3), [round(x, 3) for x in ts[k]], round(max(ts[k]) - min(ts[k]), 3)
+        for k in arms:
+            if k != "plain":
+                us = float(np.median(contrast_us[k.split("_", 1)[1]]))
+                rec[f"{k}_added_ms"], rec[f"{k}_over_plain"] = round(med[k] - med["plain"], 3), round(med[k] / med["plain"], 3)
+                rec[f"{k}_contrast_us"] = round(us, 2)
+        if stackable:
+            rec["stacked_minus_second_ms"] = round(med["dola_stacked"] - med["dola_second"], 3)
+            rec["stacked_faster_by_more_than_second_spread"] = bool(med["dola_second"] - med["dola_stacked"] > max(ts["dola_second"]) - min(ts["dola_second"]))
+        recs.append(rec)
+    return recs
+
+
 def processors_ab(geo, B, prompt, new, reps=3):
     from radvlm_amd.generation import LogitsProcessors, parse_generate_kwargs
     eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
@@ -1526,6 +1680,8 @@ def main():
     ap.add_argument("--lookup-kernel-ab", action="store_true")
     ap.add_argument("--cfg", action="store_true")
     ap.add_argument("--cfg-kernel-ab", action="store_true")
+    ap.add_argument("--dola", action="store_true")
+    ap.add_argument("--dola-shapes", action="store_true")
     ap.add_argument("--shared-shapes", action="store_true")
     ap.add_argument("--share-prefix", action="store_true")
     ap.add_argument("--score", action="store_true")
@@ -1570,6 +1726,10 @@ def main():
         recs = [r for g in a.geos.split(",") for r in lookup_kernel_ab(g) + lookup_e2e(g, a.prompt, a.new, reps=min(a.reps, 3))]
     elif a.cfg_kernel_ab:
         recs = cfg_kernel_ab()
+    elif a.dola_shapes:
+        recs = dola_shapes()
+    elif a.dola:
+        recs = [r for g in a.geos.split(",") for r in dola_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new, reps=min(a.reps, 3))]
     elif a.shared_shapes:
         recs = shared_shapes()
     elif a.score_shapes:
