@@ -386,7 +386,8 @@ int64_t rv_w4_scale_row_bytes(int K);
 int rv_gemv_w4_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp, const void* scales, int64_t lds, void* Y, int64_t ldy,
                     const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
                     int64_t ws_bytes, void* stream);
-/* Decode attention (flash-decoding, decode.hip): for every sequence b and q head h, softmax(scale * q[b,h] K^T) V over the cached keys
+/* Decode attention (flash-decoding, decode.hip; the kernel body, the partial layout, the combine and the launcher that the six
+ * other rv_attn_decode_* / rv_attn_extend_* entry points below share with it or with each other are csrc/attn_split.h): for every sequence b and q head h, softmax(scale * q[b,h] K^T) V over the cached keys
  * [0, kv_len[b]) of kv head h / (H / Hkv), hd in {64, 128}, up to 8 q heads per kv head (GQA), fp32 softmax and accumulation.
  * cache: bf16 [B][L_max][ld_c] (sequence stride bs_c), K of kv head g at columns g*hd, V at v_off + g*hd.  q: [B, H*hd] rows (ld_q);
  * out: bf16 [B, H*hd] rows (ld_o).  Keys are split into chunks of `chunk` rows (a multiple of 16 for hd 128, of 32 for hd 64,

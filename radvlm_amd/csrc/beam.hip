@@ -3,6 +3,7 @@
 // As in decode.hip every reduction runs in a fixed order that depends on the problem shape only and there are no global or float
 // atomics: a row's (a prompt's) result is bit-identical whatever else shares the launch.
 // Reference call sites are listed per entry point in include/radvlm_hip.h.
+#include "attn_split.h"
 #include "common.h"
 #include "log_softmax.h"
 #include "radvlm_hip.h"
@@ -16,31 +17,22 @@ namespace {
 //   src(b, j) = j < prefix_len[b] ? prefix_row[b] : tail_src[b][j - prefix_len[b]],   clamped into [0, cache_rows).
 // The chunk's source rows are resolved once into LDS (one coalesced int32 read of the table per chunk; a chunk inside the prefix reads
 // no table at all), so the K and V loads stay what they are there: LPR lanes read one 16-byte slice each of a key row, and the lookup
-// only changes the row base the slices hang from.  Scores, chunk statistics, P V and the combine are that kernel's statement for
-// statement, which is what makes the output bit-identical to it on the gathered cache.
-constexpr int AD_GMAX = 8;
-constexpr int AD_CHUNK_MAX = 512;
-
+// only changes the row base the slices hang from.  Scores, chunk statistics, P V and the combine are that kernel's own -- both run
+// attn_split.h's attn_decode_body -- which is what makes the output bit-identical to it on the gathered cache.
 template <int HD>
 __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16* __restrict__ q, long ld_q, const bf16* __restrict__ cache, long ld_c,
                                                                long bs_c, int v_off, const int* __restrict__ kv_len, int L_max,
                                                                const int* __restrict__ prefix_row, const int* __restrict__ prefix_len,
                                                                const int* __restrict__ tail_src, long ld_t, int tail_cols, int cache_rows,
                                                                float* __restrict__ part, int H, int Hkv, int chunk, float scale) {
-    constexpr int LPR = HD / 8, RPW = 64 / LPR, RPB = 4 * RPW;
-    __shared__ float sc[AD_GMAX][AD_CHUNK_MAX];
-    __shared__ float ored[4][AD_GMAX][HD];
-    __shared__ float mstat[AD_GMAX];
     __shared__ int srow[AD_CHUNK_MAX];
-    const int c = blockIdx.x, kh = blockIdx.y, b = blockIdx.z;
+    const int c = blockIdx.x, b = blockIdx.z;
     const int G = H / Hkv;
     const int nch = gridDim.x;
     const int len = min(kv_len[b], L_max);
     const int j0 = c * chunk;
     if (j0 >= len) return;                     // the combine reads chunks < ceil(len / chunk) only
     const int j1 = min(j0 + chunk, len), n = j1 - j0;
-    const int lane = lane_id(), w = wave_id();
-    const int li = lane % LPR, lr = lane / LPR;
     // source rows of the chunk's keys; an entry past tail_cols cannot be looked up and falls back to the prefix row
     {
         const int plen = max(prefix_len[b], 0);
@@ -53,115 +45,7 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16* __res
         }
     }
     __syncthreads();
-    const bf16* kbase = cache + kh * HD + li * 8;
-    const bf16* vbase = kbase + v_off;
-    float qv[AD_GMAX][8];
-#pragma unroll
-    for (int g = 0; g < AD_GMAX; ++g) {
-        if (g < G) {
-            const bf16x8 t = *(const bf16x8*)(q + (long)b * ld_q + (kh * G + g) * HD + li * 8);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) qv[g][i] = bf2f(t[i]);
-        }
-    }
-    // scores
-    for (int jb = j0; jb < j1; jb += RPB) {
-        const int j = jb + w * RPW + lr;
-        const bool ok = j < j1;
-        const bf16x8 kt = ok ? *(const bf16x8*)(kbase + (long)srow[j - j0] * bs_c + (long)j * ld_c) : zero8();
-#pragma unroll
-        for (int g = 0; g < AD_GMAX; ++g) {
-            if (g < G) {
-                float d = 0.f;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) d += qv[g][i] * bf2f(kt[i]);
-#pragma unroll
-                for (int o = 1; o < LPR; o <<= 1) d += __shfl_xor(d, o, 64);
-                if (ok && li == 0) sc[g][j - j0] = d * scale;
-            }
-        }
-    }
-    __syncthreads();
-    // chunk softmax statistics: wave w owns heads w and w + 4
-    for (int g = w; g < G; g += 4) {
-        float m = -INFINITY;
-        for (int j = lane; j < n; j += 64) m = fmaxf(m, sc[g][j]);
-        m = wave_max(m);
-        float l = 0.f;
-        for (int j = lane; j < n; j += 64) {
-            const float p = expf(sc[g][j] - m);
-            sc[g][j] = p;
-            l += p;
-        }
-        l = wave_sum(l);
-        if (lane == 0) {
-            mstat[g] = m;
-            float* pp = part + (((long)b * H + kh * G + g) * nch + c) * (HD + 2);
-            pp[HD] = m;
-            pp[HD + 1] = l;
-        }
-    }
-    __syncthreads();
-    // P V
-    float acc[AD_GMAX][8];
-#pragma unroll
-    for (int g = 0; g < AD_GMAX; ++g)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[g][i] = 0.f;
-    for (int jb = j0; jb < j1; jb += RPB) {
-        const int j = jb + w * RPW + lr;
-        if (j < j1) {
-            const bf16x8 vt = *(const bf16x8*)(vbase + (long)srow[j - j0] * bs_c + (long)j * ld_c);
-#pragma unroll
-            for (int g = 0; g < AD_GMAX; ++g) {
-                if (g < G) {
-                    const float p = sc[g][j - j0];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[g][i] += p * bf2f(vt[i]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < AD_GMAX; ++g) {
-        if (g < G) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                float a = acc[g][i];
-#pragma unroll
-                for (int o = LPR; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
-                if (lr == 0) ored[w][g][li * 8 + i] = a;
-            }
-        }
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < G * HD; idx += 256) {
-        const int g = idx / HD, dd = idx % HD;
-        float o = ored[0][g][dd];
-        o += ored[1][g][dd];
-        o += ored[2][g][dd];
-        o += ored[3][g][dd];
-        part[(((long)b * H + kh * G + g) * nch + c) * (HD + 2) + dd] = o;
-    }
-}
-
-// decode.hip's attn_decode_combine_kernel: one block of HD threads per (row, q head), chunks merged in chunk order
-template <int HD>
-__global__ __launch_bounds__(HD) void attn_decode_beam_combine_kernel(const float* __restrict__ part, const int* __restrict__ kv_len, int L_max,
-                                                                      bf16* __restrict__ out, long ld_o, int H, int nch, int chunk) {
-    const int bh = blockIdx.x, b = bh / H, h = bh % H, dd = threadIdx.x;
-    const int len = min(kv_len[b], L_max);
-    const int nc = min((len + chunk - 1) / chunk, nch);
-    const float* pp = part + (long)bh * nch * (HD + 2);
-    float M = -INFINITY;
-    for (int c = 0; c < nc; ++c) M = fmaxf(M, pp[c * (HD + 2) + HD]);
-    float L = 0.f, o = 0.f;
-    for (int c = 0; c < nc; ++c) {
-        const float e = expf(pp[c * (HD + 2) + HD] - M);
-        L += pp[c * (HD + 2) + HD + 1] * e;
-        o += pp[c * (HD + 2) + dd] * e;
-    }
-    out[(long)b * ld_o + h * HD + dd] = f2bf(nc > 0 ? o / L : 0.f);
+    attn_decode_body<HD>(q, ld_q, cache, ld_c, v_off, [&](int jj) { return (long)srow[jj] * bs_c; }, j0, j1, part, H, G, nch, scale);
 }
 
 // ------------------------------------------------------------------------------------------------ row log-softmax
@@ -216,19 +100,13 @@ constexpr int TK_PER = 16;
 constexpr int TK_SLICE = 256 * TK_PER;
 constexpr int TK_NONE = 0x7fffffff;
 
-DEVINL bool tk_better(float v, int i, float bv, int bi) {
-    const bool vn = v != v, bn = bv != bv;
-    if (vn || bn) return vn && (!bn || i < bi);
-    return v > bv || (v == bv && i < bi);
-}
-
 // best of the workgroup's candidates (bv, bi), known to every thread on return; `rv`/`ri` are 2 x 4 LDS words, `par` flips per call
 DEVINL void tk_block_best(float& bv, int& bi, float (*rv)[4], int (*ri)[4], int par) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(bv, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
-        if (tk_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        if (am_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
     if (lane_id() == 0) { rv[par][wave_id()] = bv; ri[par][wave_id()] = bi; }
     __syncthreads();
@@ -236,7 +114,7 @@ DEVINL void tk_block_best(float& bv, int& bi, float (*rv)[4], int (*ri)[4], int 
     bi = ri[par][0];
 #pragma unroll
     for (int k = 1; k < 4; ++k)
-        if (tk_better(rv[par][k], ri[par][k], bv, bi)) { bv = rv[par][k]; bi = ri[par][k]; }
+        if (am_better(rv[par][k], ri[par][k], bv, bi)) { bv = rv[par][k]; bi = ri[par][k]; }
 }
 
 __global__ __launch_bounds__(256) void beam_topk_slices_kernel(const float* __restrict__ x, long ld, int n, int nb,
@@ -268,8 +146,8 @@ __global__ __launch_bounds__(256) void beam_topk_slices_kernel(const float* __re
         int bi = TK_NONE;
 #pragma unroll
         for (int e = 0; e < TK_PER; ++e) {
-            const bool after = pi < 0 || tk_better(pv, pi, v[e], id[e]);
-            if (after && tk_better(v[e], id[e], bv, bi)) { bv = v[e]; bi = id[e]; }
+            const bool after = pi < 0 || am_better(pv, pi, v[e], id[e]);
+            if (after && am_better(v[e], id[e], bv, bi)) { bv = v[e]; bi = id[e]; }
         }
         tk_block_best(bv, bi, rv, ri, k & 1);
         if (threadIdx.x == 0) { ov[k] = bv; oi[k] = bi; }
@@ -297,8 +175,8 @@ __global__ __launch_bounds__(256) void beam_topk_merge_kernel(const float* __res
         for (int e = threadIdx.x; e < cand; e += 256) {
             const float v = cv[e];
             const int i = ci[e];
-            const bool after = pi < 0 || tk_better(pv, pi, v, i);
-            if (after && tk_better(v, i, bv, bi)) { bv = v; bi = i; }
+            const bool after = pi < 0 || am_better(pv, pi, v, i);
+            if (after && am_better(v, i, bv, bi)) { bv = v; bi = i; }
         }
         tk_block_best(bv, bi, rv, ri, k & 1);
         if (threadIdx.x == 0) { out_v[(long)g * K + k] = bv; out_i[(long)g * K + k] = bi; }
@@ -314,28 +192,14 @@ extern "C" int rv_attn_decode_beam_bf16(const void* q, int64_t ld_q, const void*
                                         const int32_t* tail_src, int64_t ld_t, int tail_cols, int cache_rows, void* out, int64_t ld_o,
                                         void* part, int64_t part_bytes, int rows, int H, int Hkv, int hd, int chunk, float scale,
                                         void* stream) {
-    if (!q || !cache || !kv_len || !prefix_row || !prefix_len || !out || !part || rows <= 0 || cache_rows <= 0 || Hkv <= 0 || H % Hkv ||
-        H / Hkv > AD_GMAX || (hd != 64 && hd != 128) || L_max <= 0 || chunk <= 0 || chunk > AD_CHUNK_MAX || chunk % (hd == 128 ? 16 : 32) ||
-        (ld_q & 7) || (ld_c & 7) || (bs_c & 7) || (v_off & 7) || ld_q < (int64_t)H * hd || ld_o < (int64_t)H * hd ||
-        ld_c < v_off + (int64_t)Hkv * hd || bs_c < (int64_t)L_max * ld_c || tail_cols < 0 || (tail_cols > 0 && (!tail_src || ld_t < tail_cols)))
-        return RV_ERR_ARG;
-    const int nch = (L_max + chunk - 1) / chunk;
-    if (part_bytes < (int64_t)rows * H * nch * (hd + 2) * 4) return RV_ERR_ARG;
-    const dim3 grid(nch, Hkv, rows);
-    if (hd == 128) {
-        hipLaunchKernelGGL(attn_decode_beam_kernel<128>, grid, dim3(256), 0, ST, (const bf16*)q, (long)ld_q, (const bf16*)cache, (long)ld_c,
-                           (long)bs_c, v_off, kv_len, L_max, prefix_row, prefix_len, tail_src, (long)ld_t, tail_cols, cache_rows, (float*)part, H,
-                           Hkv, chunk, scale);
-        hipLaunchKernelGGL(attn_decode_beam_combine_kernel<128>, dim3(rows * H), dim3(128), 0, ST, (const float*)part, kv_len, L_max, (bf16*)out,
-                           (long)ld_o, H, nch, chunk);
-    } else {
-        hipLaunchKernelGGL(attn_decode_beam_kernel<64>, grid, dim3(256), 0, ST, (const bf16*)q, (long)ld_q, (const bf16*)cache, (long)ld_c,
-                           (long)bs_c, v_off, kv_len, L_max, prefix_row, prefix_len, tail_src, (long)ld_t, tail_cols, cache_rows, (float*)part, H,
-                           Hkv, chunk, scale);
-        hipLaunchKernelGGL(attn_decode_beam_combine_kernel<64>, dim3(rows * H), dim3(64), 0, ST, (const float*)part, kv_len, L_max, (bf16*)out,
-                           (long)ld_o, H, nch, chunk);
-    }
-    return rv_check_launch();
+    const bool ok = kv_len && prefix_row && prefix_len && cache_rows > 0 && tail_cols >= 0 && (tail_cols == 0 || (tail_src && ld_t >= tail_cols)) &&
+                    ad_chunk_ok(chunk, hd) && split_cache_ok(cache, ld_c, bs_c, v_off, Hkv, hd, L_max);
+    return attn_split_launch(ok, q, ld_q, out, ld_o, part, part_bytes, rows, H, Hkv, hd, L_max, chunk, stream, RowsKvLen{kv_len, L_max},
+                             [&](auto hd_c, int nch) {
+                                 hipLaunchKernelGGL(attn_decode_beam_kernel<hd_c()>, dim3(nch, Hkv, rows), dim3(256), 0, ST, (const bf16*)q,
+                                                    (long)ld_q, (const bf16*)cache, (long)ld_c, (long)bs_c, v_off, kv_len, L_max, prefix_row,
+                                                    prefix_len, tail_src, (long)ld_t, tail_cols, cache_rows, (float*)part, H, Hkv, chunk, scale);
+                             });
 }
 
 extern "C" int rv_log_softmax_rows_f32(float* x, int64_t ld, int rows, int n, void* stream) {

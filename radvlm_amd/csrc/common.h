@@ -58,6 +58,14 @@ DEVINL float wave_max(float v) {
     return v;
 }
 
+// torch.argmax's order: does candidate (v, i) rank before (bv, bi)?  NaN above everything, then the larger value, then the lower index.
+// rv_argmax_rows_f32 and the logits processors (decode.hip), rv_beam_topk_f32 (beam.hip) and rv_token_logprob_rows_f32 (score.hip).
+DEVINL bool am_better(float v, int i, float bv, int bi) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > bv || (v == bv && i < bi);
+}
+
 // Block-wide sum for blocks of NW waves; `red` is NW floats of LDS. All threads get the result.
 template <int NW>
 DEVINL float block_sum(float v, float* red) {

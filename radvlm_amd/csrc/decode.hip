@@ -3,6 +3,7 @@
 // Reductions use a fixed order that depends on the problem shape only (a sequence's own kv_len) -- never on other rows or on
 // timing -- and no float atomics: a row's result is bit-identical whatever else shares its launch.
 // Reference call sites are listed per entry point in include/radvlm_hip.h.
+#include "attn_split.h"
 #include "common.h"
 #include "radvlm_hip.h"
 
@@ -11,138 +12,20 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------ decode attention
-// Block (chunk c, kv head kh, sequence b): keys [c*chunk, min((c+1)*chunk, kv_len[b])) for the G = H / Hkv query heads of kv head kh,
-// which share every K / V read.  LPR = HD/8 lanes read one 16-byte slice each of a key row; a wave covers 64/LPR rows per step.
-// Writes the chunk's (unnormalised o, running max m, sum l) to part[b][h][c][HD + 2]; attn_decode_combine_kernel merges the chunks.
-constexpr int AD_GMAX = 8;
-constexpr int AD_CHUNK_MAX = 512;
-
+// Block (chunk c, kv head kh, sequence b): keys [c*chunk, min((c+1)*chunk, kv_len[b])) of the sequence's own cache row, through
+// attn_split.h's register-q body.  Writes the chunk's partial; attn_split_combine_kernel merges the chunks.
 template <int HD>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16* __restrict__ q, long ld_q, const bf16* __restrict__ cache, long ld_c,
                                                           long bs_c, int v_off, const int* __restrict__ kv_len, int L_max, float* __restrict__ part,
                                                           int H, int Hkv, int chunk, float scale) {
-    constexpr int LPR = HD / 8, RPW = 64 / LPR, RPB = 4 * RPW;
-    __shared__ float sc[AD_GMAX][AD_CHUNK_MAX];
-    __shared__ float ored[4][AD_GMAX][HD];
-    __shared__ float mstat[AD_GMAX];
-    const int c = blockIdx.x, kh = blockIdx.y, b = blockIdx.z;
+    const int c = blockIdx.x, b = blockIdx.z;
     const int G = H / Hkv;
     const int nch = gridDim.x;
     const int len = min(kv_len[b], L_max);
     const int j0 = c * chunk;
     if (j0 >= len) return;                     // the combine reads chunks < ceil(len / chunk) only
-    const int j1 = min(j0 + chunk, len), n = j1 - j0;
-    const int lane = lane_id(), w = wave_id();
-    const int li = lane % LPR, lr = lane / LPR;
-    const bf16* kbase = cache + (long)b * bs_c + kh * HD + li * 8;
-    const bf16* vbase = kbase + v_off;
-    float qv[AD_GMAX][8];
-#pragma unroll
-    for (int g = 0; g < AD_GMAX; ++g) {
-        if (g < G) {
-            const bf16x8 t = *(const bf16x8*)(q + (long)b * ld_q + (kh * G + g) * HD + li * 8);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) qv[g][i] = bf2f(t[i]);
-        }
-    }
-    // scores
-    for (int jb = j0; jb < j1; jb += RPB) {
-        const int j = jb + w * RPW + lr;
-        const bool ok = j < j1;
-        const bf16x8 kt = ok ? *(const bf16x8*)(kbase + (long)j * ld_c) : zero8();
-#pragma unroll
-        for (int g = 0; g < AD_GMAX; ++g) {
-            if (g < G) {
-                float d = 0.f;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) d += qv[g][i] * bf2f(kt[i]);
-#pragma unroll
-                for (int o = 1; o < LPR; o <<= 1) d += __shfl_xor(d, o, 64);
-                if (ok && li == 0) sc[g][j - j0] = d * scale;
-            }
-        }
-    }
-    __syncthreads();
-    // chunk softmax statistics: wave w owns heads w and w + 4
-    for (int g = w; g < G; g += 4) {
-        float m = -INFINITY;
-        for (int j = lane; j < n; j += 64) m = fmaxf(m, sc[g][j]);
-        m = wave_max(m);
-        float l = 0.f;
-        for (int j = lane; j < n; j += 64) {
-            const float p = expf(sc[g][j] - m);
-            sc[g][j] = p;
-            l += p;
-        }
-        l = wave_sum(l);
-        if (lane == 0) {
-            mstat[g] = m;
-            float* pp = part + (((long)b * H + kh * G + g) * nch + c) * (HD + 2);
-            pp[HD] = m;
-            pp[HD + 1] = l;
-        }
-    }
-    __syncthreads();
-    // P V
-    float acc[AD_GMAX][8];
-#pragma unroll
-    for (int g = 0; g < AD_GMAX; ++g)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[g][i] = 0.f;
-    for (int jb = j0; jb < j1; jb += RPB) {
-        const int j = jb + w * RPW + lr;
-        if (j < j1) {
-            const bf16x8 vt = *(const bf16x8*)(vbase + (long)j * ld_c);
-#pragma unroll
-            for (int g = 0; g < AD_GMAX; ++g) {
-                if (g < G) {
-                    const float p = sc[g][j - j0];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[g][i] += p * bf2f(vt[i]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < AD_GMAX; ++g) {
-        if (g < G) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                float a = acc[g][i];
-#pragma unroll
-                for (int o = LPR; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
-                if (lr == 0) ored[w][g][li * 8 + i] = a;
-            }
-        }
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < G * HD; idx += 256) {
-        const int g = idx / HD, dd = idx % HD;
-        float o = ored[0][g][dd];
-        o += ored[1][g][dd];
-        o += ored[2][g][dd];
-        o += ored[3][g][dd];
-        part[(((long)b * H + kh * G + g) * nch + c) * (HD + 2) + dd] = o;
-    }
-}
-
-// one block of HD threads per (sequence, q head): chunks merged in chunk order, bf16 out [B, H*HD]
-template <int HD>
-__global__ __launch_bounds__(HD) void attn_decode_combine_kernel(const float* __restrict__ part, const int* __restrict__ kv_len, int L_max,
-                                                                 bf16* __restrict__ out, long ld_o, int H, int nch, int chunk) {
-    const int bh = blockIdx.x, b = bh / H, h = bh % H, dd = threadIdx.x;
-    const int len = min(kv_len[b], L_max);
-    const int nc = min((len + chunk - 1) / chunk, nch);
-    const float* pp = part + (long)bh * nch * (HD + 2);
-    float M = -INFINITY;
-    for (int c = 0; c < nc; ++c) M = fmaxf(M, pp[c * (HD + 2) + HD]);
-    float L = 0.f, o = 0.f;
-    for (int c = 0; c < nc; ++c) {
-        const float e = expf(pp[c * (HD + 2) + HD] - M);
-        L += pp[c * (HD + 2) + HD + 1] * e;
-        o += pp[c * (HD + 2) + dd] * e;
-    }
-    out[(long)b * ld_o + h * HD + dd] = f2bf(nc > 0 ? o / L : 0.f);
+    const int j1 = min(j0 + chunk, len);
+    attn_decode_body<HD>(q, ld_q, cache + (long)b * bs_c, ld_c, v_off, [](int) { return 0L; }, j0, j1, part, H, G, nch, scale);
 }
 
 // ------------------------------------------------------------------------------------------------ cache append
@@ -157,13 +40,7 @@ __global__ void kv_append_kernel(const bf16* __restrict__ src, long ld_src, bf16
 }
 
 // ------------------------------------------------------------------------------------------------ row argmax
-// torch.argmax semantics over the first n columns: the lowest index among equal maxima, NaN above everything
-DEVINL bool am_better(float v, int i, float bv, int bi) {
-    const bool vn = v != v, bn = bv != bv;
-    if (vn || bn) return vn && (!bn || i < bi);
-    return v > bv || (v == bv && i < bi);
-}
-
+// torch.argmax semantics over the first n columns (common.h's am_better): the lowest index among equal maxima, NaN above everything
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, long ld, int n, int64_t* __restrict__ out) {
     __shared__ float rv[4];
     __shared__ int ri[4];
@@ -404,25 +281,12 @@ __global__ __launch_bounds__(256) void logits_process_argmax_rows_kernel(
 extern "C" int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
                                    int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk,
                                    float scale, void* stream) {
-    if (!q || !cache || !kv_len || !out || !part || B <= 0 || Hkv <= 0 || H % Hkv || H / Hkv > AD_GMAX || (hd != 64 && hd != 128) ||
-        L_max <= 0 || chunk <= 0 || chunk > AD_CHUNK_MAX || chunk % (hd == 128 ? 16 : 32) || (ld_q & 7) || (ld_c & 7) || (bs_c & 7) ||
-        (v_off & 7) || ld_q < (int64_t)H * hd || ld_o < (int64_t)H * hd || ld_c < v_off + (int64_t)Hkv * hd || bs_c < (int64_t)L_max * ld_c)
-        return RV_ERR_ARG;
-    const int nch = (L_max + chunk - 1) / chunk;
-    if (part_bytes < (int64_t)B * H * nch * (hd + 2) * 4) return RV_ERR_ARG;
-    const dim3 grid(nch, Hkv, B);
-    if (hd == 128) {
-        hipLaunchKernelGGL(attn_decode_kernel<128>, grid, dim3(256), 0, ST, (const bf16*)q, (long)ld_q, (const bf16*)cache, (long)ld_c, (long)bs_c,
-                           v_off, kv_len, L_max, (float*)part, H, Hkv, chunk, scale);
-        hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(B * H), dim3(128), 0, ST, (const float*)part, kv_len, L_max, (bf16*)out,
-                           (long)ld_o, H, nch, chunk);
-    } else {
-        hipLaunchKernelGGL(attn_decode_kernel<64>, grid, dim3(256), 0, ST, (const bf16*)q, (long)ld_q, (const bf16*)cache, (long)ld_c, (long)bs_c,
-                           v_off, kv_len, L_max, (float*)part, H, Hkv, chunk, scale);
-        hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(B * H), dim3(64), 0, ST, (const float*)part, kv_len, L_max, (bf16*)out,
-                           (long)ld_o, H, nch, chunk);
-    }
-    return rv_check_launch();
+    return attn_split_launch(kv_len && ad_chunk_ok(chunk, hd) && split_cache_ok(cache, ld_c, bs_c, v_off, Hkv, hd, L_max), q, ld_q, out, ld_o,
+                             part, part_bytes, B, H, Hkv, hd, L_max, chunk, stream, RowsKvLen{kv_len, L_max}, [&](auto hd_c, int nch) {
+                                 hipLaunchKernelGGL(attn_decode_kernel<hd_c()>, dim3(nch, Hkv, B), dim3(256), 0, ST, (const bf16*)q, (long)ld_q,
+                                                    (const bf16*)cache, (long)ld_c, (long)bs_c, v_off, kv_len, L_max, (float*)part, H, Hkv, chunk,
+                                                    scale);
+                             });
 }
 
 extern "C" int rv_kv_append_bf16(const void* src, int64_t ld_src, void* cache, int64_t ld_c, int64_t bs_c, const int32_t* pos, int L_max, int B,

@@ -5,6 +5,7 @@
 // is decode.hip's attn_decode_kernel otherwise -- the same (key row, 8-element slice) per (wave, lane), the same xor butterflies, wave-order
 // sum and chunk combine -- so its output is bit-identical to rv_attn_decode_bf16 on the dequantised cache.  No atomics; every reduction
 // runs in a fixed order.  Reference call sites are listed per entry point in include/radvlm_hip.h.
+#include "attn_split.h"
 #include "common.h"
 #include "radvlm_hip.h"
 
@@ -70,8 +71,6 @@ __global__ __launch_bounds__(256) void kv_quantize_kernel(const bf16* __restrict
 // AK_U key rows are loaded before the first is used (8-byte loads need more of them in flight than the 16-byte ones of the bf16 kernel);
 // they are consumed in ascending order, so nothing above changes.  A key at or past kv_len is never loaded: its bytes and scale may be
 // anything.
-constexpr int AD_GMAX = 8;
-constexpr int AD_CHUNK_MAX = 512;
 constexpr int AK_U = 4;
 
 DEVINL void dq8f(u32x2 r, float s, float* out) {
@@ -219,25 +218,6 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const bf16* __rest
     }
 }
 
-// decode.hip's attn_decode_combine_kernel, restated: one block of HD threads per (sequence, q head), chunks merged in chunk order
-template <int HD>
-__global__ __launch_bounds__(HD) void attn_decode_kv8_combine_kernel(const float* __restrict__ part, const int* __restrict__ kv_len, int L_max,
-                                                                     bf16* __restrict__ out, long ld_o, int H, int nch, int chunk) {
-    const int bh = blockIdx.x, b = bh / H, h = bh % H, dd = threadIdx.x;
-    const int len = min(kv_len[b], L_max);
-    const int nc = min((len + chunk - 1) / chunk, nch);
-    const float* pp = part + (long)bh * nch * (HD + 2);
-    float M = -INFINITY;
-    for (int c = 0; c < nc; ++c) M = fmaxf(M, pp[c * (HD + 2) + HD]);
-    float L = 0.f, o = 0.f;
-    for (int c = 0; c < nc; ++c) {
-        const float e = expf(pp[c * (HD + 2) + HD] - M);
-        L += pp[c * (HD + 2) + HD + 1] * e;
-        o += pp[c * (HD + 2) + dd] * e;
-    }
-    out[(long)b * ld_o + h * HD + dd] = f2bf(nc > 0 ? o / L : 0.f);
-}
-
 int kv_quantize_launch(const void* src, int64_t ld_src, void* q8, int64_t ld_q, float* s, int64_t ld_s, void* xhat, int64_t ld_x,
                        const int64_t* rows, const int32_t* pos, int L_max, int64_t cache_rows, int M, int Hkv, int hd, void* stream) {
     const int64_t width = 2 * (int64_t)Hkv * hd;
@@ -280,24 +260,12 @@ extern "C" int rv_attn_decode_kv8_bf16(const void* q, int64_t ld_q, const void* 
                                        const float* cache_s, int64_t ld_s, int64_t bs_s, int vs_off, const int32_t* kv_len, int L_max, void* out,
                                        int64_t ld_o, void* part, int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk, float scale,
                                        void* stream) {
-    if (!q || !cache_q8 || !cache_s || !kv_len || !out || !part || B <= 0 || Hkv <= 0 || H % Hkv || H / Hkv > AD_GMAX ||
-        (hd != 64 && hd != 128) || L_max <= 0 || chunk <= 0 || chunk > AD_CHUNK_MAX || chunk % (hd == 128 ? 16 : 32) || (ld_q & 7) ||
-        (ld_c & 7) || (bs_c & 7) || (v_off & 7) || v_off < 0 || vs_off < 0 || ld_q < (int64_t)H * hd || ld_o < (int64_t)H * hd ||
-        ld_c < v_off + (int64_t)Hkv * hd || bs_c < (int64_t)L_max * ld_c || ld_s < vs_off + (int64_t)Hkv || bs_s < (int64_t)L_max * ld_s)
-        return RV_ERR_ARG;
-    const int nch = (L_max + chunk - 1) / chunk;
-    if (part_bytes < (int64_t)B * H * nch * (hd + 2) * 4) return RV_ERR_ARG;
-    const dim3 grid(nch, Hkv, B);
-    if (hd == 128) {
-        hipLaunchKernelGGL(attn_decode_kv8_kernel<128>, grid, dim3(256), 0, ST, (const bf16*)q, (long)ld_q, (const signed char*)cache_q8, (long)ld_c,
-                           (long)bs_c, v_off, cache_s, (long)ld_s, (long)bs_s, vs_off, kv_len, L_max, (float*)part, H, Hkv, chunk, scale);
-        hipLaunchKernelGGL(attn_decode_kv8_combine_kernel<128>, dim3(B * H), dim3(128), 0, ST, (const float*)part, kv_len, L_max, (bf16*)out,
-                           (long)ld_o, H, nch, chunk);
-    } else {
-        hipLaunchKernelGGL(attn_decode_kv8_kernel<64>, grid, dim3(256), 0, ST, (const bf16*)q, (long)ld_q, (const signed char*)cache_q8, (long)ld_c,
-                           (long)bs_c, v_off, cache_s, (long)ld_s, (long)bs_s, vs_off, kv_len, L_max, (float*)part, H, Hkv, chunk, scale);
-        hipLaunchKernelGGL(attn_decode_kv8_combine_kernel<64>, dim3(B * H), dim3(64), 0, ST, (const float*)part, kv_len, L_max, (bf16*)out,
-                           (long)ld_o, H, nch, chunk);
-    }
-    return rv_check_launch();
+    const bool ok = kv_len && cache_s && v_off >= 0 && vs_off >= 0 && ld_s >= vs_off + (int64_t)Hkv && bs_s >= (int64_t)L_max * ld_s &&
+                    ad_chunk_ok(chunk, hd) && split_cache_ok(cache_q8, ld_c, bs_c, v_off, Hkv, hd, L_max);
+    return attn_split_launch(ok, q, ld_q, out, ld_o, part, part_bytes, B, H, Hkv, hd, L_max, chunk, stream, RowsKvLen{kv_len, L_max},
+                             [&](auto hd_c, int nch) {
+                                 hipLaunchKernelGGL(attn_decode_kv8_kernel<hd_c()>, dim3(nch, Hkv, B), dim3(256), 0, ST, (const bf16*)q, (long)ld_q,
+                                                    (const signed char*)cache_q8, (long)ld_c, (long)bs_c, v_off, cache_s, (long)ld_s, (long)bs_s,
+                                                    vs_off, kv_len, L_max, (float*)part, H, Hkv, chunk, scale);
+                             });
 }

@@ -664,19 +664,28 @@ def gemv_w4(x, packed, scales, K, out=None, bias=None, residual=None, out_dtype=
     return out
 
 
+def _attn_split_args(q, rows, H, hd, keys, out, chunk, scale):
+    """What the seven split-KV attention wrappers share (csrc/attn_split.h's launcher checks the same on its side): the default scale,
+    `out` (bf16 [rows, H*hd], allocated unless passed in, rows of unit stride) and the fp32 partial buffer for ceil(keys / chunk)
+    chunks of every (row, head).  Returns (out, part, part_bytes, scale)."""
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if out is None:
+        out = torch.empty(rows, H * hd, dtype=BF16, device=q.device)
+    assert out.shape == (rows, H * hd) and out.stride(1) == 1
+    nch = (keys + chunk - 1) // chunk
+    part = torch.empty(rows * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    return out, part, part.numel() * 4, float(scale)
+
+
 def attn_decode(q, cache, kv_len, H, Hkv, hd, v_off, out=None, chunk=128, scale=None):
     """One query row per (sequence, q head) against the cached keys [0, kv_len[b]): q [B, H*hd] rows; cache bf16 [B, L_max, width]
     with K of kv head g at columns g*hd and V at v_off + g*hd; kv_len int32 [B] (device).  Returns bf16 [B, H*hd]."""
     _chk(q), _chk(cache), _chk(kv_len, torch.int32)
     B, L_max, width = cache.shape
     assert q.shape == (B, H * hd) and q.stride(1) == 1 and cache.is_contiguous() and kv_len.numel() == B and kv_len.is_contiguous()
-    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
-    if out is None:
-        out = torch.empty(B, H * hd, dtype=BF16, device=q.device)
-    nch = (L_max + chunk - 1) // chunk
-    part = torch.empty(B * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    out, part, part_bytes, scale = _attn_split_args(q, B, H, hd, L_max, out, chunk, scale)
     lib.call("rv_attn_decode_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len, L_max, out, out.stride(0), part,
-             part.numel() * 4, B, H, Hkv, hd, chunk, float(scale))
+             part_bytes, B, H, Hkv, hd, chunk, scale)
     return out
 
 
@@ -692,13 +701,9 @@ def attn_extend(q, cache, cu_q, r, H, Hkv, hd, v_off, max_q, out=None, chunk=EXT
     M = q.shape[0]
     assert q.shape == (M, H * hd) and q.stride(1) == 1 and cache.is_contiguous() and cu_q.numel() == B + 1 and r.numel() == B
     assert cu_q.is_contiguous() and r.is_contiguous() and 1 <= max_q <= M
-    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
-    if out is None:
-        out = torch.empty(M, H * hd, dtype=BF16, device=q.device)
-    nch = (L_max + chunk - 1) // chunk
-    part = torch.empty(M * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    out, part, part_bytes, scale = _attn_split_args(q, M, H, hd, L_max, out, chunk, scale)
     lib.call("rv_attn_extend_bf16", q, q.stride(0), cache, width, L_max * width, v_off, cu_q, r, L_max, out, out.stride(0), part,
-             part.numel() * 4, B, M, int(max_q), H, Hkv, hd, chunk, float(scale))
+             part_bytes, B, M, int(max_q), H, Hkv, hd, chunk, scale)
     return out
 
 
@@ -716,15 +721,10 @@ def attn_extend_prefix(q, prefix, tail, cu_q, prefix_row, prefix_len, H, Hkv, hd
     assert tw == width and q.shape == (M, H * hd) and q.stride(1) == 1 and cu_q.numel() == B + 1
     assert prefix_row.numel() == B and prefix_len.numel() == B
     assert cu_q.is_contiguous() and prefix_row.is_contiguous() and prefix_len.is_contiguous() and 1 <= max_q <= M
-    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
-    if out is None:
-        out = torch.empty(M, H * hd, dtype=BF16, device=q.device)
-    assert out.shape == (M, H * hd) and out.stride(1) == 1
-    nch = (P_max + T_max + chunk - 1) // chunk
-    part = torch.empty(M * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    out, part, part_bytes, scale = _attn_split_args(q, M, H, hd, P_max + T_max, out, chunk, scale)
     lib.call("rv_attn_extend_prefix_bf16", q, q.stride(0), prefix, width, P_max * width, P_rows, P_max, tail, width, T_max * width, T_max,
-             v_off, cu_q, prefix_row, prefix_len, out, out.stride(0), part, part.numel() * 4, B, M, int(max_q), H, Hkv, hd, chunk,
-             float(scale))
+             v_off, cu_q, prefix_row, prefix_len, out, out.stride(0), part, part_bytes, B, M, int(max_q), H, Hkv, hd, chunk,
+             scale)
     return out
 
 
@@ -808,13 +808,9 @@ def attn_decode_kv8(q, cache, kv_len, H, Hkv, hd, v_off, out=None, chunk=128, sc
     B, L_max, width = q8.shape
     assert q.shape == (B, H * hd) and q.stride(1) == 1 and q8.is_contiguous() and kv_len.numel() == B and kv_len.is_contiguous()
     assert s.shape == (B, L_max, 2 * Hkv) and s.is_contiguous()
-    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
-    if out is None:
-        out = torch.empty(B, H * hd, dtype=BF16, device=q.device)
-    nch = (L_max + chunk - 1) // chunk
-    part = torch.empty(B * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    out, part, part_bytes, scale = _attn_split_args(q, B, H, hd, L_max, out, chunk, scale)
     lib.call("rv_attn_decode_kv8_bf16", q, q.stride(0), q8, width, L_max * width, v_off, s, 2 * Hkv, L_max * 2 * Hkv, Hkv, kv_len, L_max,
-             out, out.stride(0), part, part.numel() * 4, B, H, Hkv, hd, chunk, float(scale))
+             out, out.stride(0), part, part_bytes, B, H, Hkv, hd, chunk, scale)
     return out
 
 
@@ -939,14 +935,10 @@ def attn_decode_beam(q, cache, kv_len, prefix_row, prefix_len, tail_src, H, Hkv,
         tail_cols = tail_src.shape[1] if tail_cols is None else int(tail_cols)
         assert 0 <= tail_cols <= tail_src.shape[1]
         ld_t = tail_src.stride(0)
-    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
-    if out is None:
-        out = torch.empty(rows, H * hd, dtype=BF16, device=q.device)
-    nch = (L_max + chunk - 1) // chunk
-    part = torch.empty(rows * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    out, part, part_bytes, scale = _attn_split_args(q, rows, H, hd, L_max, out, chunk, scale)
     lib.call("rv_attn_decode_beam_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len, L_max, prefix_row, prefix_len,
-             tail_src if tail_cols else None, ld_t, tail_cols, cache_rows, out, out.stride(0), part, part.numel() * 4, rows, H, Hkv, hd, chunk,
-             float(scale))
+             tail_src if tail_cols else None, ld_t, tail_cols, cache_rows, out, out.stride(0), part, part_bytes, rows, H, Hkv, hd, chunk,
+             scale)
     return out
 
 
@@ -962,14 +954,9 @@ def attn_decode_verify(q, cache, kv_len0, R, H, Hkv, hd, v_off, out=None, chunk=
     B, L_max, width = cache.shape
     R = int(R)
     assert q.shape == (B * R, H * hd) and q.stride(1) == 1 and cache.is_contiguous() and kv_len0.numel() == B and kv_len0.is_contiguous()
-    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
-    if out is None:
-        out = torch.empty(B * R, H * hd, dtype=BF16, device=q.device)
-    assert out.shape == (B * R, H * hd) and out.stride(1) == 1
-    nch = (L_max + chunk - 1) // chunk
-    part = torch.empty(B * R * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    out, part, part_bytes, scale = _attn_split_args(q, B * R, H, hd, L_max, out, chunk, scale)
     lib.call("rv_attn_decode_verify_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len0, L_max, out, out.stride(0), part,
-             part.numel() * 4, B, R, H, Hkv, hd, chunk, float(scale))
+             part_bytes, B, R, H, Hkv, hd, chunk, scale)
     return out
 
 
@@ -999,14 +986,9 @@ def attn_decode_shared(q, cache, kv_len, c0, tile, H, Hkv, hd, v_off, out=None, 
     B, L_max, width = cache.shape
     assert q.shape == (B, H * hd) and q.stride(1) == 1 and cache.is_contiguous() and kv_len.numel() == B and kv_len.is_contiguous()
     assert c0.shape == (B,) and c0.is_contiguous() and tile.shape == (B, SHARED_TILE_COLS) and tile.is_contiguous()
-    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
-    if out is None:
-        out = torch.empty(B, H * hd, dtype=BF16, device=q.device)
-    assert out.shape == (B, H * hd) and out.stride(1) == 1
-    nch = (L_max + chunk - 1) // chunk
-    part = torch.empty(B * H * nch * (hd + 2), dtype=torch.float32, device=q.device)
+    out, part, part_bytes, scale = _attn_split_args(q, B, H, hd, L_max, out, chunk, scale)
     lib.call("rv_attn_decode_shared_bf16", q, q.stride(0), cache, width, L_max * width, v_off, kv_len, c0, tile, L_max, out, out.stride(0),
-             part, part.numel() * 4, B, H, Hkv, hd, chunk, float(scale))
+             part, part_bytes, B, H, Hkv, hd, chunk, scale)
     return out
 
 

@@ -517,6 +517,66 @@ def test_attn_decode_refuses_bad_arguments():
     torch.cuda.synchronize()
 
 
+SPLIT_ATTN_ENTRIES = ("decode", "beam", "kv8", "verify", "shared", "extend", "extend_prefix")
+
+
+@pytest.mark.parametrize("entry", SPLIT_ATTN_ENTRIES)
+def test_split_attn_refuses_bad_arguments(entry):
+    """The seven cache-attention entry points share one launcher (csrc/attn_split.h's attn_split_launch): each accepts the base call
+    with `part` exactly large enough and refuses the same eight bad argument sets, every one before any launch (the buffers are large
+    enough for each call all the same).  2 sequences, hd 64, H 4, Hkv 2, 128 key positions, chunk 64; verify: R = 2 rows per sequence;
+    the extend pair: 2 new rows per sequence."""
+    _ops()
+    from radvlm_amd.lib import RadvlmHipError
+    B, L_max, R = 2, 128, 2
+    H_MAX, HD_MAX = 18, 128
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32).cuda()
+    rows = B if entry in ("decode", "beam", "kv8", "shared") else B * R
+    q = torch.zeros(rows * (H_MAX * HD_MAX + 8), dtype=BF16, device="cuda")
+    out = torch.zeros(rows * H_MAX * HD_MAX, dtype=BF16, device="cuda")
+    cache = torch.zeros(B * L_max * 2 * 2 * HD_MAX, dtype=BF16, device="cuda")
+    cache8 = torch.zeros(B * L_max * 2 * 2 * HD_MAX, dtype=torch.int8, device="cuda")
+    cache_s = torch.ones(B * L_max * 2 * 2, dtype=torch.float32, device="cuda")
+    part = torch.zeros(rows * H_MAX * 2 * (HD_MAX + 2), dtype=torch.float32, device="cuda")
+    kv_len, own_row, cu_q = i32([3, L_max]), i32([0, 1]), i32([0, 2, 4])
+    tile = i32([[0] + [-1] * 15, [1] + [-1] * 15])
+
+    def run(q_null=False, H=4, Hkv=2, hd=64, chunk=64, ld_q=None, ld_o=None, part_short=0):
+        qq = None if q_null else q
+        ld_q = H * hd if ld_q is None else ld_q
+        ld_o = H * hd if ld_o is None else ld_o
+        kvd = Hkv * hd
+        ld_c, bs_c = 2 * kvd, L_max * 2 * kvd
+        nch = (L_max + chunk - 1) // chunk if chunk > 0 else 1
+        pb = rows * H * nch * (hd + 2) * 4 - part_short
+        tail = (out, ld_o, part, pb)
+        dims = (H, Hkv, hd, chunk, 0.125)
+        if entry == "decode":
+            _call("rv_attn_decode_bf16", qq, ld_q, cache, ld_c, bs_c, kvd, kv_len, L_max, *tail, B, *dims)
+        elif entry == "beam":
+            _call("rv_attn_decode_beam_bf16", qq, ld_q, cache, ld_c, bs_c, kvd, kv_len, L_max, own_row, i32([L_max, L_max]), None, 0, 0, B, *tail, B,
+                  *dims)
+        elif entry == "kv8":
+            _call("rv_attn_decode_kv8_bf16", qq, ld_q, cache8, ld_c, bs_c, kvd, cache_s, 2 * Hkv, L_max * 2 * Hkv, Hkv, kv_len, L_max, *tail, B, *dims)
+        elif entry == "verify":
+            _call("rv_attn_decode_verify_bf16", qq, ld_q, cache, ld_c, bs_c, kvd, i32([3, L_max - 1]), L_max, *tail, B, R, *dims)
+        elif entry == "shared":
+            _call("rv_attn_decode_shared_bf16", qq, ld_q, cache, ld_c, bs_c, kvd, kv_len, i32([0, 0]), tile, L_max, *tail, B, *dims)
+        elif entry == "extend":
+            _call("rv_attn_extend_bf16", qq, ld_q, cache, ld_c, bs_c, kvd, cu_q, i32([3, L_max - 2]), L_max, *tail, B, B * R, R, *dims)
+        else:       # one prefix row of 64 positions and 64 tail positions per sequence: 128 key positions
+            P = L_max // 2
+            _call("rv_attn_extend_prefix_bf16", qq, ld_q, cache, ld_c, P * ld_c, 1, P, cache[P * ld_c:], ld_c, P * ld_c, P, kvd, cu_q, i32([0, 0]),
+                  i32([3, P]), *tail, B, B * R, R, *dims)
+
+    run()                                                              # accepted, the partial buffer exactly large enough
+    bad = [dict(q_null=True), dict(H=5), dict(H=18), dict(hd=96), dict(chunk=0), dict(ld_q=4 * 64 + 4), dict(ld_o=4 * 64 - 8), dict(part_short=4)]
+    for kw in bad:
+        with pytest.raises(RadvlmHipError):
+            run(**kw)
+    torch.cuda.synchronize()
+
+
 def test_kv_append_refuses_bad_arguments():
     _ops()
     B, L_max = 2, 4
