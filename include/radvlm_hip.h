@@ -563,6 +563,32 @@ int rv_dola_contrast_rows_f32(float* f, int64_t ld_f, const float* c, int64_t ld
 /* Host function: the bytes of scratch rv_dola_contrast_rows_f32 needs. */
 int64_t rv_dola_ws_bytes(int rows, int n_layers);
 
+/* ---- constrained decoding (generate(constraint=), radvlm_amd/csrc/constrain.hip, radvlm_amd/constraints.py) -------------------------
+ * HF reaches it through generate(prefix_allowed_tokens_fn=...): PrefixConstrainedLogitsProcessor adds a mask of 0 / -inf after
+ * MinNewTokensLength and before SuppressTokens.  Every processor of rv_logits_process_argmax*_f32 other than the repetition penalty
+ * only writes -inf and the penalty maps -inf to -inf, so masking the raw row first and running the fused kernel unchanged gives HF's
+ * row.  Two differences: an allowed -0.0 keeps its sign (HF's `+ 0.0` makes it +0.0), and a banned NaN / +inf becomes -inf where HF
+ * keeps the NaN (the deviation the bad-words processor documents).  Here the allowed sets come from a deterministic automaton over
+ * token ids instead of a Python callback per row and step. */
+/* The automaton in CSR form: edge_off int32 [n_states + 1], edge_tok int32 [n_edges] strictly ascending within a state, edge_next
+ * int32 [n_edges] in [-1, n_states).  state: int32 [state_rows]; a value s >= 0 is live (allowed ids edge_tok[edge_off[s] ..
+ * edge_off[s + 1])), -1 is free, -2 and every other value outside [0, n_states) is dead.
+ * For each of `rows` rows of x (fp32, rows of ld floats, first n columns, n <= 262144), with si = slot ? slot[r] : r (slot: int32
+ * [rows] of distinct entries, or NULL) and s = state[si]:
+ *   advance  tok != NULL (int64 [rows]: the token chosen from the row's previous step): a live s becomes the edge_next of the edge
+ *            (s, tok[r]) -- -2 when s has no such edge, or when tok[r] is no int32 -- a negative s stays, and state[si] <- s.
+ *            tok == NULL (the first step after a prompt pass or an admission): s is used as it is and state is not written.
+ *   mask     s == -1: the row is not accessed.  Dead: x[r][0 .. n) <- -inf.  Live: every column of [0, n) that is not an allowed id
+ *            <- -inf; allowed columns are neither read nor written (NaN payloads and -0.0 stay).  Edge ids outside [0, n) are ignored.
+ * The kernel loads no element of x; columns >= n are never written.  One launch, one workgroup per row, no global atomics: a row's
+ * bits and its new state depend on its own state, token and edge run alone.  Tables that break the rules above cannot fault (run
+ * bounds are clamped into [0, n_edges]); a slot outside [0, state_rows) makes the row dead and writes no state.
+ * A null x, state or table, rows < 1, n < 1 or > 262144, ld < n, state_rows < 1, slot == NULL with rows > state_rows, n_states < 1
+ * and n_edges < 1 are refused (RV_ERR_ARG). */
+int rv_constrain_rows_f32(float* x, int64_t ld, int rows, int n, int32_t* state, int state_rows, const int32_t* slot, const int64_t* tok,
+                          const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, int n_states, int n_edges,
+                          void* stream);
+
 /* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens=), radvlm_amd/csrc/lookup.hip) ----------------------------------------
  * The reference reaches it through HF generate(prompt_lookup_num_tokens=k) (HF:generation/candidate_generator.py
  * PromptLookupCandidateGenerator -> _assisted_decoding): k tokens drafted from n-gram repeats of the sequence are verified by one

@@ -33,6 +33,8 @@ _GUIDANCE = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention
 # DoLa, decoding by contrasting layers (HF's name); _parse_dola / resolve_dola_layers
 _DOLA = ("dola_layers",)
 DOLA_MAX_LAYERS = 16          # candidate layers per call (rv_dola_contrast_rows_f32)
+# constrained decoding (ours: HF's prefix_allowed_tokens_fn is a Python callback per row and step); constraints.TokenConstraint
+_CONSTRAINT = ("constraint",)
 LOOKUP_MAX_TOKENS = 31        # k drafted tokens are verified as k + 1 rows, and the skinny GEMM takes ops.GEMV_MAX_M = 32
 
 
@@ -54,12 +56,24 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     Classifier-free guidance (.guidance: None when off, else .scale and the negative prompt as given, _parse_guidance): with
     past_key_values or prompt_lookup_num_tokens NotImplementedError.
     DoLa (.dola: None when off, else the validated dola_layers spec, _parse_dola; resolve_dola_layers turns it into layer numbers
-    once the call knows the engine's depth): with guidance_scale, past_key_values or prompt_lookup_num_tokens NotImplementedError."""
-    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and k not in _DOLA and not (lookup and k in _LOOKUP))
+    once the call knows the engine's depth): with guidance_scale, past_key_values or prompt_lookup_num_tokens NotImplementedError.
+    Constrained decoding (.constraint: None when off, else a TokenConstraint or a list of them with None entries, _parse_constraint;
+    constraints.resolve_constraints checks it against the row count and the vocabulary once the call knows them): with
+    prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError."""
+    unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and k not in _DOLA and k not in _CONSTRAINT
+                     and not (lookup and k in _LOOKUP))
     if unknown:
         raise TypeError(f"generate() got unexpected keyword arguments {unknown}")
     guidance = _parse_guidance(kwargs)
     dola = _parse_dola(kwargs)
+    constraint = _parse_constraint(kwargs)
+    if constraint is not None and kwargs.get("prompt_lookup_num_tokens") is not None:
+        raise NotImplementedError("constraint with prompt_lookup_num_tokens: every drafted row of a verify step would need its own "
+                                  "automaton state, which is not implemented")
+    if constraint is not None and guidance is not None:
+        raise NotImplementedError("constraint with guidance_scale: masking the two branches of a guided step is not implemented")
+    if constraint is not None and dola is not None:
+        raise NotImplementedError("constraint with dola_layers: masking the contrasted scores is not implemented")
     if kwargs.get("inputs_embeds") is not None:
         raise NotImplementedError("`inputs_embeds` is not supported")      # the reference's generate() raises the same
     if kwargs.get("do_sample") and kwargs.get("seed") is None:
@@ -116,8 +130,49 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
                            past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
-                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola,
+                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola, constraint=constraint,
                            **_parse_processors(kwargs, eos))
+
+
+def _parse_constraint(kwargs):
+    """The constraint keyword as far as it can be checked without the row count and the vocabulary: None (off), a TokenConstraint, or
+    a list of TokenConstraint and None entries (a tuple becomes a list).  ValueError for anything else."""
+    from .constraints import TokenConstraint
+    v = kwargs.get("constraint")
+    if v is None or isinstance(v, TokenConstraint):
+        return v
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"`constraint` has to be a TokenConstraint or a list with one (or None) per row, not {type(v).__name__}")
+    for i, c in enumerate(v):
+        if c is not None and not isinstance(c, TokenConstraint):
+            raise ValueError(f"`constraint[{i}]` has to be a TokenConstraint or None, not {type(c).__name__}")
+    return list(v)
+
+
+class ConstraintMirror:
+    """The host's copy of the automaton states a constrained call keeps on the device, one per row (generate) or per cache slot
+    (generate_batch), advanced with the tokens the loop reads back anyway: it finds a dead end at the step where it happens, without
+    another copy from the device.  A dead end: the processors or warpers banned everything the state allows -- min_new_tokens against
+    a state that allows only EOS, say -- so the row is all -inf and its token means nothing."""
+
+    def __init__(self, table, n):
+        self.table = table
+        self.state = np.full(n, -1, dtype=np.int64)
+
+    def take(self, idx, tokens, minus_inf, who, steps):
+        """Entries idx (int array) emitted `tokens` at their steps `steps`.  minus_inf(k): is the score of tokens[k] -inf?  Asked only
+        for a live entry that emitted token 0, which is what the argmax of an all -inf row gives; a negative token is the sampler's mark
+        for such a row.  RuntimeError naming who(k) and the step at the first dead end."""
+        idx, tokens = np.asarray(idx, dtype=np.int64), np.asarray(tokens, dtype=np.int64)
+        s = self.state[idx]
+        nxt = self.table.advance(s, tokens)
+        for k in np.flatnonzero((s >= 0) & ((nxt == -2) | (tokens == 0))):
+            if nxt[k] == -2 or minus_inf(int(k)):
+                ids = self.table.allowed(int(s[k]))
+                raise RuntimeError(f"constraint: {who(int(k))} reached a dead end at step {int(np.broadcast_to(steps, idx.shape)[k])}: "
+                                   f"its automaton state allows only the ids {ids[:8].tolist()}{' ...' if ids.size > 8 else ''}, and "
+                                   f"the logits processors or warpers banned all of them (or left no finite score)")
+        self.state[idx] = nxt
 
 
 def _parse_dola(kwargs):
@@ -849,7 +904,14 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     layers' logits (tap_layers=) and ops.dola_contrast_rows turns each step's raw rows into the contrasted rows in place, after
     output_logits has cloned the raw ones and before the processors, the argmax or the sampler, output_scores and the stopping
     criteria, which all see the contrasted rows (the place guidance puts the guided rows).  The dict output then carries
-    dola_premature_layers, int64 [B, steps]: the layer each row chose, -1 at steps after the row has finished."""
+    dola_premature_layers, int64 [B, steps]: the layer each row chose, -1 at steps after the row has finished.
+    cfg.constraint (constrained decoding): the rows' automata become one table and one int32 state per row on the device
+    (constraints.resolve_constraints), every call starting at the start states.  ops.constrain_rows runs on each step's logits after
+    output_logits has cloned the raw rows and before the processors, the argmax or the sampler: it advances every live state by the
+    token the row emitted last (the device copy of the tokens that decode_step is fed) and writes -inf on what the new state does
+    not allow, so output_scores, the stopping criteria and the sampler see the masked rows.  A row that took an EOS edge is free and
+    no longer touched; a row finished by a stopping criterion is fed pads, which may kill its state, and its rows mean nothing
+    then as before.  ConstraintMirror follows the states on the host and raises RuntimeError at the step of a dead end."""
     from . import ops
     ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids)
     if ids.ndim == 1:
@@ -878,6 +940,12 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             raise NotImplementedError("dola_layers with past_key_values or prompt_lookup_num_tokens is not implemented")
         dola = resolve_dola_layers(dola, engine.l["layers"])
         tap = dict(tap_layers=dola)
+    ctab = None
+    if getattr(cfg, "constraint", None) is not None:
+        if lookup or dola is not None:
+            raise NotImplementedError("constraint with prompt_lookup_num_tokens or dola_layers is not implemented")
+        from .constraints import resolve_constraints
+        ctab, cstart = resolve_constraints(cfg.constraint, B, engine.vocab)
     # prompt length in HF's sense: the spliced inputs_embeds width (the longest spliced prompt of the batch)
     plan_len = None
     if (cfg.max_new_tokens is None and cfg.max_length is not None) or min_needs_prompt_len(cfg):
@@ -923,11 +991,17 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             prompt_ids = ids[0] if am is None else ids[0][np.asarray(am).reshape(B, -1)[0].astype(bool)]
             lookup_stats = _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
         plain_steps = 0 if lookup else T     # the accept loop above has run the whole generation
+        if ctab is not None:              # every call starts at the start states, a continued conversation too
+            ctabs, cstate, ctok = ctab.device_tables(dev), engine._dev(cstart), None
+            mirror = ConstraintMirror(ctab, B)
+            mirror.state[:] = cstart
         for t in range(plain_steps):
             if cfg.output_logits:
                 raw.append(logits.clone())
             if dola is not None:          # in place: the raw mature rows become the contrasted rows
                 picks.append((ops.dola_contrast_rows(logits, cand[0], engine.vocab, ws=dws)[1], st.unfinished.copy()))
+            if ctab is not None:          # in place: each live row's state takes the row's last token, then bans what it does not allow
+                ops.constrain_rows(logits, engine.vocab, cstate, ctabs, tok=ctok)
             if lp.active:                 # in place: logits become HF's processed scores
                 nxt = ops.logits_process_argmax(logits, engine.vocab, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
             elif sm is None:
@@ -936,15 +1010,25 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                 nxt = ops.sample_rows(logits, engine.vocab, sm_seed, sm_t[t], sm.temperature, sm.top_k, sm.top_p, sm.min_p, write_scores=sm_write,
                                       ws=sm_ws)
                 nxt = nxt.cpu().numpy()
+                if ctab is not None:      # the sampler's -1 on a constrained row is a dead end, named as one
+                    bad = np.flatnonzero(st.unfinished & (nxt < 0))
+                    mirror.take(bad, nxt[bad], None, lambda k: f"row {bad[k]}", t)
                 _check_sampled(nxt, np.flatnonzero(st.unfinished))
             if cfg.output_scores:
                 scores.append(logits.clone())
+            was = st.unfinished.copy() if ctab is not None else None
             tok = st.step(nxt, logits, device=dev)
             if hist is not None:
                 hist[:, t] = torch.from_numpy(tok.astype(np.int32)).to(dev)
+            if ctab is not None:
+                was = np.flatnonzero(was)
+                mirror.take(was, tok[was], lambda k: lp.active and bool(torch.isneginf(logits[was[k], 0])), lambda k: f"row {was[k]}", t)
             if st.all_done or t == T - 1:
                 break
-            if dola is None:
+            if ctab is not None:          # one upload serves the next step's advance and the decode step
+                ctok = engine._dev(tok)
+                logits = engine.decode_step(cache, ctok)
+            elif dola is None:
                 logits = engine.decode_step(cache, torch.from_numpy(tok))
             else:
                 logits, *cand = engine.decode_step(cache, torch.from_numpy(tok), **tap)
@@ -989,7 +1073,8 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
     """generate_batch() keywords: generate()'s greedy and sampling settings (seed: an int, or a list of n ints), validated by parse_generate_kwargs and applied per request;
     max_new_tokens may also be a list of n budgets (cfg.budgets).  TypeError for arguments without a per-request meaning.
     share_prefix (cfg.share_prefix, default False): a bool, ValueError otherwise; NotImplementedError together with
-    kv_cache_dtype="int8", guidance_scale or dola_layers."""
+    kv_cache_dtype="int8", guidance_scale or dola_layers.  constraint (cfg.constraint): one TokenConstraint for every request or a
+    list of n entries, None for an unconstrained request; ValueError for another length."""
     given = sorted(k for k in _NO_PER_REQUEST if kwargs.get(k) is not None and kwargs.get(k) is not False)
     if given:
         raise TypeError(f"generate_batch() got arguments without a per-request meaning: {given}")
@@ -1027,6 +1112,8 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
             _per_request(k, getattr(cfg.guidance, k), n)      # a list of another length: ValueError here, before anything runs
     if cfg.sampling is not None:
         sampling_seeds(cfg.sampling, n)                       # a list of another length: ValueError here, before anything runs
+    if isinstance(cfg.constraint, list) and len(cfg.constraint) != n:
+        raise ValueError(f"`constraint` holds {len(cfg.constraint)} entries for {n} requests")
     return cfg
 
 
@@ -1279,9 +1366,18 @@ class BatchScheduler:
     cfg.dola (DoLa): the spec is resolved against the engine's depth once per call; admissions and decode steps ask the engine for the
     candidate layers' logits (tap_layers=) and `contrast(logits, candidates)` -- default ops.dola_contrast_rows -- turns the rows into
     the contrasted rows in place where `guide` runs in a guided call, before the picker.  Every row chooses its own layer, so an idle
-    slot's garbage row touches no other row.  Not combined with guidance or share_prefix.  Without cfg.dola nothing here changes."""
+    slot's garbage row touches no other row.  Not combined with guidance or share_prefix.  Without cfg.dola nothing here changes.
+    cfg.constraint (constrained decoding): the requests' automata become one table (constraints.resolve_constraints, checked against
+    the vocabulary before anything runs) and the device keeps one int32 state per cache slot.  _step runs `constrain(logits, slots,
+    starts, fed)` -- default: ops.constrain_rows -- before the picker.  After an admission (fed None) it first writes the admitted
+    requests' start states into their slots and masks the group's rows through slot=; in a decode step (fed: the device copy of the
+    tokens decode_step was given, one upload for both) row s is slot s, each live state takes its token's edge and the row is
+    masked.  An idle slot keeps whatever state its last request left, advanced by the 0 an idle slot is fed; its row is ignored as
+    ever and the next admission overwrites the state.  ConstraintMirror follows the states per slot on the host and raises
+    RuntimeError naming the request and its step at a dead end.  Without cfg.constraint nothing here changes."""
 
-    def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None, guide=None):
+    def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None, guide=None,
+                 constrain=None):
         if not _is_int(max_batch_size) or max_batch_size < 1:
             raise ValueError(f"max_batch_size must be an int >= 1, got {max_batch_size!r}")
         self.engine, self.reqs, self.cfg = engine, reqs, cfg
@@ -1308,6 +1404,12 @@ class BatchScheduler:
             if self.guidance is not None or self.share:
                 raise NotImplementedError("dola_layers with guidance_scale or share_prefix=True is not implemented")
             self.dola = resolve_dola_layers(self.dola, engine.l["layers"])
+        self.ctab, self.constrain = None, constrain
+        if getattr(cfg, "constraint", None) is not None:
+            if self.guidance is not None or self.dola is not None:
+                raise NotImplementedError("constraint with guidance_scale or dola_layers is not implemented")
+            from .constraints import resolve_constraints
+            self.ctab, self.cstart = resolve_constraints(cfg.constraint, n, engine.vocab, what="request")
         if self.guidance is not None:
             self.neg_spliced = [int(engine.plan(r.neg_ids[None], None, None, r.neg_images, r.neg_sizes)["lens"][0]) for r in reqs]
             self.L_max = max([max(self.spliced[i], self.neg_spliced[i]) + self.budget[i] for i in self.runs], default=0)
@@ -1360,6 +1462,10 @@ class BatchScheduler:
             from . import ops
             dws, V = ops.dola_workspace(S, len(self.dola), eng.device), eng.vocab
             self.contrast = lambda f, c: ops.dola_contrast_rows(f, c, V, ws=dws)
+        if self.ctab is not None:
+            self.mirror = ConstraintMirror(self.ctab, S)
+            if self.constrain is None:
+                self.constrain = self._device_constrain()
         self.owner = np.full(S, -1, dtype=np.int64)           # request in each slot, -1: idle
         self.t = np.zeros(S, dtype=np.int64)                  # tokens the slot's request has generated
         self.mn = np.zeros(S, dtype=np.int64)                 # its EOS minimum
@@ -1519,22 +1625,53 @@ class BatchScheduler:
             self._step(logits, list(range(self.slots)))
             return
         plan = self._shared_plan() if self.share else None
+        feed = np.where(idle, 0, self.pending)
+        fed = None
+        if self.ctab is not None:         # one upload: the decode step's tokens are the ones the automaton states take
+            feed = fed = self.engine._dev(feed.astype(np.int64))
         if plan is None:
-            logits = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending))
+            logits = self.engine.decode_step(self.cache, feed)
         else:
-            logits = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending), shared=plan)
+            logits = self.engine.decode_step(self.cache, feed, shared=plan)
         self.cache.lens[idle] = 0
-        self._step(logits, list(range(self.slots)))
+        self._step(logits, list(range(self.slots)), fed)
 
-    def _step(self, logits, row_slots):
-        """Choose the tokens of logits' rows (row r belongs to slot row_slots[r]) and book them per request."""
+    def _device_constrain(self):
+        """The default `constrain`: the call's table and one int32 state per slot on the device, ops.constrain_rows."""
+        from . import ops
+        eng, V = self.engine, self.engine.vocab
+        tabs = self.ctab.device_tables(eng.device)
+        state = torch.full((self.slots,), -1, dtype=torch.int32, device=eng.device)
+
+        def constrain(logits, slots, starts, fed):
+            if fed is None:               # an admission: the start states go into the slots, then the rows are masked through slot=
+                info = eng._dev(np.stack([slots, starts]).astype(np.int32))
+                state.index_copy_(0, info[0].long(), info[1])
+                ops.constrain_rows(logits, V, state, tabs, slot=info[0])
+            else:                         # a decode step: row s is slot s
+                ops.constrain_rows(logits, V, state, tabs, tok=fed)
+        return constrain
+
+    def _step(self, logits, row_slots, fed=None):
+        """Choose the tokens of logits' rows (row r belongs to slot row_slots[r]) and book them per request.  fed (constrained
+        decoding): the device tokens of the decode step that made these rows; None after an admission."""
         cfg = self.cfg
         sl = np.asarray(row_slots, dtype=np.int64)
+        if self.ctab is not None:
+            starts = self.cstart[self.owner[sl]] if fed is None else None
+            self.constrain(logits, sl, starts, fed)
+            if fed is None:
+                self.mirror.state[sl] = starts
         if self.seeds is None:
             tok, lps = self.picker(logits, sl, self.t[sl], self.mn[sl])
         else:
             seed = np.array([self.seeds[q] if q >= 0 else 0 for q in self.owner[sl]], dtype=np.int64)
             tok, lps = self.picker(logits, sl, self.t[sl], self.mn[sl], seed=seed)
+        if self.ctab is not None:         # before the booking below frees slots: a dead end names its request and step
+            act = np.flatnonzero(self.owner[sl] >= 0)
+            self.mirror.take(sl[act], np.asarray(tok)[act],
+                             lambda k: getattr(self.picker, "active", True) and float(logits[act[k], 0]) == float("-inf"),
+                             lambda k: f"request {int(self.owner[sl[act[k]]])}", self.t[sl[act]])
         for r, s in enumerate(row_slots):
             q = int(self.owner[s])
             if q < 0:

@@ -132,6 +132,8 @@ _SIGS = {
     "rv_cfg_guide_rows_f32": [_c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _f32, _c_void_p, _i64, _c_void_p],
     "rv_dola_contrast_rows_f32": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _i32, _i32, _f32, _c_void_p, _c_void_p, _c_void_p, _i64,
                                   _c_void_p],
+    "rv_constrain_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32,
+                              _c_void_p],
     "rv_attn_extend_prefix_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _i64, _i64, _i32, _i32, _c_void_p, _c_void_p,
                                    _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
     "rv_token_logprob_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p],

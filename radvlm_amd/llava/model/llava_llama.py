@@ -323,6 +323,18 @@ class LlavaLlamaForCausalLM:
         sampling, kv_cache_dtype="int8" and quantised decoders; with guidance_scale, past_key_values or prompt_lookup_num_tokens
         NotImplementedError; another string, an empty list, a duplicate, a non-int, a bool, a layer outside [0, layers) (HF drops
         those silently) or more than 16 candidates: ValueError.
+        Constrained decoding: constraint=c, a radvlm_amd.constraints.TokenConstraint for every row or a list of B with None for an
+        unconstrained row (None: off, no launch added).  It is a deterministic automaton over token ids -- from_choices (a closed
+        answer set), from_char_dfa (a character DFA lifted to the tokenizer's vocabulary; boxes_char_dfa gives the one of
+        format_boxes' strings) -- and does what HF's prefix_allowed_tokens_fn does, without a Python callback per row and step: each
+        step's raw row gets -inf outside the ids the row's state allows (rv_constrain_rows_f32, the place of HF's
+        PrefixConstrainedLogitsProcessor), then the processors, the argmax or the seeded sampler run on it unchanged.  The
+        constraint sees the generated tokens only and starts at its start state on every call, with past_key_values too; after an
+        EOS edge the row is free.  output_logits returns the raw rows, output_scores the masked, processed ones.  When the
+        processors or warpers ban everything a state allows (min_new_tokens against a state that allows only EOS), the call raises
+        RuntimeError naming the row and the step.  It composes with the processors, sampling, kv_cache_dtype="int8", quantised
+        decoders and past_key_values; with prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError; another
+        type, a list of another length or an automaton naming an id beyond the vocabulary: ValueError.
         The training state (weights, optimizer, RNG counters) is not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
@@ -363,6 +375,10 @@ class LlavaLlamaForCausalLM:
         NotImplementedError.
         dola_layers (one value for the call): DoLa as in generate().  Every request chooses its own layer at every step, so a
         request's tokens are those of generate(dola_layers=...) on it alone; the cache keeps one row per slot.
+        constraint: one TokenConstraint for every request or a list of N with None entries, as in generate().  The automaton states
+        live on the device, one per cache slot; an admission writes the request's start state into its slot.  A request's tokens,
+        and its logprobs (of the masked, processed row, so renormalised over the allowed ids), are those of generate(constraint=)
+        on it alone; it works with share_prefix=True.  A dead end raises RuntimeError naming the request and its step.
         The training state is not touched."""
         from ...generation import generate_batch, parse_batch_kwargs
         inputs = list(inputs)

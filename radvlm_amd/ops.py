@@ -1066,6 +1066,38 @@ def dola_contrast_rows(f, c, n, ws=None, want_jsd=False):
     return (f, chosen, jsd) if want_jsd else (f, chosen)
 
 
+CONSTRAIN_TILE = 1024     # columns per sweep step of rv_constrain_rows_f32's workgroup (csrc/constrain.hip: CR_SWEEP)
+
+
+def constrain_rows(x, n, state, tables, tok=None, slot=None):
+    """Constrained decoding's advance and mask in place (rv_constrain_rows_f32).  x: fp32 [rows, >= n], a step's raw logits; state:
+    int32 [state_rows], one automaton state per row, or per cache slot with slot= (int32 [rows], distinct: row r uses state[slot[r]]);
+    tables: (edge_off int32 [n_states + 1], edge_tok int32 [n_edges], edge_next int32 [n_edges]) on the device
+    (constraints.TokenConstraint.device_tables).  tok (int64 [rows], the token chosen from each row's previous step): a live state
+    first takes that token's edge (-2 when it has none) and is written back; None: the states are used as they are.  Then a free row
+    (-1) is not accessed, a dead row (-2, or a number outside [0, n_states)) becomes -inf, and a live row gets -inf on every column of
+    [0, n) its state does not allow, the allowed columns keeping their bits.  Columns >= n are not touched.  Returns x."""
+    _chk(x, torch.float32), _chk(state, torch.int32)
+    off, etok, enext = tables
+    for a in (off, etok, enext):
+        _chk(a, torch.int32)
+        assert a.dim() == 1 and a.is_contiguous()
+    rows, n_states, n_edges = x.shape[0], off.numel() - 1, etok.numel()
+    assert x.dim() == 2 and x.stride(1) == 1 and rows >= 1 and 0 < n <= min(x.shape[1], LOGITS_PROCESS_MAX_N)
+    assert n_states >= 1 and n_edges >= 1 and enext.numel() == n_edges
+    assert state.dim() == 1 and state.is_contiguous() and state.numel() >= 1
+    if slot is None:
+        assert rows <= state.numel()
+    else:
+        _chk(slot, torch.int32)
+        assert slot.dim() == 1 and slot.numel() == rows and slot.is_contiguous()
+    if tok is not None:
+        _chk(tok, torch.int64)
+        assert tok.dim() == 1 and tok.numel() == rows and tok.is_contiguous()
+    lib.call("rv_constrain_rows_f32", x, x.stride(0), rows, int(n), state, state.numel(), slot, tok, off, etok, enext, n_states, n_edges)
+    return x
+
+
 BEAM_MAX = 16             # beams per prompt (rv_beam_topk_f32)
 BEAM_TOPK_MAX = 64        # candidates kept per prompt and step
 

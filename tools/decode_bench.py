@@ -103,6 +103,12 @@
         # pass of every arm, then the arms alternated three times; median ms per step per arm, the spread of the three medians, the
         # added ms per step, and the candidates' lm_head rows in a second launch against stacked with the mature rows into one
         # skinny launch where that keeps the mature rows' bits (LlavaEngine.tap_lm_head)
+  python tools/decode_bench.py --constraint [--geos ..] [--batches 1,32] [--prompt 704] [--new 128] [--out FILE]
+        # constrained decoding: (1) rv_constrain_rows_f32 alone at 32,000 and 152,064 columns, 1 and 32 rows, a state that allows one
+        # id (the mask stores n - 1 columns) and one that allows every id (no store), each with and without the advance in front,
+        # device time, median of 50, warm; (2) the decode step (decode_step + constrain + argmax) with a from_choices constraint of
+        # 8 choices of --new tokens, so that every row stays live for the whole loop, beside the plain step on one engine: one untimed
+        # pass of both arms, then the arms alternated three times; median ms per step per arm, the plain arm's spread, the added ms
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -443,13 +449,18 @@ def w8_trace(geo, prompt, new):
                  kernel_src=_src_hash())]
 
 
-def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None):
+def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None, con=None):
     """Median decode step (decode_step + token choice) in ms; with `lp` (generation.LogitsProcessors) the token comes from
     rv_logits_process_argmax_f32 and is recorded in the device history, as greedy_generate does; with `sm` (the sampling settings of
     parse_generate_kwargs) it is drawn by rv_sample_rows_f32, row b with seed sm.seed + b, as greedy_generate does.  kv_dtype: the
-    cache's dtype (prefill's kv_dtype)."""
+    cache's dtype (prefill's kv_dtype).  con (a constraints.TokenConstraint for every row): ops.constrain_rows advances and masks each
+    step's rows before the token choice, as greedy_generate does (the host mirror of the states is not part of the loop)."""
     B = ids.shape[0]
     cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new, **({} if kv_dtype is None else dict(kv_dtype=kv_dtype)))
+    if con is not None:
+        tabs = con.device_tables(logits.device)
+        cstate = torch.full((B,), con.start, dtype=torch.int32, device=logits.device)
+        ops.constrain_rows(logits, eng.vocab, cstate, tabs)
     hist = torch.zeros(B, new, dtype=torch.int32, device=logits.device) if lp is not None else None
     if sm is not None:
         seeds = torch.tensor([sm.seed + b for b in range(B)], dtype=torch.int64, device=logits.device)
@@ -471,11 +482,82 @@ def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         logits = eng.decode_step(cache, tok.to(torch.int32))
+        if con is not None:
+            ops.constrain_rows(logits, eng.vocab, cstate, tabs, tok=tok)
         tok = choose(logits, t)
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3)
     del cache
+    if con is not None:
+        assert int((cstate < 0).sum()) == 0                        # every row stayed inside its choice for the whole loop
     return times[warm:]
+
+
+def _long_choices(vocab, new, k=8, seed=0):
+    """k answer choices of `new` tokens each over distinct ids, so that a row stays live for a whole loop of `new` steps: the first step
+    allows k ids, every later one a single id, and the mask stores vocab - 1 columns of -inf per row and step."""
+    from radvlm_amd.constraints import TokenConstraint
+    ids = np.random.default_rng(seed).permutation(vocab)[:k * new + 1]
+    return TokenConstraint.from_choices(ids[:k * new].reshape(k, new).tolist(), eos=[int(ids[-1])])
+
+
+def constraint_ab(geo, batches, prompt, new, reps=3):
+    """The decode step with a from_choices constraint (ops.constrain_rows before the argmax) beside the plain decode step on one
+    engine, interleaved `reps` times as --kv8 does: one untimed pass of both arms, then the median step of every pass."""
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    con = _long_choices(eng.vocab, new)
+    recs = []
+    for B in batches:
+        ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+        arms = {"plain": lambda: _decode_loop(eng, ids, new), "constrained": lambda: _decode_loop(eng, ids, new, con=con)}
+        for fn in arms.values():
+            fn()
+        ts = {k: [] for k in arms}
+        for _ in range(reps):
+            for k, fn in arms.items():
+                ts[k].append(float(np.median(fn())))
+        p, c = float(np.median(ts["plain"])), float(np.median(ts["constrained"]))
+        spread = max(ts["plain"]) - min(ts["plain"])
+        recs.append(dict(geo=geo, mode="constraint_ab", B=B, prompt=prompt, new_tokens=new, reps=reps, vocab=eng.vocab, n_states=con.n_states,
+                         n_edges=con.n_edges, plain_ms_per_step=round(p, 3), constrained_ms_per_step=round(c, 3),
+                         plain_ms_all=[round(x, 3) for x in ts["plain"]], constrained_ms_all=[round(x, 3) for x in ts["constrained"]],
+                         plain_spread_ms=round(spread, 3), added_ms=round(c - p, 3), constrained_over_plain=round(c / p, 4),
+                         added_beyond_plain_spread=bool(c - p > spread)))
+    return recs
+
+
+def constraint_shapes(reps=50):
+    """rv_constrain_rows_f32 alone at n = 32,000 and 152,064, rows 1 and 32: a state that allows one id (the mask stores n - 1
+    columns), a state that allows every id (no store: the walk over n edges alone), each also with the advance (tok=) in front.
+    Device time per call (events around it), median of `reps`, warm."""
+    from radvlm_amd.constraints import TokenConstraint
+    recs = []
+    for n in (32000, 152064):
+        every = {i: 0 for i in range(n)}
+        con = TokenConstraint._from_edges([every, {n // 2: 1}])
+        tabs = con.device_tables("cuda")
+        for rows in (1, 32):
+            x = torch.randn(rows, n, device="cuda")
+            rec = dict(mode="constraint_kernel", kernel_form="whole-row bitmap", rows=rows, vocab=n, reps=reps, stored_bytes_one_id=4 * (n - 1) * rows)
+            for name, s in (("one_id", 1), ("every_id", 0)):
+                for adv in (False, True):
+                    state = torch.full((rows,), s, dtype=torch.int32, device="cuda")
+                    tok = torch.full((rows,), n // 2, dtype=torch.int64, device="cuda") if adv else None
+                    us = []
+                    for _ in range(reps + 5):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        ops.constrain_rows(x, n, state, tabs, tok=tok)
+                        e1.record()
+                        e1.synchronize()
+                        us.append(e0.elapsed_time(e1) * 1e3)
+                    assert int(state[0]) == s                       # both states loop on n // 2
+                    us = us[5:]
+                    key = f"{name}{'_advance' if adv else ''}"
+                    rec[f"{key}_us"] = round(float(np.median(us)), 2)
+                    rec[f"{key}_p10_p90_us"] = [round(float(np.percentile(us, 10)), 2), round(float(np.percentile(us, 90)), 2)]
+            recs.append(rec)
+    return recs
 
 
 def kv8_ab(geo, batches, prompt, new, reps=3):
@@ -1682,6 +1764,7 @@ def main():
     ap.add_argument("--cfg-kernel-ab", action="store_true")
     ap.add_argument("--dola", action="store_true")
     ap.add_argument("--dola-shapes", action="store_true")
+    ap.add_argument("--constraint", action="store_true")
     ap.add_argument("--shared-shapes", action="store_true")
     ap.add_argument("--share-prefix", action="store_true")
     ap.add_argument("--score", action="store_true")
@@ -1730,6 +1813,10 @@ def main():
         recs = dola_shapes()
     elif a.dola:
         recs = [r for g in a.geos.split(",") for r in dola_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new, reps=min(a.reps, 3))]
+    elif a.constraint:
+        batches = a.batches if a.batches != ap.get_default("batches") else "1,32"
+        recs = constraint_shapes() + [r for g in a.geos.split(",") for r in constraint_ab(g, list(map(int, batches.split(","))), a.prompt, a.new,
+                                                                                          reps=min(a.reps, 3))]
     elif a.shared_shapes:
         recs = shared_shapes()
     elif a.score_shapes:
