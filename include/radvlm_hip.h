@@ -279,6 +279,24 @@ int rv_cross_entropy(const void* logits, int64_t ld, const int64_t* labels, floa
                      int64_t ld_d, int rows, int V, float inv_count, void* stream);
 /* out[0] = scale * sum(in[0..n))  (deterministic, single block). */
 int rv_sum_f32(const float* in, int64_t n, float scale, float* out, void* stream);
+/* The GRPO token loss (TRL GRPOTrainer._compute_loss, token level) on the rows rv_cross_entropy takes: bf16 logits, rows of ld >=
+ * ceil8(V) columns, labels[r] the already shifted target (outside [0, V): an ignored row).  Per live row, in fp32, with lse and the
+ * softmax p computed by the statements of rv_cross_entropy:
+ *   logp = z[y] - lse;  r = exp(logp - old_logp[r])  (old_logp == NULL: r = 1 exactly);  rc = min(max(r, 1 - eps_low), 1 + eps_high)
+ *   act  = (r A <= rc A);  loss = -min(r A, rc A);  beta > 0: q = ref_logp[r] - logp, kl = exp(q) - q - 1, loss += beta kl  (else kl = 0)
+ *   g    = gweight[r] (A r [act])  -  gweight[r] beta (1 - exp(q))  when beta > 0;   dlogits[r][j] = (p[j] - [j == y]) * g
+ * stats: five fp32 planes of `rows` entries each -- logp, loss, lweight[r] * loss, kl, clip code (0 active; 1: r < 1 - eps_low and
+ * A < 0; 2: r > 1 + eps_high and A > 0).  An ignored row writes zeros to all of them and to its dlogits row and reads none of its
+ * per-row floats.  dlogits may be the logits buffer (the target logit is read before any store), another buffer with its own ld_d, or
+ * NULL (statistics only).  Pad columns are read as -inf and written as 0.
+ * Bit promises: logp == -loss_rows of rv_cross_entropy on the same logits; with adv = 1, old_logp = NULL, beta = 0 and gweight = c
+ * the dlogits are those of rv_cross_entropy with inv_count = c.
+ * Refused (RV_ERR_ARG, nothing launched): a null logits / labels / adv / lweight / gweight / stats, rows < 1, V < 1, ld or ld_d not a
+ * multiple of 8 or below ceil8(V), logits or dlogits not 16-byte aligned, eps_low / eps_high / beta negative or NaN, beta > 0 without
+ * ref_logp.  Non-finite adv / old_logp / ref_logp on a live row are outside the contract. */
+int rv_policy_loss_bf16(const void* logits, int64_t ld, const int64_t* labels, const float* adv, const float* lweight,
+                        const float* gweight, const float* old_logp, const float* ref_logp, float eps_low, float eps_high, float beta,
+                        float* stats, void* dlogits, int64_t ld_d, int rows, int V, void* stream);
 
 /* ---- embedding splice ---------------------------------------------------------------------------------------------
  * prepare_inputs_labels_for_multimodal steps (vi)-(viii), llava_arch.py:449-531, as one gather:

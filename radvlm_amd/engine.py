@@ -159,6 +159,7 @@ class LlavaEngine:
         self.sync = FlatGradSync(self.grads, process_group, force=self.force_grad_sync) if (self.world > 1 or self.force_grad_sync) else None
         self._select_gemm_launch_shape()
         self.ctx = None
+        self.last_policy = None               # per-scored-token statistics of the last forward(policy=) / token_logps()
         self.grad_accum_started = False
         self.loss_scale = 1.0
         import os
@@ -657,10 +658,15 @@ class LlavaEngine:
             pix = pix if pix.dtype == BF16 else ops.to_bf16(pix.float())
         return pix.contiguous()
 
-    def forward(self, input_ids, attention_mask, labels, images, image_sizes=None, want_logits=False, loss_scale=None):
+    def forward(self, input_ids, attention_mask, labels, images, image_sizes=None, want_logits=False, loss_scale=None, policy=None,
+                _score_only=False):
         """One training forward. Returns loss (fp32 device tensor [1], never scaled); keeps the context for backward().
         loss_scale multiplies the GRADIENTS only (default: self.loss_scale; a trainer sets 1 / gradient_accumulation_steps, which is
-        what HF Trainer.training_step back-propagates, HF:trainer.py training_step `loss / gradient_accumulation_steps`)."""
+        what HF Trainer.training_step back-propagates, HF:trainer.py training_step `loss / gradient_accumulation_steps`).
+        policy: None (the cross entropy) or a policy.PolicyTerms: the GRPO token loss (rv_policy_loss_bf16) takes the cross entropy's
+        place on the same logits buffer, in place; everything before it and all of backward() are the same.  The loss returned is then
+        sum(weight * loss) over the scored tokens, and self.last_policy holds the per-token statistics (see _policy_loss).
+        _score_only (token_logps): the same pass with the statistics alone -- no dlogits, no activations kept, no context."""
         dev = self.device
         l = self.l
         d, F, H, V, L = l["d"], l["ffn"], l["heads"], l["vocab"], l["layers"]
@@ -709,12 +715,13 @@ class LlavaEngine:
         geom = dict(B=B, S=S, s_pad=s_pad, lens=lens, cu=cu, pos=pos, cs=cs)
         # activation recompute (the reference's --gradient_checkpointing, train/train.py:164,1505-1513): layers [0, n_re) keep only their
         # input and re-run their forward inside backward (bit-identical: the kernels are deterministic, LoRA dropout masks regenerable)
-        n_re = self._recompute_layers(M)
+        n_re = 0 if _score_only else self._recompute_layers(M)
         tgt = shifted_labels(plan["labels"])
         if tgt.size and int(tgt.max()) >= self.vocab:     # torch's cross_entropy raises on an out-of-range target too
             raise IndexError(f"label {int(tgt.max())} is out of range for a vocabulary of {self.vocab}")
         count = int((tgt != -100).sum())
         inv = (1.0 / count) if count > 0 else float("nan")
+        scored = (tgt != -100).sum(1)                     # per sample: the scored tokens of policy.PolicyTerms
         tgt = tgt.reshape(-1)
         if packed:
             tgt = tgt[valid_idx]
@@ -742,7 +749,8 @@ class LlavaEngine:
         layers = []
         for i in range(L):
             x_out, acts = self._layer_forward(i, x, geom, rows=self._dev(head_idx) if (last_sel and i == L - 1) else None)
-            layers.append(dict(x=x, lora={}) if i < n_re else acts)
+            if not _score_only:
+                layers.append(dict(x=x, lora={}) if i < n_re else acts)
             x = x_out
         ctx["geom"], ctx["n_recomputed"] = geom, n_re
         if head_idx is None or last_sel:
@@ -766,7 +774,13 @@ class LlavaEngine:
             logits_out = logits_out.view(B, S, V)[..., :self.vocab]
         # CE writes dlogits (scaled by loss_scale/count/world) over the logits buffer
         gscale = (self.loss_scale if loss_scale is None else loss_scale) / self.world
-        loss, _ = self._cross_entropy(logits, tgt_t, self.vocab, inv, gscale)   # V = table rows (pad rows included), CE sees the logical vocabulary
+        if policy is None and not _score_only:
+            loss, _ = self._cross_entropy(logits, tgt_t, self.vocab, inv, gscale)   # V = table rows (pad rows included), CE sees the logical vocabulary
+        else:
+            loss = self._policy_loss(logits, tgt_t, lab_rows, head_idx is not None, scored, policy, gscale, grad=not _score_only)
+        if _score_only:                                  # token_logps(): nothing is kept for a backward pass
+            self.ctx = None
+            return loss
         ctx.update(B=B, S=S, M=M, s_pad=s_pad, lens=lens, cu=cu, pos=pos, layers=layers, x_last=x_head, rstdN=rstdN, hN=hN, dlogits=logits,
                    table_rows=table.shape[0], count=count, head_idx=head_idx, head_rows=int(lab_rows.size), last_sel=last_sel)
         self.ctx = ctx
@@ -1467,6 +1481,52 @@ class LlavaEngine:
             am.index_copy_(0, row_out[m0:m1], s_am)
             del sl
         return lp, am
+
+    def _policy_loss(self, logits, tgt, lab_rows, gathered, scored, terms, gscale, grad=True):
+        """The GRPO token loss in the cross entropy's place: logits (bf16, overwritten by dlogits when grad) and tgt are forward()'s head
+        rows; lab_rows the labelled rows among forward()'s token rows, ascending -- the scored order of policy.PolicyTerms, sample by
+        sample.  gathered: the head ran on the labelled rows alone (rows 0 .. n - 1 in scored order, then pad rows with label -100);
+        else the per-token terms are scattered by lab_rows.  terms None (token_logps): statistics only, every coefficient zero.
+        Leaves self.last_policy: logp, loss, kl, clip (0 active / 1 low / 2 high) fp32 [n_scored] and ratio_one bool [n_scored] (no old
+        log-probs were given: r = 1 exactly), device tensors in scored order, plus scored = the per-sample counts (host)."""
+        n, rows = int(lab_rows.size), logits.shape[0]
+        assert n == int(scored.sum()), "a scored token on a padding row"
+        if terms is None:
+            adv, w, old, ref = np.zeros(n), np.zeros(n), None, None
+            eps_low = eps_high = beta = 0.0
+        else:
+            adv, w, old, ref = terms.per_token(scored)
+            eps_low, eps_high, beta = float(terms.epsilon), terms.eps_high, float(terms.beta)
+
+        def per_row(a):
+            if a is None:
+                return None
+            full = np.zeros(rows, dtype=np.float64)          # rows without a label are never read by the kernel
+            if gathered:
+                full[:n] = a
+            else:
+                full[lab_rows] = a
+            return full
+        loss, stats = ops.policy_loss(logits, tgt, self.vocab, per_row(adv), per_row(w), gscale, per_row(old), per_row(ref if beta > 0 else None),
+                                      eps_low, eps_high, beta, dlogits="inplace" if grad else None)
+        st = stats[:, :n] if gathered else stats[:, self._dev(lab_rows.astype(np.int64))]
+        self.last_policy = dict(logp=st[0], loss=st[1], kl=st[3], clip=st[4], scored=np.asarray(scored),
+                                ratio_one=torch.full((n,), old is None, dtype=torch.bool, device=logits.device))
+        return loss
+
+    def token_logps(self, input_ids, attention_mask, labels, images, image_sizes=None):
+        """log p(label) of every scored token (the positions of each spliced row whose shifted target is not -100, sample by sample,
+        ascending): fp32 [n_scored] on the device.  It is forward()'s own arithmetic -- the tiled GEMMs, the bf16 logits, the cross
+        entropy's lse, the same labelled-rows head -- without a gradient and without a saved context, so old log-probs taken with it
+        before an update make the first iteration's ratio exactly 1 (the sampler's fp32 GEMV logits are other bits).  LoRA engines run
+        it in eval form (no adapter dropout).  The training state is not touched."""
+        saved = (self.lora_step, getattr(self, "lora_p", 0.0), self.ctx)
+        self.lora_p = 0.0
+        try:
+            self.forward(input_ids, attention_mask, labels, images, image_sizes=image_sizes, _score_only=True)
+        finally:
+            self.lora_step, self.lora_p, self.ctx = saved
+        return self.last_policy["logp"]
 
     def _cross_entropy(self, logits, tgt, V, inv, gscale):
         from . import lib

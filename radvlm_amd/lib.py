@@ -83,6 +83,8 @@ _SIGS = {
     "rv_gelu_bwd": [_c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p],
     "rv_cross_entropy": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32, _f32, _c_void_p],
     "rv_sum_f32": [_c_void_p, _i64, _f32, _c_void_p, _c_void_p],
+    "rv_policy_loss_bf16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _f32, _f32, _f32, _c_void_p,
+                            _c_void_p, _i64, _i32, _i32, _c_void_p],
     "rv_gather_rows": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p],
     "rv_segment_sum_rows": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i64, _i32, _c_void_p],
     "rv_normalize_tiles_u8": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _c_void_p],

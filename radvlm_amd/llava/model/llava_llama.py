@@ -265,6 +265,44 @@ class LlavaLlamaForCausalLM:
 
     __call__ = forward
 
+    @staticmethod
+    def _host_batch(input_ids, attention_mask, labels, images):
+        if images is None:
+            raise ValueError("images is required (text-only samples carry a dummy zero image, train.py:1227-1232)")
+        host = lambda t: t.cpu().numpy() if torch.is_tensor(t) else t
+        return host(input_ids), host(attention_mask), host(labels), (list(images) if not torch.is_tensor(images) else [im for im in images])
+
+    def policy_loss(self, input_ids, attention_mask, labels, images, image_sizes=None, *, advantages, weights=None, old_logps=None,
+                    ref_logps=None, epsilon=0.2, epsilon_high=None, beta=0.0):
+        """The GRPO token loss (TRL's GRPOTrainer: the clipped surrogate, plus beta times the k3 KL estimate against ref_logps) on a batch
+        of prompt + completion rows; labels mark the completion tokens, as for forward().  Scored tokens of sample b: the positions of
+        its spliced row whose shifted target is not -100, ascending.  advantages: one float per sample, or one array per sample, or
+        the concatenation in scored order; weights likewise (None: 1 / number of scored tokens); old_logps / ref_logps per scored
+        token (token_logps() gives them; None old_logps: the on-policy case, ratio exactly 1).  A shape that does not match the scored
+        counts, a non-finite value, a negative epsilon / beta, or beta > 0 without ref_logps: ValueError.
+        Returns an output with .loss = sum(weight * loss) (fp32 scalar; .loss.backward() runs the engine's backward, gradients scaled
+        by engine.loss_scale as in forward()), .logps / .kl / .clip per scored token (device tensors) and .stats: n_scored and the
+        device scalars kl, clip_ratio/low, clip_ratio/high (means over the scored tokens)."""
+        from ...policy import PolicyTerms
+        ids, am, lab, imgs = self._host_batch(input_ids, attention_mask, labels, images)
+        terms = PolicyTerms(advantages=advantages, weights=weights, old_logps=old_logps, ref_logps=ref_logps, epsilon=epsilon,
+                            epsilon_high=epsilon_high, beta=beta)
+        loss = self.engine.forward(ids, am, lab, imgs, image_sizes=image_sizes, policy=terms)
+        lp = self.engine.last_policy
+        n = int(lp["logp"].numel())
+        mean = lambda t: t.float().mean() if n else torch.zeros((), device=self.engine.device)
+        stats = {"n_scored": n, "kl": mean(lp["kl"]), "clip_ratio/low": mean(lp["clip"] == 1), "clip_ratio/high": mean(lp["clip"] == 2)}
+        return SimpleNamespace(loss=_StepFunction.apply(self._anchor, self.engine, loss), logps=lp["logp"], kl=lp["kl"], clip=lp["clip"],
+                               stats=stats)
+
+    @torch.no_grad()
+    def token_logps(self, input_ids, attention_mask, labels, images, image_sizes=None):
+        """log p(label) of every scored token of the batch, fp32 [n_scored] on the device, in scored order (see policy_loss), computed by
+        the training path's own arithmetic (LlavaEngine.token_logps): the old / reference log-probs of policy_loss.  No gradient, and
+        no training state is touched."""
+        ids, am, lab, imgs = self._host_batch(input_ids, attention_mask, labels, images)
+        return self.engine.token_logps(ids, am, lab, imgs, image_sizes=image_sizes)
+
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, modalities=("image",), **kwargs):
         """Greedy or seeded-sampling generation (the reference's generate(): the multimodal splice once, then HF generate on the spliced inputs_embeds).

@@ -445,6 +445,33 @@ def cross_entropy(logits, labels_shifted, V, inv_count, grad_inplace=True):
     return loss, loss_rows
 
 
+POLICY_STATS = ("logp", "loss", "wloss", "kl", "clip")       # the planes of rv_policy_loss_bf16's stats buffer, in order
+
+
+def policy_loss(logits, labels_shifted, V, adv, weight, gscale=1.0, old_logp=None, ref_logp=None, eps_low=0.2, eps_high=0.2, beta=0.0,
+                dlogits="inplace"):
+    """The GRPO token loss on bf16 logits rows (rv_policy_loss_bf16).  adv, weight: per-row host or device floats; the loss value is
+    weighted by fp32(weight), the gradient by fp32(weight * gscale) formed in double -- the engine's `inv * gscale` convention.
+    dlogits: "inplace" (the logits buffer is overwritten), a bf16 buffer, or None (statistics only).
+    Returns (loss fp32 [1] = sum of weight * loss, stats fp32 [5, rows] in POLICY_STATS order)."""
+    _chk(logits)
+    rows, dev = logits.shape[0], logits.device
+    f32 = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous()
+    w64 = torch.as_tensor(weight).detach().to("cpu", torch.float64)
+    assert w64.numel() == rows and labels_shifted.numel() == rows and labels_shifted.dtype == torch.int64
+    adv, old_logp, ref_logp = f32(adv), f32(old_logp), f32(ref_logp)
+    assert adv.numel() == rows and all(t is None or t.numel() == rows for t in (old_logp, ref_logp))
+    lweight, gweight = f32(w64.to(torch.float32)), f32((w64 * float(gscale)).to(torch.float32))
+    dl = logits if isinstance(dlogits, str) else dlogits
+    assert not isinstance(dlogits, str) or dlogits == "inplace"
+    stats = torch.empty(len(POLICY_STATS), rows, dtype=torch.float32, device=dev)
+    lib.call("rv_policy_loss_bf16", logits, logits.stride(0), labels_shifted, adv, lweight, gweight, old_logp, ref_logp, float(eps_low),
+             float(eps_high), float(beta), stats, dl, dl.stride(0) if dl is not None else 0, rows, V)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    lib.call("rv_sum_f32", stats[2], rows, 1.0, loss)
+    return loss, stats
+
+
 def gather_rows(idx, d, table_a, table_b=None, out=None):
     rows = idx.numel()
     assert idx.dtype == torch.int32
