@@ -627,9 +627,16 @@ __global__ __launch_bounds__(TPB) void transpose_kernel(const bf16* in, long in_
 }
 
 // ------------------------------------------------------------------------------------------------ optimizer / misc
-// The update is written out twice on purpose.  The compiler contracts m = b1 * m + (1 - b1) * g differently in the two places (the
-// 4-wide body fuses (1 - b1) * g into the sum, the scalar tail fuses nothing), and which way it goes follows the shape of the code
-// around the expression: with the formula in one shared function, called from both, m changed in its last bit in one place or the other.
+// One element's update, every fused multiply-add written out.  Left to the compiler, m = b1 * m + (1 - b1) * g, v = b2 * v + (1 - b2) * g * g
+// and p = p * decay - step * m / denom were contracted one way in the 4-wide body (the three fmaf below) and not at all in the scalar
+// tail, and which way it went followed the shape of the code around the expression: the last elements of a tensor whose size is no multiple
+// of 4 got an m, v and master one ulp away from what the same element gets in the body.  With the forms spelled out there is nothing left
+// to contract, so the body and the tail share the function and round alike (the body compiles to the instructions it had before).
+DEVINL void adamw_update(float& pp, float& mm, float& vv, float gg, float decay, float step, float b1, float b2, float rs2, float eps) {
+    mm = fmaf(1.f - b1, gg, b1 * mm);
+    vv = fmaf(b2, vv, ((1.f - b2) * gg) * gg);
+    pp = fmaf(decay, pp, -(step * mm / fmaf(sqrtf(vv), rs2, eps)));
+}
 __global__ void adamw_kernel(bf16* p, float* master, const bf16* g, float* m, float* v, long n, float lr, float b1, float b2,
                              float eps, float wd, float bc1, float bc2, const float* gscale) {
     const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -637,29 +644,24 @@ __global__ void adamw_kernel(bf16* p, float* master, const bf16* g, float* m, fl
     const float gs = gscale ? gscale[0] : 1.f;
     const float rs2 = rsqrtf(bc2);
     const float step = lr / bc1;
+    const float decay = fmaf(-lr, wd, 1.f);
     if (i + 4 <= n) {
         const bf16x4 gv = *(const bf16x4*)(g + i);
         f32x4 mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i), pv = *(f32x4*)(master + i);
         bf16x4 po;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float gg = bf2f(gv[j]) * gs;
-            float pp = pv[j] * (1.f - lr * wd);
-            mv[j] = b1 * mv[j] + (1.f - b1) * gg;
-            vv[j] = b2 * vv[j] + (1.f - b2) * gg * gg;
-            pp -= step * mv[j] / (sqrtf(vv[j]) * rs2 + eps);
-            pv[j] = pp;
+            float pp = pv[j], mm = mv[j], v2 = vv[j];
+            adamw_update(pp, mm, v2, bf2f(gv[j]) * gs, decay, step, b1, b2, rs2, eps);
+            mv[j] = mm; vv[j] = v2; pv[j] = pp;
             po[j] = f2bf(pp);
         }
         *(f32x4*)(m + i) = mv; *(f32x4*)(v + i) = vv; *(f32x4*)(master + i) = pv; *(bf16x4*)(p + i) = po;
     } else {
         for (long k = i; k < n; ++k) {
-            const float gg = bf2f(g[k]) * gs;
-            float pp = master[k] * (1.f - lr * wd);
-            m[k] = b1 * m[k] + (1.f - b1) * gg;
-            v[k] = b2 * v[k] + (1.f - b2) * gg * gg;
-            pp -= step * m[k] / (sqrtf(v[k]) * rs2 + eps);
-            master[k] = pp;
+            float pp = master[k], mm = m[k], v2 = v[k];
+            adamw_update(pp, mm, v2, bf2f(g[k]) * gs, decay, step, b1, b2, rs2, eps);
+            m[k] = mm; v[k] = v2; master[k] = pp;
             p[k] = f2bf(pp);
         }
     }
@@ -827,13 +829,13 @@ extern "C" int rv_sum_f32(const float* in, int64_t n, float scale, float* out, v
 }
 extern "C" int rv_gather_rows(void* dst, int64_t ld_dst, const void* ta, int64_t ld_a, const void* tb, int64_t ld_b, const int32_t* idx,
                               int rows, int d, void* stream) {
-    if (!dst || !idx || rows <= 0 || (d & 7) || (ld_dst & 7) || (ld_a & 7) || (ld_b & 7)) return RV_ERR_ARG;
+    if (!dst || !idx || rows <= 0 || d <= 0 || (d & 7) || (ld_dst & 7) || (ld_a & 7) || (ld_b & 7)) return RV_ERR_ARG;
     hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, ST, (bf16*)dst, (long)ld_dst, (const bf16*)ta, (long)ld_a, (const bf16*)tb, (long)ld_b, idx, d);
     return rv_check_launch();
 }
 extern "C" int rv_segment_sum_rows(const void* src, int64_t ld_src, const int32_t* seg_off, const int32_t* pos, const int32_t* out_row,
                                    int nseg, void* out, int64_t ld_out, int d, void* stream) {
-    if (!src || !seg_off || !pos || !out_row || !out || nseg <= 0 || (d & 7) || (ld_src & 7) || (ld_out & 7)) return RV_ERR_ARG;
+    if (!src || !seg_off || !pos || !out_row || !out || nseg <= 0 || d <= 0 || (d & 7) || (ld_src & 7) || (ld_out & 7)) return RV_ERR_ARG;
     hipLaunchKernelGGL(segment_sum_rows_kernel, dim3(nseg), dim3(256), 0, ST, (const bf16*)src, (long)ld_src, seg_off, pos, out_row, (bf16*)out, (long)ld_out, d);
     return rv_check_launch();
 }
@@ -884,7 +886,7 @@ extern "C" int rv_normalize_tiles_u8(const uint8_t* img, void* out, int n, int g
     return rv_check_launch();
 }
 extern "C" int rv_clip_embed(const void* patch_out, const void* cls, const void* pos, void* out, int n, int P, int d, void* stream) {
-    if (!patch_out || !cls || !pos || !out || n <= 0 || P <= 0 || (d & 7)) return RV_ERR_ARG;
+    if (!patch_out || !cls || !pos || !out || n <= 0 || P <= 0 || d <= 0 || (d & 7)) return RV_ERR_ARG;
     const long total = (long)n * (P + 1) * (d / 8);
     hipLaunchKernelGGL(clip_embed_kernel, dim3(nblocks(total, 256)), dim3(256), 0, ST, (const bf16*)patch_out, (const bf16*)cls, (const bf16*)pos, (bf16*)out, n, P, d);
     return rv_check_launch();
