@@ -298,6 +298,40 @@ int rv_policy_loss_bf16(const void* logits, int64_t ld, const int64_t* labels, c
                         const float* gweight, const float* old_logp, const float* ref_logp, float eps_low, float eps_high, float beta,
                         float* stats, void* dlogits, int64_t ld_d, int rows, int V, void* stream);
 
+/* ---- DPO preference training (csrc/preference.hip) -------------------------------------------------------------------
+ * The sequence-level part of the DPO loss, between two calls of rv_policy_loss_bf16: (A) with dlogits = NULL gives the logp plane,
+ * rv_dpo_pairs_f64 turns it into one gradient coefficient per scored token, (C) with adv = those coefficients writes dlogits.
+ * Scored order: the scored tokens of sequence 0, then of sequence 1, ...; sequence b owns [seg_off[b], seg_off[b + 1]).  Scored token j
+ * lives in row j of logp / coef (row_idx == NULL: the gathered head) or in row row_idx[j] (the all-rows head).  `rows` is the length
+ * of logp and coef; a token whose row lies outside [0, rows) contributes nothing and is not written.
+ *
+ * THE SUM ORDER (fp64, a promise): 64 accumulators start at +0.0; element j of the sequence (j = 0, 1, ... in scored order) is added
+ * to accumulator j mod 64, ascending in j; then for o = 32, 16, 8, 4, 2, 1: acc[l] = acc[l] + acc[l xor o] for all l at once; the sum
+ * is acc[0].  It depends on the sequence's own length alone -- not on the batch, the layout, row_idx or the other sequences -- and an
+ * empty sequence sums to +0.0.  No atomics.
+ *
+ * sums[b] = the sum of sequence b, b < B. */
+int rv_seq_logp_sums_f64(const float* logp, const int32_t* seg_off, const int32_t* row_idx, double* sums, int B, int rows, void* stream);
+/* P pairs as 2 P sequences: sequence p is prompt + chosen, sequence P + p prompt + rejected (seg_off has 2 P + 1 entries).  One
+ * workgroup per pair; the two sums are rv_seq_logp_sums_f64's, bit for bit.  With n the scored tokens of a sequence, in fp64, one
+ * rounding per operation (no fused multiply-adds):
+ *   pi = sum  (loss_type 2, ipo: sum / n);   rho = rho[sequence], 0 when rho == NULL (reference-free);   s = 1  (ipo: 1 / n)
+ *   u = (pi_c - pi_r) - (rho_c - rho_r);   h = beta u;   logsig(x) = -(max(-x, 0) + log1p(exp(-|x|)));   sig(x) = {1, e}[x < 0] / (1 + e), e = exp(-|x|)
+ *   0 sigmoid: loss = -(1 - eps) logsig(h) - eps logsig(-h);   dl = beta (eps sig(h) - (1 - eps) sig(-h))
+ *   1 hinge:   loss = max(0, 1 - h);                           dl = 1 - h > 0 ? -beta : 0            (eps is not used)
+ *   2 ipo:     loss = (u - 1 / (2 beta))^2;                    dl = 2 (u - 1 / (2 beta))
+ *   k = alpha_over_P dl;   coef of every chosen scored token = fp32(gamma_over_Nc - k s_c), of every rejected one = fp32(k s_r)
+ * (one fp64 value rounded once: A = -dL/dlogp_token of L below).  Rows of coef that hold no scored token are not touched.
+ * planes: seven fp64 planes of P entries -- pi_c, pi_r, h, loss, beta (pi_c - rho_c), beta (pi_r - rho_r), the chosen sum (pi_c
+ * unless ipo).  batch (fp64 [3], written by a one-wave kernel in the same fixed order over the pairs, after the pair kernel):
+ *   batch[0] = L = alpha_over_P sum_p loss_p - gamma_over_Nc sum_p chosen_sum_p;   batch[1] = alpha_over_P sum_p loss_p;
+ *   batch[2] = -sum_p chosen_sum_p / N_c, N_c = seg_off[P] - seg_off[0].
+ * Refused (RV_ERR_ARG, nothing launched): a null logp / seg_off / planes / batch / coef, P < 1, rows < 1, beta not finite or <= 0,
+ * label_smoothing outside [0, 0.5), a loss_type other than 0, 1, 2, ipo with label_smoothing != 0, a NaN alpha_over_P or gamma_over_Nc. */
+int rv_dpo_pairs_f64(const float* logp, const int32_t* seg_off, const int32_t* row_idx, const double* rho, int P, int loss_type, double beta,
+                     double label_smoothing, double alpha_over_P, double gamma_over_Nc, double* planes, double* batch, float* coef,
+                     int rows, void* stream);
+
 /* ---- embedding splice ---------------------------------------------------------------------------------------------
  * prepare_inputs_labels_for_multimodal steps (vi)-(viii), llava_arch.py:449-531, as one gather:
  * dst[r] = idx[r] >= 0 ? table_a[idx[r]] : (idx[r] == -1 ? 0 : table_b[-idx[r] - 2]).  (exact-zero pad rows) */

@@ -159,6 +159,7 @@ class LlavaEngine:
         self.sync = FlatGradSync(self.grads, process_group, force=self.force_grad_sync) if (self.world > 1 or self.force_grad_sync) else None
         self._select_gemm_launch_shape()
         self.ctx = None
+        self.last_preference = None           # pair terms of the last forward(preference=)
         self.last_policy = None               # per-scored-token statistics of the last forward(policy=) / token_logps()
         self.grad_accum_started = False
         self.loss_scale = 1.0
@@ -659,13 +660,16 @@ class LlavaEngine:
         return pix.contiguous()
 
     def forward(self, input_ids, attention_mask, labels, images, image_sizes=None, want_logits=False, loss_scale=None, policy=None,
-                _score_only=False):
+                preference=None, _score_only=False):
         """One training forward. Returns loss (fp32 device tensor [1], never scaled); keeps the context for backward().
         loss_scale multiplies the GRADIENTS only (default: self.loss_scale; a trainer sets 1 / gradient_accumulation_steps, which is
         what HF Trainer.training_step back-propagates, HF:trainer.py training_step `loss / gradient_accumulation_steps`).
         policy: None (the cross entropy) or a policy.PolicyTerms: the GRPO token loss (rv_policy_loss_bf16) takes the cross entropy's
         place on the same logits buffer, in place; everything before it and all of backward() are the same.  The loss returned is then
         sum(weight * loss) over the scored tokens, and self.last_policy holds the per-token statistics (see _policy_loss).
+        preference: None or a preference.PreferenceTerms: the batch is P (chosen, rejected) pairs as 2 P sequences and the DPO loss takes
+        the cross entropy's place the same way, as three launches on the same logits buffer (see _preference_loss); the loss returned
+        is dpo_alpha * mean pair loss + gamma * SFT, and self.last_preference holds the pair terms.
         _score_only (token_logps): the same pass with the statistics alone -- no dlogits, no activations kept, no context."""
         dev = self.device
         l = self.l
@@ -774,7 +778,11 @@ class LlavaEngine:
             logits_out = logits_out.view(B, S, V)[..., :self.vocab]
         # CE writes dlogits (scaled by loss_scale/count/world) over the logits buffer
         gscale = (self.loss_scale if loss_scale is None else loss_scale) / self.world
-        if policy is None and not _score_only:
+        if preference is not None:
+            if policy is not None or _score_only:
+                raise ValueError("preference= does not combine with policy= or a score-only pass")
+            loss = self._preference_loss(logits, tgt_t, lab_rows, head_idx is not None, scored, preference, gscale)
+        elif policy is None and not _score_only:
             loss, _ = self._cross_entropy(logits, tgt_t, self.vocab, inv, gscale)   # V = table rows (pad rows included), CE sees the logical vocabulary
         else:
             loss = self._policy_loss(logits, tgt_t, lab_rows, head_idx is not None, scored, policy, gscale, grad=not _score_only)
@@ -1527,6 +1535,45 @@ class LlavaEngine:
         finally:
             self.lora_step, self.lora_p, self.ctx = saved
         return self.last_policy["logp"]
+
+    def _preference_loss(self, logits, tgt, lab_rows, gathered, scored, terms, gscale):
+        """The DPO loss in the cross entropy's place, three launches on forward()'s head rows (arguments as _policy_loss):
+          (A) rv_policy_loss_bf16 without dlogits: the logp row of every scored token (token_logps()'s bits);
+          (B) rv_dpo_pairs_f64: per-sequence fp64 sums in a fixed order, the pair terms, one coefficient A = -dL/dlogp per scored token;
+          (C) rv_policy_loss_bf16 in place with adv = those device rows, lweight 1, gweight fp32(gscale), no old or reference log-probs,
+              beta 0: r = 1 exactly, so dlogits = (p - onehot) * gweight * A.
+        Nothing comes back to the host in between.  Leaves self.last_preference: planes (fp64 [7, P], ops.DPO_PLANES order), batch
+        (fp64 [3]: L, dpo_alpha * mean pair loss, SFT loss), coefs and logp (fp32 [n_scored], scored order) on the device, scored (host counts)
+        and P.  Returns L as fp32 [1]."""
+        from . import lib
+        n, rows, dev = int(lab_rows.size), logits.shape[0], logits.device
+        assert n == int(scored.sum()), "a scored token on a padding row"
+        P, seg_off, rho, a_P, g_N = terms.per_pair(scored)
+        zero = torch.zeros(rows, dtype=torch.float32, device=dev)
+        stats = torch.empty(len(ops.POLICY_STATS), rows, dtype=torch.float32, device=dev)
+        lib.call("rv_policy_loss_bf16", logits, logits.stride(0), tgt, zero, zero, zero, None, None, 0.0, 0.0, 0.0, stats, None, 0, rows, self.vocab)
+        row_idx = None if gathered else self._dev(lab_rows.astype(np.int32))
+        coef = torch.zeros(rows, dtype=torch.float32, device=dev)
+        planes, batch = ops.dpo_pairs(stats[0], self._dev(seg_off), row_idx, None if rho is None else self._dev(rho), terms.loss_type,
+                                      terms.beta, terms.label_smoothing, a_P, g_N, coef)
+        ones = torch.ones(rows, dtype=torch.float32, device=dev)
+        gweight = torch.full((rows,), float(np.float32(gscale)), dtype=torch.float32, device=dev)
+        stats_c = torch.empty_like(stats)
+        lib.call("rv_policy_loss_bf16", logits, logits.stride(0), tgt, coef, ones, gweight, None, None, 0.0, 0.0, 0.0, stats_c, logits,
+                 logits.stride(0), rows, self.vocab)
+        pick = (lambda t: t[:n]) if gathered else (lambda t, i=self._dev(lab_rows.astype(np.int64)): t[i])
+        self.last_preference = dict(planes=planes, batch=batch, coefs=pick(coef), logp=pick(stats[0]), scored=np.asarray(scored), P=P)
+        return batch[:1].to(torch.float32)
+
+    def sequence_logps(self, input_ids, attention_mask, labels, images, image_sizes=None):
+        """The summed log-prob of every sample's scored tokens: token_logps() followed by rv_seq_logp_sums_f64 -- fp64 [B] on the
+        device, the bits the pair kernel forms for the same batch -- and the per-sample scored counts (host int64 [B])."""
+        lp = self.token_logps(input_ids, attention_mask, labels, images, image_sizes=image_sizes)
+        counts = np.asarray(self.last_policy["scored"], dtype=np.int64)
+        if lp.numel() == 0:
+            return torch.zeros(counts.size, dtype=torch.float64, device=self.device), counts
+        from .preference import pair_offsets
+        return ops.seq_logp_sums(lp.contiguous(), self._dev(pair_offsets(counts))), counts
 
     def _cross_entropy(self, logits, tgt, V, inv, gscale):
         from . import lib

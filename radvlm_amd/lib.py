@@ -16,6 +16,7 @@ _c_void_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int
 _f32 = ctypes.c_float
+_f64 = ctypes.c_double
 
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU, ACT_GELU_TANH = 0, 1, 2, 3
 
@@ -85,6 +86,9 @@ _SIGS = {
     "rv_sum_f32": [_c_void_p, _i64, _f32, _c_void_p, _c_void_p],
     "rv_policy_loss_bf16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _f32, _f32, _f32, _c_void_p,
                             _c_void_p, _i64, _i32, _i32, _c_void_p],
+    "rv_seq_logp_sums_f64": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _c_void_p],
+    "rv_dpo_pairs_f64": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _f64, _f64, _f64, _f64, _c_void_p, _c_void_p, _c_void_p, _i32,
+                         _c_void_p],
     "rv_gather_rows": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p],
     "rv_segment_sum_rows": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i64, _i32, _c_void_p],
     "rv_normalize_tiles_u8": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _c_void_p],

@@ -239,7 +239,8 @@ class LlavaLlamaForCausalLM:
                 use_cache=None, output_attentions=None, output_hidden_states=None, images=None, image_sizes=None, return_dict=None,
                 modalities=("image",), dpo_forward=None, cache_position=None, output_logits=None):
         if past_key_values is not None or dpo_forward:
-            raise NotImplementedError("key/value caches and the DPO forward are serving / preference-tuning paths (SURVEY section 2: out of scope)")
+            raise NotImplementedError("forward() takes no key/value cache (generate() owns it) and returns no raw DPO logits "
+                                      "(dpo_forward=True): preference training goes through preference_loss() / sequence_logps()")
         if inputs_embeds is not None:
             # llava_llama.py:83-120 with inputs_embeds given: no multimodal splice, the decoder runs on the embeddings (eval loss, the
             # per-step call of a generation loop without cache); fp32 logits, loss when labels are passed; no backward
@@ -302,6 +303,53 @@ class LlavaLlamaForCausalLM:
         no training state is touched."""
         ids, am, lab, imgs = self._host_batch(input_ids, attention_mask, labels, images)
         return self.engine.token_logps(ids, am, lab, imgs, image_sizes=image_sizes)
+
+    def preference_loss(self, chosen_input_ids, chosen_attention_mask, chosen_labels, rejected_input_ids, rejected_attention_mask,
+                        rejected_labels, images, image_sizes=None, *, ref_chosen_logps=None, ref_rejected_logps=None, beta=0.1, dpo_alpha=1.0,
+                        gamma=1.0, loss_type="sigmoid", label_smoothing=0.0, reference_free=False):
+        """The DPO preference loss of the reference's LLaVADPOTrainer on P (chosen, rejected) pairs that share their prompts and images:
+        L = dpo_alpha * mean_p l(h_p) + gamma * SFT, h = beta ((pi_c - pi_r) - (rho_c - rho_r)), pi / rho the policy's / the reference's
+        summed log-prob of an answer's scored tokens (the mean for "ipo"), l the "sigmoid" (with label_smoothing), "hinge" or "ipo"
+        pair loss, SFT = -(sum of the chosen scored log-probs) / (their number).  The batch runs as 2 P right-padded sequences -- the
+        chosen rows, then the rejected rows, each half with the same images -- through forward()'s own path; labels mark the answer
+        tokens.  ref_chosen_logps / ref_rejected_logps: P floats each, the reference's SUMMED log-probs (sequence_logps() of the
+        reference model gives them), or reference_free=True.  ValueError: a pair without a scored chosen or rejected token,
+        reference log-probs missing, of the wrong length or non-finite, beta <= 0, label_smoothing outside [0, 0.5) or with "ipo",
+        an unknown loss_type.
+        Returns an output with .loss (fp32 scalar; .loss.backward() runs the engine's backward, gradients scaled by engine.loss_scale
+        as in forward()), .chosen_logps / .rejected_logps (pi), .margins (h), .pair_loss, .rewards_chosen / .rewards_rejected (fp64 [P]
+        on the device), .coefs (fp32 per scored token, scored order: -dL/dlogp) and .stats under TRL's names -- rewards/chosen,
+        rewards/rejected, rewards/accuracies, rewards/margins, logps/chosen, logps/rejected -- plus dpo_loss = dpo_alpha * mean pair loss and sft_loss (device
+        scalars)."""
+        from ...preference import PreferenceTerms, concatenate_pairs
+        host = lambda t: t.cpu().numpy() if torch.is_tensor(t) else t
+        if images is None:
+            raise ValueError("images is required (text-only samples carry a dummy zero image, train.py:1227-1232)")
+        terms = PreferenceTerms(ref_chosen_logps=ref_chosen_logps, ref_rejected_logps=ref_rejected_logps, beta=beta, dpo_alpha=dpo_alpha,
+                                gamma=gamma, loss_type=loss_type, label_smoothing=label_smoothing, reference_free=reference_free)
+        terms.check()
+        ids, am, lab = concatenate_pairs(host(chosen_input_ids), host(chosen_attention_mask), host(chosen_labels), host(rejected_input_ids),
+                                         host(rejected_attention_mask), host(rejected_labels))
+        imgs = list(images) if not torch.is_tensor(images) else [im for im in images]
+        sizes = None if image_sizes is None else list(image_sizes) * 2
+        loss = self.engine.forward(ids, am, lab, imgs + imgs, image_sizes=sizes, preference=terms)
+        lp = self.engine.last_preference
+        pl = dict(zip(("pi_c", "pi_r", "h", "loss", "reward_c", "reward_r"), lp["planes"]))
+        stats = {"rewards/chosen": pl["reward_c"].mean(), "rewards/rejected": pl["reward_r"].mean(),
+                 "rewards/accuracies": (pl["reward_c"] > pl["reward_r"]).double().mean(),
+                 "rewards/margins": (pl["reward_c"] - pl["reward_r"]).mean(), "logps/chosen": pl["pi_c"].mean(),
+                 "logps/rejected": pl["pi_r"].mean(), "dpo_loss": lp["batch"][1], "sft_loss": lp["batch"][2]}
+        return SimpleNamespace(loss=_StepFunction.apply(self._anchor, self.engine, loss), chosen_logps=pl["pi_c"], rejected_logps=pl["pi_r"],
+                               margins=pl["h"], pair_loss=pl["loss"], rewards_chosen=pl["reward_c"], rewards_rejected=pl["reward_r"],
+                               coefs=lp["coefs"], stats=stats)
+
+    @torch.no_grad()
+    def sequence_logps(self, input_ids, attention_mask, labels, images, image_sizes=None):
+        """The summed log-prob of every sample's scored tokens, fp64 [B] on the device, and the scored counts (host int64 [B]):
+        token_logps() summed per sample by rv_seq_logp_sums_f64 in its fixed order -- the reference log-probs of preference_loss.
+        No gradient, and no training state is touched."""
+        ids, am, lab, imgs = self._host_batch(input_ids, attention_mask, labels, images)
+        return self.engine.sequence_logps(ids, am, lab, imgs, image_sizes=image_sizes)
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, modalities=("image",), **kwargs):

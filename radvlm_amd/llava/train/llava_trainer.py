@@ -300,6 +300,18 @@ class LLaVATrainer:
                                         generator=g, variable_length=True)
         return None
 
+    # the three places a trainer with another objective (dpo_trainer.LLaVADPOTrainer) differs from this loop
+    def compute_loss(self, batch):
+        """One micro-batch's forward: an output whose .loss.backward() runs the engine's backward."""
+        return self.model(**batch)
+
+    def _before_train(self, start):
+        """Called once after a resume and before the first batch is drawn; start = optimizer steps already done."""
+
+    def _extra_log(self):
+        """More entries for the step's log record."""
+        return {}
+
     def train(self, resume_from_checkpoint=None):
         a = self.args
         eng = self.model.engine
@@ -314,6 +326,7 @@ class LLaVATrainer:
         kind = getattr(kind, "value", kind)
 
         start = self._maybe_resume(resume_from_checkpoint)
+        self._before_train(start)
         eng.check_replicas("start of training")       # after init / load / resume: every rank holds the same parameters and optimizer state
         for _ in range(start * accum):       # a resumed run continues the same sample stream (epoch orders are regenerated from the seed)
             next(it)
@@ -334,7 +347,7 @@ class LLaVATrainer:
                     t_data += time.perf_counter() - td
                     eng.sync_this_backward = micro == accum - 1
                     try:
-                        out = self.model(**batch)
+                        out = self.compute_loss(batch)
                         out.loss.backward()
                     except torch.cuda.OutOfMemoryError:
                         # the "auto" recompute policy sized this batch from an estimate of free memory (fragmented cache blocks count as
@@ -348,7 +361,7 @@ class LLaVATrainer:
                         torch.cuda.empty_cache()
                         if rank == 0:
                             print("[train] out of device memory under recompute='auto': retrying the step with every decoder layer recomputed", flush=True)
-                        out = self.model(**batch)
+                        out = self.compute_loss(batch)
                         out.loss.backward()
                     losses.append(out.loss)
                 lr = lr_at(step, total, a.learning_rate, warm, kind)
@@ -363,6 +376,7 @@ class LLaVATrainer:
                     rec = {"step": step, "loss": float(sum(float(l.detach()) for l in losses) / len(losses)), "learning_rate": lr,
                            "grad_norm": float(eng.last_grad_norm) if eng.last_grad_norm is not None else None,
                            "epoch": step / steps_per_epoch, "step_time_s": time.perf_counter() - t0, "data_wait_s": t_data}
+                    rec.update(self._extra_log())
                     self.state["log_history"].append(rec)
                     if rank == 0:
                         print(rec, flush=True)

@@ -149,9 +149,10 @@ class TrainingArguments:
     process_index: int = 0
 
 
-def parse_args_into_dataclasses(argv=None):
-    """HfArgumentParser-style CLI: every dataclass field is a --flag; unknown flags are an error like the reference."""
-    groups = (ModelArguments, DataArguments, TrainingArguments)
+def parse_args_into_dataclasses(argv=None, groups=None):
+    """HfArgumentParser-style CLI: every dataclass field is a --flag; unknown flags are an error like the reference.
+    groups: the three dataclasses (train_dpo.py passes its own TrainingArguments)."""
+    groups = groups or (ModelArguments, DataArguments, TrainingArguments)
     ap = argparse.ArgumentParser()
     for g in groups:
         for f in dataclasses.fields(g):
@@ -536,11 +537,14 @@ def resolve_model_sources(model_args, verbose=False):
     return geometry, lm_dir, tower_dir, is_qwen, true_vocab
 
 
-def train(attn_implementation=None, argv=None, tokenizer=None):
+def train(attn_implementation=None, argv=None, tokenizer=None, arg_groups=None, make_trainer=None):
+    """arg_groups / make_trainer: another objective on the same setup (train_dpo.py) -- its argument dataclasses, and a callable
+    (model, tokenizer, data_args, training_args, new_model) -> trainer in LLaVATrainer's place; new_model() builds one more model of
+    the same configuration carrying the policy's current weights (a frozen reference)."""
     from ..model import LlavaConfig, LlavaLlamaForCausalLM, LlavaQwenConfig, LlavaQwenForCausalLM
     from ..mm_utils import SigLipImageProcessor
     from ...config import GEOMETRIES
-    model_args, data_args, training_args = parse_args_into_dataclasses(argv)
+    model_args, data_args, training_args = parse_args_into_dataclasses(argv, arg_groups)
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     training_args.world_size, training_args.process_index, training_args.local_rank = world, rank, local
     torch.cuda.set_device(local)
@@ -620,12 +624,21 @@ def train(attn_implementation=None, argv=None, tokenizer=None):
     model.engine.image_mean, model.engine.image_std = tuple(data_args.image_processor.image_mean), tuple(data_args.image_processor.image_std)
     data_args.is_multimodal = True
     data_args.mm_use_im_start_end = model_args.mm_use_im_start_end
-    module = make_supervised_data_module(tokenizer=tokenizer, data_args=data_args)
     # the switches the trainer's checkpoint policy reads (train/train.py:1578-1611 copies them onto training_args)
     training_args.tune_mm_mlp_adapter = model_args.tune_mm_mlp_adapter
     training_args.mm_tunable_parts = model_args.mm_tunable_parts
     training_args.use_im_start_end = model_args.mm_use_im_start_end
-    trainer = LLaVATrainer(model=model, tokenizer=tokenizer, args=training_args, **module)
+    if make_trainer is None:
+        trainer = LLaVATrainer(model=model, tokenizer=tokenizer, args=training_args, **make_supervised_data_module(tokenizer=tokenizer, data_args=data_args))
+    else:
+        def new_model():
+            twin = Model(cfg, device=f"cuda:{local}", process_group=None, init="fast")
+            if true_vocab != geometry["lm"]["vocab"]:
+                twin.engine.resize_token_embeddings(model.engine.vocab)
+            twin.load_state_dict(model.state_dict())
+            twin.engine.image_mean, twin.engine.image_std, twin.engine.padding_side = model.engine.image_mean, model.engine.image_std, model.engine.padding_side
+            return twin
+        trainer = make_trainer(model, tokenizer, data_args, training_args, new_model)
     # auto-resume like the reference (train/train.py:1699-1702): continue from the newest checkpoint-* of output_dir
     has_ckpt = bool(training_args.output_dir) and os.path.isdir(training_args.output_dir) and any(
         d.startswith("checkpoint-") for d in os.listdir(training_args.output_dir))

@@ -472,6 +472,36 @@ def policy_loss(logits, labels_shifted, V, adv, weight, gscale=1.0, old_logp=Non
     return loss, stats
 
 
+def seq_logp_sums(logp, seg_off, row_idx=None):
+    """fp64 [B] sums of the scored tokens' log-probs of every sequence, in the fixed order include/radvlm_hip.h documents
+    (rv_seq_logp_sums_f64).  logp fp32 rows; seg_off int32 [B + 1] in scored order; row_idx int32 (scored token -> row) or None."""
+    assert logp.dtype == torch.float32 and logp.is_contiguous() and seg_off.dtype == torch.int32
+    assert row_idx is None or row_idx.dtype == torch.int32
+    B = seg_off.numel() - 1
+    sums = torch.empty(B, dtype=torch.float64, device=logp.device)
+    lib.call("rv_seq_logp_sums_f64", logp, seg_off, row_idx, sums, B, logp.numel())
+    return sums
+
+
+DPO_PLANES = ("pi_chosen", "pi_rejected", "h", "loss", "reward_chosen", "reward_rejected", "sum_chosen")     # rv_dpo_pairs_f64's planes, in order
+DPO_BATCH = ("loss", "dpo_loss", "sft_loss")
+DPO_LOSS_TYPES = ("sigmoid", "hinge", "ipo")
+
+
+def dpo_pairs(logp, seg_off, row_idx, rho, loss_type, beta, label_smoothing, alpha_over_P, gamma_over_Nc, coef):
+    """The pairwise DPO terms and the per-token gradient coefficients (rv_dpo_pairs_f64).  seg_off int32 [2P + 1]; rho fp64 [2P] or
+    None; coef fp32 [rows], written at the scored rows only.  Returns (planes fp64 [7, P] in DPO_PLANES order, batch fp64 [3])."""
+    assert logp.dtype == torch.float32 and logp.is_contiguous() and coef.dtype == torch.float32 and coef.numel() == logp.numel()
+    assert seg_off.dtype == torch.int32 and seg_off.numel() % 2 == 1 and (row_idx is None or row_idx.dtype == torch.int32)
+    P = (seg_off.numel() - 1) // 2
+    assert rho is None or (rho.dtype == torch.float64 and rho.numel() == 2 * P)
+    planes = torch.empty(len(DPO_PLANES), P, dtype=torch.float64, device=logp.device)
+    batch = torch.empty(len(DPO_BATCH), dtype=torch.float64, device=logp.device)
+    lib.call("rv_dpo_pairs_f64", logp, seg_off, row_idx, rho, P, DPO_LOSS_TYPES.index(loss_type), float(beta), float(label_smoothing),
+             float(alpha_over_P), float(gamma_over_Nc), planes, batch, coef, logp.numel())
+    return planes, batch
+
+
 def gather_rows(idx, d, table_a, table_b=None, out=None):
     rows = idx.numel()
     assert idx.dtype == torch.int32
