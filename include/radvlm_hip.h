@@ -438,6 +438,29 @@ int64_t rv_w4_scale_row_bytes(int K);
 int rv_gemv_w4_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp, const void* scales, int64_t lds, void* Y, int64_t ldy,
                     const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
                     int64_t ws_bytes, void* stream);
+/* Decoding with live LoRA adapters (lora_decode.hip; reference: a peft LoraLayer in eval mode, y = W x + (alpha / r) B A x, which the
+ * reference only ever evaluates merged).  The two calls a fused projection takes at M <= 32 rows; the arithmetic is that of the
+ * training path's adapted linear at dropout 0: t rounded once to bf16, already scaled, then one fp32 sum and one store for y. */
+/* T[M, j r .. (j + 1) r) = bf16(scale * X[M, K] A_j[r, K]^T) for the n_mod <= 3 adapters A0, A1, A2 that share the input X (q|k|v,
+ * gate|up); each A_j has its own base pointer (rows of lda elements).  K is split over workgroups in rv_lora_down_split(r, K)
+ * slices, summed in slice order through `workspace` (split * M * n_mod * r * 4 bytes when split > 1) by a second launch; no atomics,
+ * a row's bits do not depend on M.  1 <= M <= 32, r % 8 == 0, 8 <= r <= 64, K % 8 == 0, ldx % 8 == 0, lda % 8 == 0, X and A_j
+ * 16-byte aligned, ldt >= n_mod * r. */
+int rv_lora_down_rows_bf16(const void* X, int64_t ldx, const void* A0, const void* A1, const void* A2, int64_t lda, int n_mod, void* T,
+                           int64_t ldt, int M, int r, int K, float scale, void* workspace, int64_t ws_bytes, void* stream);
+/* Number of K slices rv_lora_down_rows_bf16 uses (host function, no launch). */
+int rv_lora_down_split(int r, int K);
+/* Y[M, N] = X[M, K] W[N, K]^T + T_j B_j^T (+ bias[N]) (+ residual[M, N]), bf16 Y, 1 <= M <= 32: rv_gemv_bf16 with the adapter riding it.
+ * Module j < n_mod owns the columns [col0_j, col1_j) of Y, reads its t from columns [toff_j, toff_j + r) of T[M, ldt] and its
+ * B_j[col1_j - col0_j, r] from its own pointer (rows of ldb elements); ranges ascend and do not overlap, col0_j is a multiple of 64
+ * and col1_j is a multiple of 64 or N; columns outside every range get no adapter.  The W part takes rv_gemv_bf16's K split
+ * (rv_gemv_split(N, K)), k-to-lane assignment, step order, four-wave reduction, combine and epilogue; the adapter's ceil(r / 32)
+ * steps follow all W steps of the one accumulator that takes them, so with B = 0 every bit of Y is rv_gemv_bf16's.  r as above,
+ * K % 8 == 0, ldx, ldw, ldt, ldb, toff_j multiples of 8, X, W, T, B_j 16-byte aligned.  Workspace as rv_gemv_bf16. */
+int rv_gemv_lora_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* T, int64_t ldt, int r, int n_mod, const void* B0,
+                      int col0_0, int col1_0, int toff0, const void* B1, int col0_1, int col1_1, int toff1, const void* B2, int col0_2,
+                      int col1_2, int toff2, int64_t ldb, void* Y, int64_t ldy, const void* bias, const void* residual, int64_t ldr, int M,
+                      int N, int K, void* workspace, int64_t ws_bytes, void* stream);
 /* Decode attention (flash-decoding, decode.hip; the kernel body, the partial layout, the combine and the launcher that the six
  * other rv_attn_decode_* / rv_attn_extend_* entry points below share with it or with each other are csrc/attn_split.h): for every sequence b and q head h, softmax(scale * q[b,h] K^T) V over the cached keys
  * [0, kv_len[b]) of kv head h / (H / Hkv), hd in {64, 128}, up to 8 q heads per kv head (GQA), fp32 softmax and accumulation.

@@ -619,16 +619,16 @@ class LlavaEngine:
         if rows is not None:
             attn_sel = ops.gather_rows(rows, d, attn)
             if self.lora:
-                x_mid = self._lora_linear(attn_sel, lv["o"], i, (("self_attn.o_proj", 0, d),), sv, residual=ops.gather_rows(rows, d, x))
+                x_mid = self._lora_linear(attn_sel, lv["o"], i, self._MODS_O(d), sv, residual=ops.gather_rows(rows, d, x))
             else:
                 x_mid = ops.gemm_nt(attn_sel, lv["o"], residual=ops.gather_rows(rows, d, x))
         elif self.lora:
-            x_mid = self._lora_linear(attn, lv["o"], i, (("self_attn.o_proj", 0, d),), sv, residual=x)
+            x_mid = self._lora_linear(attn, lv["o"], i, self._MODS_O(d), sv, residual=x)
         else:
             x_mid = ops.gemm_nt(attn, lv["o"], residual=x)
         h2, rstd2 = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
         if self.lora:
-            gu = self._lora_linear(h2, lv["gu"], i, (("mlp.gate_proj", 0, F), ("mlp.up_proj", F, 2 * F)), sv)
+            gu = self._lora_linear(h2, lv["gu"], i, self._MODS_GU(F), sv)
             act = ops.swiglu_fwd(gu, F)
         elif not self.fused:
             gu = ops.gemm_nt(h2, lv["gu"])
@@ -636,7 +636,7 @@ class LlavaEngine:
         else:       # gate|up projection and silu(gate) * up in one launch
             gu, act = ops.gemm_swiglu_fwd(h2, lv["gu"], F)
         if self.lora:
-            x_out = self._lora_linear(act, lv["down"], i, (("mlp.down_proj", 0, d),), sv, residual=x_mid)
+            x_out = self._lora_linear(act, lv["down"], i, self._MODS_DOWN(d), sv, residual=x_mid)
         else:
             x_out = ops.gemm_nt(act, lv["down"], residual=x_mid)
         acts = dict(x=x, rstd1=rstd1, h1=h1, qkv=qkv, attn=attn, lse=lse, x_mid=x_mid, rstd2=rstd2, h2=h2, gu=gu, act=act, lora=sv)
@@ -923,7 +923,9 @@ class LlavaEngine:
         This format is lossy: about 12 % relative Frobenius error per matrix against about 1 % for int8."""
         if fmt not in ("int8", "mxfp4"):
             raise ValueError(f"quantize_decoder_(fmt={fmt!r}): expected 'int8' or 'mxfp4'")
-        self._check_generation()
+        if self.lora:                        # also with adapter_decoding on: the quantised skinny kernels carry no adapter
+            raise NotImplementedError("quantize_decoder_() on a model with LoRA adapters: merge them into the base weights first with "
+                                      "model.merge_and_unload()")
         if self.is_quantized:
             raise RuntimeError("quantize_decoder_(): the decoder is already quantised; a second pass would round the weights again")
         quantize = ops.quantize_rows_w8 if fmt == "int8" else ops.quantize_rows_mxfp4
@@ -942,10 +944,38 @@ class LlavaEngine:
                     off, n = self.lm.offsets[f"model.layers.{i}.{t}.weight"]
                     self.master[off:off + n].copy_(ops.to_f32(self.lm.flat[off:off + n]))
 
+    # Generation on unmerged adapters (model.enable_adapter_decoding()): off, every generation entry point refuses a LoRA engine as it
+    # always has; on, prefill() runs the training path's adapted linears in eval form and the cached steps go through
+    # _decode_lora_linear.  The adapters are read from self.lm on every call, so an optimizer_step() is seen by the next token.
+    adapter_decoding = False
+    # True: every adapted linear, on the training path and the decode path alike, behaves as if every lora_B were zero -- the frozen
+    # base model, peft's disable_adapter() (model.disable_adapter()).  Forward only: backward() raises.
+    adapters_off = False
+
     def _check_generation(self):
-        if self.lora:
+        if self.lora and not self.adapter_decoding:
             raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
-                                      "model.merge_and_unload() (the reference merges adapters before evaluation)")
+                                      "model.merge_and_unload() (the reference merges adapters before evaluation), or decode on the "
+                                      "live adapters with model.enable_adapter_decoding() (engine.adapter_decoding)")
+
+    def _decode_lora_linear(self, x, w, i, mods, bias=None, residual=None, wq=None, skinny=False):
+        """_decode_linear for a fused projection of layer i whose modules `mods` (name, c0, c1) may carry adapters.  No adapters: that
+        call.  Rows that take the skinny route: one rv_lora_down_rows_bf16 launch for the modules' t = (alpha / r) x A_j^T and one
+        rv_gemv_lora_bf16 launch, the adapter riding rv_gemv_bf16 (a row's bits do not depend on the row count, as there).  More rows:
+        _lora_linear's arithmetic without dropout.  adapters_off: a zero B -- on the skinny route that is rv_gemv_bf16's result bit
+        for bit (the kernel's contract), so the two adapter launches are skipped."""
+        if not self.lora:
+            return self._decode_linear(x, w, bias=bias, residual=residual, wq=wq, skinny=skinny)
+        max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
+        if not skinny and x.shape[0] > min(max_m, ops.GEMV_MAX_M):
+            return self._lora_linear(x, w, i, mods, {}, residual=residual, bias=bias, p=0.0)
+        if self.adapters_off:
+            return ops.gemv(x, w, bias=bias, residual=residual)
+        pre = f"model.layers.{i}."
+        r = self.lora["r"]
+        t = ops.lora_down_rows(x, [self.W(f"{pre}{lname}.lora_A.weight") for lname, _, _ in mods], self.lora_scale)
+        table = [(c0, c1, j * r, self.W(f"{pre}{lname}.lora_B.weight")) for j, (lname, c0, c1) in enumerate(mods)]
+        return ops.gemv_lora(x, w, t, table, bias=bias, residual=residual)
 
     # An int8-dtype KVCache is stored as (int8, fp32 scale) tensors and read by rv_attn_decode_kv8_bf16; False keeps it as bf16 tensors
     # that hold the dequantised values (written by the same quantise kernels) and reads it with rv_attn_decode_bf16.  The two are
@@ -1064,20 +1094,25 @@ class LlavaEngine:
             cache = self.new_kv_cache(B, L_max, kv_dtype)           # seq = 0 .. B - 1: filled like a passed cache's slots
         if taps is not None:
             tap_rows, tapped = self._dev((cu[1:] - 1).astype(np.int32)), {}
-        for i in range(L):
-            if taps is not None and i in taps:
-                tapped[i] = ops.gather_rows(tap_rows, d, x)
-            x, acts = self._layer_forward(i, x, geom)
-            if cache is None:
-                kv = torch.zeros(B, L_max, 2 * kvd, dtype=BF16, device=dev)
-                layers.append(kv)
-            else:
-                kv = cache.layers[i]
-            if kv_dtype == "int8":
-                self._kv_write_rows(kv, cache.scales[i] if cache.scales is not None else None, acts["qkv"][:, d:], rows)
-            else:
-                kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:])
-            del acts
+        saved_p = getattr(self, "lora_p", 0.0)
+        self.lora_p = 0.0                    # live adapters (adapter_decoding): eval form, as in forward_embeds; lora_step is only read
+        try:
+            for i in range(L):
+                if taps is not None and i in taps:
+                    tapped[i] = ops.gather_rows(tap_rows, d, x)
+                x, acts = self._layer_forward(i, x, geom)
+                if cache is None:
+                    kv = torch.zeros(B, L_max, 2 * kvd, dtype=BF16, device=dev)
+                    layers.append(kv)
+                else:
+                    kv = cache.layers[i]
+                if kv_dtype == "int8":
+                    self._kv_write_rows(kv, cache.scales[i] if cache.scales is not None else None, acts["qkv"][:, d:], rows)
+                else:
+                    kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:])
+                del acts
+        finally:
+            self.lora_p = saved_p
         last = self._dev((cu[1:] - 1).astype(np.int32))
         hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
         if taps is None:
@@ -1179,7 +1214,7 @@ class LlavaEngine:
                 tapped[i] = x                      # every statement below makes a new x: the row stays as it is
             lv, wq = self._layer_views(i), self._layer_wq(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"))
+            qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
             if kv8 and cache.scales is not None:
                 kvq = (cache.layers[i], cache.scales[i])
@@ -1198,10 +1233,10 @@ class LlavaEngine:
                 ops.kv_append(qkv[:, d:], cache.layers[i], pos)
                 attn = ops.attn_decode_beam(qkv[:, :d], cache.layers[i], kv_len, beams.prefix_row, beams.prefix_len, beams.tail_src, H, Hkv,
                                             hd, kvd, tail_cols=beams.tail_cols, chunk=cache.chunk)
-            x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"))
+            x_mid = self._decode_lora_linear(attn, lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu")), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"))
+            act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu")), F)
+            x = self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"))
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         if taps is not None:
             logits, cand = self._tap_logits(hN, [tapped[c] for c in taps])
@@ -1305,7 +1340,7 @@ class LlavaEngine:
         for i in range(L):
             lv, wq = self._layer_views(i), self._layer_wq(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"), skinny=True)
+            qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"), skinny=True)
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
             kv = cache.layers[i]
             kv.view(L_max, 2 * kvd).index_copy_(0, slots, qkv[:, d:])
@@ -1313,10 +1348,10 @@ class LlavaEngine:
                 attn = ops.attn_decode_beam(qkv[:, :d], kv, kv_len, zero, plen, None, H, Hkv, hd, kvd, chunk=cache.chunk)
             else:
                 attn = ops.attn_decode_verify(qkv[:, :d], kv, kv0, R, H, Hkv, hd, kvd, chunk=cache.chunk)
-            x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"), skinny=True)
+            x_mid = self._decode_lora_linear(attn, lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"), skinny=True)
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu"), skinny=True), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"), skinny=True)
+            act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu"), skinny=True), F)
+            x = self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"), skinny=True)
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32, skinny=True)
         return logits[:, :self.vocab]
@@ -1403,15 +1438,15 @@ class LlavaEngine:
         for i in range(L):
             lv, wq = self._layer_views(i), self._layer_wq(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"))
+            qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
             kv = cache.layers[i]
             kv.view(CB * L_max, 2 * kvd).index_copy_(0, rows, qkv[:, d:])
             attn = ops.attn_extend(qkv[:, :d], kv, cu_d, r_d, H, Hkv, hd, kvd, int(n.max()))
-            x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"))
+            x_mid = self._decode_lora_linear(attn, lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu")), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"))
+            act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu")), F)
+            x = self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"))
         last = self._dev((cu_q[seq + 1] - 1).astype(np.int32))              # sequence b's last new row, in the prompt batch's order
         hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
         logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
@@ -1468,14 +1503,14 @@ class LlavaEngine:
         for i in range(L):
             lv, wq = self._layer_views(i), self._layer_wq(i)
             h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_linear(h1, lv["qkv"], bias=lv.get("bqkv"), wq=wq.get("qkv"))
+            qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"))
             ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
             tail[i].view(C * T_max, 2 * kvd).index_copy_(0, rows, qkv[:, d:])
             attn = ops.attn_extend_prefix(qkv[:, :d], prefix.layers[i], tail[i], cu_d, prow_d, plen_d, H, Hkv, hd, kvd, a.max_q)
-            x_mid = self._decode_linear(attn, lv["o"], residual=x, wq=wq.get("o"))
+            x_mid = self._decode_lora_linear(attn, lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"))
             h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_linear(h2, lv["gu"], wq=wq.get("gu")), F)
-            x = self._decode_linear(act, lv["down"], residual=x_mid, wq=wq.get("down"))
+            act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu")), F)
+            x = self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"))
         del tail
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         w_head = self.W("lm_head.weight")
@@ -1605,20 +1640,40 @@ class LlavaEngine:
         kvd = self.kvd      # == d without grouped-query attention
         return (("self_attn.q_proj", 0, d), ("self_attn.k_proj", d, d + kvd), ("self_attn.v_proj", d + kvd, d + 2 * kvd))
 
+    def _MODS_O(self, d):
+        return (("self_attn.o_proj", 0, d),)
+
+    def _MODS_GU(self, F):
+        return (("mlp.gate_proj", 0, F), ("mlp.up_proj", F, 2 * F))
+
+    def _MODS_DOWN(self, d):
+        return (("mlp.down_proj", 0, d),)
+
     def _lora_ws(self):
         if getattr(self, "_ws", None) is None:
             self._ws = torch.empty(32 << 20, dtype=torch.float32, device=self.device)   # split-K scratch (128 MiB)
         return self._ws
 
-    def _lora_linear(self, x, w, i, mods, saved, residual=None, bias=None):
+    def _zero_B(self, B):
+        """adapters_off: a zero matrix of lora_B's shape, so that the launch is the zero-B call itself."""
+        z = getattr(self, "_zero_b", None)
+        if z is None or z.numel() < B.numel():
+            z = self._zero_b = torch.zeros(B.numel(), dtype=BF16, device=self.device)
+        return z[:B.numel()].view(B.shape)
+
+    def _lora_linear(self, x, w, i, mods, saved, residual=None, bias=None, p=None):
         """y[:, c0:c1] = x W[c0:c1]^T + t B^T (+ residual) with t = (alpha/r) dropout(x) A^T: ONE launch per adapted module,
-        the adapter rides the main GEMM as a second operand pair (K + r), no second pass over y."""
+        the adapter rides the main GEMM as a second operand pair (K + r), no second pass over y.
+        p: the dropout rate when it is not self.lora_p (the decode path passes 0)."""
+        p = self.lora_p if p is None else p
         y = torch.empty(x.shape[0], w.shape[0], dtype=BF16, device=self.device)
         for lname, c0, c1 in mods:
             pre = f"model.layers.{i}.{lname}."
             A, B = self.W(pre + "lora_A.weight"), self.W(pre + "lora_B.weight")
+            if self.adapters_off:
+                B = self._zero_B(B)
             # t = (alpha / r) * dropout(x) A^T: one pass over x, the mask applied to the operand fragments (rv_lora_down_bf16)
-            t = ops.lora_down(x, A, self.lora_scale, self.lora_p, self._lora_seed(i, lname))
+            t = ops.lora_down(x, A, self.lora_scale, p, self._lora_seed(i, lname))
             ops.gemm(x, w[c0:c1], out=y[:, c0:c1], bias=None if bias is None else bias[c0:c1],
                      residual=None if residual is None else residual[:, c0:c1], a2=t, b2=B)
             saved[lname] = t
@@ -1666,6 +1721,8 @@ class LlavaEngine:
         """Backward of the last forward(); gradients land in self.grads (bf16, flat)."""
         c = self.ctx
         assert c is not None, "forward() first"
+        if self.adapters_off:
+            raise RuntimeError("backward() with the adapters switched off (model.disable_adapter()): that forward is for evaluation")
         self._select_gemm_launch_shape()
         l = self.l
         d, F, H, V, L = l["d"], l["ffn"], l["heads"], l["vocab"], l["layers"]
@@ -1695,14 +1752,14 @@ class LlavaEngine:
             lv, gv = self._layer_views(i), self._layer_views(i, self.grads)
             sv = a["lora"]
             if self.lora or not self.fused:
-                dact = self._lm_linear_bwd(dx, a["act"], lv["down"], gv.get("down"), i, (("mlp.down_proj", 0, d),), sv)
+                dact = self._lm_linear_bwd(dx, a["act"], lv["down"], gv.get("down"), i, self._MODS_DOWN(d), sv)
                 dgu = ops.swiglu_bwd(dact, a["gu"], F)
             else:       # down_proj: weight gradient, then the input gradient with the SwiGLU backward in its epilogue (d(act) never stored)
                 self._linear_bwd(dx, a["act"], lv["down"], gv.get("down"), need_dx=False)
                 dgu = ops.gemm_swiglu_bwd(dx, lv["down"], a["gu"], F)
-            dh2 = self._lm_linear_bwd(dgu, a["h2"], lv["gu"], gv.get("gu"), i, (("mlp.gate_proj", 0, F), ("mlp.up_proj", F, 2 * F)), sv)
+            dh2 = self._lm_linear_bwd(dgu, a["h2"], lv["gu"], gv.get("gu"), i, self._MODS_GU(F), sv)
             ops.rmsnorm_bwd(dh2, a["x_mid"], lv["ln2"], a["rstd2"], dx=dx, dx_add=True, dw=gv.get("ln2"), dw_accumulate=acc)
-            dattn = self._lm_linear_bwd(dx, a.get("attn_sel", a["attn"]), lv["o"], gv.get("o"), i, (("self_attn.o_proj", 0, d),), sv)
+            dattn = self._lm_linear_bwd(dx, a.get("attn_sel", a["attn"]), lv["o"], gv.get("o"), i, self._MODS_O(d), sv)
             if "attn_sel" in a:       # last layer on the labelled rows: back to all token rows (zero elsewhere) for the attention backward
                 dattn, dx = ops.gather_rows(back, d, dattn), ops.gather_rows(back, d, dx)
             qkv = a["qkv"]

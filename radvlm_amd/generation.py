@@ -94,7 +94,8 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
             raise ValueError("use_cache=False contradicts past_key_values: pass one or the other")
     if lora:
         raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
-                                  "model.merge_and_unload() (the reference merges adapters before evaluation)")
+                                  "model.merge_and_unload() (the reference merges adapters before evaluation), or decode on the "
+                                  "live adapters with model.enable_adapter_decoding()")
     if guidance is not None and pkv is not None:
         raise NotImplementedError("guidance_scale with past_key_values: a guided call fills one cache with both branches and keeps none "
                                   "of it across calls")

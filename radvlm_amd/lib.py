@@ -144,11 +144,16 @@ _SIGS = {
                                    _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
     "rv_token_logprob_rows_f32": [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p],
     "rv_lora_merge_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p],
+    "rv_lora_down_rows_bf16": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _c_void_p, _i64, _i32, _i32, _i32, _f32, _c_void_p,
+                               _i64, _c_void_p],
+    "rv_gemv_lora_bf16": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _i32, _i32, _i32,
+                          _c_void_p, _i32, _i32, _i32, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _c_void_p, _i64,
+                          _c_void_p],
 }
 
 EXPORTED_SYMBOLS = ["rv_version", "rv_gemm_select_kernel", "rv_gemm_set_cu_budget", "rv_attn_fwd_nat_pairs", "rv_gemv_split",
                     "rv_w8_row_bytes", "rv_w4_row_bytes", "rv_w4_scale_row_bytes", "rv_sample_uniform24", "rv_sample_ws_bytes", "rv_beam_topk_ws_bytes", "rv_cfg_guide_ws_bytes",
-                    "rv_dola_ws_bytes"] + sorted(_SIGS)
+                    "rv_dola_ws_bytes", "rv_lora_down_split"] + sorted(_SIGS)
 
 _lib = None
 

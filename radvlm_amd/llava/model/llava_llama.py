@@ -7,6 +7,7 @@ same ``forward`` keyword list, ``.loss`` (fp32 scalar, mean CE over non-ignored 
 ``initialize_vision_tokenizer``, reference state-dict names.  ``out.loss.backward()`` runs the engine's hand-written
 backward (one autograd node for the whole step), so an HF-Trainer-style ``training_step`` drives it unchanged.
 """
+import contextlib
 import os
 from types import SimpleNamespace
 
@@ -423,7 +424,7 @@ class LlavaLlamaForCausalLM:
         type, a list of another length or an automaton naming an id beyond the vocabulary: ValueError.
         The training state (weights, optimizer, RNG counters) is not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
-        cfg = parse_generate_kwargs(kwargs, lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
+        cfg = parse_generate_kwargs(kwargs, lora=self._lora_refused, config_eos=getattr(self.config, "eos_token_id", None),
                                     config_pad=getattr(self.config, "pad_token_id", None), lookup=True)
         if inputs is None:
             raise ValueError("generate() needs the prompt token ids (`inputs`)")
@@ -468,7 +469,7 @@ class LlavaLlamaForCausalLM:
         The training state is not touched."""
         from ...generation import generate_batch, parse_batch_kwargs
         inputs = list(inputs)
-        cfg = parse_batch_kwargs(kwargs, len(inputs), lora=bool(self.engine.lora), config_eos=getattr(self.config, "eos_token_id", None),
+        cfg = parse_batch_kwargs(kwargs, len(inputs), lora=self._lora_refused, config_eos=getattr(self.config, "eos_token_id", None),
                                  config_pad=getattr(self.config, "pad_token_id", None))
         return generate_batch(self.engine, inputs, images, image_sizes, cfg, max_batch_size=max_batch_size, return_logprobs=return_logprobs)
 
@@ -486,7 +487,8 @@ class LlavaLlamaForCausalLM:
         argmax; .best(length_normalized=False) the best candidate's index per prompt (ties: the lower index).
         The raw distribution is the point: no logits processors, no sampling, no kv_cache_dtype (any other keyword: TypeError).
         ValueError for an empty prompt, candidate or candidate list, candidate ids outside [0, vocab) and lists of different lengths;
-        NotImplementedError for LoRA models (merge_and_unload() first).  int8 / MXFP4 decoders work.  The training state is not touched."""
+        NotImplementedError for LoRA models (merge_and_unload() or enable_adapter_decoding() first).  int8 / MXFP4 decoders work.
+        The training state is not touched."""
         if kwargs:
             raise TypeError(f"score() got unexpected keyword arguments {sorted(kwargs)}")
         from ...scoring import score
@@ -509,7 +511,7 @@ class LlavaLlamaForCausalLM:
         None and "bf16" are accepted and change nothing), and so do classifier-free guidance (guidance_scale or any negative_*
         argument) and dola_layers.  The training state is not touched."""
         from ...generation import beam_generate, parse_beam_kwargs
-        cfg = parse_beam_kwargs(dict(kwargs, num_beams=num_beams), lora=bool(self.engine.lora),
+        cfg = parse_beam_kwargs(dict(kwargs, num_beams=num_beams), lora=self._lora_refused,
                                 config_eos=getattr(self.config, "eos_token_id", None), config_pad=getattr(self.config, "pad_token_id", None))
         if inputs is None:
             raise ValueError("generate_beams() needs the prompt token ids (`inputs`)")
@@ -579,6 +581,37 @@ class LlavaLlamaForCausalLM:
         self.engine.merge_lora()
         self.config.lora = None
         return self
+
+    @property
+    def _lora_refused(self):
+        """What the generation parsers take as `lora=`: unmerged adapters that generation may not read."""
+        return bool(self.engine.lora) and not self.engine.adapter_decoding
+
+    def enable_adapter_decoding(self, on=True):
+        """Let generate(), generate_batch(), generate_beams(), score() and everything built on them (past_key_values,
+        prompt_lookup_num_tokens, guidance, DoLa, constraints, share_prefix, kv_cache_dtype="int8") run on the UNMERGED adapters: the
+        prompt pass takes the training path's adapted linears without dropout, every cached step two launches per fused projection
+        (rv_lora_down_rows_bf16, rv_gemv_lora_bf16).  The adapters are read as they are at every call, so a LoRA run can sample from
+        and evaluate its own policy between optimizer steps; the training state is not touched.  on=False restores the refusal.
+        Needs a model with adapters (ValueError); quantised decoders with adapters stay refused.  Returns self."""
+        if not self.engine.lora:
+            raise ValueError("enable_adapter_decoding() needs a model with LoRA adapters")
+        self.engine.adapter_decoding = bool(on)
+        return self
+
+    @contextlib.contextmanager
+    def disable_adapter(self):
+        """peft's disable_adapter(): inside the block every adapted linear behaves as if its lora_B were zero -- the frozen base
+        model, e.g. the reference policy of GRPO / DPO on adapters -- in forward(), token_logps(), sequence_logps() and generation
+        alike.  Evaluation only: loss.backward() inside the block raises.  The earlier state is restored on exit, also on an
+        exception.  ValueError on a model without adapters."""
+        if not self.engine.lora:
+            raise ValueError("disable_adapter() needs a model with LoRA adapters")
+        saved, self.engine.adapters_off = self.engine.adapters_off, True
+        try:
+            yield self
+        finally:
+            self.engine.adapters_off = saved
 
     def load_adapter(self, path):
         """Inverse of the LoRA branch of save_pretrained (resume / continued training): adapter_model.bin + non_lora_trainables.bin."""

@@ -6,7 +6,8 @@ A micro-batch of P records runs as 2 P sequences (TRL's concatenated_forward).  
 of the same 2 P sequence batch, or -- precompute_ref_log_probs -- a table indexed by dataset item, filled once before the first
 update from the micro-batches of the run's first epoch (items that epoch drops are taken one by one), after which ref_model is not
 needed; with ref_model None the table is taken from the policy's own initial weights (TRL).  The table is kept in every checkpoint, so
-a resumed run does not take it again from trained weights.  One rank only: a pair never straddles ranks and no collective is added;
+a resumed run does not take it again from trained weights.  reference_adapters_off=True (a LoRA policy, ref_model None): the reference
+is the policy itself under model.disable_adapter(), per micro-batch or into the table.  One rank only: a pair never straddles ranks and no collective is added;
 N > 1 ranks are untested.
 """
 import copy
@@ -111,13 +112,20 @@ PAIR_KEYS = ("chosen_input_ids", "chosen_attention_mask", "chosen_labels", "reje
 
 class LLaVADPOTrainer(LLaVATrainer):
     def __init__(self, model=None, ref_model=None, args=None, dpo_alpha=1.0, beta=0.1, gamma=1.0, train_dataset=None, data_collator=None,
-                 tokenizer=None, precompute_ref_log_probs=False, loss_type="sigmoid", label_smoothing=0.0, reference_free=False, **_):
+                 tokenizer=None, precompute_ref_log_probs=False, loss_type="sigmoid", label_smoothing=0.0, reference_free=False,
+                 reference_adapters_off=False, **_):
         super().__init__(model=model, tokenizer=tokenizer, args=args, train_dataset=train_dataset,
                          data_collator=data_collator if data_collator is not None else DPODataCollator(tokenizer=tokenizer))
         self.ref_model, self.precompute, self.reference_free = ref_model, bool(precompute_ref_log_probs), bool(reference_free)
         self.terms = dict(beta=beta, dpo_alpha=dpo_alpha, gamma=gamma, loss_type=loss_type, label_smoothing=label_smoothing)
         PreferenceTerms(reference_free=True, **self.terms).check()          # the scalar arguments, before any device work
-        if ref_model is None and not self.precompute and not self.reference_free:
+        # reference_adapters_off (a LoRA policy, ref_model None): the reference is the policy with its adapters switched off
+        # (model.disable_adapter(), peft's way) -- the frozen base it started from, without a second copy of the model
+        self.ref_off = bool(reference_adapters_off)
+        if self.ref_off and (ref_model is not None or not model.engine.lora):
+            raise ValueError("reference_adapters_off=True takes the reference from the policy's own frozen base: it needs a model with "
+                             "LoRA adapters and ref_model=None")
+        if ref_model is None and not self.precompute and not self.reference_free and not self.ref_off:
             raise ValueError("LLaVADPOTrainer needs a ref_model, precompute_ref_log_probs=True (the policy's initial weights are the "
                              "reference) or reference_free=True")
         if ref_model is model and not self.precompute:
@@ -146,7 +154,11 @@ class LLaVADPOTrainer(LLaVATrainer):
 
     def _reference_sums(self, model, batch):
         """The reference's summed log-probs of the micro-batch's 2 P sequences: (chosen fp64 [P], rejected fp64 [P]) on the device."""
-        sums, _ = model.sequence_logps(**self._pair_batch(batch))
+        if self.ref_off:
+            with self.model.disable_adapter():
+                sums, _ = self.model.sequence_logps(**self._pair_batch(batch))
+        else:
+            sums, _ = model.sequence_logps(**self._pair_batch(batch))
         P = sums.numel() // 2
         return sums[:P], sums[P:]
 

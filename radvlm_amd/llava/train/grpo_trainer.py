@@ -6,7 +6,8 @@ One optimizer step, on `per_device_train_batch_size` prompts x `num_generations`
   1. sample   model.generate_batch(do_sample=True, seed=policy.sample_seeds(...), share_prefix=True): a group's prompt is prefilled once;
   2. score    reward_funcs, weighted sum; policy.group_advantages; policy.token_weights over the whole step; policy.assemble;
   3. log-probs  old (num_iterations > 1) and reference (beta > 0) log-probs by token_logps(), the training path's own arithmetic, so
-              the first iteration's ratio is exactly 1;
+              the first iteration's ratio is exactly 1; a LoRA policy (model.enable_adapter_decoding()) without ref_model takes the
+              reference from itself under model.disable_adapter();
   4. update   num_iterations passes over the step's micro-batches through model.policy_loss(...).loss.backward(), each followed by
               optimizer_step().  engine.loss_scale is 1: the token weights already normalise the step.
 The step's groups are split into `gradient_accumulation_steps` micro-batches of whole groups (HF's meaning of the field: the number
@@ -45,10 +46,12 @@ class GRPOTrainer(LLaVATrainer):
         if self.G < 2:
             raise ValueError(f"num_generations must be at least 2 (the group is the baseline), got {self.G}")
         self.beta = float(getattr(a, "beta", 0.0) or 0.0)
-        if self.beta > 0 and ref_model is None:
+        live = bool(model.engine.lora) and model.engine.adapter_decoding    # rollouts on the unmerged adapters
+        if self.beta > 0 and ref_model is None and not live:
             raise ValueError("beta > 0 needs ref_model (the KL term is taken against its token_logps)")
-        if model.engine.lora:
-            raise NotImplementedError("GRPO on a LoRA engine: generation refuses unmerged adapters; merge_and_unload() first")
+        if model.engine.lora and not live:
+            raise NotImplementedError("GRPO on a LoRA engine: generation refuses unmerged adapters; merge_and_unload() first, "
+                                      "or model.enable_adapter_decoding() to sample from the live adapters")
         self.loss_type, self.scale_rewards = getattr(a, "loss_type", "dapo"), getattr(a, "scale_rewards", "group")
         if self.loss_type not in LOSS_TYPES or self.scale_rewards not in SCALE_REWARDS:
             raise ValueError(f"loss_type must be one of {LOSS_TYPES} and scale_rewards one of {SCALE_REWARDS}")
@@ -77,6 +80,14 @@ class GRPOTrainer(LLaVATrainer):
         out = self.model.generate_batch(prompts, images=[it.get("images") for it in reps] if with_images else None,
                                         image_sizes=[it.get("image_sizes") for it in reps] if with_images else None, **kw)
         return prompts, [np.asarray(out[f"req_{i}"].generated_tokens, dtype=np.int64) for i in range(len(reps))]
+
+    def _ref_logps(self, batch):
+        """The reference log-probs of a micro-batch: ref_model's, or -- a LoRA policy without one -- the policy's own with the
+        adapters switched off (peft's disable_adapter()): no second copy of the model."""
+        if self.ref_model is not None:
+            return self.ref_model.token_logps(**batch)
+        with self.model.disable_adapter():
+            return self.model.token_logps(**batch)
 
     def _rewards(self, items, prompts, completions):
         G = self.G
@@ -156,7 +167,7 @@ class GRPOTrainer(LLaVATrainer):
                 t2 = time.perf_counter()
                 batch_of = lambda m: {k: m[k] for k in ("input_ids", "attention_mask", "labels", "images", "image_sizes")}
                 old = [model.token_logps(**batch_of(m)) for m in micros] if K > 1 else [None] * len(micros)
-                ref = [self.ref_model.token_logps(**batch_of(m)) for m in micros] if self.beta > 0 else [None] * len(micros)
+                ref = [self._ref_logps(batch_of(m)) for m in micros] if self.beta > 0 else [None] * len(micros)
                 sync()
                 t3 = time.perf_counter()
                 iters = []

@@ -721,6 +721,58 @@ def gemv_w4(x, packed, scales, K, out=None, bias=None, residual=None, out_dtype=
     return out
 
 
+LORA_DECODE_MAX_MODS = 3
+
+
+def lora_down_split(r, K):
+    """K slices rv_lora_down_rows_bf16 uses for adapters of rank r over K input features (a function of (r, K) alone)."""
+    return int(lib.load().rv_lora_down_split(int(r), int(K)))
+
+
+def lora_down_rows(x, adapters, scale, out=None, workspace=None):
+    """t[M, j*r:(j+1)*r] = bf16(scale * x[M,K] @ adapters[j][r,K]^T) for the 1..3 lora_A matrices that share the input x, M <= 32 rows
+    (decode): rv_lora_down_rows_bf16, one call for a fused projection's adapters, K split over workgroups.  Row m of the result is
+    bit-identical for every M."""
+    _chk(x)
+    M, K = x.shape
+    n, r = len(adapters), adapters[0].shape[0]
+    assert 1 <= n <= LORA_DECODE_MAX_MODS and x.stride(1) == 1
+    lda = adapters[0].stride(0)
+    for a in adapters:
+        _chk(a)
+        assert a.shape == (r, K) and a.stride(1) == 1 and a.stride(0) == lda
+    if out is None:
+        out = torch.empty(M, n * r, dtype=BF16, device=x.device)
+    assert out.shape == (M, n * r) and out.stride(1) == 1 and out.dtype == BF16
+    ws = default_workspace(x.device) if workspace is None else workspace
+    ptrs = list(adapters) + [None] * (LORA_DECODE_MAX_MODS - n)
+    lib.call("rv_lora_down_rows_bf16", x, x.stride(0), ptrs[0], ptrs[1], ptrs[2], lda, n, out, out.stride(0), M, r, K, float(scale), ws,
+             ws.numel() * ws.element_size())
+    return out
+
+
+def gemv_lora(x, w, t, mods, out=None, bias=None, residual=None, workspace=None):
+    """out[M,N] = x[M,K] @ w[N,K]^T + sum_j t[:, toff_j:toff_j+r] @ B_j^T on columns [c0_j, c1_j) (+ bias) (+ residual), bf16, M <= 32
+    rows (decode): rv_gemv_lora_bf16.  mods: 1..3 entries (c0, c1, toff, B_j [c1 - c0, r]), ascending and disjoint, boundaries multiples
+    of 64 (c1 may be N).  With every B_j zero the result is gemv(x, w, ...)'s, bit for bit; row m is bit-identical for every M."""
+    _chk(w), _chk(t)
+    N, K = w.shape
+    n = len(mods)
+    assert w.stride(1) == 1 and t.stride(1) == 1 and 1 <= n <= LORA_DECODE_MAX_MODS
+    r, ldb = mods[0][3].shape[1], mods[0][3].stride(0)
+    flat = []
+    for c0, c1, toff, b in mods:
+        _chk(b)
+        assert b.shape == (c1 - c0, r) and b.stride(1) == 1 and b.stride(0) == ldb
+        flat += [b, int(c0), int(c1), int(toff)]
+    flat += [None, 0, 0, 0] * (LORA_DECODE_MAX_MODS - n)
+    M, out, ldr, ws, ws_bytes = _gemv_args(x, N, K, out, bias, residual, BF16, workspace)
+    assert out.dtype == BF16 and t.shape[0] == M
+    lib.call("rv_gemv_lora_bf16", x, x.stride(0), w, w.stride(0), t, t.stride(0), r, n, *flat, ldb, out, out.stride(0), bias, residual, ldr,
+             M, N, K, ws, ws_bytes)
+    return out
+
+
 def _attn_split_args(q, rows, H, hd, keys, out, chunk, scale):
     """What the seven split-KV attention wrappers share (csrc/attn_split.h's launcher checks the same on its side): the default scale,
     `out` (bf16 [rows, H*hd], allocated unless passed in, rows of unit stride) and the fp32 partial buffer for ceil(keys / chunk)

@@ -109,6 +109,10 @@
         # device time, median of 50, warm; (2) the decode step (decode_step + constrain + argmax) with a from_choices constraint of
         # 8 choices of --new tokens, so that every row stays live for the whole loop, beside the plain step on one engine: one untimed
         # pass of both arms, then the arms alternated three times; median ms per step per arm, the plain arm's spread, the added ms
+  python tools/decode_bench.py --lora [--geos ..] [--batches 1,32] [--prompt 704] [--new 40] [--out FILE]
+        # decoding on live LoRA adapters (r = 64): the decode step on merged weights, on the live adapters and on the live adapters
+        # switched off, interleaved on one box; median and p10 / p90 of 20 samples per arm (a sample: the median step of one loop),
+        # live / merged beside the adapters' share of the streamed weight bytes
 
 Per case: prefill ms, median decode ms / token after warm-up, tokens / s, weight + KV bytes per step and the implied HBM rate as a share
 of the 8 TB/s peak.  Random-init weights (the arithmetic does not depend on the values); text-only prompts of --prompt tokens (the
@@ -1158,6 +1162,55 @@ def dola_ab(geo, batches, prompt, new, reps=3):
     return recs
 
 
+def lora_weight_bytes(eng):
+    """Bytes of the adapters a decode step streams: lora_A [r, in] and lora_B [out, r] of every layer's seven modules."""
+    return 2 * sum(eng.lm.view(n).numel() for n in eng.lm.names() if ".lora_" in n)
+
+
+def lora_ab(geo, batches, prompt, new, samples=20, r=64):
+    """The decode step on (a) merged weights, (b) live adapters (engine.adapter_decoding: rv_lora_down_rows_bf16 + rv_gemv_lora_bf16 per
+    fused projection) and (c) live adapters switched off (engine.adapters_off: the skinny route is rv_gemv_bf16 again), interleaved on
+    one box: one untimed pass of every arm, then `samples` rounds of a, b, c; a sample is the median step of one decode loop.  The
+    merged arm is a second engine of the same run after merge_lora(); (b) and (c) share one engine."""
+    lora = dict(r=r, alpha=16, dropout=0.05)
+    live = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0, lora=lora)
+    merged = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0, lora=lora)
+    for eng in (live, merged):
+        for n in eng.lm.names():
+            if n.endswith("lora_B.weight"):                             # peft starts B at zero; the time does not depend on the values
+                eng.lm.view(n).normal_(0.0, 0.02)
+    ad_bytes, wb = lora_weight_bytes(live), weight_bytes(live)
+    merged.merge_lora()
+    live.adapter_decoding = True
+    recs = []
+    for B in batches:
+        ids = np.random.default_rng(0).integers(0, live.vocab, (B, prompt))
+
+        def off():
+            live.adapters_off = True
+            try:
+                return _decode_loop(live, ids, new)
+            finally:
+                live.adapters_off = False
+
+        arms = {"merged": lambda: _decode_loop(merged, ids, new), "live": lambda: _decode_loop(live, ids, new), "off": off}
+        for fn in arms.values():
+            fn()
+        ts = {k: [] for k in arms}
+        for _ in range(samples):
+            for k, fn in arms.items():
+                ts[k].append(float(np.median(fn())))
+        rec = dict(geo=geo, mode="lora_ab", B=B, r=r, prompt=prompt, new_tokens=new, samples=samples, weight_bytes=wb, adapter_bytes=ad_bytes,
+                   adapter_over_weight_bytes=round(ad_bytes / wb, 4), entry_calls_per_layer=dict(merged=4, live=8, off=4))
+        for k in arms:
+            rec[f"{k}_ms_per_step"] = round(float(np.median(ts[k])), 3)
+            rec[f"{k}_ms_p10"], rec[f"{k}_ms_p90"] = round(float(np.percentile(ts[k], 10)), 3), round(float(np.percentile(ts[k], 90)), 3)
+        rec["live_over_merged"] = round(rec["live_ms_per_step"] / rec["merged_ms_per_step"], 3)
+        rec["off_over_merged"] = round(rec["off_ms_per_step"] / rec["merged_ms_per_step"], 3)
+        recs.append(rec)
+    return recs
+
+
 def processors_ab(geo, B, prompt, new, reps=3):
     from radvlm_amd.generation import LogitsProcessors, parse_generate_kwargs
     eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
@@ -1765,6 +1818,7 @@ def main():
     ap.add_argument("--dola", action="store_true")
     ap.add_argument("--dola-shapes", action="store_true")
     ap.add_argument("--constraint", action="store_true")
+    ap.add_argument("--lora", action="store_true")
     ap.add_argument("--shared-shapes", action="store_true")
     ap.add_argument("--share-prefix", action="store_true")
     ap.add_argument("--score", action="store_true")
@@ -1813,6 +1867,10 @@ def main():
         recs = dola_shapes()
     elif a.dola:
         recs = [r for g in a.geos.split(",") for r in dola_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new, reps=min(a.reps, 3))]
+    elif a.lora:
+        batches = a.batches if a.batches != ap.get_default("batches") else "1,32"
+        new = a.new if a.new != ap.get_default("new") else 40
+        recs = [r for g in a.geos.split(",") for r in lora_ab(g, list(map(int, batches.split(","))), a.prompt, new)]
     elif a.constraint:
         batches = a.batches if a.batches != ap.get_default("batches") else "1,32"
         recs = constraint_shapes() + [r for g in a.geos.split(",") for r in constraint_ab(g, list(map(int, batches.split(","))), a.prompt, a.new,

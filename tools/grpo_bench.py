@@ -1,7 +1,7 @@
 """GRPO measurements: JSON lines appended to profiles/grpo_bench.jsonl.
 
   python tools/grpo_bench.py kernel  [--reps 20] [--out FILE]
-  python tools/grpo_bench.py trainer [--geometry llava15_7b] [--prompts 8] [--generations 8] [--new-tokens 128] [--accum 4] [--out FILE]
+  python tools/grpo_bench.py trainer [--geometry llava15_7b] [--prompts 8] [--generations 8] [--new-tokens 128] [--accum 4] [--lora] [--out FILE]
 
 kernel   A/B of rv_cross_entropy (unchanged) against rv_policy_loss_bf16 on the same bf16 logits, in place, at [2048, 32000] and
          [2048, 152064].  Both are two sweeps of the row plus a handful of per-row loads.  The two bit anchors (logp == -loss_rows; the
@@ -12,6 +12,9 @@ kernel   A/B of rv_cross_entropy (unchanged) against rv_policy_loss_bf16 on the 
 trainer  One GRPOTrainer step at a full geometry with random weights: --prompts x --generations, prompts of 128 text tokens and one
          image (704 positions at llava15_7b), --new-tokens sampled tokens, num_iterations 2 so that the old-log-prob pass runs; a first
          step warms up, the second is reported, split into sampling / log-prob / update seconds.
+         --lora: the same step on a LoRA model (r 64, alpha 16, dropout 0.05) that samples from its live adapters
+         (enable_adapter_decoding()), with beta 0.04 and no ref_model, so that the log-prob pass includes the reference taken under
+         disable_adapter().
 """
 import argparse
 import json
@@ -106,7 +109,10 @@ def trainer_step(a):
     geo = GEOMETRIES[a.geometry]
     Config, Model = (LlavaQwenConfig, LlavaQwenForCausalLM) if "qwen" in a.geometry else (LlavaConfig, LlavaLlamaForCausalLM)
     t0 = time.perf_counter()
-    model = Model(Config(geometry=geo), device="cuda:0", init="fast", seed=0).train()
+    lora = dict(r=64, alpha=16, dropout=0.05) if a.lora else None
+    model = Model(Config(geometry=geo, lora=lora), device="cuda:0", init="fast", seed=0).train()
+    if a.lora:
+        model.enable_adapter_decoding()
     torch.cuda.synchronize()
     t_init = time.perf_counter() - t0
     rng = np.random.default_rng(0)
@@ -119,11 +125,11 @@ def trainer_step(a):
     reward = lambda completion_ids, **_: [float(np.mean([t % 2 == 0 for t in c])) if len(c) else 0.0 for c in completion_ids]
     args = SimpleNamespace(per_device_train_batch_size=a.prompts, num_generations=a.generations, max_completion_length=a.new_tokens, max_steps=2,
                            learning_rate=1e-6, weight_decay=0.0, lr_scheduler_type="constant", seed=0, num_iterations=2,
-                           gradient_accumulation_steps=a.accum, max_grad_norm=1.0)
+                           gradient_accumulation_steps=a.accum, max_grad_norm=1.0, beta=0.04 if a.lora else 0.0)
     state = GRPOTrainer(model, args, data, reward).train()
     rec = state["log_history"][-1]
     return [dict(tool="grpo_bench", part="trainer", geometry=a.geometry, prompts=a.prompts, generations=a.generations, new_tokens=a.new_tokens,
-                 prompt_positions=int(model.engine.P) + 128, micro_batches=a.accum, num_iterations=2, init_s=round(t_init, 2),
+                 prompt_positions=int(model.engine.P) + 128, micro_batches=a.accum, num_iterations=2, lora=lora, beta=args.beta, init_s=round(t_init, 2),
                  sampling_s=round(rec["time/sampling_s"], 3), scoring_s=round(rec["time/scoring_s"], 3), logps_s=round(rec["time/logps_s"], 3),
                  update_s=round(rec["time/update_s"], 3), mean_completion_length=rec["completions/mean_length"],
                  peak_mem_gib=round(torch.cuda.max_memory_allocated() / 2 ** 30, 1), device=torch.cuda.get_device_name(0), kernel_src=_src_hash())]
@@ -138,6 +144,7 @@ def main():
     ap.add_argument("--generations", type=int, default=8)
     ap.add_argument("--new-tokens", type=int, default=128)
     ap.add_argument("--accum", type=int, default=4)
+    ap.add_argument("--lora", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grpo_bench.jsonl"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
