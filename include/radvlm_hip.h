@@ -438,7 +438,7 @@ int64_t rv_w4_scale_row_bytes(int K);
 int rv_gemv_w4_bf16(const void* X, int64_t ldx, const void* packed, int64_t ldp, const void* scales, int64_t lds, void* Y, int64_t ldy,
                     const void* bias, const void* residual, int64_t ldr, int M, int N, int K, int out_f32, void* workspace,
                     int64_t ws_bytes, void* stream);
-/* Decoding with live LoRA adapters (lora_decode.hip; reference: a peft LoraLayer in eval mode, y = W x + (alpha / r) B A x, which the
+/* Decoding with live LoRA adapters (the down-projection in lora_decode.hip, the fused product in gemv.hip; reference: a peft LoraLayer in eval mode, y = W x + (alpha / r) B A x, which the
  * reference only ever evaluates merged).  The two calls a fused projection takes at M <= 32 rows; the arithmetic is that of the
  * training path's adapted linear at dropout 0: t rounded once to bf16, already scaled, then one fp32 sum and one store for y. */
 /* T[M, j r .. (j + 1) r) = bf16(scale * X[M, K] A_j[r, K]^T) for the n_mod <= 3 adapters A0, A1, A2 that share the input X (q|k|v,
@@ -450,7 +450,8 @@ int rv_lora_down_rows_bf16(const void* X, int64_t ldx, const void* A0, const voi
                            int64_t ldt, int M, int r, int K, float scale, void* workspace, int64_t ws_bytes, void* stream);
 /* Number of K slices rv_lora_down_rows_bf16 uses (host function, no launch). */
 int rv_lora_down_split(int r, int K);
-/* Y[M, N] = X[M, K] W[N, K]^T + T_j B_j^T (+ bias[N]) (+ residual[M, N]), bf16 Y, 1 <= M <= 32: rv_gemv_bf16 with the adapter riding it.
+/* Y[M, N] = X[M, K] W[N, K]^T + T_j B_j^T (+ bias[N]) (+ residual[M, N]), bf16 Y, 1 <= M <= 32: rv_gemv_bf16 with the adapter riding it
+ * (an instantiation of rv_gemv_bf16's kernel, behind the same launch routine and split-K combine).
  * Module j < n_mod owns the columns [col0_j, col1_j) of Y, reads its t from columns [toff_j, toff_j + r) of T[M, ldt] and its
  * B_j[col1_j - col0_j, r] from its own pointer (rows of ldb elements); ranges ascend and do not overlap, col0_j is a multiple of 64
  * and col1_j is a multiple of 64 or N; columns outside every range get no adapter.  The W part takes rv_gemv_bf16's K split

@@ -52,6 +52,11 @@ DEVINL float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+DEVINL double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 DEVINL float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -111,5 +116,7 @@ static inline unsigned rv_dropout_thr16(float p) { return (unsigned)((double)p *
 // host side of every entry point: its `void* stream` argument as a HIP stream, and the block count of a grid
 #define ST ((hipStream_t)stream)
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool lora_rank_ok(int r) { return r >= 8 && r <= 64 && !(r & 7); }     // the ranks the training path accepts
 
 static inline int rv_check_launch() { return hipGetLastError() == hipSuccess ? RV_OK : RV_ERR_LAUNCH; }

@@ -1,6 +1,6 @@
 // The skinny NT GEMM of decoding for gfx950, Y[M,N] = X[M,K] W[N,K]^T of one generated token per sequence (M = batch, 1..32 rows), in
-// its three weight formats -- bf16, int8 rows (w8) and MXFP4 (w4) -- with the two row quantisers that write the packed copies.  One
-// split-K combine kernel and one host launch routine serve all three.
+// its three weight formats -- bf16, int8 rows (w8) and MXFP4 (w4) -- with the two row quantisers that write the packed copies, and the
+// bf16 format with a live LoRA adapter (Y = X W^T + T_j B_j^T).  One split-K combine kernel and one host launch routine serve all four.
 // Reductions use a fixed order that depends on the weight's shape only (N, K) -- never on M, on other rows or on timing -- and no
 // atomics: a row's result is bit-identical whatever else shares its launch.  The quantised kernels rebuild in registers the bf16 weight
 // W^ their quantiser left in place, with the bf16 kernel's K steps per wave, k-to-lane assignment per MFMA, ascending step order per
@@ -46,18 +46,38 @@ DEVINL bf16x8 dq8(unsigned lo, unsigned hi, float s) {
     return r;
 }
 
-// The scale pointer is a trailing parameter pack, empty for bf16.  It exists for one reason: the bf16 instantiation keeps the parent
-// kernel's exact parameter list, and with it the parent's device code instruction for instruction (an extra pointer, or the body moved
-// into an inlined helper, changed its register allocation).  W8 = "a scale was passed".
-DEVINL const float* gv_scale() { return nullptr; }
-DEVINL const float* gv_scale(const float* p) { return p; }
+// The adapter of rv_gemv_lora_bf16, Y = X W^T + T_j B_j^T: after the bf16 K loop, wave 0 of slice 0 runs ceil(r / 32) more steps into the
+// same accumulators with T in X's place (columns toff .. toff + r of T) and the block's rows of B_j in W's.  Every product of a zero B
+// is a zero, so with B = 0 the accumulators, and every bit of Y, are rv_gemv_bf16's.  T and B are a few KB, read by every column block:
+// plain loads, L2-resident.  A 64-column block lies in at most one module (boundaries are multiples of 64; the entry point checks), so
+// the module is block-uniform.
+constexpr int GV_MODS = 3;
+struct GvLora {
+    const bf16* T;
+    long ldt;
+    const bf16* b[GV_MODS];
+    int c0[GV_MODS], c1[GV_MODS], toff[GV_MODS];
+    int n_mod;
+    long ldb;
+    int r;
+};
+
+// What the weight operand needs beyond W and ldw is a trailing parameter pack: empty for bf16, the row scales (const float*) for int8,
+// a GvLora for bf16 with a live adapter.  It is a pack, not a defaulted parameter, for one reason: the bf16 instantiation keeps the
+// parent kernel's exact parameter list, and with it the parent's device code instruction for instruction (an extra pointer, or the bf16
+// body moved into an inlined helper, changed its register allocation).  The adapter kind therefore adds its steps under `if constexpr`
+// after the bf16 K loop, which it shares untouched; gemv_w4_kernel, whose parameter list differs, restates the prologue and epilogue.
+template <typename... S> struct gv_kind { static constexpr bool w8 = false, lora = false; };
+template <> struct gv_kind<const float*> { static constexpr bool w8 = true, lora = false; };
+template <> struct gv_kind<GvLora> { static constexpr bool w8 = false, lora = true; };
+template <typename A> DEVINL const A& gv_arg(const A& a) { return a; }
 
 template <int MT, typename... S>
 __global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W, long ldw, int M, int N,
                                                    int K, int split, float* __restrict__ part, void* __restrict__ Y, long ldy,
                                                    const bf16* __restrict__ bias, const bf16* __restrict__ R, long ldr, int out_f32,
-                                                   S... scale_arg) {
-    constexpr bool W8 = sizeof...(S) == 1;
+                                                   S... kind_arg) {
+    constexpr bool W8 = gv_kind<S...>::w8, LORA = gv_kind<S...>::lora;
     __shared__ float red[4][MT * 16][GV_COLS];
     const int lane = lane_id(), w = wave_id();
     const int c = lane & 15, kg = lane >> 4;
@@ -91,7 +111,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ X, l
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (W8) {
-        const float* __restrict__ wscale = gv_scale(scale_arg...);
+        const float* __restrict__ wscale = gv_arg(kind_arg...);
         float sc[4];
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) sc[ct] = n_ok[ct] ? wscale[n0 + ct * 16 + c] : 0.f;
@@ -169,6 +189,37 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ X, l
                 for (int rt = 0; rt < MT; ++rt)
 #pragma unroll
                     for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = mfma16(xf[u][rt], wf[u][ct], acc[rt][ct]);
+        }
+    }
+    if constexpr (LORA) {
+        const GvLora& mods = gv_arg(kind_arg...);
+        if (unit == 0) {                                                 // wave-uniform: the adapter's steps, after all of this wave's W steps
+            int j = -1;
+#pragma unroll
+            for (int i = 0; i < GV_MODS; ++i)
+                if (i < mods.n_mod && n0 >= mods.c0[i] && n0 < mods.c1[i]) j = i;
+            if (j >= 0) {
+                const bf16* __restrict__ Bj = j == 0 ? mods.b[0] : (j == 1 ? mods.b[1] : mods.b[2]);
+                const int c0 = j == 0 ? mods.c0[0] : (j == 1 ? mods.c0[1] : mods.c0[2]);
+                const int c1 = j == 0 ? mods.c1[0] : (j == 1 ? mods.c1[1] : mods.c1[2]);
+                const int toff = j == 0 ? mods.toff[0] : (j == 1 ? mods.toff[1] : mods.toff[2]);
+                for (int k = 0; k < mods.r; k += 32) {
+                    const bool kin = k + kg * 8 < mods.r;                // r % 8 == 0
+                    bf16x8 bfr[4], tf[MT];
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        const int n = n0 + ct * 16 + c;
+                        bfr[ct] = (kin && n < c1) ? *(const bf16x8*)(Bj + (long)(n - c0) * mods.ldb + k + kg * 8) : zero8();
+                    }
+#pragma unroll
+                    for (int rt = 0; rt < MT; ++rt)
+                        tf[rt] = (kin && m_ok[rt]) ? *(const bf16x8*)(mods.T + (long)(rt * 16 + c) * mods.ldt + toff + k + kg * 8) : zero8();
+#pragma unroll
+                    for (int rt = 0; rt < MT; ++rt)
+#pragma unroll
+                        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = mfma16(tf[rt], bfr[ct], acc[rt][ct]);
+                }
+            }
         }
     }
 #pragma unroll
@@ -479,7 +530,7 @@ __global__ __launch_bounds__(256) void quantize_rows_mxfp4_kernel(bf16* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// The one launch routine behind the three rv_gemv_* entry points: the checks every format shares, the K split and its workspace, the
+// The one launch routine behind the four rv_gemv_* entry points: the checks every format shares, the K split and its workspace, the
 // grid, the row-tile count MT, the combine.  An entry point passes whether its own weight operand is acceptable and
 // launch(MT as an integral_constant, grid, split, part), which starts its kernel: the kernels' parameter lists differ.
 template <typename Launch>
@@ -521,6 +572,40 @@ extern "C" int rv_gemv_bf16(const void* X, int64_t ldx, const void* W, int64_t l
                        [&](auto mt, dim3 grid, int split, float* part) {
                            hipLaunchKernelGGL(gemv_kernel<mt()>, grid, dim3(256), 0, ST, (const bf16*)X, (long)ldx, (const bf16*)W, (long)ldw, M, N,
                                               K, split, part, Y, (long)ldy, (const bf16*)bias, (const bf16*)residual, (long)ldr, out_f32);
+                       });
+}
+
+extern "C" int rv_gemv_lora_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* T, int64_t ldt, int r, int n_mod,
+                                 const void* B0, int col0_0, int col1_0, int toff0, const void* B1, int col0_1, int col1_1, int toff1, const void* B2,
+                                 int col0_2, int col1_2, int toff2, int64_t ldb, void* Y, int64_t ldy, const void* bias, const void* residual,
+                                 int64_t ldr, int M, int N, int K, void* workspace, int64_t ws_bytes, void* stream) {
+    // its own checks: the rank, T / B alignment and strides, then the module table; gemv_launch makes the rest
+    if (!T || !lora_rank_ok(r) || n_mod < 1 || n_mod > GV_MODS || (ldt & 7) || (ldb & 7) || ldb < r || !aligned16(X) || !aligned16(W) ||
+        !aligned16(T))
+        return RV_ERR_ARG;
+    const void* b[GV_MODS] = {B0, B1, B2};
+    const int c0[GV_MODS] = {col0_0, col0_1, col0_2}, c1[GV_MODS] = {col1_0, col1_1, col1_2}, to[GV_MODS] = {toff0, toff1, toff2};
+    GvLora mods;
+    mods.T = (const bf16*)T, mods.ldt = (long)ldt, mods.n_mod = n_mod, mods.ldb = (long)ldb, mods.r = r;
+    int prev = 0;
+    for (int j = 0; j < GV_MODS; ++j) {
+        if (j < n_mod) {
+            // ascending, disjoint column ranges; a boundary inside Y is a multiple of 64 (a column block never straddles two modules)
+            if (!b[j] || !aligned16(b[j]) || c0[j] < prev || c1[j] <= c0[j] || c1[j] > N || (c0[j] % GV_COLS) || (c1[j] != N && (c1[j] % GV_COLS)) ||
+                to[j] < 0 || (to[j] & 7) || (int64_t)to[j] + r > ldt)
+                return RV_ERR_ARG;
+            prev = c1[j];
+        }
+        mods.b[j] = (const bf16*)(j < n_mod ? b[j] : b[0]);
+        mods.c0[j] = j < n_mod ? c0[j] : 0;
+        mods.c1[j] = j < n_mod ? c1[j] : 0;
+        mods.toff[j] = j < n_mod ? to[j] : 0;
+    }
+    return gemv_launch(W && !(ldw & 7) && ldw >= K, X, ldx, Y, ldy, bias, residual, ldr, M, N, K, 0, workspace, ws_bytes, stream,
+                       [&](auto mt, dim3 grid, int split, float* part) {
+                           hipLaunchKernelGGL((gemv_kernel<mt(), GvLora>), grid, dim3(256), 0, ST, (const bf16*)X, (long)ldx, (const bf16*)W,
+                                              (long)ldw, M, N, K, split, part, Y, (long)ldy, (const bf16*)bias, (const bf16*)residual, (long)ldr,
+                                              0, mods);
                        });
 }
 

@@ -10,12 +10,6 @@
 
 constexpr int LS_U = 8;           // loads a thread keeps in flight per sweep step
 
-DEVINL double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the row maximum, known to every thread on return; redm: 4 floats of LDS
 DEVINL float ls_row_max(const float* __restrict__ row, int n, float* redm) {
     const int tid = threadIdx.x;

@@ -2,6 +2,7 @@
 // splice, CLIP embeddings, transposes, reductions, AdamW.  All loads/stores are 16-byte vectors (8 bf16 per lane);
 // reductions are wave shuffles + one LDS hop; no atomics (results are run-to-run deterministic).
 // Reference call sites are listed per entry point in include/radvlm_hip.h.
+#include "ce_rows.h"            // ld8 / st8 and the cross-entropy row sweeps, shared with policy.hip
 #include "common.h"
 #include "radvlm_hip.h"
 
@@ -9,17 +10,6 @@ namespace {
 
 constexpr int TPB = 256;
 
-DEVINL void ld8(const bf16* p, float (&v)[8]) {
-    const bf16x8 t = *(const bf16x8*)p;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = bf2f(t[i]);
-}
-DEVINL void st8(bf16* p, const float (&v)[8]) {
-    bf16x8 t;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = f2bf(v[i]);
-    *(bf16x8*)p = t;
-}
 DEVINL float rbf(float x) { return bf2f(f2bf(x)); }  // round through bf16
 
 // The row tiling of the norm kernels: a 256-thread block covers a row of d <= 8192 elements (d % 8 == 0) in four passes of 8 elements
@@ -349,70 +339,22 @@ __global__ void dropout_kernel(const bf16* x, bf16* y, long n8, unsigned thr16, 
 }
 
 // ------------------------------------------------------------------------------------------------ cross entropy
-__global__ __launch_bounds__(TPB) void cross_entropy_kernel(const bf16* logits, long ld, const int64_t* labels, float* loss_rows,
-                                                            bf16* dlogits, long ld_d, int V, float inv_count) {
-    // V need not be a multiple of 8 (a vocabulary grown by a few special tokens): rows are padded to ld >= ceil8(V) columns, the
-    // pad columns are ignored on read (-inf) and their gradient is written as zero.
+// The row sweeps, and the note on the in-place call (dlogits == logits), are in ce_rows.h.
+__global__ __launch_bounds__(CE_TPB) void cross_entropy_kernel(const bf16* logits, long ld, const int64_t* labels, float* loss_rows,
+                                                               bf16* dlogits, long ld_d, int V, float inv_count) {
     __shared__ float red[8];
     const long row = blockIdx.x;
     const int64_t label = labels[row];
     const bf16* lr = logits + row * ld;
-    const int nvec = (V + 7) / 8;
-    // The target logit is read BEFORE any dlogits store: the engine calls this kernel in place (dlogits == logits), and other
-    // waves of the block start overwriting the row as soon as they pass the barrier below.
-    const float target = (label >= 0 && label < V) ? bf2f(lr[label]) : 0.f;
+    const float target = (label >= 0 && label < V) ? bf2f(lr[label]) : 0.f;     // before any dlogits store
     if (label < 0 || label >= V) {  // ignore_index; labels >= V never index the row (the host side rejects them before launch)
         if (threadIdx.x == 0) loss_rows[row] = 0.f;
-        if (dlogits) {
-            const float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = threadIdx.x; i < nvec; i += TPB) st8(dlogits + row * ld_d + i * 8, z);
-        }
+        if (dlogits) ce_row_zero(dlogits + row * ld_d, V);
         return;
     }
-    float m = -INFINITY, s = 0.f;
-    for (int i = threadIdx.x; i < nvec; i += TPB) {
-        float v[8];
-        ld8(lr + i * 8, v);
-        if (i * 8 + 8 > V) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) if (i * 8 + j >= V) v[j] = -INFINITY;
-        }
-        float vm = v[0];
-#pragma unroll
-        for (int j = 1; j < 8; ++j) vm = fmaxf(vm, v[j]);
-        const float mn = fmaxf(m, vm);
-        // Nothing finite seen yet (masked logits: a run of -inf that is this thread's first vector): shift by 0, not by -inf, so that
-        // every term is exp(-inf) = 0 and not exp(-inf - -inf) = NaN, which s would keep once m turns finite.
-        const float sh = mn == -INFINITY ? 0.f : mn;
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a += __expf(v[j] - sh);
-        s = s * __expf(m - sh) + a;
-        m = mn;
-    }
-    // block combine of (m, s)
-    const float wm = wave_max(m);
-    s = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - wm));
-    if (lane_id() == 0) { red[threadIdx.x >> 6] = wm; red[4 + (threadIdx.x >> 6)] = s; }
-    __syncthreads();
-    const float gm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float gs = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) gs += (red[i] == -INFINITY) ? 0.f : red[4 + i] * __expf(red[i] - gm);
-    const float lse = gm + __logf(gs);
+    const float lse = ce_row_lse(lr, V, red);
     if (threadIdx.x == 0) loss_rows[row] = lse - target;
-    if (dlogits) {
-        for (int i = threadIdx.x; i < nvec; i += TPB) {
-            float v[8], o[8];
-            ld8(lr + i * 8, v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float p = __expf(v[j] - lse);
-                o[j] = (i * 8 + j < V) ? (p - ((int64_t)(i * 8 + j) == label ? 1.f : 0.f)) * inv_count : 0.f;
-            }
-            st8(dlogits + row * ld_d + i * 8, o);
-        }
-    }
+    if (dlogits) ce_row_grad(lr, dlogits + row * ld_d, V, label, lse, inv_count);
 }
 
 __global__ __launch_bounds__(1024) void sum_f32_kernel(const float* in, long n, float scale, float* out) {
@@ -819,7 +761,7 @@ extern "C" int rv_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, v
 extern "C" int rv_cross_entropy(const void* logits, int64_t ld, const int64_t* labels, float* loss_rows, void* dlogits, int64_t ld_d,
                                 int rows, int V, float inv_count, void* stream) {
     if (!logits || !labels || !loss_rows || rows <= 0 || V <= 0 || (ld & 7) || ld < ((V + 7) & ~7) || (dlogits && ((ld_d & 7) || ld_d < ((V + 7) & ~7)))) return RV_ERR_ARG;
-    hipLaunchKernelGGL(cross_entropy_kernel, dim3(rows), dim3(TPB), 0, ST, (const bf16*)logits, (long)ld, labels, loss_rows, (bf16*)dlogits, (long)ld_d, V, inv_count);
+    hipLaunchKernelGGL(cross_entropy_kernel, dim3(rows), dim3(CE_TPB), 0, ST, (const bf16*)logits, (long)ld, labels, loss_rows, (bf16*)dlogits, (long)ld_d, V, inv_count);
     return rv_check_launch();
 }
 extern "C" int rv_sum_f32(const float* in, int64_t n, float scale, float* out, void* stream) {

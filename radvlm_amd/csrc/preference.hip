@@ -14,12 +14,6 @@ constexpr int PAIR_TPB = 128;          // wave 0 sums the chosen answer, wave 1 
 enum { LOSS_SIGMOID = 0, LOSS_HINGE = 1, LOSS_IPO = 2 };
 enum { PL_PI_C = 0, PL_PI_R, PL_H, PL_LOSS, PL_REWARD_C, PL_REWARD_R, PL_SUM_C, N_PLANES };
 
-DEVINL double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Scored token j lives in row j (row_idx NULL) or row_idx[j]; a row outside [0, rows) is never touched.
 DEVINL long row_of(const int32_t* row_idx, int j) { return row_idx ? (long)row_idx[j] : (long)j; }
 

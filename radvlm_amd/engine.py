@@ -864,12 +864,17 @@ class LlavaEngine:
     # The same switch for the MXFP4 copy (quantize_decoder_("mxfp4")): the A/B arm of tools/decode_bench.py --w4.
     w4_decode = True
 
+    def _takes_skinny(self, w, rows, skinny=False):
+        """Does a decode product of `rows` rows with the weight w take the skinny kernel?  skinny=True: whatever the row count
+        (<= ops.GEMV_MAX_M, which the kernel enforces) and the weight's height."""
+        max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
+        return skinny or rows <= min(max_m, ops.GEMV_MAX_M)
+
     def _decode_linear(self, x, w, bias=None, residual=None, out_dtype=BF16, wq=None, skinny=False):
         """wq: the weight's quantised copy (packed, scales) from _layer_wq, int8 or MXFP4 by its dtype, or None.
         skinny: the skinny kernel whatever the row count (<= ops.GEMV_MAX_M) and the weight's height -- verify_step, whose rows must
         carry the bits of the one-row decode step, which always takes that kernel."""
-        max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
-        if not skinny and x.shape[0] > min(max_m, ops.GEMV_MAX_M):
+        if not self._takes_skinny(w, x.shape[0], skinny):
             return ops.gemm_nt(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
         if wq is None:
             return ops.gemv(x, w, bias=bias, residual=residual, out_dtype=out_dtype)
@@ -966,8 +971,7 @@ class LlavaEngine:
         for bit (the kernel's contract), so the two adapter launches are skipped."""
         if not self.lora:
             return self._decode_linear(x, w, bias=bias, residual=residual, wq=wq, skinny=skinny)
-        max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
-        if not skinny and x.shape[0] > min(max_m, ops.GEMV_MAX_M):
+        if not self._takes_skinny(w, x.shape[0], skinny):
             return self._lora_linear(x, w, i, mods, {}, residual=residual, bias=bias, p=0.0)
         if self.adapters_off:
             return ops.gemv(x, w, bias=bias, residual=residual)
@@ -1152,8 +1156,7 @@ class LlavaEngine:
         of sequence b -- and the mature rows carry the bits of the call without taps (tap_lm_head)."""
         w = self.W("lm_head.weight")
         B, n = hN.shape[0], len(hs)
-        max_m = self.gemv_max_m_wide if w.shape[0] >= 65536 else self.gemv_max_m
-        if self.tap_lm_head == "stacked" and B <= min(max_m, ops.GEMV_MAX_M) and (1 + n) * B <= ops.GEMV_MAX_M:
+        if self.tap_lm_head == "stacked" and self._takes_skinny(w, B) and (1 + n) * B <= ops.GEMV_MAX_M:
             both = self._decode_linear(torch.cat([hN] + list(hs), 0), w, out_dtype=torch.float32, skinny=True)
             return both[:B], both[B:].view(n, B, -1)[:, :, :self.vocab]
         logits = self._decode_linear(hN, w, out_dtype=torch.float32)

@@ -592,7 +592,8 @@ def test_kv_append_refuses_bad_arguments():
 
 @pytest.mark.parametrize("kernel", ["bf16", "w8", "w4"])
 def test_gemv_refuses_bad_arguments(kernel):
-    """The three entry points share one argument check (gemv.hip's gemv_launch): each refuses the same six bad argument sets."""
+    """The three entry points share one argument check (gemv.hip's gemv_launch; rv_gemv_lora_bf16, the fourth behind it, is held to
+    its refusals in test_lora_decode_kernels_gpu.py): each refuses the same six bad argument sets."""
     ops = _ops()
     N, K = 64, 2056
     split = ops.gemv_split(N, K)

@@ -1,4 +1,4 @@
-"""Host tests of live-adapter decoding: the C ABI of csrc/lora_decode.hip as declared, bound and exported, the K split of the
+"""Host tests of live-adapter decoding: the C ABI of csrc/lora_decode.hip and of gemv.hip's adapter entry as declared, bound and exported, the K split of the
 down-projection (a host function), and the generation parsers' refusal, which now names the switch as well."""
 import os
 import re

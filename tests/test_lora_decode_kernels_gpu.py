@@ -1,4 +1,4 @@
-"""GPU tests of the live-adapter decode kernels (radvlm_amd/csrc/lora_decode.hip): rv_lora_down_rows_bf16 and rv_gemv_lora_bf16.
+"""GPU tests of the live-adapter decode kernels : rv_lora_down_rows_bf16 (radvlm_amd/csrc/lora_decode.hip) and rv_gemv_lora_bf16 (gemv.hip).
 P1  with B = 0 the fused kernel gives rv_gemv_bf16's bits;  P2  a row's bits do not depend on M (both kernels);
 P3  both against a float64 product of the bf16 inputs, test_gemv_matches_fp32_matmul's gate;  P4  bad arguments launch nothing.
 The shapes are the smallest at which each mechanism can go wrong:

@@ -1201,7 +1201,8 @@ def lora_ab(geo, batches, prompt, new, samples=20, r=64):
             for k, fn in arms.items():
                 ts[k].append(float(np.median(fn())))
         rec = dict(geo=geo, mode="lora_ab", B=B, r=r, prompt=prompt, new_tokens=new, samples=samples, weight_bytes=wb, adapter_bytes=ad_bytes,
-                   adapter_over_weight_bytes=round(ad_bytes / wb, 4), entry_calls_per_layer=dict(merged=4, live=8, off=4))
+                   adapter_over_weight_bytes=round(ad_bytes / wb, 4), entry_calls_per_layer=dict(merged=4, live=8, off=4),
+                   build=os.path.basename(os.environ.get("RADVLM_HIP_LIB", "default")))
         for k in arms:
             rec[f"{k}_ms_per_step"] = round(float(np.median(ts[k])), 3)
             rec[f"{k}_ms_p10"], rec[f"{k}_ms_p90"] = round(float(np.percentile(ts[k], 10)), 3), round(float(np.percentile(ts[k], 90)), 3)

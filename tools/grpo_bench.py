@@ -88,7 +88,8 @@ def kernel_ab(reps):
                 if rep >= 2:
                     times[name].append(e0.elapsed_time(e1))
         nbytes = 3 * rows * V * 2                        # two reads and one write of the row
-        rec = dict(tool="grpo_bench", part="kernel", rows=rows, V=V, reps=reps, bytes=nbytes, device=torch.cuda.get_device_name(0), kernel_src=_src_hash())
+        rec = dict(tool="grpo_bench", part="kernel", rows=rows, V=V, reps=reps, bytes=nbytes, device=torch.cuda.get_device_name(0),
+                   build=os.path.basename(os.environ.get("RADVLM_HIP_LIB", "default")), kernel_src=_src_hash())
         for name, ts in times.items():
             rec[name] = dict(ms_median=round(_median(ts), 4), ms_min=round(min(ts), 4), ms_max=round(max(ts), 4),
                              tb_per_s=round(nbytes / _median(ts) / 1e9, 3), ms_all=[round(t, 4) for t in ts])
