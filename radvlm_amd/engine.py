@@ -13,6 +13,7 @@ Reference semantics followed (paths under /root/reference/finetuning/llava):
   optimizer  : AdamW groups of LLaVATrainer.create_optimizer train/llava_trainer.py:356-433
   grad sync  : what DDP would do for the reference: mean over ranks of per-rank mean losses
 """
+import contextlib
 import math
 
 import numpy as np
@@ -795,6 +796,18 @@ class LlavaEngine:
         self.last_logits = logits_out
         return loss
 
+    @contextlib.contextmanager
+    def _eval_form(self, *also):
+        """Eval form: the adapters' input dropout is off inside the block (module.eval() in the reference) and lora_p is put back after
+        it, with the attributes named in `also` ("lora_step", "ctx") where the block's forward pass writes them."""
+        saved = dict({a: getattr(self, a) for a in also}, lora_p=getattr(self, "lora_p", 0.0))
+        self.lora_p = 0.0
+        try:
+            yield
+        finally:
+            for name, value in saved.items():
+                setattr(self, name, value)
+
     def forward_embeds(self, inputs_embeds, attention_mask=None, labels=None):
         """The decoder + head on caller-supplied input embeddings -- the call form of LlavaLlamaForCausalLM.forward with `inputs_embeds`
         given (llava_llama.py:69-120: the multimodal splice is skipped and super().forward runs on the embeddings; what generate() and
@@ -822,13 +835,9 @@ class LlavaEngine:
             pos = self._dev((np.arange(B * S, dtype=np.int32) % S)[valid])
             x = x[self._dev(valid_idx.astype(np.int64))].contiguous()
         geom = dict(B=B, S=S, s_pad=s_pad, lens=lens, cu=cu, pos=pos, cs=self.rope_table(S))
-        saved = (self.lora_step, getattr(self, "lora_p", 0.0))
-        self.lora_p = 0.0                    # eval form: the adapters' input dropout is off (module.eval() in the reference)
-        try:
+        with self._eval_form("lora_step"):
             for i in range(L):
                 x, _ = self._layer_forward(i, x, geom)
-        finally:
-            self.lora_step, self.lora_p = saved
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         lf = ops.gemm_nt(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
         if valid_idx is not None:
@@ -1036,6 +1045,41 @@ class LlavaEngine:
             raise NotImplementedError(f"{what} on an int8 KV cache: only prefill() and the plain decode_step() read it; "
                                       "use a bf16 cache (kv_cache_dtype=None)")
 
+    @staticmethod
+    def _slot_rows(slots, B, cache, ok=True):
+        """slots= of prefill() and extend() as an int64 array: one distinct row of `cache` per prompt (ok: the caller's own count check)."""
+        seq = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if not ok or seq.shape[0] != B or np.unique(seq).shape[0] != B or (seq < 0).any() or (seq >= cache.B).any():
+            raise ValueError(f"slots must be {B} distinct indices into the cache's {cache.B} sequences, got {seq.tolist()}")
+        return seq
+
+    def _tokens_dev(self, tokens):       # the token ids of a cached step (int, host or device) as a device int32 tensor
+        return tokens.to(self.device, torch.int32) if torch.is_tensor(tokens) else self._dev(np.asarray(tokens, dtype=np.int32))
+
+    def _head_logits(self, x, skinny=False, tapped=None):
+        """The tail of a generation entry point: final norm, lm_head in fp32, the vocabulary's columns -> fp32 [rows, vocab].  tapped
+        (DoLa: the tapped rows, in tap_layers' order): (those logits, the candidates' fp32 [n, rows, vocab]) through _tap_logits."""
+        hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
+        if tapped is None:
+            return self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32, skinny=skinny)[:, :self.vocab]
+        logits, cand = self._tap_logits(hN, tapped)
+        return logits[:, :self.vocab], cand
+
+    def _cached_layer(self, i, x, cs, pos, attend, skinny=False):
+        """Decoder layer i of the KV-cached path on the rows x [M, d] -> [M, d]: RMSNorm, fused q|k|v (_decode_lora_linear: quantised
+        copies and live adapters ride there), RoPE in place at the rows' positions `pos` from the table cs, attend(i, qkv) -- the
+        entry point's own K|V write (qkv[:, d:]) and attention of qkv[:, :d] over the cached keys -- then o_proj + residual, RMSNorm,
+        gate|up, SwiGLU, down + residual.  skinny: as in _decode_linear.  Every statement makes a new tensor: x is left as it is."""
+        d, F = self.l["d"], self.l["ffn"]
+        lv, wq = self._layer_views(i), self._layer_wq(i)
+        h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
+        qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"), skinny=skinny)
+        ops.rope_inplace(qkv, cs, 1, self.l["heads"] + self.Hkv, self.hd, 1, 1, positions=pos)
+        x_mid = self._decode_lora_linear(attend(i, qkv), lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"), skinny=skinny)
+        h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
+        act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu"), skinny=skinny), F)
+        return self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"), skinny=skinny)
+
     def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0, cache=None, slots=None, kv_dtype=None,
                 tap_layers=None):
         """The prompt pass of generation: multimodal splice (plan / encode_images, as in forward) and every decoder layer in the packed
@@ -1082,9 +1126,7 @@ class LlavaEngine:
             L_max = int(lens.max()) + int(max_new_tokens)
             seq = np.arange(B)
         else:
-            seq = np.asarray(slots, dtype=np.int64).reshape(-1)
-            if seq.shape[0] != B or np.unique(seq).shape[0] != B or (seq < 0).any() or (seq >= cache.B).any():
-                raise ValueError(f"slots must be {B} distinct indices into the cache's {cache.B} sequences, got {seq.tolist()}")
+            seq = self._slot_rows(slots, B, cache)
             L_max = cache.L_max
             if (lens + int(max_new_tokens) > L_max).any():
                 raise ValueError(f"the prompts need {int(lens.max()) + int(max_new_tokens)} positions, the cache holds {L_max}")
@@ -1098,9 +1140,7 @@ class LlavaEngine:
             cache = self.new_kv_cache(B, L_max, kv_dtype)           # seq = 0 .. B - 1: filled like a passed cache's slots
         if taps is not None:
             tap_rows, tapped = self._dev((cu[1:] - 1).astype(np.int32)), {}
-        saved_p = getattr(self, "lora_p", 0.0)
-        self.lora_p = 0.0                    # live adapters (adapter_decoding): eval form, as in forward_embeds; lora_step is only read
-        try:
+        with self._eval_form():              # live adapters (adapter_decoding): as in forward_embeds; lora_step is only read
             for i in range(L):
                 if taps is not None and i in taps:
                     tapped[i] = ops.gather_rows(tap_rows, d, x)
@@ -1115,21 +1155,13 @@ class LlavaEngine:
                 else:
                     kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:])
                 del acts
-        finally:
-            self.lora_p = saved_p
-        last = self._dev((cu[1:] - 1).astype(np.int32))
-        hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
-        if taps is None:
-            logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
-        else:
-            logits, cand = self._tap_logits(hN, [tapped[c] for c in taps])
+        x = ops.gather_rows(self._dev((cu[1:] - 1).astype(np.int32)), d, x)       # every sequence's last prompt row
+        out = self._head_logits(x, tapped=taps and [tapped[c] for c in taps])
         if cache is None:
             cache = KVCache(layers, lens, L_max)
         else:
             cache.lens[seq] = lens
-        if taps is not None:
-            return cache, logits[:, :self.vocab], cand
-        return cache, logits[:, :self.vocab]
+        return (cache, out) if taps is None else (cache, *out)
 
     # lm_head of a tapped step: "stacked" puts [mature; candidates] into one skinny launch (skinny=True: a row's bits do not depend on
     # the row count) where that keeps the mature rows' bits, i.e. where the mature rows alone take the skinny kernel today and
@@ -1165,8 +1197,8 @@ class LlavaEngine:
 
     def decode_step(self, cache, tokens, beams=None, shared=None, tap_layers=None):
         """One generated token per sequence: tokens [B] (int, host or device) at position cache.lens[b] -> fp32 logits [B, vocab].
-        Per layer: RMSNorm, q|k|v projection, RoPE at the token's position, cache append, decode attention over the sequence's cached
-        keys, o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual; then the final norm and the lm_head (fp32 scores).
+        Every layer is _cached_layer at the token's position, its attention step the cache append and decode attention over the
+        sequence's cached keys; then the final norm and the lm_head (_head_logits).
         beams (beam search, generation.beam_generate): .prefix_row / .prefix_len (int32 [B] device) and .tail_src (int32 [B, >=
         .tail_cols] device, or None).  Row r still appends its K|V at position cache.lens[r] of its OWN row, but reads key position j
         from row prefix_row[r] while j < prefix_len[r] and from row tail_src[r, j - prefix_len[r]] after it (rv_attn_decode_beam_bf16,
@@ -1196,8 +1228,7 @@ class LlavaEngine:
                 raise ValueError(f"the tile table has {shared.c0.numel()} rows, the cache {cache.B}")
             if not self._use_shared(shared, cache):
                 shared = None
-        l = self.l
-        d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
+        d, H, L = self.l["d"], self.l["heads"], self.l["layers"]
         hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
         B = cache.B
         kv8 = getattr(cache, "dtype", "bf16") == "int8"
@@ -1205,49 +1236,38 @@ class LlavaEngine:
             self._refuse_int8(cache, "decode_step(beams=...)")
         if (cache.lens >= cache.L_max).any():
             raise ValueError(f"the KV cache is full ({cache.L_max} slots per sequence)")
-        tok = tokens.to(self.device, torch.int32) if torch.is_tensor(tokens) else self._dev(np.asarray(tokens, dtype=np.int32))
+        tok = self._tokens_dev(tokens)
         assert tok.numel() == B
         pos = self._dev(cache.lens.astype(np.int32))
         kv_len = self._dev((cache.lens + 1).astype(np.int32))
         cs = self.rope_table(cache.L_max)
+
+        def attend(i, qkv):
+            if kv8 and cache.scales is not None:
+                kvq = (cache.layers[i], cache.scales[i])
+                ops.kv_append_q8(qkv[:, d:], pos, Hkv, hd, cache=kvq)
+                return ops.attn_decode_kv8(qkv[:, :d], kvq, kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            if kv8:         # the reference arm: the dequantised values as bf16, read by the bf16 kernel
+                ops.kv_append_q8(qkv[:, d:], pos, Hkv, hd, xhat=cache.layers[i])
+                return ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            if shared is not None:
+                ops.kv_append(qkv[:, d:], cache.layers[i], pos)
+                return ops.attn_decode_shared(qkv[:, :d], cache.layers[i], kv_len, shared.c0, shared.tile, H, Hkv, hd, kvd, chunk=cache.chunk)
+            if beams is None:
+                ops.kv_append(qkv[:, d:], cache.layers[i], pos)
+                return ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
+            ops.kv_append(qkv[:, d:], cache.layers[i], pos)
+            return ops.attn_decode_beam(qkv[:, :d], cache.layers[i], kv_len, beams.prefix_row, beams.prefix_len, beams.tail_src, H, Hkv,
+                                        hd, kvd, tail_cols=beams.tail_cols, chunk=cache.chunk)
         x = ops.gather_rows(tok.contiguous(), d, self.W("model.embed_tokens.weight"))
         tapped = {}
         for i in range(L):
             if taps is not None and i in taps:
-                tapped[i] = x                      # every statement below makes a new x: the row stays as it is
-            lv, wq = self._layer_views(i), self._layer_wq(i)
-            h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"))
-            ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
-            if kv8 and cache.scales is not None:
-                kvq = (cache.layers[i], cache.scales[i])
-                ops.kv_append_q8(qkv[:, d:], pos, Hkv, hd, cache=kvq)
-                attn = ops.attn_decode_kv8(qkv[:, :d], kvq, kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
-            elif kv8:       # the reference arm: the dequantised values as bf16, read by the bf16 kernel
-                ops.kv_append_q8(qkv[:, d:], pos, Hkv, hd, xhat=cache.layers[i])
-                attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
-            elif shared is not None:
-                ops.kv_append(qkv[:, d:], cache.layers[i], pos)
-                attn = ops.attn_decode_shared(qkv[:, :d], cache.layers[i], kv_len, shared.c0, shared.tile, H, Hkv, hd, kvd, chunk=cache.chunk)
-            elif beams is None:
-                ops.kv_append(qkv[:, d:], cache.layers[i], pos)
-                attn = ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
-            else:
-                ops.kv_append(qkv[:, d:], cache.layers[i], pos)
-                attn = ops.attn_decode_beam(qkv[:, :d], cache.layers[i], kv_len, beams.prefix_row, beams.prefix_len, beams.tail_src, H, Hkv,
-                                            hd, kvd, tail_cols=beams.tail_cols, chunk=cache.chunk)
-            x_mid = self._decode_lora_linear(attn, lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"))
-            h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu")), F)
-            x = self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"))
-        hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
-        if taps is not None:
-            logits, cand = self._tap_logits(hN, [tapped[c] for c in taps])
-            cache.lens += 1
-            return logits[:, :self.vocab], cand
-        logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
+                tapped[i] = x                      # _cached_layer makes a new x: the row stays as it is
+            x = self._cached_layer(i, x, cs, pos, attend)
+        out = self._head_logits(x, tapped=taps and [tapped[c] for c in taps])
         cache.lens += 1
-        return logits[:, :self.vocab]
+        return out
 
     # decode_step(shared=)'s attention.  rv_attn_decode_shared_bf16 reads a tile's shared chunks once for its 16 / G rows and gives
     # rv_attn_decode_bf16's bits, so the route changes time only.  shared_route: None = the measured table below; "shared" / "plain"
@@ -1307,20 +1327,18 @@ class LlavaEngine:
     def verify_step(self, cache, tokens):
         """Prompt-lookup verification on a B = 1 cache: tokens [R] (1 <= R <= 32; the last emitted token, then R - 1 drafted ones) are
         fed at positions cache.lens[0] .. cache.lens[0] + R - 1 -> fp32 logits [R, vocab], row i being bit for bit what decode_step
-        returns at that position after tokens[:i] were fed one by one.  decode_step's sequence on R rows: RMSNorm, q|k|v, RoPE at each
-        row's position, one launch that writes the R K|V rows into the cache row, attention where row i sees the keys
-        [0, lens[0] + i + 1) (rv_attn_decode_verify_bf16: the chunk's K / V read once for a group of rows), o_proj + residual,
-        RMSNorm, gate|up, SwiGLU, down + residual, final norm, lm_head.  Every product takes the skinny kernel (a row's bits do not
-        depend on M there), the lm_head included whatever its height.  cache.lens is NOT advanced: the caller adds the number of
-        tokens it emits; the K|V rows of rejected drafts stay past lens as stale rows, which every kernel ignores."""
+        returns at that position after tokens[:i] were fed one by one.  _cached_layer on R rows at their positions: one launch writes
+        the R K|V rows into the cache row, and row i attends to the keys [0, lens[0] + i + 1) (rv_attn_decode_verify_bf16: the chunk's
+        K / V read once for a group of rows; or the beam kernel, verify_route).  Every product takes the skinny kernel (a row's bits
+        do not depend on M there), the lm_head included whatever its height.  cache.lens is NOT advanced: the caller adds the number
+        of tokens it emits; the K|V rows of rejected drafts stay past lens as stale rows, which every kernel ignores."""
         self._check_generation()
         self._refuse_int8(cache, "verify_step()")
-        l = self.l
-        d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
+        d, H, L = self.l["d"], self.l["heads"], self.l["layers"]
         hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
         if cache.B != 1:
             raise ValueError(f"verify_step() takes a cache of one sequence, this one holds {cache.B}")
-        tok = tokens.to(self.device, torch.int32) if torch.is_tensor(tokens) else self._dev(np.asarray(tokens, dtype=np.int32))
+        tok = self._tokens_dev(tokens)
         R, n0, L_max = int(tok.numel()), int(cache.lens[0]), cache.L_max
         if not 1 <= R <= min(ops.GEMV_MAX_M, ops.VERIFY_MAX_R):
             raise ValueError(f"verify_step() takes 1 .. {min(ops.GEMV_MAX_M, ops.VERIFY_MAX_R)} tokens, got {R}")
@@ -1339,32 +1357,24 @@ class LlavaEngine:
         pos, kv_len, zero, plen, kv0 = hd_[:R], hd_[R:2 * R], hd_[2 * R:3 * R], hd_[3 * R:4 * R], hd_[4 * R:4 * R + 1]
         slots = hd_[off:].view(torch.int64)
         cs = self.rope_table(L_max)
-        x = ops.gather_rows(tok.contiguous().view(-1), d, self.W("model.embed_tokens.weight"))
-        for i in range(L):
-            lv, wq = self._layer_views(i), self._layer_wq(i)
-            h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"), skinny=True)
-            ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos)
+
+        def attend(i, qkv):
             kv = cache.layers[i]
             kv.view(L_max, 2 * kvd).index_copy_(0, slots, qkv[:, d:])
             if use_beam:
-                attn = ops.attn_decode_beam(qkv[:, :d], kv, kv_len, zero, plen, None, H, Hkv, hd, kvd, chunk=cache.chunk)
-            else:
-                attn = ops.attn_decode_verify(qkv[:, :d], kv, kv0, R, H, Hkv, hd, kvd, chunk=cache.chunk)
-            x_mid = self._decode_lora_linear(attn, lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"), skinny=True)
-            h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu"), skinny=True), F)
-            x = self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"), skinny=True)
-        hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
-        logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32, skinny=True)
-        return logits[:, :self.vocab]
+                return ops.attn_decode_beam(qkv[:, :d], kv, kv_len, zero, plen, None, H, Hkv, hd, kvd, chunk=cache.chunk)
+            return ops.attn_decode_verify(qkv[:, :d], kv, kv0, R, H, Hkv, hd, kvd, chunk=cache.chunk)
+        x = ops.gather_rows(tok.contiguous().view(-1), d, self.W("model.embed_tokens.weight"))
+        for i in range(L):
+            x = self._cached_layer(i, x, cs, pos, attend, skinny=True)
+        return self._head_logits(x, skinny=True)
 
     def extend(self, cache, input_ids, attention_mask=None, images=None, image_sizes=None, reuse=None, max_new_tokens=0, plan=None, slots=None):
         """The prompt pass of a continued generation over a KV cache of an earlier call on the same weights: sequence b's positions
         0 .. reuse[b] - 1 are kept from `cache` (a KVCache; later positions are dropped), its positions reuse[b] .. len_b - 1 (at least one)
-        run through every decoder layer as one packed batch of M = sum(len_b - reuse[b]) rows -- RMSNorm, q|k|v, RoPE at the explicit
-        positions, the K|V rows written into their cache slots, extend attention against the sequence's cached keys (rv_attn_extend_bf16),
-        o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual -- then the final norm and the lm_head on each sequence's last row.
+        run through every decoder layer as one packed batch of M = sum(len_b - reuse[b]) rows -- _cached_layer at the explicit positions,
+        its attention step the K|V rows written into their cache slots and extend attention against the sequence's cached keys
+        (rv_attn_extend_bf16) -- then the final norm and the lm_head on each sequence's last row (_head_logits).
         The vision tower runs only when an image feature row (image_newline aside) is among the new rows.  The cache grows (one copy of
         the kept rows) when len_b + max_new_tokens exceeds its slots.  Every reuse[b] == 0 (or no cache): prefill(), bit for bit.
         plan: this prompt's self.plan(...), when the caller has it already.
@@ -1383,8 +1393,7 @@ class LlavaEngine:
             return self.prefill(input_ids, attention_mask, images, image_sizes, max_new_tokens=max_new_tokens)
         self._check_generation()
         from .generation import grown_length
-        l = self.l
-        d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
+        d, H, L = self.l["d"], self.l["heads"], self.l["layers"]
         hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
         ids = np.asarray(input_ids)
         B = int(ids.shape[0])
@@ -1398,9 +1407,7 @@ class LlavaEngine:
             if cache.B != B or r.shape[0] != B:
                 raise ValueError(f"the cache holds {cache.B} sequences, the prompt {B}")
         else:
-            seq = np.asarray(slots, dtype=np.int64).reshape(-1)
-            if seq.shape[0] != B or r.shape[0] != B or np.unique(seq).shape[0] != B or (seq < 0).any() or (seq >= cache.B).any():
-                raise ValueError(f"slots must be {B} distinct indices into the cache's {cache.B} sequences, got {seq.tolist()}")
+            seq = self._slot_rows(slots, B, cache, ok=r.shape[0] == B)
         if (r < 0).any() or (r > cache.lens[seq]).any() or (r >= lens).any():
             raise ValueError("reuse[b] must lie in [0, min(cached length, prompt length - 1)]")
         n = lens - r
@@ -1437,36 +1444,30 @@ class LlavaEngine:
         rows = self._dev(np.concatenate([seq[b] * L_max + np.arange(r[b], lens[b]) for b in order]).astype(np.int64))
         pos_d, cu_d, r_d = self._dev(pos.astype(np.int32)), self._dev(cu_q), self._dev(r_all.astype(np.int32))
         cs = self.rope_table(L_max)
-        x = ops.gather_rows(self._dev(src), d, self.W("model.embed_tokens.weight"), table)
-        for i in range(L):
-            lv, wq = self._layer_views(i), self._layer_wq(i)
-            h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"))
-            ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
+
+        def attend(i, qkv):
             kv = cache.layers[i]
             kv.view(CB * L_max, 2 * kvd).index_copy_(0, rows, qkv[:, d:])
-            attn = ops.attn_extend(qkv[:, :d], kv, cu_d, r_d, H, Hkv, hd, kvd, int(n.max()))
-            x_mid = self._decode_lora_linear(attn, lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"))
-            h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu")), F)
-            x = self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"))
+            return ops.attn_extend(qkv[:, :d], kv, cu_d, r_d, H, Hkv, hd, kvd, int(n.max()))
+        x = ops.gather_rows(self._dev(src), d, self.W("model.embed_tokens.weight"), table)
+        for i in range(L):
+            x = self._cached_layer(i, x, cs, pos_d, attend)
         last = self._dev((cu_q[seq + 1] - 1).astype(np.int32))              # sequence b's last new row, in the prompt batch's order
-        hN, _ = ops.rmsnorm_fwd(ops.gather_rows(last, d, x), self.W("model.norm.weight"), self.eps)
-        logits = self._decode_linear(hN, self.W("lm_head.weight"), out_dtype=torch.float32)
+        logits = self._head_logits(ops.gather_rows(last, d, x))
         if slots is None:
             cache.lens = lens.copy()
         else:
             cache.lens[seq] = lens
-        return cache, logits[:, :self.vocab]
+        return cache, logits
 
     def score_tails(self, prefix, prefix_row, tails, logits, arrays=None):
         """Log-probs of given continuations of prefilled prompts (model.score()).  prefix: a bf16 KVCache filled by prefill(), one row
         per distinct prompt, and `logits` the fp32 last-row logits prefill() returned with it; candidate k continues row prefix_row[k]
         with the tokens tails[k] (n_k >= 1 ids).  Its tokens t_0 .. t_{n-2} run at positions P .. P + n - 2 (P = prefix.lens[row]) as
-        one packed batch of M = sum(n_k - 1) rows through extend()'s layer sequence -- RMSNorm, q|k|v, RoPE at the explicit positions,
-        the K|V rows written into a tail cache [C, T_max, 2*kvd] per layer, attention over the prompt's keys read in place from
-        `prefix` and then the candidate's own (rv_attn_extend_prefix_bf16: no copy of a prompt, however many candidates share it),
-        o_proj + residual, RMSNorm, gate|up, SwiGLU, down + residual -- then the final norm on every row and the lm_head in row slices
+        one packed batch of M = sum(n_k - 1) rows through _cached_layer at the explicit positions -- its attention step the K|V rows
+        written into a tail cache [C, T_max, 2*kvd] per layer and attention over the prompt's keys read in place from `prefix` and
+        then the candidate's own (rv_attn_extend_prefix_bf16: no copy of a prompt, however many candidates share it) -- then the
+        final norm on every row and the lm_head in row slices
         whose fp32 logits stay under scoring.LOGITS_BYTES_CAP, each slice going straight into rv_token_logprob_rows_f32 with the next
         token as target.  t_0 is scored from row prefix_row[k] of `logits`; a one-token candidate runs no row.  The quantised decoders
         work as in extend() (_decode_linear).  prefix is only read; self.ctx and the optimizer state are not touched.
@@ -1476,8 +1477,7 @@ class LlavaEngine:
         self._check_generation()
         self._refuse_int8(prefix, "score_tails()")
         from . import scoring
-        l = self.l
-        d, F, H, L = l["d"], l["ffn"], l["heads"], l["layers"]
+        d, H, L = self.l["d"], self.l["heads"], self.l["layers"]
         hd, Hkv, kvd, V = self.hd, self.Hkv, self.kvd, self.vocab
         prow = np.asarray(prefix_row, dtype=np.int64).reshape(-1)
         if prow.shape[0] != len(tails) or (prow < 0).any() or (prow >= prefix.B).any():
@@ -1503,18 +1503,13 @@ class LlavaEngine:
         table = torch.zeros(1, d, dtype=BF16, device=self.device)      # candidates are text: the splice reads token embeddings only
         x = ops.gather_rows(self._dev(a.tokens), d, self.W("model.embed_tokens.weight"), table)
         tail = [torch.zeros(C, T_max, 2 * kvd, dtype=BF16, device=self.device) for _ in range(L)]
-        for i in range(L):
-            lv, wq = self._layer_views(i), self._layer_wq(i)
-            h1, _ = ops.rmsnorm_fwd(x, lv["ln1"], self.eps)
-            qkv = self._decode_lora_linear(h1, lv["qkv"], i, self._MODS_QKV(d), bias=lv.get("bqkv"), wq=wq.get("qkv"))
-            ops.rope_inplace(qkv, cs, 1, H + Hkv, hd, 1, 1, positions=pos_d)
+
+        def attend(i, qkv):
             tail[i].view(C * T_max, 2 * kvd).index_copy_(0, rows, qkv[:, d:])
-            attn = ops.attn_extend_prefix(qkv[:, :d], prefix.layers[i], tail[i], cu_d, prow_d, plen_d, H, Hkv, hd, kvd, a.max_q)
-            x_mid = self._decode_lora_linear(attn, lv["o"], i, self._MODS_O(d), residual=x, wq=wq.get("o"))
-            h2, _ = ops.rmsnorm_fwd(x_mid, lv["ln2"], self.eps)
-            act = ops.swiglu_fwd(self._decode_lora_linear(h2, lv["gu"], i, self._MODS_GU(F), wq=wq.get("gu")), F)
-            x = self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"))
-        del tail
+            return ops.attn_extend_prefix(qkv[:, :d], prefix.layers[i], tail[i], cu_d, prow_d, plen_d, H, Hkv, hd, kvd, a.max_q)
+        for i in range(L):
+            x = self._cached_layer(i, x, cs, pos_d, attend)
+        del tail                             # empties the cell attend reads: the tail cache is freed here
         hN, _ = ops.rmsnorm_fwd(x, self.W("model.norm.weight"), self.eps)
         w_head = self.W("lm_head.weight")
         step = max(1, scoring.LOGITS_BYTES_CAP // (int(w_head.shape[0]) * 4))
@@ -1528,6 +1523,25 @@ class LlavaEngine:
             del sl
         return lp, am
 
+    def _scored_rows(self, rows, lab_rows, gathered, scored):
+        """The n scored tokens among forward()'s `rows` head rows (_policy_loss, _preference_loss): rows 0 .. n - 1 when gathered, else
+        the rows lab_rows.  Returns (n, per_row, pick): per_row(a) scatters a host array of n entries (or None) to fp64 [rows];
+        pick(*ts) takes the scored entries, in scored order, out of device tensors [..., rows] with one upload of the row index."""
+        n = int(lab_rows.size)
+        assert n == int(scored.sum()), "a scored token on a padding row"
+
+        def per_row(a):
+            if a is None:
+                return None
+            full = np.zeros(rows, dtype=np.float64)          # rows without a label are never read by the kernel
+            full[slice(n) if gathered else lab_rows] = a
+            return full
+
+        def pick(*ts):
+            sel = slice(n) if gathered else self._dev(lab_rows.astype(np.int64))
+            return [t[..., sel] for t in ts]
+        return n, per_row, pick
+
     def _policy_loss(self, logits, tgt, lab_rows, gathered, scored, terms, gscale, grad=True):
         """The GRPO token loss in the cross entropy's place: logits (bf16, overwritten by dlogits when grad) and tgt are forward()'s head
         rows; lab_rows the labelled rows among forward()'s token rows, ascending -- the scored order of policy.PolicyTerms, sample by
@@ -1535,27 +1549,16 @@ class LlavaEngine:
         else the per-token terms are scattered by lab_rows.  terms None (token_logps): statistics only, every coefficient zero.
         Leaves self.last_policy: logp, loss, kl, clip (0 active / 1 low / 2 high) fp32 [n_scored] and ratio_one bool [n_scored] (no old
         log-probs were given: r = 1 exactly), device tensors in scored order, plus scored = the per-sample counts (host)."""
-        n, rows = int(lab_rows.size), logits.shape[0]
-        assert n == int(scored.sum()), "a scored token on a padding row"
+        n, per_row, pick = self._scored_rows(logits.shape[0], lab_rows, gathered, scored)
         if terms is None:
             adv, w, old, ref = np.zeros(n), np.zeros(n), None, None
             eps_low = eps_high = beta = 0.0
         else:
             adv, w, old, ref = terms.per_token(scored)
             eps_low, eps_high, beta = float(terms.epsilon), terms.eps_high, float(terms.beta)
-
-        def per_row(a):
-            if a is None:
-                return None
-            full = np.zeros(rows, dtype=np.float64)          # rows without a label are never read by the kernel
-            if gathered:
-                full[:n] = a
-            else:
-                full[lab_rows] = a
-            return full
         loss, stats = ops.policy_loss(logits, tgt, self.vocab, per_row(adv), per_row(w), gscale, per_row(old), per_row(ref if beta > 0 else None),
                                       eps_low, eps_high, beta, dlogits="inplace" if grad else None)
-        st = stats[:, :n] if gathered else stats[:, self._dev(lab_rows.astype(np.int64))]
+        st, = pick(stats)
         self.last_policy = dict(logp=st[0], loss=st[1], kl=st[3], clip=st[4], scored=np.asarray(scored),
                                 ratio_one=torch.full((n,), old is None, dtype=torch.bool, device=logits.device))
         return loss
@@ -1566,12 +1569,8 @@ class LlavaEngine:
         entropy's lse, the same labelled-rows head -- without a gradient and without a saved context, so old log-probs taken with it
         before an update make the first iteration's ratio exactly 1 (the sampler's fp32 GEMV logits are other bits).  LoRA engines run
         it in eval form (no adapter dropout).  The training state is not touched."""
-        saved = (self.lora_step, getattr(self, "lora_p", 0.0), self.ctx)
-        self.lora_p = 0.0
-        try:
+        with self._eval_form("lora_step", "ctx"):
             self.forward(input_ids, attention_mask, labels, images, image_sizes=image_sizes, _score_only=True)
-        finally:
-            self.lora_step, self.lora_p, self.ctx = saved
         return self.last_policy["logp"]
 
     def _preference_loss(self, logits, tgt, lab_rows, gathered, scored, terms, gscale):
@@ -1584,8 +1583,8 @@ class LlavaEngine:
         (fp64 [3]: L, dpo_alpha * mean pair loss, SFT loss), coefs and logp (fp32 [n_scored], scored order) on the device, scored (host counts)
         and P.  Returns L as fp32 [1]."""
         from . import lib
-        n, rows, dev = int(lab_rows.size), logits.shape[0], logits.device
-        assert n == int(scored.sum()), "a scored token on a padding row"
+        rows, dev = logits.shape[0], logits.device
+        _, _, pick = self._scored_rows(rows, lab_rows, gathered, scored)
         P, seg_off, rho, a_P, g_N = terms.per_pair(scored)
         zero = torch.zeros(rows, dtype=torch.float32, device=dev)
         stats = torch.empty(len(ops.POLICY_STATS), rows, dtype=torch.float32, device=dev)
@@ -1599,8 +1598,8 @@ class LlavaEngine:
         stats_c = torch.empty_like(stats)
         lib.call("rv_policy_loss_bf16", logits, logits.stride(0), tgt, coef, ones, gweight, None, None, 0.0, 0.0, 0.0, stats_c, logits,
                  logits.stride(0), rows, self.vocab)
-        pick = (lambda t: t[:n]) if gathered else (lambda t, i=self._dev(lab_rows.astype(np.int64)): t[i])
-        self.last_preference = dict(planes=planes, batch=batch, coefs=pick(coef), logp=pick(stats[0]), scored=np.asarray(scored), P=P)
+        coefs, logp = pick(coef, stats[0])
+        self.last_preference = dict(planes=planes, batch=batch, coefs=coefs, logp=logp, scored=np.asarray(scored), P=P)
         return batch[:1].to(torch.float32)
 
     def sequence_logps(self, input_ids, attention_mask, labels, images, image_sizes=None):
