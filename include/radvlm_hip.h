@@ -480,7 +480,14 @@ int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cache, int64_t 
  * cu_q (B + 1 entries) and r (B entries) are int32 device arrays with r[b] + n_b <= L_max; max_q >= every n_b.  Keys are split into
  * chunks of `chunk` positions (a multiple of 64) fixed in absolute key position; each workgroup (chunk, kv head, tile of query rows
  * of one sequence) writes (o, m, l) partials to `part` (M * H * ceil(L_max / chunk) * (hd + 2) floats) and a second launch merges a
- * row's chunks in chunk order: a row's result is bit-identical whatever else shares the launch. */
+ * row's chunks in chunk order: a row's result is bit-identical whatever else shares the launch, the other rows of its own sequence
+ * included (a row of an n-row call has the bits of the same query sent alone as a one-row call at its position).  Cache positions at
+ * or past r[b] + n_b are never loaded and may hold anything (NaN included), and the combine reads only partial slots some workgroup
+ * wrote, so `part` needs no initialisation.  A key INSIDE the suffix that a row may not see (positions r[b] + i + 1 .. r[b] + n_b - 1)
+ * is not skipped: a workgroup stages the keys up to its tile's last row (tiles of 64 / 32 / 16 rows for 1 / 2 / >= 3 q heads per kv
+ * head, counted from the sequence's first new row) and gives such a key an exact-zero weight, so the suffix's own K|V rows must be
+ * finite: a non-finite K|V row at position j makes non-finite, beside the rows that see it, the earlier rows of j's own tile whose
+ * position lies in j's chunk (0 * inf); every other row keeps its bits. */
 int rv_attn_extend_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* cu_q,
                         const int32_t* r, int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int M, int max_q,
                         int H, int Hkv, int hd, int chunk, float scale, void* stream);
@@ -745,8 +752,10 @@ int rv_attn_decode_shared_bf16(const void* q, int64_t ld_q, const void* cache, i
  * max_q <= T_max.  The work split, the 64-key stages, the online softmax, the partials and the combine are rv_attn_extend_bf16's and
  * the chunk grid is fixed in absolute key positions (only the address a staged key is loaded from is chosen per key): out is
  * BIT-IDENTICAL to rv_attn_extend_bf16 with r = prefix_len and the same `chunk` on the cache materialised as
- * prefix[prefix_row[b], :prefix_len[b]] ++ tail[b, :n_b], for hd 64 and 128 and up to 8 q heads per kv head.  Keys past a query's own
- * position are never loaded: prefix positions >= prefix_len[b] and tail positions >= n_b may hold anything (NaN included).  A sequence
+ * prefix[prefix_row[b], :prefix_len[b]] ++ tail[b, :n_b], for hd 64 and 128 and up to 8 q heads per kv head.  Keys at or past
+ * prefix_len[b] + n_b are never loaded: prefix positions >= prefix_len[b] and tail positions >= n_b may hold anything (NaN included).
+ * A tail row that a query may not see (a later row of the same sequence) is staged with its tile and gets an exact-zero weight, as in
+ * rv_attn_extend_bf16: the n_b tail rows must be finite.  A sequence
  * with n_b == 0 writes nothing.  A sequence whose prefix_row[b] is outside [0, P_rows) or whose prefix_len[b] is outside [0, P_max]
  * is not read at all and its rows of out are zeros.  part: M * H * ceil((P_max + T_max) / chunk) * (hd + 2) floats.  Refusals
  * (RV_ERR_ARG) as rv_attn_extend_bf16's, and a null prefix_row / prefix_len, P_rows <= 0, P_max <= 0, T_max <= 0, max_q > T_max. */
