@@ -473,6 +473,22 @@ int rv_gemv_lora_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, co
 int rv_attn_decode_bf16(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, int v_off, const int32_t* kv_len,
                         int L_max, void* out, int64_t ld_o, void* part, int64_t part_bytes, int B, int H, int Hkv, int hd, int chunk,
                         float scale, void* stream);
+/* Decode attention probabilities (attn_probs.hip; reference: output_attentions in modeling_llama.py:352-382, attn_weights =
+ * softmax(Q K^T / sqrt(hd) + mask) in fp32): for every sequence b and q head h the normalised fp32 row softmax(scale * q[b,h] K^T) over
+ * the cached keys [0, n_b), n_b = min(kv_len[b], L_max, L_out), of kv head h / (H / Hkv).  q, cache, ld_c, bs_c, kv_len, L_max, H, Hkv,
+ * hd as for rv_attn_decode_bf16; V is never read.  L_out <= L_max is the number of columns the caller wants (pass L_out >= every
+ * kv_len[b] for the distribution over all of a row's keys).  probs: fp32 [B][H][ld_p], ld_p >= L_out, or null; mean: fp32 [B][ld_m],
+ * ld_m >= L_out, the mean over the H heads added in head order 0 .. H-1 then divided by H, or null; not both null.  Columns
+ * [n_b, L_out) are written as 0.0f (kv_len[b] <= 0: the whole row), columns >= L_out are not touched.  A key at or past n_b is never
+ * loaded.  ws: fp32 scratch of rv_attn_decode_probs_ws_bytes(B, H, L_out) bytes (the scaled scores and (max, sum) per (row, head)),
+ * contents arbitrary, not to be shared by launches that can overlap.  No atomics, every reduction in a fixed order that is a function
+ * of n_b alone: row b has the same bits alone and in any batch, and for every L_out >= n_b.  RV_ERR_ARG before any launch for a null
+ * q / cache / kv_len / ws, both outputs null, hd not 64 or 128, H % Hkv, H / Hkv > 8, ld_q / ld_c / bs_c not multiples of 8 or too
+ * small, ld_p / ld_m < L_out, L_out > L_max, B > 65535 and a short workspace. */
+int rv_attn_decode_probs_f32(const void* q, int64_t ld_q, const void* cache, int64_t ld_c, int64_t bs_c, const int32_t* kv_len, int L_max,
+                             int L_out, void* probs, int64_t ld_p, void* mean, int64_t ld_m, void* ws, int64_t ws_bytes, int B, int H,
+                             int Hkv, int hd, float scale, void* stream);
+int64_t rv_attn_decode_probs_ws_bytes(int B, int H, int L_out);
 /* Extend attention (the prompt pass of a continued generation, over a reused KV cache): sequence b has n_b = cu_q[b+1] - cu_q[b] >= 1
  * new query rows q[cu_q[b] .. cu_q[b+1]) at positions r[b] .. r[b] + n_b - 1, whose K|V rows are already in the cache; query i attends
  * causally to the keys [0, r[b] + i] of kv head h / (H / Hkv).  hd in {64, 128}, up to 8 q heads per kv head, fp32 softmax and

@@ -1081,7 +1081,7 @@ class LlavaEngine:
         return self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"), skinny=skinny)
 
     def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0, cache=None, slots=None, kv_dtype=None,
-                tap_layers=None):
+                tap_layers=None, attn_layers=None, attn_mean=False):
         """The prompt pass of generation: multimodal splice (plan / encode_images, as in forward) and every decoder layer in the packed
         varlen layout, sequence b at cache rows and positions 0 .. len_b - 1 whatever the padding side.  Each layer's post-RoPE K|V rows go
         into a KVCache of len_b + max_new_tokens slots per sequence; the activations are dropped.  No loss, no saved context (self.ctx and
@@ -1096,11 +1096,27 @@ class LlavaEngine:
         value, fp32 [n, B, vocab]: lm_head of every sequence's last prompt row as it ENTERS decoder layer c (c = 0: the spliced
         embedding row; c = k: the residual stream after layer k), without the final norm, in tap_layers' order (_tap_logits).  Only
         those rows are kept, never whole activations; the cache and the mature logits are bit for bit those of the call without it.
-        Returns (cache, fp32 logits [B, vocab] of every sequence's last prompt row)."""
+        attn_layers / attn_mean (generate(output_attentions=True)): as in decode_step, for the first generated token -- the call then
+        returns (cache, logits, attn), attn a list in attn_layers' order of fp32 [B, H, S] ([B, S] under attn_mean, S the longest
+        prompt): the attention probabilities of every sequence's LAST prompt row over its cache positions 0 .. len_b - 1, zeros beyond.
+        For each asked layer that row of q is gathered from the layer's own post-RoPE acts["qkv"] (rows cu[1:] - 1) and
+        ops.attn_decode_probs runs on those B rows against the cache layer just written, kv_len = len_b; the prompt pass's own
+        attention is not touched and only those rows are kept.  The cache and the logits are the bits of the call without it.  Not
+        combined with cache= / slots=, kv_dtype "int8" or tap_layers= (NotImplementedError).
+        Returns (cache, fp32 logits [B, vocab] of every sequence's last prompt row), plus the third value above when asked for."""
         self._check_generation()
         dev, l = self.device, self.l
         d, L, kvd = l["d"], l["layers"], self.kvd
         taps = self._check_taps(tap_layers)
+        want = self._check_attn_layers(attn_layers)
+        if want is not None:
+            if cache is not None or slots is not None:
+                raise NotImplementedError("prefill(attn_layers=...) with cache= / slots=: attention maps are read from a cache of the "
+                                          "call's own sequences")
+            if kv_dtype is not None and self._kv_dtype(kv_dtype) == "int8":
+                raise NotImplementedError("prefill(attn_layers=...) with an int8 KV cache: the probability kernel reads a bf16 cache only")
+            if taps is not None:
+                raise NotImplementedError("prefill(attn_layers=...) with tap_layers=: attention maps run on the plain prompt pass")
         if cache is not None:
             if kv_dtype is not None and self._kv_dtype(kv_dtype) != cache.dtype:
                 raise ValueError(f"kv_dtype {kv_dtype!r} does not match the passed cache's dtype {cache.dtype!r}")
@@ -1140,6 +1156,8 @@ class LlavaEngine:
             cache = self.new_kv_cache(B, L_max, kv_dtype)           # seq = 0 .. B - 1: filled like a passed cache's slots
         if taps is not None:
             tap_rows, tapped = self._dev((cu[1:] - 1).astype(np.int32)), {}
+        if want is not None:
+            last_rows, lens_dev, attn = self._dev((cu[1:] - 1).astype(np.int32)), self._dev(lens.astype(np.int32)), {}
         with self._eval_form():              # live adapters (adapter_decoding): as in forward_embeds; lora_step is only read
             for i in range(L):
                 if taps is not None and i in taps:
@@ -1154,6 +1172,9 @@ class LlavaEngine:
                     self._kv_write_rows(kv, cache.scales[i] if cache.scales is not None else None, acts["qkv"][:, d:], rows)
                 else:
                     kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:])
+                if want is not None and i in want:
+                    attn[i] = ops.attn_decode_probs(ops.gather_rows(last_rows, d, acts["qkv"]), kv, lens_dev, l["heads"], self.Hkv, self.hd, S,
+                                                    per_head=not attn_mean, mean=bool(attn_mean))[1 if attn_mean else 0]
                 del acts
         x = ops.gather_rows(self._dev((cu[1:] - 1).astype(np.int32)), d, x)       # every sequence's last prompt row
         out = self._head_logits(x, tapped=taps and [tapped[c] for c in taps])
@@ -1161,6 +1182,8 @@ class LlavaEngine:
             cache = KVCache(layers, lens, L_max)
         else:
             cache.lens[seq] = lens
+        if want is not None:
+            return cache, out, [attn[c] for c in want]
         return (cache, out) if taps is None else (cache, *out)
 
     # lm_head of a tapped step: "stacked" puts [mature; candidates] into one skinny launch (skinny=True: a row's bits do not depend on
@@ -1182,6 +1205,16 @@ class LlavaEngine:
             raise ValueError(f"tap_layers must be 1 .. {ops.DOLA_MAX_LAYERS} distinct ints in [0, {L}), got {tap_layers!r}")
         return tuple(int(c) for c in taps)
 
+    def _check_attn_layers(self, attn_layers):
+        if attn_layers is None:
+            return None
+        want = tuple(attn_layers)
+        L = self.l["layers"]
+        if not 1 <= len(want) <= L or len(set(want)) != len(want) or any(
+                isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < L for c in want):
+            raise ValueError(f"attn_layers must be 1 .. {L} distinct ints in [0, {L}), got {attn_layers!r}")
+        return tuple(int(c) for c in want)
+
     def _tap_logits(self, hN, hs):
         """(mature fp32 logits [B, ld], candidate fp32 logits [n, B, vocab]) from the normed last rows hN and the n tapped bf16 rows
         hs (each [B, d], no norm): the candidates are _decode_linear(cat(hs), lm_head, out_dtype=fp32) -- row k * B + b is candidate k
@@ -1195,7 +1228,7 @@ class LlavaEngine:
         cand = self._decode_linear(torch.cat(list(hs), 0), w, out_dtype=torch.float32)
         return logits, cand.view(n, B, -1)[:, :, :self.vocab]
 
-    def decode_step(self, cache, tokens, beams=None, shared=None, tap_layers=None):
+    def decode_step(self, cache, tokens, beams=None, shared=None, tap_layers=None, attn_layers=None, attn_mean=False):
         """One generated token per sequence: tokens [B] (int, host or device) at position cache.lens[b] -> fp32 logits [B, vocab].
         Every layer is _cached_layer at the token's position, its attention step the cache append and decode attention over the
         sequence's cached keys; then the final norm and the lm_head (_head_logits).
@@ -1215,9 +1248,22 @@ class LlavaEngine:
         tap_layers (DoLa): as in prefill -- a tuple of n distinct layer numbers c in [0, layers); the call then returns (logits, fp32
         [n, B, vocab]): lm_head of the token's row as it enters layer c, no final norm, in tap_layers' order.  The logits and the
         cache are bit for bit those of the call without it; it works with quantised decoders and an int8 cache (lm_head stays bf16,
-        the attention branch is not touched) and is not combined with beams= or shared= (NotImplementedError)."""
+        the attention branch is not touched) and is not combined with beams= or shared= (NotImplementedError).
+        attn_layers (generate(output_attentions=True)): a tuple of distinct layer numbers in [0, layers); the call then returns
+        (logits, attn), attn a list in attn_layers' order of fp32 [B, H, L_t] -- or [B, L_t], the mean over the heads, under attn_mean --
+        with L_t = max_b(cache.lens[b] + 1) at this step: softmax(q K^T / sqrt(hd)) of the step's query row over the sequence's cache
+        positions 0 .. cache.lens[b], zeros beyond.  In those layers ops.attn_decode_probs runs on the same qkv[:, :d], cache layer and
+        kv_len, after the K|V append and beside the unchanged ops.attn_decode call, so the logits and the cache are the bits of the
+        call without it.  Not combined with beams=, shared=, tap_layers= or an int8 cache (NotImplementedError)."""
         self._check_generation()
         taps = self._check_taps(tap_layers)
+        want = self._check_attn_layers(attn_layers)
+        if want is not None:
+            for name, v in (("beams", beams), ("shared", shared), ("tap_layers", tap_layers)):
+                if v is not None:
+                    raise NotImplementedError(f"decode_step(attn_layers=...) with {name}=: attention maps run on the plain decode step")
+            if getattr(cache, "dtype", "bf16") == "int8":
+                raise NotImplementedError("decode_step(attn_layers=...) on an int8 KV cache: the probability kernel reads a bf16 cache only")
         if taps is not None and (beams is not None or shared is not None):
             raise NotImplementedError("decode_step(tap_layers=...) with beams= or shared=: DoLa runs on the plain decode step")
         if shared is not None:
@@ -1241,6 +1287,8 @@ class LlavaEngine:
         pos = self._dev(cache.lens.astype(np.int32))
         kv_len = self._dev((cache.lens + 1).astype(np.int32))
         cs = self.rope_table(cache.L_max)
+        if want is not None:
+            L_t, attn = int(cache.lens.max()) + 1, {}
 
         def attend(i, qkv):
             if kv8 and cache.scales is not None:
@@ -1255,6 +1303,9 @@ class LlavaEngine:
                 return ops.attn_decode_shared(qkv[:, :d], cache.layers[i], kv_len, shared.c0, shared.tile, H, Hkv, hd, kvd, chunk=cache.chunk)
             if beams is None:
                 ops.kv_append(qkv[:, d:], cache.layers[i], pos)
+                if want is not None and i in want:
+                    attn[i] = ops.attn_decode_probs(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, L_t, per_head=not attn_mean,
+                                                    mean=bool(attn_mean))[1 if attn_mean else 0]
                 return ops.attn_decode(qkv[:, :d], cache.layers[i], kv_len, H, Hkv, hd, kvd, chunk=cache.chunk)
             ops.kv_append(qkv[:, d:], cache.layers[i], pos)
             return ops.attn_decode_beam(qkv[:, :d], cache.layers[i], kv_len, beams.prefix_row, beams.prefix_len, beams.tail_src, H, Hkv,
@@ -1267,7 +1318,7 @@ class LlavaEngine:
             x = self._cached_layer(i, x, cs, pos, attend)
         out = self._head_logits(x, tapped=taps and [tapped[c] for c in taps])
         cache.lens += 1
-        return out
+        return out if want is None else (out, [attn[c] for c in want])
 
     # decode_step(shared=)'s attention.  rv_attn_decode_shared_bf16 reads a tile's shared chunks once for its 16 / G rows and gives
     # rv_attn_decode_bf16's bits, so the route changes time only.  shared_route: None = the measured table below; "shared" / "plain"

@@ -35,18 +35,22 @@ _DOLA = ("dola_layers",)
 DOLA_MAX_LAYERS = 16          # candidate layers per call (rv_dola_contrast_rows_f32)
 # constrained decoding (ours: HF's prefix_allowed_tokens_fn is a Python callback per row and step); constraints.TokenConstraint
 _CONSTRAINT = ("constraint",)
+# decode attention maps (output_attentions is HF's name; attention_layers / attention_reduce are ours): generate() alone takes them,
+# generate_batch() and generate_beams() reject them as unknown; _parse_attentions / resolve_attention_layers
+_ATTENTIONS = ("output_attentions", "attention_layers", "attention_reduce")
 LOOKUP_MAX_TOKENS = 31        # k drafted tokens are verified as k + 1 rows, and the skinny GEMM takes ops.GEMV_MAX_M = 32
 
 
 class GenerateDecoderOnlyOutput(SimpleNamespace):
     """HF's return_dict_in_generate output: .sequences [B, T_new]; .scores (output_scores: the processed fp32 [B, vocab] scores of each
-    step) and .logits (output_logits: the raw ones), each a tuple or None."""
+    step) and .logits (output_logits: the raw ones), each a tuple or None.  output_attentions: .attentions, a tuple over the generated
+    steps of a tuple over .attention_layers (the resolved layer numbers) of fp32 [B, H, 1, L_t] ([B, 1, 1, L_t] under "mean_heads")."""
 
     def __getitem__(self, k):
         return getattr(self, k)
 
 
-def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, lookup=False):
+def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, lookup=False, attentions=False):
     """Validate generate() keyword arguments; returns a namespace with the normalised settings (.sampling: None for greedy, else the
     warper settings and the seed as given; sampling_seeds() resolves it per row).  Raises NotImplementedError for what this build does
     not do (do_sample=True without seed=, beam search, streamers, caller-supplied inputs_embeds, LoRA engines, kv_cache_dtype="int8"
@@ -59,14 +63,29 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     once the call knows the engine's depth): with guidance_scale, past_key_values or prompt_lookup_num_tokens NotImplementedError.
     Constrained decoding (.constraint: None when off, else a TokenConstraint or a list of them with None entries, _parse_constraint;
     constraints.resolve_constraints checks it against the row count and the vocabulary once the call knows them): with
-    prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError."""
+    prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError.
+    attentions: also take output_attentions / attention_layers / attention_reduce (.attentions: None when off, else .layers and
+    .reduce, _parse_attentions; resolve_attention_layers turns .layers into layer numbers once the call knows the engine's depth):
+    with kv_cache_dtype="int8", past_key_values, prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError."""
     unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and k not in _DOLA and k not in _CONSTRAINT
-                     and not (lookup and k in _LOOKUP))
+                     and not (lookup and k in _LOOKUP) and not (attentions and k in _ATTENTIONS))
     if unknown:
         raise TypeError(f"generate() got unexpected keyword arguments {unknown}")
     guidance = _parse_guidance(kwargs)
     dola = _parse_dola(kwargs)
     constraint = _parse_constraint(kwargs)
+    att = _parse_attentions(kwargs)
+    if att is not None:
+        for name, on, why in (
+                ("kv_cache_dtype='int8'", parse_kv_cache_dtype(kwargs.get("kv_cache_dtype")) == "int8", "the probability kernel reads a "
+                 "bf16 cache only"),
+                ("past_key_values", kwargs.get("past_key_values") is not None, "the extend pass hands out no attention rows"),
+                ("prompt_lookup_num_tokens", kwargs.get("prompt_lookup_num_tokens") is not None, "the verify step hands out no "
+                 "attention rows"),
+                ("guidance_scale", guidance is not None, "maps of the two branches of a guided step are not implemented"),
+                ("dola_layers", dola is not None, "the tapped decode step hands out no attention rows")):
+            if on:
+                raise NotImplementedError(f"output_attentions with {name}: {why}")
     if constraint is not None and kwargs.get("prompt_lookup_num_tokens") is not None:
         raise NotImplementedError("constraint with prompt_lookup_num_tokens: every drafted row of a verify step would need its own "
                                   "automaton state, which is not implemented")
@@ -131,8 +150,51 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
                            past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
-                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola, constraint=constraint,
+                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola, constraint=constraint, attentions=att,
                            **_parse_processors(kwargs, eos))
+
+
+def _parse_attentions(kwargs):
+    """The attention-map keywords as far as they can be checked without the model's depth; None when output_attentions is off.
+    output_attentions: a bool (None: off), and True needs return_dict_in_generate=True; attention_layers: None (all layers) or a list
+    or tuple of ints, negative ones counting from the last layer as in HF's hidden_states (-1: the last); attention_reduce: None or
+    "mean_heads".  ValueError for anything else, and for attention_layers / attention_reduce while output_attentions is off."""
+    on = kwargs.get("output_attentions")
+    if on is not None and not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"`output_attentions` has to be True or False, but is {on!r}")
+    layers, reduce = kwargs.get("attention_layers"), kwargs.get("attention_reduce")
+    if not on:
+        given = [k for k, v in (("attention_layers", layers), ("attention_reduce", reduce)) if v is not None]
+        if given:
+            raise ValueError(f"{given} given without output_attentions=True")
+        return None
+    if not kwargs.get("return_dict_in_generate"):
+        raise ValueError("output_attentions=True needs return_dict_in_generate=True: the maps are returned as .attentions")
+    if reduce is not None and not (isinstance(reduce, str) and reduce == "mean_heads"):
+        raise ValueError(f"`attention_reduce` has to be None or 'mean_heads', but is {reduce!r}")
+    if layers is not None:
+        if not isinstance(layers, (list, tuple)):
+            raise ValueError(f"`attention_layers` has to be None or a list of layer numbers, but is {layers!r}")
+        if any(isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) for c in layers):
+            raise ValueError(f"`attention_layers` has to hold ints, but is {layers!r}")
+        if not layers:
+            raise ValueError("`attention_layers` is an empty list: pass None for every layer")
+        layers = tuple(int(c) for c in layers)
+    return SimpleNamespace(layers=layers, reduce=reduce)
+
+
+def resolve_attention_layers(spec, L):
+    """The layer numbers of an output_attentions call on a decoder of L layers, in the given order: None is every layer; a negative
+    entry c means L + c.  ValueError for a value outside [-L, L) and for a layer named twice after that normalisation."""
+    L = int(L)
+    if spec is None:
+        return tuple(range(L))
+    if any(not -L <= c < L for c in spec):
+        raise ValueError(f"attention_layers={list(spec)}: every entry has to lie in [-{L}, {L})")
+    layers = tuple(c + L if c < 0 else c for c in spec)
+    if len(set(layers)) != len(layers):
+        raise ValueError(f"attention_layers={list(spec)} names a layer twice: {list(layers)}")
+    return layers
 
 
 def _parse_constraint(kwargs):
@@ -947,6 +1009,17 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             raise NotImplementedError("constraint with prompt_lookup_num_tokens or dola_layers is not implemented")
         from .constraints import resolve_constraints
         ctab, cstart = resolve_constraints(cfg.constraint, B, engine.vocab)
+    att = getattr(cfg, "attentions", None)
+    akw, amap, attns = {}, None, []
+    if att is not None:
+        if gc is not None or lookup or dola is not None or getattr(cfg, "kv_cache_dtype", "bf16") == "int8":
+            raise NotImplementedError("output_attentions with past_key_values, prompt_lookup_num_tokens, dola_layers or "
+                                      "kv_cache_dtype='int8' is not implemented")
+        if engine.lora:
+            raise NotImplementedError("output_attentions with LoRA adapters: attention maps on the live adapters are not implemented; "
+                                      "merge them first with model.merge_and_unload()")
+        att_layers = resolve_attention_layers(att.layers, engine.l["layers"])
+        akw = dict(attn_layers=att_layers, attn_mean=att.reduce == "mean_heads")
     # prompt length in HF's sense: the spliced inputs_embeds width (the longest spliced prompt of the batch)
     plan_len = None
     if (cfg.max_new_tokens is None and cfg.max_length is not None) or min_needs_prompt_len(cfg):
@@ -971,6 +1044,8 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                     raise NotImplementedError("kv_cache_dtype='int8' with prompt-lookup decoding: the verify-attention kernel reads a bf16 "
                                               "cache only")
                 cache, logits, *cand = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, kv_dtype="int8", **tap)
+            elif att is not None:
+                cache, logits, amap = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **akw)
             else:
                 cache, logits, *cand = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **tap)
             if dola is not None:
@@ -999,6 +1074,8 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
         for t in range(plain_steps):
             if cfg.output_logits:
                 raw.append(logits.clone())
+            if att is not None:           # the maps of the step that gave these logits: HF's [B, H, 1, L_t]
+                attns.append(tuple(a[:, None, None, :] if a.dim() == 2 else a[:, :, None, :] for a in amap))
             if dola is not None:          # in place: the raw mature rows become the contrasted rows
                 picks.append((ops.dola_contrast_rows(logits, cand[0], engine.vocab, ws=dws)[1], st.unfinished.copy()))
             if ctab is not None:          # in place: each live row's state takes the row's last token, then bans what it does not allow
@@ -1028,7 +1105,12 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                 break
             if ctab is not None:          # one upload serves the next step's advance and the decode step
                 ctok = engine._dev(tok)
-                logits = engine.decode_step(cache, ctok)
+                if att is not None:
+                    logits, amap = engine.decode_step(cache, ctok, **akw)
+                else:
+                    logits = engine.decode_step(cache, ctok)
+            elif att is not None:
+                logits, amap = engine.decode_step(cache, torch.from_numpy(tok), **akw)
             elif dola is None:
                 logits = engine.decode_step(cache, torch.from_numpy(tok))
             else:
@@ -1043,6 +1125,8 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
                                         logits=tuple(raw) if cfg.output_logits else None, past_key_values=cfg.past_key_values)
         if lookup:
             out.lookup_stats = lookup_stats
+        if att is not None:
+            out.attentions, out.attention_layers = tuple(attns), att_layers
         if dola is not None:
             lay = np.full((B, len(picks)), -1, dtype=np.int64)
             if picks:

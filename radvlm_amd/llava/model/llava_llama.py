@@ -422,10 +422,25 @@ class LlavaLlamaForCausalLM:
         RuntimeError naming the row and the step.  It composes with the processors, sampling, kv_cache_dtype="int8", quantised
         decoders and past_key_values; with prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError; another
         type, a list of another length or an automaton naming an id beyond the vocabulary: ValueError.
+        Attention maps: output_attentions=True (HF's keyword; needs return_dict_in_generate=True) returns .attentions, a tuple over
+        the generated steps of a tuple over the asked layers of fp32 [B, H, 1, L_t]: softmax(q K^T / sqrt(hd)) of the step's query
+        row, computed by a HIP kernel family of its own (rv_attn_decode_probs_f32) beside the unchanged decode attention, so
+        .sequences, .scores and .logits are bit for bit those of the call without it.  attention_layers (ours): None = every layer, or
+        a list of layer numbers, negative ones counting from the end (-1: the last layer); .attention_layers carries the resolved
+        numbers.  attention_reduce (ours): None, or "mean_heads" for the mean over the heads, [B, 1, 1, L_t], taken on the device.  Two
+        deviations from HF: step 0 gives only the LAST prompt row, [B, H, 1, S_0] (S_0 the longest spliced prompt), not HF's [B, H, S,
+        S]; and the key axis is each sequence's cache positions 0 .. len_b - 1 whatever the padding side (position k is the k-th
+        valid position of the spliced row), with zeros beyond a row's length -- L_t grows by one per step.  A finished row's entries
+        at later steps are whatever the padded step computes and mean nothing; .sequences tells where each row ended.
+        radvlm_amd.attention_maps turns the rows into per-image patch maps.  It composes with the processors, sampling, constraint,
+        stopping_criteria and quantised decoders; with kv_cache_dtype="int8", past_key_values, prompt_lookup_num_tokens,
+        guidance_scale, dola_layers or live LoRA adapters NotImplementedError; a non-bool, a missing return_dict_in_generate, a bad
+        attention_reduce, attention_layers with a bool, a non-int, a duplicate or a value outside [-layers, layers), or either of
+        our two keywords without output_attentions: ValueError.
         The training state (weights, optimizer, RNG counters) is not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=self._lora_refused, config_eos=getattr(self.config, "eos_token_id", None),
-                                    config_pad=getattr(self.config, "pad_token_id", None), lookup=True)
+                                    config_pad=getattr(self.config, "pad_token_id", None), lookup=True, attentions=True)
         if inputs is None:
             raise ValueError("generate() needs the prompt token ids (`inputs`)")
         imgs = None if images is None else (list(images) if not torch.is_tensor(images) else [im for im in images])

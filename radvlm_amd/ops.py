@@ -798,6 +798,38 @@ def attn_decode(q, cache, kv_len, H, Hkv, hd, v_off, out=None, chunk=128, scale=
     return out
 
 
+def attn_decode_probs(q, cache, kv_len, H, Hkv, hd, L_out, per_head=True, mean=False, scale=None, out=None, mean_out=None):
+    """The attention probabilities attn_decode's softmax never writes out (rv_attn_decode_probs_f32): q, cache, kv_len as in attn_decode
+    (the cache's rows may be strided: a layer's K|V view; V is not read), L_out <= L_max columns.  Returns (probs, mean): fp32
+    [B, H, L_out] softmax(scale * q K^T) over each row's keys [0, min(kv_len[b], L_out)) when per_head, and fp32 [B, L_out], its mean
+    over the heads in head order, when mean; None for the one not asked for.  Columns at or past a row's key count are 0.
+    out / mean_out: write into these instead (fp32 [B, H, >= L_out] with rows packed per sequence / [B, >= L_out], unit column
+    stride; columns >= L_out are left as they are); they turn per_head / mean on."""
+    _chk(q), _chk(cache), _chk(kv_len, torch.int32)
+    B, L_max, width = cache.shape
+    L_out = int(L_out)
+    per_head, mean = per_head or out is not None, mean or mean_out is not None
+    assert q.shape == (B, H * hd) and q.stride(1) == 1 and cache.stride(2) == 1 and kv_len.numel() == B and kv_len.is_contiguous()
+    assert (per_head or mean) and 1 <= L_out <= L_max
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if per_head and out is None:
+        out = torch.empty(B, H, L_out, dtype=torch.float32, device=q.device)
+    if mean and mean_out is None:
+        mean_out = torch.empty(B, L_out, dtype=torch.float32, device=q.device)
+    if out is not None:
+        _chk(out, torch.float32)
+        assert out.shape[:2] == (B, H) and out.shape[2] >= L_out and out.stride(2) == 1 and (B == 1 or out.stride(0) == H * out.stride(1))
+    if mean_out is not None:
+        _chk(mean_out, torch.float32)
+        assert mean_out.shape[0] == B and mean_out.shape[1] >= L_out and mean_out.stride(1) == 1
+    ws_bytes = lib.load().rv_attn_decode_probs_ws_bytes(B, H, L_out)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q.device)
+    lib.call("rv_attn_decode_probs_f32", q, q.stride(0), cache, cache.stride(1), cache.stride(0), kv_len, L_max, L_out, out,
+             out.stride(1) if out is not None else 0, mean_out, mean_out.stride(0) if mean_out is not None else 0, ws, ws_bytes, B, H, Hkv,
+             hd, float(scale))
+    return (out[:, :, :L_out] if out is not None else None), (mean_out[:, :L_out] if mean_out is not None else None)
+
+
 EXTEND_CHUNK = 256        # keys per extend-attention workgroup: fixed, so a row's result never depends on the batch around it
 
 

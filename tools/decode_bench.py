@@ -453,12 +453,14 @@ def w8_trace(geo, prompt, new):
                  kernel_src=_src_hash())]
 
 
-def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None, con=None):
+def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None, con=None, attn=None):
     """Median decode step (decode_step + token choice) in ms; with `lp` (generation.LogitsProcessors) the token comes from
     rv_logits_process_argmax_f32 and is recorded in the device history, as greedy_generate does; with `sm` (the sampling settings of
     parse_generate_kwargs) it is drawn by rv_sample_rows_f32, row b with seed sm.seed + b, as greedy_generate does.  kv_dtype: the
     cache's dtype (prefill's kv_dtype).  con (a constraints.TokenConstraint for every row): ops.constrain_rows advances and masks each
-    step's rows before the token choice, as greedy_generate does (the host mirror of the states is not part of the loop)."""
+    step's rows before the token choice, as greedy_generate does (the host mirror of the states is not part of the loop).  attn
+    (decode_step's attn_layers= / attn_mean= as a dict): every step also returns its attention maps, as generate(output_attentions=True)
+    asks for them; they are dropped here."""
     B = ids.shape[0]
     cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new, **({} if kv_dtype is None else dict(kv_dtype=kv_dtype)))
     if con is not None:
@@ -485,7 +487,7 @@ def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None, con=Non
     for t in range(1, new):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        logits = eng.decode_step(cache, tok.to(torch.int32))
+        logits = eng.decode_step(cache, tok.to(torch.int32)) if attn is None else eng.decode_step(cache, tok.to(torch.int32), **attn)[0]
         if con is not None:
             ops.constrain_rows(logits, eng.vocab, cstate, tabs, tok=tok)
         tok = choose(logits, t)
@@ -1162,6 +1164,36 @@ def dola_ab(geo, batches, prompt, new, reps=3):
     return recs
 
 
+def attentions_ab(geo, batches, prompt, new, reps=3):
+    """The decode step that also returns its attention maps (decode_step(attn_layers=), what generate(output_attentions=True) runs)
+    beside the plain decode step on one engine, interleaved `reps` times after one untimed pass of every arm: every layer and the
+    last layer only, per head and as the head mean.  One record per batch size; nothing gates on it."""
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    L = eng.l["layers"]
+    recs = []
+    for B in batches:
+        ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+        arms = {"plain": None}
+        for lname, layers in (("all", tuple(range(L))), ("last", (L - 1,))):
+            for rname, mean in (("per_head", False), ("mean_heads", True)):
+                arms[f"{lname}_{rname}"] = dict(attn_layers=layers, attn_mean=mean)
+        for kw in arms.values():                                        # one untimed pass of every arm
+            _decode_loop(eng, ids, min(new, 16), attn=kw, warm=0)
+        ts = {k: [] for k in arms}
+        for _ in range(reps):
+            for k, kw in arms.items():
+                ts[k].append(float(np.median(_decode_loop(eng, ids, new, attn=kw))))
+        med = {k: float(np.median(v)) for k, v in ts.items()}
+        rec = dict(geo=geo, mode="attentions_ab", B=B, prompt=prompt, new_tokens=new, reps=reps, layers=L, heads=eng.l["heads"],
+                   kv_heads=eng.Hkv, head_dim=eng.hd)
+        for k in arms:
+            rec[f"{k}_ms_per_step"], rec[f"{k}_ms_all"], rec[f"{k}_spread_ms"] = round(med[k], 3), [round(x, 3) for x in ts[k]], round(max(ts[k]) - min(ts[k]), 3)
+            if k != "plain":
+                rec[f"{k}_added_ms"], rec[f"{k}_over_plain"] = round(med[k] - med["plain"], 3), round(med[k] / med["plain"], 3)
+        recs.append(rec)
+    return recs
+
+
 def lora_weight_bytes(eng):
     """Bytes of the adapters a decode step streams: lora_A [r, in] and lora_B [out, r] of every layer's seven modules."""
     return 2 * sum(eng.lm.view(n).numel() for n in eng.lm.names() if ".lora_" in n)
@@ -1818,6 +1850,7 @@ def main():
     ap.add_argument("--cfg-kernel-ab", action="store_true")
     ap.add_argument("--dola", action="store_true")
     ap.add_argument("--dola-shapes", action="store_true")
+    ap.add_argument("--attentions", action="store_true")
     ap.add_argument("--constraint", action="store_true")
     ap.add_argument("--lora", action="store_true")
     ap.add_argument("--shared-shapes", action="store_true")
@@ -1868,6 +1901,9 @@ def main():
         recs = dola_shapes()
     elif a.dola:
         recs = [r for g in a.geos.split(",") for r in dola_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new, reps=min(a.reps, 3))]
+    elif a.attentions:
+        batches = a.batches if a.batches != ap.get_default("batches") else "1,32"
+        recs = [r for g in a.geos.split(",") for r in attentions_ab(g, list(map(int, batches.split(","))), a.prompt, a.new, reps=min(a.reps, 3))]
     elif a.lora:
         batches = a.batches if a.batches != ap.get_default("batches") else "1,32"
         new = a.new if a.new != ap.get_default("new") else 40
