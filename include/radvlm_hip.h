@@ -331,6 +331,29 @@ int rv_seq_logp_sums_f64(const float* logp, const int32_t* seg_off, const int32_
 int rv_dpo_pairs_f64(const float* logp, const int32_t* seg_off, const int32_t* row_idx, const double* rho, int P, int loss_type, double beta,
                      double label_smoothing, double alpha_over_P, double gamma_over_Nc, double* planes, double* batch, float* coef,
                      int rows, void* stream);
+/* GRPO with sequence-level importance ratios (GSPO; TRL importance_sampling_level="sequence"), launch (B) between the same two sweeps:
+ * B sequences in scored order (seg_off has B + 1 entries, row_idx as above), one workgroup per sequence.  lweight, gweight, old_logp
+ * (NULL: on-policy) and ref_logp (NULL unless beta > 0) are the fp32 per-row arrays rv_policy_loss_bf16 takes, adv_seq fp32 [B] one
+ * advantage per sequence.  With n the scored tokens of sequence b and A = adv_seq[b], in fp64 on the fp32 inputs, one rounding per
+ * operation (no fused multiply-adds), every sum over the sequence's tokens in THE SUM ORDER:
+ *   m = sum_j (logp_j - old_j) / n  (each difference formed in fp64; old_logp == NULL or n == 0: m = +0);   s = exp(m), exactly 1 when m == 0
+ *   sc = min(max(s, 1 - eps_low), 1 + eps_high);   act = (s A <= sc A);   l = -(act ? s A : sc A)  (n == 0: l = 0)
+ *   beta > 0: q_j = ref_j - logp_j, kl_j = expm1(q_j) - q_j  (else kl_j = 0);   W_l = sum_j lweight_j, W_g = sum_j gweight_j
+ *   coef_j = fp32(([act] s A) (W_g / n) + (gweight_j beta) expm1(q_j))  (beta == 0: the first product alone);   kl_j is stored as fp32(kl_j)
+ * coef_j = -dL/dlogp_j of L below with gweight in lweight's place: sweep (C) with adv = coef, lweight = gweight = 1, no old or reference
+ * log-probs and beta = 0 writes dlogits = (p - onehot) coef.  coef and kl are written at scored rows only.
+ * planes: five fp64 planes of B entries -- m, s, l, the clip code (0 active; 1: s < 1 - eps_low and A < 0; 2: s > 1 + eps_high and
+ * A > 0), sum_j lweight_j kl_j.  batch (fp64 [2], written by a one-wave kernel, the sums over the sequences in THE SUM ORDER, after
+ * the sequence kernel):   batch[1] = beta sum_b planes[4][b];   batch[0] = L = sum_b (W_l,b l_b) + batch[1].
+ * An empty sequence writes m = +0, s = 1, l = 0, code 0 and touches no row.
+ * Bit promise: with old_logp NULL or equal to logp, beta == 0 or ref_logp equal to logp, and gweight constant inside each sequence,
+ * coef_j == gweight_j * adv_seq[b] as fp32 multiplies them -- the coefficient of rv_policy_loss_bf16 at r = 1 (n < 2^29 copies of one
+ * fp32 value sum exactly in fp64, the division by n is exact, and one rounding of the exact 48-bit product is the fp32 product).
+ * Refused (RV_ERR_ARG, nothing launched): a null logp / seg_off / adv_seq / lweight / gweight / planes / batch / coef / kl, B < 1,
+ * rows < 1, eps_low / eps_high / beta negative or NaN, beta > 0 without ref_logp. */
+int rv_gspo_seqs_f64(const float* logp, const int32_t* seg_off, const int32_t* row_idx, const float* adv_seq, const float* lweight,
+                     const float* gweight, const float* old_logp, const float* ref_logp, double eps_low, double eps_high, double beta,
+                     double* planes, double* batch, float* coef, float* kl, int B, int rows, void* stream);
 
 /* ---- embedding splice ---------------------------------------------------------------------------------------------
  * prepare_inputs_labels_for_multimodal steps (vi)-(viii), llava_arch.py:449-531, as one gather:

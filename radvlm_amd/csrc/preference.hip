@@ -1,5 +1,6 @@
-// DPO preference training, the sequence-level part between the two sweeps of rv_policy_loss_bf16: per-sequence sums of the scored
-// tokens' log-probs (rv_seq_logp_sums_f64) and the pairwise loss with its per-token gradient coefficients (rv_dpo_pairs_f64).
+// The sequence-level part between the two sweeps of rv_policy_loss_bf16, for DPO and for GRPO with sequence-level importance ratios
+// (GSPO): per-sequence sums of the scored tokens' log-probs (rv_seq_logp_sums_f64), the pairwise DPO loss (rv_dpo_pairs_f64) and the
+// clipped sequence ratio (rv_gspo_seqs_f64), the last two with their per-token gradient coefficients.
 // Everything here is fp64 on fp32 inputs, in a fixed order (include/radvlm_hip.h states it), without atomics and without a host
 // round trip.  The arithmetic is written one rounding per operation: no contraction into fused multiply-adds, so that
 // tests/preference_ref.py can restate it operation by operation.
@@ -11,21 +12,28 @@
 namespace {
 
 constexpr int PAIR_TPB = 128;          // wave 0 sums the chosen answer, wave 1 the rejected one; both write coefficients
+constexpr int GSPO_TPB = 256;          // one wave per sum of the sequence (log-ratio, lweight, gweight, lweight * kl); all write coefficients
 enum { LOSS_SIGMOID = 0, LOSS_HINGE = 1, LOSS_IPO = 2 };
 enum { PL_PI_C = 0, PL_PI_R, PL_H, PL_LOSS, PL_REWARD_C, PL_REWARD_R, PL_SUM_C, N_PLANES };
+enum { GP_M = 0, GP_S, GP_L, GP_CLIP, GP_WKL, N_GSPO_PLANES };
 
 // Scored token j lives in row j (row_idx NULL) or row_idx[j]; a row outside [0, rows) is never touched.
 DEVINL long row_of(const int32_t* row_idx, int j) { return row_idx ? (long)row_idx[j] : (long)j; }
 
-// The sum of one sequence by one wave: lane l adds elements l, l + 64, ... of [j0, j1) in ascending order to a +0.0 accumulator,
-// then the xor butterfly 32, 16, 8, 4, 2, 1 (every lane ends with the same bits).  It depends on the sequence's own length alone.
-DEVINL double seq_sum(const float* logp, const int32_t* row_idx, int j0, int j1, int rows) {
+// The sum of one sequence by one wave: lane l adds term(row) of elements l, l + 64, ... of [j0, j1) in ascending order to a +0.0
+// accumulator, then the xor butterfly 32, 16, 8, 4, 2, 1 (every lane ends with the same bits).  It depends on the sequence's own
+// length alone.
+template <class Term>
+DEVINL double seq_sum_of(const int32_t* row_idx, int j0, int j1, int rows, Term term) {
     double a = 0.0;
     for (int j = j0 + lane_id(); j < j1; j += 64) {
         const long r = row_of(row_idx, j);
-        if (r >= 0 && r < rows) a += (double)logp[r];
+        if (r >= 0 && r < rows) a += term(r);
     }
     return wave_sum_f64(a);
+}
+DEVINL double seq_sum(const float* logp, const int32_t* row_idx, int j0, int j1, int rows) {
+    return seq_sum_of(row_idx, j0, j1, rows, [=](long r) { return (double)logp[r]; });
 }
 
 __global__ __launch_bounds__(64) void seq_logp_sums_kernel(const float* logp, const int32_t* seg_off, const int32_t* row_idx, double* sums,
@@ -112,6 +120,93 @@ __global__ __launch_bounds__(64) void dpo_batch_kernel(const double* planes, con
     }
 }
 
+// GSPO's clipped sequence term: ua = s A, ca = clamp(s, 1 - eps_low, 1 + eps_high) A; the unclipped one is active when it is the minimum.
+struct SeqClip { double ua, loss; bool act; };
+DEVINL SeqClip seq_clip(double s, double A, double eps_low, double eps_high) {
+    const double sc = fmin(fmax(s, 1.0 - eps_low), 1.0 + eps_high);
+    const double ua = s * A, ca = sc * A;
+    const bool act = ua <= ca;
+    return {ua, -(act ? ua : ca), act};
+}
+// k3 of one token: q = ref - logp, em1 = expm1(q), kl = em1 - q
+DEVINL double k3(const float* ref_logp, const float* logp, long r, double* em1) {
+    const double q = (double)ref_logp[r] - (double)logp[r];
+    *em1 = expm1(q);
+    return *em1 - q;
+}
+
+__global__ __launch_bounds__(GSPO_TPB) void gspo_seqs_kernel(const float* logp, const int32_t* seg_off, const int32_t* row_idx,
+                                                             const float* adv_seq, const float* lweight, const float* gweight,
+                                                             const float* old_logp, const float* ref_logp, double eps_low, double eps_high,
+                                                             double beta, int B, double* planes, float* coef, float* kl, int rows) {
+    __shared__ double red[4];
+    const int b = blockIdx.x, w = wave_id();
+    const int j0 = seg_off[b], j1 = seg_off[b + 1], n = j1 - j0;
+    double mine = 0.0;
+    if (w == 0) {
+        if (old_logp) mine = seq_sum_of(row_idx, j0, j1, rows, [=](long r) { return (double)logp[r] - (double)old_logp[r]; });
+    } else if (w == 1) {
+        mine = seq_sum_of(row_idx, j0, j1, rows, [=](long r) { return (double)lweight[r]; });
+    } else if (w == 2) {
+        mine = seq_sum_of(row_idx, j0, j1, rows, [=](long r) { return (double)gweight[r]; });
+    } else if (beta > 0.0) {                                 // the entry point has checked ref_logp
+        mine = seq_sum_of(row_idx, j0, j1, rows, [=](long r) {
+            double em1;
+            return (double)lweight[r] * k3(ref_logp, logp, r, &em1);
+        });
+    }
+    if (lane_id() == 0) red[w] = mine;
+    __syncthreads();
+    // every thread forms the sequence's scalars: a few uniform flops
+    const double m = n > 0 ? red[0] / (double)n : 0.0;
+    const double s = m == 0.0 ? 1.0 : exp(m);                // on-policy is exactly 1, whatever the library's exp returns at 0
+    const double A = (double)adv_seq[b];
+    const SeqClip c = seq_clip(s, A, eps_low, eps_high);
+    if (threadIdx.x == 0) {
+        const double code = c.act ? 0.0 : (A < 0.0 && s < 1.0 - eps_low) ? 1.0 : (A > 0.0 && s > 1.0 + eps_high) ? 2.0 : 0.0;
+        planes[GP_M * (long)B + b] = m;
+        planes[GP_S * (long)B + b] = s;
+        planes[GP_L * (long)B + b] = red[1];                 // the lweight sum, until gspo_batch_kernel has used it and writes l here
+        planes[GP_CLIP * (long)B + b] = code;
+        planes[GP_WKL * (long)B + b] = red[3];
+    }
+    if (n <= 0) return;
+    const double pg = (c.act ? c.ua : 0.0) * (red[2] / (double)n);
+    for (int j = j0 + (int)threadIdx.x; j < j1; j += GSPO_TPB) {
+        const long r = row_of(row_idx, j);
+        if (r < 0 || r >= rows) continue;
+        double g = pg, k = 0.0;
+        if (beta > 0.0) {
+            double em1;
+            k = k3(ref_logp, logp, r, &em1);
+            g = pg + ((double)gweight[r] * beta) * em1;
+        }
+        coef[r] = (float)g;
+        kl[r] = (float)k;
+    }
+}
+
+// Plane l = -min(s A, sc A) (0 for an empty sequence); batch[1] = beta * sum_b plane_wkl, batch[0] = L = sum_b (lweight sum)_b l_b +
+// batch[1]: one wave, the sums over the sequences in seq_sum's order, as dpo_batch_kernel.
+__global__ __launch_bounds__(64) void gspo_batch_kernel(double* planes, const int32_t* seg_off, const float* adv_seq, int B, double eps_low,
+                                                        double eps_high, double beta, double* batch) {
+    double sl = 0.0, sk = 0.0;
+    for (int b = lane_id(); b < B; b += 64) {
+        const double W = planes[GP_L * (long)B + b];
+        const double l = seg_off[b + 1] > seg_off[b] ? seq_clip(planes[GP_S * (long)B + b], (double)adv_seq[b], eps_low, eps_high).loss : 0.0;
+        planes[GP_L * (long)B + b] = l;
+        sl += W * l;
+        sk += planes[GP_WKL * (long)B + b];
+    }
+    sl = wave_sum_f64(sl);
+    sk = wave_sum_f64(sk);
+    if (threadIdx.x == 0) {
+        const double bk = beta * sk;
+        batch[0] = sl + bk;
+        batch[1] = bk;
+    }
+}
+
 }  // namespace
 
 extern "C" int rv_seq_logp_sums_f64(const float* logp, const int32_t* seg_off, const int32_t* row_idx, double* sums, int B, int rows,
@@ -133,5 +228,16 @@ extern "C" int rv_dpo_pairs_f64(const float* logp, const int32_t* seg_off, const
     hipLaunchKernelGGL(dpo_pairs_kernel, dim3(P), dim3(PAIR_TPB), 0, ST, logp, seg_off, row_idx, rho, P, loss_type, beta, label_smoothing,
                        alpha_over_P, gamma_over_Nc, planes, coef, rows);
     hipLaunchKernelGGL(dpo_batch_kernel, dim3(1), dim3(64), 0, ST, (const double*)planes, seg_off, P, alpha_over_P, gamma_over_Nc, batch);
+    return rv_check_launch();
+}
+
+extern "C" int rv_gspo_seqs_f64(const float* logp, const int32_t* seg_off, const int32_t* row_idx, const float* adv_seq, const float* lweight,
+                                const float* gweight, const float* old_logp, const float* ref_logp, double eps_low, double eps_high,
+                                double beta, double* planes, double* batch, float* coef, float* kl, int B, int rows, void* stream) {
+    if (!logp || !seg_off || !adv_seq || !lweight || !gweight || !planes || !batch || !coef || !kl || B < 1 || rows < 1) return RV_ERR_ARG;
+    if (!(eps_low >= 0.0) || !(eps_high >= 0.0) || !(beta >= 0.0) || (beta > 0.0 && !ref_logp)) return RV_ERR_ARG;
+    hipLaunchKernelGGL(gspo_seqs_kernel, dim3(B), dim3(GSPO_TPB), 0, ST, logp, seg_off, row_idx, adv_seq, lweight, gweight, old_logp,
+                       ref_logp, eps_low, eps_high, beta, B, planes, coef, kl, rows);
+    hipLaunchKernelGGL(gspo_batch_kernel, dim3(1), dim3(64), 0, ST, planes, seg_off, adv_seq, B, eps_low, eps_high, beta, batch);
     return rv_check_launch();
 }

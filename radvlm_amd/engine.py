@@ -1599,7 +1599,10 @@ class LlavaEngine:
         sample.  gathered: the head ran on the labelled rows alone (rows 0 .. n - 1 in scored order, then pad rows with label -100);
         else the per-token terms are scattered by lab_rows.  terms None (token_logps): statistics only, every coefficient zero.
         Leaves self.last_policy: logp, loss, kl, clip (0 active / 1 low / 2 high) fp32 [n_scored] and ratio_one bool [n_scored] (no old
-        log-probs were given: r = 1 exactly), device tensors in scored order, plus scored = the per-sample counts (host)."""
+        log-probs were given: r = 1 exactly), device tensors in scored order, plus scored = the per-sample counts (host).
+        terms.importance_sampling_level == "sequence": the three launches of _policy_loss_sequence instead."""
+        if terms is not None and terms.importance_sampling_level == "sequence":
+            return self._policy_loss_sequence(logits, tgt, lab_rows, gathered, scored, terms, gscale, grad)
         n, per_row, pick = self._scored_rows(logits.shape[0], lab_rows, gathered, scored)
         if terms is None:
             adv, w, old, ref = np.zeros(n), np.zeros(n), None, None
@@ -1613,6 +1616,44 @@ class LlavaEngine:
         self.last_policy = dict(logp=st[0], loss=st[1], kl=st[3], clip=st[4], scored=np.asarray(scored),
                                 ratio_one=torch.full((n,), old is None, dtype=torch.bool, device=logits.device))
         return loss
+
+    def _policy_loss_sequence(self, logits, tgt, lab_rows, gathered, scored, terms, gscale, grad=True):
+        """_policy_loss with one importance ratio per sample (GSPO), the three launches of _preference_loss on the same head rows:
+          (A) rv_policy_loss_bf16 without dlogits: the logp row of every scored token (token_logps()'s bits);
+          (B) rv_gspo_seqs_f64: per-sample fp64 sums in the fixed order, the clipped sequence ratio, one coefficient -dL/dlogp and the
+              k3 term per scored token, from the lweight / gweight / old / reference rows the token level hands to its kernel;
+          (C) (grad) rv_policy_loss_bf16 in place with adv = those device rows, lweight 1, gweight 1, no old or reference log-probs,
+              beta 0: r = 1 exactly, so dlogits = (p - onehot) * coef.
+        Nothing comes back to the host in between.  Leaves self.last_policy with _policy_loss's keys per scored token -- loss and clip
+        are the sample's l and clip code, repeated -- plus coefs (fp32 [n_scored]) and seq_logratio, seq_ratio, seq_clip (fp64 [B]).
+        Returns L as fp32 [1]."""
+        from . import lib
+        rows, dev = logits.shape[0], logits.device
+        n, per_row, pick = self._scored_rows(rows, lab_rows, gathered, scored)
+        _, w, old, ref = terms.per_token(scored)
+        adv_seq, seg_off = terms.per_sequence(scored)
+        eps_low, eps_high, beta = float(terms.epsilon), terms.eps_high, float(terms.beta)
+        f32 = lambda a: None if a is None else self._dev(a.astype(np.float32))
+        w_rows = per_row(w)
+        lweight, gweight = f32(w_rows), f32(w_rows * float(gscale))         # ops.policy_loss's two roundings of the weight
+        zero = torch.zeros(rows, dtype=torch.float32, device=dev)
+        stats = torch.empty(len(ops.POLICY_STATS), rows, dtype=torch.float32, device=dev)
+        lib.call("rv_policy_loss_bf16", logits, logits.stride(0), tgt, zero, zero, zero, None, None, 0.0, 0.0, 0.0, stats, None, 0, rows, self.vocab)
+        row_idx = None if gathered else self._dev(lab_rows.astype(np.int32))
+        coef, kl = torch.zeros(rows, dtype=torch.float32, device=dev), torch.zeros(rows, dtype=torch.float32, device=dev)
+        planes, batch = ops.gspo_seqs(stats[0], self._dev(seg_off), row_idx, f32(adv_seq), lweight, gweight, f32(per_row(old)),
+                                      f32(per_row(ref if beta > 0 else None)), eps_low, eps_high, beta, coef, kl)
+        if grad:
+            ones = torch.ones(rows, dtype=torch.float32, device=dev)
+            lib.call("rv_policy_loss_bf16", logits, logits.stride(0), tgt, coef, ones, ones, None, None, 0.0, 0.0, 0.0, torch.empty_like(stats),
+                     logits, logits.stride(0), rows, self.vocab)
+        logp, coefs, kls = pick(stats[0], coef, kl)
+        seq_of = self._dev(np.repeat(np.arange(len(adv_seq)), np.asarray(scored, dtype=np.int64)))
+        plane = dict(zip(ops.GSPO_PLANES, planes))
+        self.last_policy = dict(logp=logp, loss=plane["loss"][seq_of].to(torch.float32), kl=kls, clip=plane["clip"][seq_of].to(torch.float32),
+                                scored=np.asarray(scored), ratio_one=torch.full((n,), old is None, dtype=torch.bool, device=dev),
+                                coefs=coefs, seq_logratio=plane["logratio"], seq_ratio=plane["ratio"], seq_clip=plane["clip"])
+        return batch[:1].to(torch.float32)
 
     def token_logps(self, input_ids, attention_mask, labels, images, image_sizes=None):
         """log p(label) of every scored token (the positions of each spliced row whose shifted target is not -100, sample by sample,

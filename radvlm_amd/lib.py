@@ -89,6 +89,8 @@ _SIGS = {
     "rv_seq_logp_sums_f64": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _c_void_p],
     "rv_dpo_pairs_f64": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _f64, _f64, _f64, _f64, _c_void_p, _c_void_p, _c_void_p, _i32,
                          _c_void_p],
+    "rv_gspo_seqs_f64": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _f64, _f64, _f64, _c_void_p,
+                         _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _c_void_p],
     "rv_gather_rows": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p],
     "rv_segment_sum_rows": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i64, _i32, _c_void_p],
     "rv_normalize_tiles_u8": [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _c_void_p],

@@ -275,7 +275,7 @@ class LlavaLlamaForCausalLM:
         return host(input_ids), host(attention_mask), host(labels), (list(images) if not torch.is_tensor(images) else [im for im in images])
 
     def policy_loss(self, input_ids, attention_mask, labels, images, image_sizes=None, *, advantages, weights=None, old_logps=None,
-                    ref_logps=None, epsilon=0.2, epsilon_high=None, beta=0.0):
+                    ref_logps=None, epsilon=0.2, epsilon_high=None, beta=0.0, importance_sampling_level="token"):
         """The GRPO token loss (TRL's GRPOTrainer: the clipped surrogate, plus beta times the k3 KL estimate against ref_logps) on a batch
         of prompt + completion rows; labels mark the completion tokens, as for forward().  Scored tokens of sample b: the positions of
         its spliced row whose shifted target is not -100, ascending.  advantages: one float per sample, or one array per sample, or
@@ -284,18 +284,29 @@ class LlavaLlamaForCausalLM:
         counts, a non-finite value, a negative epsilon / beta, or beta > 0 without ref_logps: ValueError.
         Returns an output with .loss = sum(weight * loss) (fp32 scalar; .loss.backward() runs the engine's backward, gradients scaled
         by engine.loss_scale as in forward()), .logps / .kl / .clip per scored token (device tensors) and .stats: n_scored and the
-        device scalars kl, clip_ratio/low, clip_ratio/high (means over the scored tokens)."""
+        device scalars kl, clip_ratio/low, clip_ratio/high (means over the scored tokens).
+        importance_sampling_level="sequence" (TRL's keyword; GSPO): one ratio per sample, s = exp(mean over its scored tokens of logp -
+        old_logp), clipped once, every token of the sample weighted alike; the KL term stays per token.  It needs one advantage per
+        sample (advantages that vary inside a sample: ValueError); GSPO's usual clip range is a few 1e-4, not 0.2.  .loss and .clip
+        then repeat the sample's term and clip code over its tokens, the output adds .coefs (fp32 per scored token: -dL/dlogp) and
+        .seq_ratio / .seq_logratio / .seq_clip (fp64 [B], device), and clip_ratio/low and clip_ratio/high are means over the samples
+        that have a scored token -- the reduction TRL uses at this level."""
         from ...policy import PolicyTerms
         ids, am, lab, imgs = self._host_batch(input_ids, attention_mask, labels, images)
         terms = PolicyTerms(advantages=advantages, weights=weights, old_logps=old_logps, ref_logps=ref_logps, epsilon=epsilon,
-                            epsilon_high=epsilon_high, beta=beta)
+                            epsilon_high=epsilon_high, beta=beta, importance_sampling_level=importance_sampling_level)
         loss = self.engine.forward(ids, am, lab, imgs, image_sizes=image_sizes, policy=terms)
         lp = self.engine.last_policy
         n = int(lp["logp"].numel())
         mean = lambda t: t.float().mean() if n else torch.zeros((), device=self.engine.device)
         stats = {"n_scored": n, "kl": mean(lp["kl"]), "clip_ratio/low": mean(lp["clip"] == 1), "clip_ratio/high": mean(lp["clip"] == 2)}
+        extra = {}
+        if importance_sampling_level == "sequence":
+            code = lp["seq_clip"][self.engine._dev(np.flatnonzero(np.asarray(lp["scored"]) > 0))]
+            stats.update({"clip_ratio/low": mean(code == 1), "clip_ratio/high": mean(code == 2)})
+            extra = dict(coefs=lp["coefs"], seq_ratio=lp["seq_ratio"], seq_logratio=lp["seq_logratio"], seq_clip=lp["seq_clip"])
         return SimpleNamespace(loss=_StepFunction.apply(self._anchor, self.engine, loss), logps=lp["logp"], kl=lp["kl"], clip=lp["clip"],
-                               stats=stats)
+                               stats=stats, **extra)
 
     @torch.no_grad()
     def token_logps(self, input_ids, attention_mask, labels, images, image_sizes=None):

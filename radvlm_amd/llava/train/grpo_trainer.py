@@ -21,7 +21,7 @@ import time
 import numpy as np
 import torch
 
-from ...policy import LOSS_TYPES, SCALE_REWARDS, assemble, group_advantages, sample_seeds, token_weights
+from ...policy import LOSS_TYPES, SCALE_REWARDS, assemble, check_importance_sampling_level, group_advantages, sample_seeds, token_weights
 from .llava_trainer import LLaVATrainer, epoch_index_batches, lr_at, warmup_steps_for
 
 _COLUMNS_SKIPPED = ("prompt_ids", "images", "image_sizes")
@@ -31,7 +31,8 @@ class GRPOTrainer(LLaVATrainer):
     """GRPOTrainer(model, args, train_dataset, reward_funcs, tokenizer=None, ref_model=None, reward_weights=None).
     args: TRL's names -- num_generations (8), max_completion_length (256), temperature (1.0), top_p (1.0), top_k (None), min_p (None),
     epsilon (0.2), epsilon_high (None: epsilon), beta (0.0), loss_type ("dapo"; "grpo", "bnpo", "dr_grpo"), scale_rewards ("group";
-    "batch", "none"), num_iterations (1), mask_truncated_completions (False), log_completions (False) -- and LLaVATrainer's for the
+    "batch", "none"), num_iterations (1), importance_sampling_level ("token"; "sequence": GSPO's one clipped ratio per completion, whose
+    usual epsilon is a few 1e-4), mask_truncated_completions (False), log_completions (False) -- and LLaVATrainer's for the
     optimizer, schedule, logging and checkpoints (per_device_train_batch_size = prompts per step, learning_rate, weight_decay,
     max_grad_norm, lr_scheduler_type, warmup_*, max_steps / num_train_epochs, seed, logging_steps, save_steps, output_dir, ...).
     A dataset item is a dict with prompt_ids (1-D token ids, IMAGE_TOKEN_INDEX where an image goes), optional images (one tensor or
@@ -56,6 +57,7 @@ class GRPOTrainer(LLaVATrainer):
         if self.loss_type not in LOSS_TYPES or self.scale_rewards not in SCALE_REWARDS:
             raise ValueError(f"loss_type must be one of {LOSS_TYPES} and scale_rewards one of {SCALE_REWARDS}")
         self.num_iterations = max(1, int(getattr(a, "num_iterations", 1) or 1))
+        self.importance_sampling_level = check_importance_sampling_level(getattr(a, "importance_sampling_level", "token"))
         self.max_completion_length = int(getattr(a, "max_completion_length", 256))
         self.ref_model = ref_model
         funcs = list(reward_funcs) if isinstance(reward_funcs, (list, tuple)) else [reward_funcs]
@@ -176,7 +178,8 @@ class GRPOTrainer(LLaVATrainer):
                     for j, m in enumerate(micros):
                         eng.sync_this_backward = j == len(micros) - 1
                         out = model.policy_loss(**batch_of(m), advantages=adv[m["rows"]], weights=weights[m["rows"]], old_logps=old[j],
-                                                ref_logps=ref[j], epsilon=eps, epsilon_high=eps_hi, beta=self.beta)
+                                                ref_logps=ref[j], epsilon=eps, epsilon_high=eps_hi, beta=self.beta,
+                                                importance_sampling_level=self.importance_sampling_level)
                         out.loss.backward()
                         outs.append(out)
                     update = (step - 1) * K + k + 1

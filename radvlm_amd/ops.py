@@ -502,6 +502,28 @@ def dpo_pairs(logp, seg_off, row_idx, rho, loss_type, beta, label_smoothing, alp
     return planes, batch
 
 
+GSPO_PLANES = ("logratio", "ratio", "loss", "clip", "wkl")      # rv_gspo_seqs_f64's planes, in order
+GSPO_BATCH = ("loss", "kl_loss")
+
+
+def gspo_seqs(logp, seg_off, row_idx, adv_seq, lweight, gweight, old_logp, ref_logp, eps_low, eps_high, beta, coef, kl):
+    """GRPO's sequence-level clipped ratio and the per-token gradient coefficients (rv_gspo_seqs_f64).  logp, lweight, gweight, old_logp
+    (or None), ref_logp (None unless beta > 0): fp32 [rows]; seg_off int32 [B + 1]; row_idx int32 or None; adv_seq fp32 [B]; coef and kl
+    fp32 [rows], written at the scored rows only.  Returns (planes fp64 [5, B] in GSPO_PLANES order, batch fp64 [2] in GSPO_BATCH order)."""
+    rows = logp.numel()
+    for t in (logp, adv_seq, lweight, gweight, coef, kl, old_logp, ref_logp):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert all(t is None or t.numel() == rows for t in (lweight, gweight, coef, kl, old_logp, ref_logp))
+    assert seg_off.dtype == torch.int32 and (row_idx is None or row_idx.dtype == torch.int32)
+    B = seg_off.numel() - 1
+    assert adv_seq.numel() == B
+    planes = torch.empty(len(GSPO_PLANES), B, dtype=torch.float64, device=logp.device)
+    batch = torch.empty(len(GSPO_BATCH), dtype=torch.float64, device=logp.device)
+    lib.call("rv_gspo_seqs_f64", logp, seg_off, row_idx, adv_seq, lweight, gweight, old_logp, ref_logp, float(eps_low), float(eps_high),
+             float(beta), planes, batch, coef, kl, B, rows)
+    return planes, batch
+
+
 def gather_rows(idx, d, table_a, table_b=None, out=None):
     rows = idx.numel()
     assert idx.dtype == torch.int32

@@ -95,7 +95,8 @@ def sample_seeds(base, step, n_prompts, num_generations):
 class PolicyTerms:
     """What the GRPO loss needs beside the batch.  advantages: one float per sample, or one array per sample (per scored token), or
     the concatenation of those.  weights: likewise (None: 1 / number of scored tokens of the batch).  old_logps / ref_logps: per
-    scored token (one array per sample or the concatenation) or None.  epsilon_high None: epsilon."""
+    scored token (one array per sample or the concatenation) or None.  epsilon_high None: epsilon.  importance_sampling_level:
+    "token" (one clipped ratio per token) or "sequence" (GSPO: one per sample, which then needs one advantage per sample)."""
     advantages: object
     weights: object = None
     old_logps: object = None
@@ -103,6 +104,10 @@ class PolicyTerms:
     epsilon: float = 0.2
     epsilon_high: object = None
     beta: float = 0.0
+    importance_sampling_level: str = "token"
+
+    def __post_init__(self):
+        check_importance_sampling_level(self.importance_sampling_level)
 
     @property
     def eps_high(self):
@@ -131,6 +136,34 @@ class PolicyTerms:
                 raise ValueError(f"{name} must be log-probabilities (<= 0)")
         assert adv.size == n and w.size == n and B == counts.size
         return adv, w, old, ref
+
+    def per_sequence(self, counts):
+        """The sequence level's view of the advantages: (adv_seq float64 [B], seg_off int32 [B + 1]), sample b owning the scored
+        tokens [seg_off[b], seg_off[b + 1]).  One ratio per sample needs one advantage per sample: ValueError when a sample's
+        per-token advantages vary.  A sample without scored tokens is legal (a masked truncated completion): it contributes
+        nothing and its advantage is reported as 0."""
+        counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+        adv = _expand("advantages", self.advantages, counts, per_sample_ok=True)
+        seg_off = np.concatenate([[0], np.cumsum(counts)])
+        if seg_off[-1] >= 1 << 31:
+            raise ValueError(f"{int(seg_off[-1])} scored tokens do not fit the kernel's int32 offsets")
+        adv_seq = np.zeros(counts.size, dtype=np.float64)
+        for b in range(counts.size):
+            a = adv[seg_off[b]:seg_off[b + 1]]
+            if a.size and (a != a[0]).any():
+                raise ValueError(f"importance_sampling_level='sequence' needs one advantage per sample; sample {b}'s vary over its tokens")
+            if a.size:
+                adv_seq[b] = a[0]
+        return adv_seq, seg_off.astype(np.int32)
+
+
+IMPORTANCE_SAMPLING_LEVELS = ("token", "sequence")
+
+
+def check_importance_sampling_level(level):
+    if level not in IMPORTANCE_SAMPLING_LEVELS:
+        raise ValueError(f"importance_sampling_level must be one of {IMPORTANCE_SAMPLING_LEVELS}, got {level!r}")
+    return level
 
 
 def _host(a):

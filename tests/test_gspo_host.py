@@ -1,0 +1,119 @@
+"""Host tests of GRPO's sequence-level importance ratios (GSPO): tests/gspo_ref.py against float64 torch autograd of the formula, its
+clip-edge refusal, the validation of policy.PolicyTerms, and the entry point's declaration.  No GPU."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import gspo_ref as G
+from radvlm_amd import policy as P
+
+COUNTS = np.array([1, 2, 0, 65], dtype=np.int64)          # one token, two, an empty sequence, one past the 64 accumulators
+ADV = np.array([-1.0, 0.7, 0.3, -0.4], dtype=np.float32).astype(np.float64)       # the kernel takes fp32 advantages
+SHIFT = np.array([0.5, -0.5, 0.0, 0.05])                    # old - logp per sequence: s = 0.61 (clipped low), 1.65 (clipped high), -, 0.95
+
+
+def _inputs(loss_type, seed=0):
+    rng = np.random.default_rng(seed)
+    n = int(COUNTS.sum())
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    logp = f32(-rng.exponential(0.7, n))
+    seq = np.repeat(np.arange(COUNTS.size), COUNTS)
+    old = f32(logp + SHIFT[seq] + rng.normal(0, 0.02, n))
+    ref = f32(logp + rng.normal(0, 0.3, n))
+    w = np.repeat(P.token_weights(COUNTS, loss_type, max_completion_length=80), COUNTS)
+    return logp, old, ref, f32(w), f32(w * 8.0)              # lweight, and gweight with a loss scale of 8
+
+
+def _autograd(logp, old, ref, weight, beta, eps_low, eps_high):
+    """L of the issue's formula in float64 torch, and -dL/dlogp per token."""
+    x = torch.tensor(logp.astype(np.float64), requires_grad=True)
+    w = torch.tensor(weight.astype(np.float64))
+    off = np.concatenate([[0], np.cumsum(COUNTS)])
+    L = torch.zeros((), dtype=torch.float64)
+    for b in range(COUNTS.size):
+        sl = slice(int(off[b]), int(off[b + 1]))
+        if COUNTS[b] == 0:
+            continue
+        d = x[sl] - torch.tensor(old[sl].astype(np.float64)) if old is not None else x[sl] - x[sl].detach()
+        s = torch.exp(d.mean())
+        sc = s.clamp(1.0 - eps_low, 1.0 + eps_high)
+        L = L + w[sl].sum() * -torch.minimum(s * ADV[b], sc * ADV[b])
+    if beta > 0:
+        q = torch.tensor(ref.astype(np.float64)) - x
+        L = L + beta * (w * (torch.expm1(q) - q)).sum()
+    L.backward()
+    return float(L), -x.grad.numpy()
+
+
+@pytest.mark.parametrize("loss_type", P.LOSS_TYPES)
+@pytest.mark.parametrize("beta", [0.0, 0.04])
+@pytest.mark.parametrize("with_old", [True, False])
+def test_restatement_matches_autograd(loss_type, beta, with_old):
+    logp, old, ref, lw, gw = _inputs(loss_type)
+    old = old if with_old else None
+    r = G.gspo(logp, COUNTS, ADV, lw, gw, old_logp=old, ref_logp=ref if beta > 0 else None, eps_low=0.2, eps_high=0.25, beta=beta)
+    L, _ = _autograd(logp, old, ref, lw, beta, 0.2, 0.25)
+    _, coef = _autograd(logp, old, ref, gw, beta, 0.2, 0.25)       # the coefficient carries gweight in lweight's place
+    assert abs(r["L"] - L) <= 1e-13 * max(1.0, abs(L))
+    assert np.abs(r["coef"] - coef).max() <= 1e-13 * max(1e-3, np.abs(coef).max())
+    assert r["clip"].tolist() == ([1.0, 2.0, 0.0, 0.0] if with_old else [0.0] * 4)
+    # the empty sequence: m = +0, s = 1, l = 0
+    assert (r["m"][2], r["s"][2], r["l"][2]) == (0.0, 1.0, 0.0) and not np.signbit(r["m"][2])
+    if not with_old:
+        assert (r["s"] == 1.0).all() and (r["m"] == 0.0).all()
+    if beta == 0:
+        assert not r["kl"].any() and r["kl_loss"] == 0.0
+
+
+def test_bit_promise_of_the_restatement():
+    """On-policy with weights constant inside each sequence, fp32(coef) is the fp32 product gweight * adv."""
+    for loss_type in P.LOSS_TYPES:
+        logp, _, _, lw, gw = _inputs(loss_type)
+        adv32 = ADV.astype(np.float32)
+        want = gw * np.repeat(adv32, COUNTS)
+        for kw in (dict(), dict(old_logp=logp), dict(ref_logp=logp, beta=0.04), dict(old_logp=logp, ref_logp=logp, beta=0.04)):
+            r = G.gspo(logp, COUNTS, adv32, lw, gw, **kw)
+            assert r["coef"].astype(np.float32).view(np.int32).tolist() == want.view(np.int32).tolist(), (loss_type, kw)
+
+
+def test_reference_rejects_a_clip_edge():
+    logp = np.full(4, -1.0, dtype=np.float32)
+    w = np.full(4, 0.25, dtype=np.float32)
+    for edge in (0.8, 1.2):
+        old = (logp - np.float32(np.log(edge))).astype(np.float32)       # s = edge up to fp32 rounding
+        with pytest.raises(AssertionError, match="clip edge"):
+            G.gspo(logp, [4], [1.0], w, w, old_logp=old, eps_low=0.2, eps_high=0.2)
+    G.gspo(logp, [4], [1.0], w, w, old_logp=(logp - np.float32(np.log(0.9))).astype(np.float32), eps_low=0.2, eps_high=0.2)
+
+
+def test_terms_validation_and_offsets():
+    with pytest.raises(ValueError, match="token.*sequence"):
+        P.PolicyTerms(advantages=[1.0], importance_sampling_level="sentence")
+    assert P.PolicyTerms(advantages=[1.0]).importance_sampling_level == "token"
+    counts = [2, 0, 3, 0]
+    t = P.PolicyTerms(advantages=[0.5, -1.0, 2.0, 7.0], importance_sampling_level="sequence")
+    adv_seq, seg_off = t.per_sequence(counts)
+    assert seg_off.dtype == np.int32 and seg_off.tolist() == [0, 2, 2, 5, 5]
+    assert adv_seq.dtype == np.float64 and adv_seq.tolist() == [0.5, 0.0, 2.0, 0.0]      # an empty sample contributes nothing
+    # per-token arrays that are constant inside each sample are one advantage per sample
+    t = P.PolicyTerms(advantages=[np.array([0.5, 0.5]), np.zeros(0), np.array([2.0, 2.0, 2.0]), np.zeros(0)], importance_sampling_level="sequence")
+    assert t.per_sequence(counts)[0].tolist() == [0.5, 0.0, 2.0, 0.0]
+    t = P.PolicyTerms(advantages=np.array([0.5, 0.5, 2.0, 2.0, 2.5]), importance_sampling_level="sequence")
+    with pytest.raises(ValueError, match="sample 2"):
+        t.per_sequence(counts)
+    # per_token keeps its results whatever the level
+    a = P.PolicyTerms(advantages=[0.5, -1.0, 2.0, 7.0], weights=[1.0, 2.0, 3.0, 4.0]).per_token(counts)
+    b = P.PolicyTerms(advantages=[0.5, -1.0, 2.0, 7.0], weights=[1.0, 2.0, 3.0, 4.0], importance_sampling_level="sequence").per_token(counts)
+    assert all(x is y or np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def test_entry_point_is_declared():
+    from radvlm_amd import lib, ops
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "radvlm_hip.h")).read()
+    assert re.search(r"\bint rv_gspo_seqs_f64\(", header)
+    assert "rv_gspo_seqs_f64" in lib._SIGS and "rv_gspo_seqs_f64" in lib.EXPORTED_SYMBOLS
+    assert ops.GSPO_PLANES == ("logratio", "ratio", "loss", "clip", "wkl") and callable(ops.gspo_seqs)
