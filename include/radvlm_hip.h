@@ -512,6 +512,38 @@ int rv_attn_decode_probs_f32(const void* q, int64_t ld_q, const void* cache, int
                              int L_out, void* probs, int64_t ld_p, void* mean, int64_t ld_m, void* ws, int64_t ws_bytes, int B, int H,
                              int Hkv, int hd, float scale, void* stream);
 int64_t rv_attn_decode_probs_ws_bytes(int B, int H, int L_out);
+/* SnapKV prompt-cache compression (kvpress.hip; reference: none -- the reference decodes with HF's uncompressed DynamicCache,
+ * transformers/cache_utils.py; the rule is Li et al. 2024, "SnapKV: LLM Knows What You Are Looking for Before Generation", restated in
+ * tests/kvpress_ref.py).  Sequence b has P_b = cu[b+1] - cu[b] rows in the packed q|k|v product of the prompt pass; its last w rows are
+ * the observation window, the n_b = P_b - w rows before it the prefix.  flags: int32 [B] or null; a sequence with flags[b] == 0 is
+ * skipped by all three.  No atomics; every reduction runs in an order that is a function of the sequence's own P_b, w and H / Hkv, so a
+ * sequence has the same bits alone and in any batch.
+ * rv_kv_votes_f32: votes[b][g][j] (fp32 [B][Hkv][ld_v], j < n_b) = the sum over the H / Hkv query heads h of kv head g and the w window
+ * rows t of softmax(scale * q[h, n_b + t] K_g^T)[j], each row's fp32 softmax over its causal keys [0, n_b + t].  q / k: the post-RoPE
+ * bf16 rows (row strides ld_q / ld_k, head h at columns h*hd), hd in {64, 128}, H / Hkv <= 8, 1 <= w <= 64; max_P >= every P_b sizes
+ * the grid.  Q K^T runs on v_mfma_f32_16x16x32_bf16 with each 128-key chunk (fixed in absolute position) staged once in LDS for all
+ * w * H / Hkv query rows; a first pass writes per-(row, chunk) max and sum, merged in chunk order, a second recomputes the scores and
+ * adds exp(s - m) / l.  V is never read; a key at or past P_b is never loaded, a key past a row's causal limit gets an exact-zero
+ * weight; columns [n_b, ld_v) are not touched, and a sequence with n_b < 1 is skipped.  ws: rv_kv_votes_ws_bytes(B, H, Hkv, w, max_P)
+ * bytes, contents arbitrary.
+ * rv_kv_select_i32: keep[b][g][0..N) (int32 [B][Hkv][N]) = the N - w prefix positions with the largest
+ * pooled[j] = max(votes[max(0, j - k/2) .. min(n_b - 1, j + k/2)]), ties to the lower position, in ascending order, then the window
+ * positions n_b .. P_b - 1.  Votes must be non-negative (they order as their bit patterns: a radix select, one bit per sweep).  Only
+ * sequences with P_b > N are written.  ws: rv_kv_select_ws_bytes(B, Hkv, ld_v) bytes.
+ * rv_kv_gather_bf16: for every sequence with P_b > N, slot s < N and kv head g, the K (columns g*hd) and V (columns v_off + g*hd) of
+ * row cu[b] + keep[b][g][s] of kv (row stride ld_kv) are copied to row seq[b] * L_max + s of cache (row stride ld_c, n_rows
+ * sequences of L_max rows); nothing else is written, and an entry of keep outside [0, P_b) or a seq[b] outside [0, n_rows) writes
+ * nothing.
+ * RV_ERR_ARG before any launch: the conditions of rv_attn_decode_probs_f32 on pointers, B, H, Hkv, hd and strides, and w outside
+ * [1, 64], max_P <= w, ld_v < max_P - w, N <= w, k even or outside [1, 63], N > L_max, a short workspace. */
+int rv_kv_votes_f32(const void* q, int64_t ld_q, const void* k, int64_t ld_k, const int32_t* cu, const int32_t* flags, int max_P, void* votes,
+                    int64_t ld_v, void* ws, int64_t ws_bytes, int B, int H, int Hkv, int hd, int w, float scale, void* stream);
+int64_t rv_kv_votes_ws_bytes(int B, int H, int Hkv, int w, int max_P);
+int rv_kv_select_i32(const void* votes, int64_t ld_v, const int32_t* cu, const int32_t* flags, void* keep, void* ws, int64_t ws_bytes, int B,
+                     int Hkv, int N, int w, int k, void* stream);
+int64_t rv_kv_select_ws_bytes(int B, int Hkv, int64_t ld_v);
+int rv_kv_gather_bf16(const void* kv, int64_t ld_kv, int v_off, const int32_t* cu, const int32_t* flags, const int32_t* keep,
+                      const int32_t* seq, void* cache, int64_t ld_c, int L_max, int n_rows, int B, int Hkv, int hd, int N, void* stream);
 /* Extend attention (the prompt pass of a continued generation, over a reused KV cache): sequence b has n_b = cu_q[b+1] - cu_q[b] >= 1
  * new query rows q[cu_q[b] .. cu_q[b+1]) at positions r[b] .. r[b] + n_b - 1, whose K|V rows are already in the cache; query i attends
  * causally to the keys [0, r[b] + i] of kv head h / (H / Hkv).  hd in {64, 128}, up to 8 q heads per kv head, fp32 softmax and

@@ -1046,6 +1046,12 @@ class LlavaEngine:
                                       "use a bf16 cache (kv_cache_dtype=None)")
 
     @staticmethod
+    def _refuse_pressed(cache, what):
+        if cache is not None and getattr(cache, "pos_off", None) is not None:
+            raise NotImplementedError(f"{what} on a cache compressed by prompt_kv_budget: its slots are not its positions, and only "
+                                      "prefill() and the plain decode_step() know the offset (KVCache.pos_off)")
+
+    @staticmethod
     def _slot_rows(slots, B, cache, ok=True):
         """slots= of prefill() and extend() as an int64 array: one distinct row of `cache` per prompt (ok: the caller's own count check)."""
         seq = np.asarray(slots, dtype=np.int64).reshape(-1)
@@ -1081,7 +1087,7 @@ class LlavaEngine:
         return self._decode_lora_linear(act, lv["down"], i, self._MODS_DOWN(d), residual=x_mid, wq=wq.get("down"), skinny=skinny)
 
     def prefill(self, input_ids, attention_mask=None, images=None, image_sizes=None, max_new_tokens=0, cache=None, slots=None, kv_dtype=None,
-                tap_layers=None, attn_layers=None, attn_mean=False):
+                tap_layers=None, attn_layers=None, attn_mean=False, compress=None):
         """The prompt pass of generation: multimodal splice (plan / encode_images, as in forward) and every decoder layer in the packed
         varlen layout, sequence b at cache rows and positions 0 .. len_b - 1 whatever the padding side.  Each layer's post-RoPE K|V rows go
         into a KVCache of len_b + max_new_tokens slots per sequence; the activations are dropped.  No loss, no saved context (self.ctx and
@@ -1103,12 +1109,34 @@ class LlavaEngine:
         ops.attn_decode_probs runs on those B rows against the cache layer just written, kv_len = len_b; the prompt pass's own
         attention is not touched and only those rows are kept.  The cache and the logits are the bits of the call without it.  Not
         combined with cache= / slots=, kv_dtype "int8" or tap_layers= (NotImplementedError).
+        compress (generate(prompt_kv_budget=N, prompt_kv_window=w, prompt_kv_pool=k)): (N, w, k), SnapKV prompt-cache compression.  A
+        sequence of P_b <= N prompt rows is cached as ever.  A longer one keeps N positions per layer and kv head: inside the layer loop
+        its window rows' attention votes for the prefix keys (ops.kv_votes on the layer's post-RoPE acts["qkv"]), ops.kv_select keeps the
+        N - w best max-pooled positions in ascending order plus the w window positions, and ops.kv_gather copies their K|V straight
+        from acts["qkv"] into slots 0 .. N - 1 of the cache layer: the full prompt is never cached.  cache.lens[b] is then N and
+        cache.pos_off[b] = P_b - N, so decode_step appends at slot lens and rotates at position lens + pos_off.  Without cache= the
+        returned cache has max_b min(P_b, N) + max_new_tokens slots and pos_off None when no sequence was compressed; with cache= /
+        slots= only those rows' lens and pos_off are set.  The prompt's own attention and the returned logits are not touched.
+        self.kvpress_trace (None; a test may set a list) receives (layer, votes, keep) per layer.  Not combined with attn_layers=,
+        tap_layers= or an int8 cache (NotImplementedError).
         Returns (cache, fp32 logits [B, vocab] of every sequence's last prompt row), plus the third value above when asked for."""
         self._check_generation()
         dev, l = self.device, self.l
         d, L, kvd = l["d"], l["layers"], self.kvd
         taps = self._check_taps(tap_layers)
         want = self._check_attn_layers(attn_layers)
+        if compress is not None:
+            cN, cw, ck = (int(v) for v in compress)
+            if not (1 <= cw <= ops.KVPRESS_MAX_WINDOW and cN > cw and 1 <= ck <= ops.KVPRESS_MAX_POOL and ck % 2 == 1):
+                raise ValueError(f"compress=(N, w, k) needs 1 <= w <= {ops.KVPRESS_MAX_WINDOW}, N > w and an odd k in "
+                                 f"[1, {ops.KVPRESS_MAX_POOL}], got {tuple(compress)!r}")
+            for name, v in (("attn_layers", want), ("tap_layers", taps)):
+                if v is not None:
+                    raise NotImplementedError(f"prefill(compress=...) with {name}= (prompt_kv_budget / prompt_kv_window): the compressed "
+                                              "prompt pass hands out neither attention rows nor tapped rows")
+            if (kv_dtype is not None and self._kv_dtype(kv_dtype) == "int8") or getattr(cache, "dtype", "bf16") == "int8":
+                raise NotImplementedError("prefill(compress=...) (prompt_kv_budget / prompt_kv_window) with an int8 KV cache: the gather "
+                                          "kernel writes bf16 rows only")
         if want is not None:
             if cache is not None or slots is not None:
                 raise NotImplementedError("prefill(attn_layers=...) with cache= / slots=: attention maps are read from a cache of the "
@@ -1138,19 +1166,33 @@ class LlavaEngine:
             raise ValueError("generation needs at least one prompt token per sequence")
         valid = plan["attention_mask"].reshape(-1)
         S = int(lens.max())
+        kept = lens if compress is None else np.minimum(lens, cN)       # cache slots each prompt takes
+        pressed = kept < lens
         if cache is None:
-            L_max = int(lens.max()) + int(max_new_tokens)
+            L_max = int(kept.max()) + int(max_new_tokens)
             seq = np.arange(B)
         else:
             seq = self._slot_rows(slots, B, cache)
             L_max = cache.L_max
-            if (lens + int(max_new_tokens) > L_max).any():
-                raise ValueError(f"the prompts need {int(lens.max()) + int(max_new_tokens)} positions, the cache holds {L_max}")
+            if (kept + int(max_new_tokens) > L_max).any():
+                raise ValueError(f"the prompts need {int(kept.max()) + int(max_new_tokens)} positions, the cache holds {L_max}")
         cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
         pos = np.concatenate([np.arange(n, dtype=np.int32) for n in lens])
-        geom = dict(B=B, S=S, s_pad=_ru(S, 64), lens=None, cu=self._dev(cu), pos=self._dev(pos), cs=self.rope_table(L_max))
+        # the rope table of the uncompressed call: a compressed prompt's positions outrun its cache slots
+        rope_S = L_max if compress is None else max(L_max, S + int(max_new_tokens))
+        geom = dict(B=B, S=S, s_pad=_ru(S, 64), lens=None, cu=self._dev(cu), pos=self._dev(pos), cs=self.rope_table(rope_S))
         x = ops.gather_rows(self._dev(plan["idx"][valid].astype(np.int32)), d, self.W("model.embed_tokens.weight"), table)
-        rows = self._dev(np.concatenate([seq[b] * L_max + np.arange(n) for b, n in enumerate(lens)]).astype(np.int64))   # cache rows
+        plain = [b for b in range(B) if not pressed[b]]                 # sequences cached whole, by index_copy_ as ever
+        rows = None
+        if plain:
+            rows = self._dev(np.concatenate([seq[b] * L_max + np.arange(lens[b]) for b in plain]).astype(np.int64))   # cache rows
+        src = None
+        if pressed.any():
+            flags_dev, seq_dev = self._dev(pressed.astype(np.int32)), self._dev(seq.astype(np.int32))
+            votes = torch.empty(B, self.Hkv, S - cw, dtype=torch.float32, device=dev)
+            keep = torch.empty(B, self.Hkv, cN, dtype=torch.int32, device=dev)
+            if plain:
+                src = self._dev(np.concatenate([cu[b] + np.arange(lens[b]) for b in plain]).astype(np.int64))
         layers = []
         if cache is None and kv_dtype == "int8":
             cache = self.new_kv_cache(B, L_max, kv_dtype)           # seq = 0 .. B - 1: filled like a passed cache's slots
@@ -1170,8 +1212,16 @@ class LlavaEngine:
                     kv = cache.layers[i]
                 if kv_dtype == "int8":
                     self._kv_write_rows(kv, cache.scales[i] if cache.scales is not None else None, acts["qkv"][:, d:], rows)
-                else:
+                elif not pressed.any():
                     kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:])
+                else:
+                    if plain:
+                        kv.view(-1, 2 * kvd).index_copy_(0, rows, acts["qkv"][:, d:].index_select(0, src))
+                    ops.kv_votes(acts["qkv"], geom["cu"], l["heads"], self.Hkv, self.hd, cw, S, flags=flags_dev, out=votes)
+                    ops.kv_select(votes, geom["cu"], cN, cw, ck, flags=flags_dev, out=keep)
+                    ops.kv_gather(acts["qkv"][:, d:], geom["cu"], keep, seq_dev, kv, self.Hkv, self.hd, flags=flags_dev)
+                    if self.kvpress_trace is not None:
+                        self.kvpress_trace.append((i, votes.clone(), keep.clone()))
                 if want is not None and i in want:
                     attn[i] = ops.attn_decode_probs(ops.gather_rows(last_rows, d, acts["qkv"]), kv, lens_dev, l["heads"], self.Hkv, self.hd, S,
                                                     per_head=not attn_mean, mean=bool(attn_mean))[1 if attn_mean else 0]
@@ -1179,9 +1229,17 @@ class LlavaEngine:
         x = ops.gather_rows(self._dev((cu[1:] - 1).astype(np.int32)), d, x)       # every sequence's last prompt row
         out = self._head_logits(x, tapped=taps and [tapped[c] for c in taps])
         if cache is None:
-            cache = KVCache(layers, lens, L_max)
+            cache = KVCache(layers, kept, L_max)
+            if pressed.any():
+                cache.pos_off = (lens - kept).astype(np.int64)
         else:
-            cache.lens[seq] = lens
+            cache.lens[seq] = kept
+            if compress is not None:
+                if cache.pos_off is None:
+                    cache.pos_off = np.zeros(cache.B, dtype=np.int64)
+                cache.pos_off[seq] = lens - kept
+            elif cache.pos_off is not None:
+                cache.pos_off[seq] = 0
         if want is not None:
             return cache, out, [attn[c] for c in want]
         return (cache, out) if taps is None else (cache, *out)
@@ -1194,6 +1252,7 @@ class LlavaEngine:
     # plain step, second -> stacked: llava15_7b 0.103 -> 0.033, Qwen2-7B 0.400 -> 0.094, each faster by more than the second arm's
     # spread (0.007 / 0.006 ms), so stacking is the default.
     tap_lm_head = "stacked"
+    kvpress_trace = None              # prefill(compress=): a list here receives (layer, votes, keep) clones per layer (tests)
 
     def _check_taps(self, tap_layers):
         if tap_layers is None:
@@ -1254,8 +1313,17 @@ class LlavaEngine:
         with L_t = max_b(cache.lens[b] + 1) at this step: softmax(q K^T / sqrt(hd)) of the step's query row over the sequence's cache
         positions 0 .. cache.lens[b], zeros beyond.  In those layers ops.attn_decode_probs runs on the same qkv[:, :d], cache layer and
         kv_len, after the K|V append and beside the unchanged ops.attn_decode call, so the logits and the cache are the bits of the
-        call without it.  Not combined with beams=, shared=, tap_layers= or an int8 cache (NotImplementedError)."""
+        call without it.  Not combined with beams=, shared=, tap_layers= or an int8 cache (NotImplementedError).
+        cache.pos_off (prefill(compress=), generate(prompt_kv_budget=)): when set, the token's K|V still goes to slot cache.lens[b]
+        and attention reads kv_len = lens + 1 slots, but its q and k are rotated at position lens[b] + pos_off[b] (the rope table
+        covers L_max + max(pos_off)); beams=, shared= and attn_layers= then raise NotImplementedError.  With pos_off None the step
+        uploads and launches exactly what it did."""
         self._check_generation()
+        off = getattr(cache, "pos_off", None)
+        if off is not None:
+            for name, v in (("beams", beams), ("shared", shared), ("attn_layers", attn_layers)):
+                if v is not None:
+                    self._refuse_pressed(cache, f"decode_step({name}=...)")
         taps = self._check_taps(tap_layers)
         want = self._check_attn_layers(attn_layers)
         if want is not None:
@@ -1287,6 +1355,10 @@ class LlavaEngine:
         pos = self._dev(cache.lens.astype(np.int32))
         kv_len = self._dev((cache.lens + 1).astype(np.int32))
         cs = self.rope_table(cache.L_max)
+        rpos = pos                             # the RoPE position; a compressed prompt's slots lag its positions by pos_off
+        if off is not None:
+            rpos = self._dev((cache.lens + off).astype(np.int32))
+            cs = self.rope_table(_ru(cache.L_max + int(off.max()), 1024))    # a position's entry does not depend on the table's length
         if want is not None:
             L_t, attn = int(cache.lens.max()) + 1, {}
 
@@ -1315,7 +1387,7 @@ class LlavaEngine:
         for i in range(L):
             if taps is not None and i in taps:
                 tapped[i] = x                      # _cached_layer makes a new x: the row stays as it is
-            x = self._cached_layer(i, x, cs, pos, attend)
+            x = self._cached_layer(i, x, cs, rpos, attend)
         out = self._head_logits(x, tapped=taps and [tapped[c] for c in taps])
         cache.lens += 1
         return out if want is None else (out, [attn[c] for c in want])
@@ -1385,6 +1457,7 @@ class LlavaEngine:
         of tokens it emits; the K|V rows of rejected drafts stay past lens as stale rows, which every kernel ignores."""
         self._check_generation()
         self._refuse_int8(cache, "verify_step()")
+        self._refuse_pressed(cache, "verify_step()")
         d, H, L = self.l["d"], self.l["heads"], self.l["layers"]
         hd, Hkv, kvd = self.hd, self.Hkv, self.kvd
         if cache.B != 1:
@@ -1436,6 +1509,7 @@ class LlavaEngine:
         arithmetic is that of extend() on a cache of these sequences alone with the same L_max.
         Returns (cache, fp32 logits [B, vocab])."""
         self._refuse_int8(cache, "extend()")
+        self._refuse_pressed(cache, "extend()")
         if slots is not None and cache is None:
             raise ValueError("extend(slots=) needs the cache the slots index")
         if cache is None or reuse is None or not np.any(reuse):
@@ -1527,6 +1601,7 @@ class LlavaEngine:
         arrays.offsets[k] .. offsets[k + 1]."""
         self._check_generation()
         self._refuse_int8(prefix, "score_tails()")
+        self._refuse_pressed(prefix, "score_tails()")
         from . import scoring
         d, H, L = self.l["d"], self.l["heads"], self.l["layers"]
         hd, Hkv, kvd, V = self.hd, self.Hkv, self.kvd, self.vocab
@@ -2148,7 +2223,9 @@ class KVCache:
     dtype "int8": every (position, kv head, K / V) group of hd values is stored as s = max|x| / 127 (1 for a zero group) and
     q = clamp(rint(x / s), -127, 127): layers[i] is int8 [B, L_max, 2 * kvd] with the bf16 cache's columns and scales[i] is fp32
     [B, L_max, 2 * Hkv] (column g: K head g; column Hkv + g: V head g); the value read back is bf16(float(q) * s).  With
-    LlavaEngine.kv8_decode False the same values are kept dequantised instead: layers[i] bf16, scales None."""
+    LlavaEngine.kv8_decode False the same values are kept dequantised instead: layers[i] bf16, scales None.
+    pos_off (None, or int64 [B]; prefill(compress=)): sequence b's slot s < lens[b] need not hold position s -- a compressed prompt
+    keeps lens[b] = N of its P positions per layer and kv head -- and the next token sits at position lens[b] + pos_off[b]."""
     chunk = 128           # keys per decode-attention workgroup: fixed, so a sequence's result never depends on the batch around it
 
     def __init__(self, layers, lens, L_max, dtype="bf16", scales=None):
@@ -2157,6 +2234,7 @@ class KVCache:
         self.dtype = dtype
         self.lens = np.asarray(lens, dtype=np.int64).copy()
         self.L_max = int(L_max)
+        self.pos_off = None
 
     @property
     def B(self):

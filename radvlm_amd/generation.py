@@ -38,6 +38,11 @@ _CONSTRAINT = ("constraint",)
 # decode attention maps (output_attentions is HF's name; attention_layers / attention_reduce are ours): generate() alone takes them,
 # generate_batch() and generate_beams() reject them as unknown; _parse_attentions / resolve_attention_layers
 _ATTENTIONS = ("output_attentions", "attention_layers", "attention_reduce")
+# prompt cache compression (ours: SnapKV, Li et al. 2024): generate() and generate_batch() take them, generate_beams() and score() reject
+# them as unknown; parse_prompt_kv
+_KVPRESS = ("prompt_kv_budget", "prompt_kv_window", "prompt_kv_pool")
+KVPRESS_MAX_WINDOW = 64       # observation window rows (rv_kv_votes_f32)
+KVPRESS_MAX_POOL = 63         # pooling width (rv_kv_select_i32)
 LOOKUP_MAX_TOKENS = 31        # k drafted tokens are verified as k + 1 rows, and the skinny GEMM takes ops.GEMV_MAX_M = 32
 
 
@@ -66,15 +71,31 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError.
     attentions: also take output_attentions / attention_layers / attention_reduce (.attentions: None when off, else .layers and
     .reduce, _parse_attentions; resolve_attention_layers turns .layers into layer numbers once the call knows the engine's depth):
-    with kv_cache_dtype="int8", past_key_values, prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError."""
+    with kv_cache_dtype="int8", past_key_values, prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError.
+    Prompt cache compression (.kvpress: None when off, else (N, w, k) from prompt_kv_budget / prompt_kv_window / prompt_kv_pool,
+    parse_prompt_kv): with past_key_values, prompt_lookup_num_tokens, guidance_scale, dola_layers, output_attentions or
+    kv_cache_dtype="int8" NotImplementedError."""
     unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and k not in _DOLA and k not in _CONSTRAINT
-                     and not (lookup and k in _LOOKUP) and not (attentions and k in _ATTENTIONS))
+                     and k not in _KVPRESS and not (lookup and k in _LOOKUP) and not (attentions and k in _ATTENTIONS))
     if unknown:
         raise TypeError(f"generate() got unexpected keyword arguments {unknown}")
     guidance = _parse_guidance(kwargs)
     dola = _parse_dola(kwargs)
     constraint = _parse_constraint(kwargs)
     att = _parse_attentions(kwargs)
+    press = parse_prompt_kv(kwargs)
+    if press is not None:
+        for name, on, why in (
+                ("past_key_values", kwargs.get("past_key_values") is not None, "the extend pass reads a cache whose slots are its positions"),
+                ("prompt_lookup_num_tokens", kwargs.get("prompt_lookup_num_tokens") is not None, "the verify step reads a cache whose "
+                 "slots are its positions"),
+                ("guidance_scale", guidance is not None, "compressing the two branches of a guided call is not implemented"),
+                ("dola_layers", dola is not None, "the compressed prompt pass hands out no tapped rows"),
+                ("output_attentions", att is not None, "a map over a compact cache's slots has no position axis"),
+                ("kv_cache_dtype='int8'", parse_kv_cache_dtype(kwargs.get("kv_cache_dtype")) == "int8", "the gather kernel writes bf16 "
+                 "rows only")):
+            if on:
+                raise NotImplementedError(f"prompt_kv_budget / prompt_kv_window with {name}: {why}")
     if att is not None:
         for name, on, why in (
                 ("kv_cache_dtype='int8'", parse_kv_cache_dtype(kwargs.get("kv_cache_dtype")) == "int8", "the probability kernel reads a "
@@ -150,7 +171,7 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
                            output_logits=bool(kwargs.get("output_logits", False)),
                            return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
                            past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
-                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola, constraint=constraint, attentions=att,
+                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola, constraint=constraint, attentions=att, kvpress=press,
                            **_parse_processors(kwargs, eos))
 
 
@@ -376,6 +397,30 @@ def resolve_negative_prompts(guidance, ids, am):
         raise ValueError("negative_image_sizes given without negative_images")
     _check_negative_images("generate()", nid[nam], imgs)
     return nid, nam, imgs, sizes
+
+
+def parse_prompt_kv(kwargs):
+    """prompt_kv_budget / prompt_kv_window / prompt_kv_pool -> None (no budget: the cache holds every prompt position) or (N, w, k):
+    N prompt positions kept per sequence, layer and kv head, the last w (default 32, 1 .. KVPRESS_MAX_WINDOW) among them, votes
+    max-pooled over k (default 7, odd, 1 .. KVPRESS_MAX_POOL) positions.  ValueError for a bool, a non-int, N <= w, an even or
+    out-of-range k, and for a window or pool given without a budget."""
+    N, w, k = (kwargs.get(name) for name in _KVPRESS)
+    if N is None:
+        given = [name for name, v in zip(_KVPRESS[1:], (w, k)) if v is not None]
+        if given:
+            raise ValueError(f"{given} given without prompt_kv_budget")
+        return None
+    w, k = 32 if w is None else w, 7 if k is None else k
+    for name, v in zip(_KVPRESS, (N, w, k)):
+        if not _is_int(v):
+            raise ValueError(f"`{name}` has to be an int, but is {v!r}")
+    if not 1 <= w <= KVPRESS_MAX_WINDOW:
+        raise ValueError(f"`prompt_kv_window` has to lie in [1, {KVPRESS_MAX_WINDOW}], but is {w!r}")
+    if not 1 <= k <= KVPRESS_MAX_POOL or k % 2 == 0:
+        raise ValueError(f"`prompt_kv_pool` has to be odd and lie in [1, {KVPRESS_MAX_POOL}], but is {k!r}")
+    if N <= w:
+        raise ValueError(f"`prompt_kv_budget` ({N!r}) has to exceed `prompt_kv_window` ({w!r}): the window is always kept")
+    return int(N), int(w), int(k)
 
 
 def parse_kv_cache_dtype(v):
@@ -1009,6 +1054,12 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             raise NotImplementedError("constraint with prompt_lookup_num_tokens or dola_layers is not implemented")
         from .constraints import resolve_constraints
         ctab, cstart = resolve_constraints(cfg.constraint, B, engine.vocab)
+    press = getattr(cfg, "kvpress", None)
+    ckw = {} if press is None else dict(compress=press)      # handed to prefill only when the keyword was given
+    if press is not None and (gc is not None or lookup or dola is not None or getattr(cfg, "attentions", None) is not None
+                              or getattr(cfg, "kv_cache_dtype", "bf16") == "int8"):
+        raise NotImplementedError("prompt_kv_budget / prompt_kv_window with past_key_values, prompt_lookup_num_tokens, dola_layers, "
+                                  "output_attentions or kv_cache_dtype='int8' is not implemented")
     att = getattr(cfg, "attentions", None)
     akw, amap, attns = {}, None, []
     if att is not None:
@@ -1047,7 +1098,7 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             elif att is not None:
                 cache, logits, amap = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **akw)
             else:
-                cache, logits, *cand = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **tap)
+                cache, logits, *cand = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **tap, **ckw)
             if dola is not None:
                 dws = ops.dola_workspace(B, len(dola), dev)
         else:
@@ -1192,6 +1243,9 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
     if cfg.share_prefix and cfg.dola is not None:
         raise NotImplementedError("share_prefix=True with dola_layers: the extend pass and the shared decode step hand out no intermediate "
                                   "hidden states")
+    if cfg.share_prefix and cfg.kvpress is not None:
+        raise NotImplementedError("prompt_kv_budget / prompt_kv_window with share_prefix=True: a follower's copy and the extend pass "
+                                  "read a cache whose slots are its positions")
     if cfg.guidance is not None:
         for k in ("negative_prompt_ids", "negative_images", "negative_image_sizes"):
             _per_request(k, getattr(cfg.guidance, k), n)      # a list of another length: ValueError here, before anything runs
@@ -1459,7 +1513,11 @@ class BatchScheduler:
     tokens decode_step was given, one upload for both) row s is slot s, each live state takes its token's edge and the row is
     masked.  An idle slot keeps whatever state its last request left, advanced by the 0 an idle slot is fed; its row is ignored as
     ever and the next admission overwrites the state.  ConstraintMirror follows the states per slot on the host and raises
-    RuntimeError naming the request and its step at a dead end.  Without cfg.constraint nothing here changes."""
+    RuntimeError naming the request and its step at a dead end.  Without cfg.constraint nothing here changes.
+    cfg.kvpress (prompt cache compression, (N, w, k)): L_max and the memory check count min(spliced, N) + budget positions per request,
+    and engine.prefill is given compress=(N, w, k) -- only then, so an engine without the argument serves every other call.  The
+    engine keeps each slot's position offset in the cache (KVCache.pos_off); nothing else here changes.  Not combined with
+    share_prefix, guidance, dola or an int8 cache."""
 
     def __init__(self, engine, reqs, cfg, max_batch_size=32, return_logprobs=False, admit_free=None, picker=None, guide=None,
                  constrain=None):
@@ -1483,6 +1541,15 @@ class BatchScheduler:
         self.runs = [i for i in range(n) if self.budget[i] > 0]
         self.slots = min(int(max_batch_size), len(self.runs))
         self.L_max = max([self.spliced[i] + self.budget[i] for i in self.runs], default=0)
+        self.press = getattr(cfg, "kvpress", None)
+        self.ckw = {}
+        if self.press is not None:            # a request then takes min(spliced, N) slots: the cache and the memory check shrink with it
+            if self.share or getattr(cfg, "guidance", None) is not None or getattr(cfg, "dola", None) is not None \
+                    or getattr(cfg, "kv_cache_dtype", "bf16") == "int8":
+                raise NotImplementedError("prompt_kv_budget / prompt_kv_window with share_prefix=True, guidance_scale, dola_layers or "
+                                          "kv_cache_dtype='int8' is not implemented")
+            self.ckw = dict(compress=self.press)
+            self.L_max = max([min(self.spliced[i], self.press[0]) + self.budget[i] for i in self.runs], default=0)
         self.guidance, self.guide = getattr(cfg, "guidance", None), guide
         self.dola, self.contrast = getattr(cfg, "dola", None), None
         if self.dola is not None:
@@ -1598,7 +1665,7 @@ class BatchScheduler:
             self.contrast(logits, cand)
             self._step(logits, rs)
             return
-        _, logits = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs)
+        _, logits = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs, **self.ckw)
         if self.guidance is not None:
             logits = self._admit_negative(logits, rq, rs)
         self._step(logits, rs)

@@ -115,6 +115,11 @@ _SIGS = {
                             _i32, _i32, _f32, _c_void_p],
     "rv_attn_decode_probs_f32": [_c_void_p, _i64, _c_void_p, _i64, _i64, _c_void_p, _i32, _i32, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64,
                                  _i32, _i32, _i32, _i32, _f32, _c_void_p],
+    "rv_kv_votes_f32": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _i32, _i32, _i32,
+                        _i32, _f32, _c_void_p],
+    "rv_kv_select_i32": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _c_void_p],
+    "rv_kv_gather_bf16": [_c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _i32, _i32,
+                          _i32, _c_void_p],
     "rv_attn_extend_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
                             _i32, _i32, _i32, _i32, _i32, _i32, _f32, _c_void_p],
     "rv_kv_append_bf16": [_c_void_p, _i64, _c_void_p, _i64, _i64, _c_void_p, _i32, _i32, _i32, _c_void_p],
@@ -157,7 +162,8 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = ["rv_version", "rv_gemm_select_kernel", "rv_gemm_set_cu_budget", "rv_attn_fwd_nat_pairs", "rv_gemv_split",
                     "rv_w8_row_bytes", "rv_w4_row_bytes", "rv_w4_scale_row_bytes", "rv_sample_uniform24", "rv_sample_ws_bytes", "rv_beam_topk_ws_bytes", "rv_cfg_guide_ws_bytes",
-                    "rv_dola_ws_bytes", "rv_lora_down_split", "rv_attn_decode_probs_ws_bytes"] + sorted(_SIGS)
+                    "rv_dola_ws_bytes", "rv_lora_down_split", "rv_attn_decode_probs_ws_bytes", "rv_kv_votes_ws_bytes",
+                    "rv_kv_select_ws_bytes"] + sorted(_SIGS)
 
 _lib = None
 
@@ -193,6 +199,10 @@ def load():
         lib.rv_dola_ws_bytes.restype = _i64
         lib.rv_attn_decode_probs_ws_bytes.argtypes = [_i32, _i32, _i32]
         lib.rv_attn_decode_probs_ws_bytes.restype = _i64
+        lib.rv_kv_votes_ws_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32]
+        lib.rv_kv_votes_ws_bytes.restype = _i64
+        lib.rv_kv_select_ws_bytes.argtypes = [_i32, _i32, _i64]
+        lib.rv_kv_select_ws_bytes.restype = _i64
         for name, sig in _SIGS.items():
             fn = getattr(lib, name)
             fn.argtypes = sig

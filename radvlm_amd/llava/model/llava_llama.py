@@ -448,6 +448,16 @@ class LlavaLlamaForCausalLM:
         guidance_scale, dola_layers or live LoRA adapters NotImplementedError; a non-bool, a missing return_dict_in_generate, a bad
         attention_reduce, attention_layers with a bool, a non-int, a duplicate or a value outside [-layers, layers), or either of
         our two keywords without output_attentions: ValueError.
+        Prompt cache compression (SnapKV, Li et al. 2024; ours, lossy, opt-in): prompt_kv_budget=N keeps N of a prompt's positions per
+        sequence, layer and kv head instead of all of them -- the last prompt_kv_window=w (default 32, 1 .. 64) positions, the text
+        question after the image, vote with their attention for the earlier keys; the votes are max-pooled over prompt_kv_pool=k
+        (default 7, odd, 1 .. 63) neighbours and the N - w best-voted positions are kept beside the window itself
+        (rv_kv_votes_f32 / rv_kv_select_i32 / rv_kv_gather_bf16 inside the prompt pass: the full prompt is never cached).  A prompt of
+        at most N positions is cached whole and the call is bit for bit the call without the keyword.  The first token comes from the
+        uncompressed prompt pass; later ones read the compact cache with the unchanged decode kernels, each new token rotated at its
+        true position.  It composes with the processors, sampling, constraint, quantised decoders and live LoRA adapters; with
+        past_key_values, prompt_lookup_num_tokens, guidance_scale, dola_layers, output_attentions or kv_cache_dtype="int8"
+        NotImplementedError; a bool, a non-int, N <= w, an even or out-of-range k, or window / pool without the budget: ValueError.
         The training state (weights, optimizer, RNG counters) is not touched."""
         from ...generation import greedy_generate, parse_generate_kwargs
         cfg = parse_generate_kwargs(kwargs, lora=self._lora_refused, config_eos=getattr(self.config, "eos_token_id", None),
@@ -492,6 +502,10 @@ class LlavaLlamaForCausalLM:
         live on the device, one per cache slot; an admission writes the request's start state into its slot.  A request's tokens,
         and its logprobs (of the masked, processed row, so renormalised over the allowed ids), are those of generate(constraint=)
         on it alone; it works with share_prefix=True.  A dead end raises RuntimeError naming the request and its step.
+        prompt_kv_budget=N / prompt_kv_window / prompt_kv_pool (one value each for the call): prompt cache compression as in
+        generate().  A request then takes min(its spliced length, N) + its budget cache positions, which is what the slots' cache
+        and the memory check are sized for; a request's tokens are those of generate() on it alone with the same three values.  With
+        share_prefix=True: NotImplementedError.
         The training state is not touched."""
         from ...generation import generate_batch, parse_batch_kwargs
         inputs = list(inputs)

@@ -4,6 +4,10 @@ Mirrors reference finetuning/llava/model/language_model/llava_qwen.py:35-149: th
 list and outputs as the Llama flavour; the decoder is Qwen2 (grouped-query attention, q/k/v biases, rope theta 1e6,
 rms eps 1e-6) and the tower handle is ``SigLipVisionTower`` (multimodal_encoder/siglip_encoder.py:538-620: 729 tokens,
 no class token, last encoder layer dropped).  The arithmetic lives in ``radvlm_amd.engine``; this file is the interface.
+
+``generate`` / ``generate_batch`` are the Llama flavour's, keywords included: ``prompt_kv_budget`` / ``prompt_kv_window`` /
+``prompt_kv_pool`` (SnapKV prompt-cache compression) matter most here -- Qwen2 + SigLIP with ``anyres_max_9`` makes prompts of
+about 7,500 positions, almost all image patches, and with 7 query heads per kv head each kept key serves 7 heads' votes.
 """
 import torch
 

@@ -852,6 +852,72 @@ def attn_decode_probs(q, cache, kv_len, H, Hkv, hd, L_out, per_head=True, mean=F
     return (out[:, :, :L_out] if out is not None else None), (mean_out[:, :L_out] if mean_out is not None else None)
 
 
+KVPRESS_MAX_WINDOW = 64   # observation window rows (rv_kv_votes_f32)
+KVPRESS_MAX_POOL = 63     # pooling width, odd (rv_kv_select_i32)
+
+
+def kv_votes(qkv, cu, H, Hkv, hd, w, max_P, flags=None, scale=None, out=None):
+    """SnapKV votes (rv_kv_votes_f32): qkv the packed post-RoPE bf16 [M, >= (H + Hkv) * hd] q|k|v rows of a prompt pass (q head h at
+    columns h*hd, K of kv head g at H*hd + g*hd), cu int32 [B + 1] (device), sequence b's last w rows its observation window.  Returns
+    fp32 [B, Hkv, max_P - w]: column j < P_b - w is the attention the window's rows of the kv head's query heads pay to prefix key j
+    (each row's causal softmax, summed); other columns and the rows of sequences with flags[b] == 0 (int32 [B], device) or
+    P_b <= w are left as they are (out: write into this tensor; a new one is torch.empty)."""
+    _chk(qkv), _chk(cu, torch.int32)
+    B = cu.numel() - 1
+    w, max_P = int(w), int(max_P)
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] >= (H + Hkv) * hd and cu.is_contiguous() and B >= 1
+    if flags is not None:
+        _chk(flags, torch.int32)
+        assert flags.numel() == B and flags.is_contiguous()
+    if out is None:
+        out = torch.empty(B, Hkv, max(max_P - w, 1), dtype=torch.float32, device=qkv.device)
+    _chk(out, torch.float32)
+    assert out.shape[:2] == (B, Hkv) and out.is_contiguous()
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    ws_bytes = lib.load().rv_kv_votes_ws_bytes(B, H, Hkv, w, max_P)
+    ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=qkv.device)
+    lib.call("rv_kv_votes_f32", qkv, qkv.stride(0), qkv[:, H * hd:], qkv.stride(0), cu, flags, max_P, out, out.shape[2], ws, ws_bytes, B, H,
+             Hkv, hd, w, float(scale))
+    return out
+
+
+def kv_select(votes, cu, N, w, k, flags=None, out=None):
+    """SnapKV selection (rv_kv_select_i32): votes fp32 [B, Hkv, ld_v] (non-negative), cu int32 [B + 1].  Returns int32 [B, Hkv, N]: per
+    sequence with P_b > N and kv head, the N - w prefix positions with the largest max-pooled vote (width k, ties to the lower
+    position) in ascending order, then the w window positions.  Rows of other sequences (and of flags[b] == 0) are left as they are."""
+    _chk(votes, torch.float32), _chk(cu, torch.int32)
+    B, Hkv, ld_v = votes.shape
+    assert votes.is_contiguous() and cu.numel() == B + 1 and cu.is_contiguous()
+    if flags is not None:
+        _chk(flags, torch.int32)
+        assert flags.numel() == B and flags.is_contiguous()
+    if out is None:
+        out = torch.empty(B, Hkv, int(N), dtype=torch.int32, device=votes.device)
+    _chk(out, torch.int32)
+    assert out.shape == (B, Hkv, int(N)) and out.is_contiguous()
+    ws_bytes = lib.load().rv_kv_select_ws_bytes(B, Hkv, ld_v)
+    ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.int32, device=votes.device)
+    lib.call("rv_kv_select_i32", votes, ld_v, cu, flags, out, ws, ws_bytes, B, Hkv, int(N), int(w), int(k))
+    return out
+
+
+def kv_gather(kv, cu, keep, seq, cache, Hkv, hd, flags=None):
+    """SnapKV gather (rv_kv_gather_bf16): kv the packed bf16 K|V rows [M, 2 * Hkv * hd] of a prompt pass (a column view of the q|k|v
+    product), keep int32 [B, Hkv, N] from kv_select, seq int32 [B] the sequences' rows of cache bf16 [rows, L_max, 2 * Hkv * hd].
+    Slot s of every sequence with P_b > N takes, per kv head, the K|V of prompt position keep[b, g, s]; nothing else is written."""
+    _chk(kv), _chk(cache), _chk(cu, torch.int32), _chk(keep, torch.int32), _chk(seq, torch.int32)
+    B, _, N = keep.shape
+    rows, L_max, width = cache.shape
+    kvd = Hkv * hd
+    assert kv.stride(1) == 1 and kv.shape[1] == 2 * kvd and width == 2 * kvd and cache.is_contiguous() and keep.is_contiguous()
+    assert keep.shape[1] == Hkv and cu.numel() == B + 1 and seq.numel() == B and cu.is_contiguous() and seq.is_contiguous()
+    if flags is not None:
+        _chk(flags, torch.int32)
+        assert flags.numel() == B and flags.is_contiguous()
+    lib.call("rv_kv_gather_bf16", kv, kv.stride(0), kvd, cu, flags, keep, seq, cache, width, L_max, rows, B, Hkv, hd, N)
+    return cache
+
+
 EXTEND_CHUNK = 256        # keys per extend-attention workgroup: fixed, so a row's result never depends on the batch around it
 
 

@@ -88,6 +88,13 @@
         # and Qwen2-7B head shapes, a 704-position prompt with 2, 8, 32 candidates of 4 and of 64 tokens (3 / 63 rows each); the
         # protocol of --kv8-shapes: cold cache, interleaved, median of 20, torch.equal asserted before timing; the extend arm's
         # p10 / p90 are its spread; plus the bytes per candidate of the copy the prefix kernel avoids, over the layers
+  python tools/decode_bench.py --kvpress-shapes [--out FILE]   # prompt cache compression's three kernels per layer: rv_kv_votes_f32,
+        # rv_kv_select_i32, rv_kv_gather_bf16 on random q|k|v rows, the 7B and Qwen2-7B head shapes, 704 and 7,603 keys (budget
+        # min(1024, keys / 2), window 32, pool 7), B = 1, 8, 32; the protocol of --kv8-shapes: cold cache, interleaved, median of 20
+  python tools/decode_bench.py --kvpress [--geos ..] [--batches 1,8,32] [--prompt 7603] [--out FILE]
+        # decode ms / step, cache bytes and prompt-pass ms with and without prompt_kv_budget=1024 at a 7,603-position prompt (one
+        # untimed pass of both arms, then interleaved), after the toy goldens' quality figures (first decode step's logits, relative
+        # L2, and the share of agreeing greedy tokens against the uncompressed call, at budgets of 1/2 and 1/4 of the prompt)
   python tools/decode_bench.py --score [--geos ..] [--reps 3] [--out FILE]
         # model.score() against the one-by-one route: the training forward on prompt + candidate with the candidate as labels,
         # reading the loss, once per candidate (the tower and the prompt's rows run every time); one image prompt of 704 spliced
@@ -453,16 +460,17 @@ def w8_trace(geo, prompt, new):
                  kernel_src=_src_hash())]
 
 
-def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None, con=None, attn=None):
+def _decode_loop(eng, ids, new, lp=None, warm=8, sm=None, kv_dtype=None, con=None, attn=None, press=None):
     """Median decode step (decode_step + token choice) in ms; with `lp` (generation.LogitsProcessors) the token comes from
     rv_logits_process_argmax_f32 and is recorded in the device history, as greedy_generate does; with `sm` (the sampling settings of
     parse_generate_kwargs) it is drawn by rv_sample_rows_f32, row b with seed sm.seed + b, as greedy_generate does.  kv_dtype: the
     cache's dtype (prefill's kv_dtype).  con (a constraints.TokenConstraint for every row): ops.constrain_rows advances and masks each
     step's rows before the token choice, as greedy_generate does (the host mirror of the states is not part of the loop).  attn
     (decode_step's attn_layers= / attn_mean= as a dict): every step also returns its attention maps, as generate(output_attentions=True)
-    asks for them; they are dropped here."""
+    asks for them; they are dropped here.  press (prefill's compress=(N, w, k)): the loop runs on the compressed prompt cache."""
     B = ids.shape[0]
-    cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new, **({} if kv_dtype is None else dict(kv_dtype=kv_dtype)))
+    cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new, **({} if kv_dtype is None else dict(kv_dtype=kv_dtype)),
+                                **({} if press is None else dict(compress=press)))
     if con is not None:
         tabs = con.device_tables(logits.device)
         cstate = torch.full((B,), con.start, dtype=torch.int32, device=logits.device)
@@ -670,6 +678,113 @@ def kv8_quality_toy(new=32):
         recs.append(dict(geo=geo, mode="kv8_quality_toy", prompts=n, new_tokens=new,
                          next_step_logits_rel_l2=[round(float((y[0] - x[0]).norm() / x[0].norm()), 5) for x, y in zip(a, b)],
                          greedy_tokens_agree=[round(float((x[1] == y[1]).mean()), 4) for x, y in zip(a, b)]))
+    return recs
+
+
+def kvpress_shapes(reps=20, keys=(704, 7603), batches=(1, 8, 32), w=32, k=7):
+    """rv_kv_votes_f32, rv_kv_select_i32 and rv_kv_gather_bf16 per layer and head shape on random q|k|v rows: B prompts of `keys`
+    positions, budget N = min(1024, keys // 2); interleaved, cold cache, median of `reps` (the protocol of kv8_shapes)."""
+    out = []
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
+    for geo in ("llava15_7b", "llava_ov_qwen2_7b"):
+        l = GEOMETRIES[geo]["lm"]
+        H, hd = l["heads"], l["d"] // l["heads"]
+        Hkv = l.get("kv_heads", H)
+        d, kvd = H * hd, Hkv * hd
+        for n in keys:
+            N = min(1024, n // 2)
+            for B in batches:
+                qkv = torch.randn(B * n, d + 2 * kvd, device="cuda", dtype=torch.bfloat16)
+                cu = torch.arange(B + 1, dtype=torch.int32, device="cuda") * n
+                seq = torch.arange(B, dtype=torch.int32, device="cuda")
+                cache = torch.zeros(B, N + 128, 2 * kvd, dtype=torch.bfloat16, device="cuda")
+                votes = torch.empty(B, Hkv, n - w, dtype=torch.float32, device="cuda")
+                keep = torch.empty(B, Hkv, N, dtype=torch.int32, device="cuda")
+                fns = {"votes": lambda: ops.kv_votes(qkv, cu, H, Hkv, hd, w, n, out=votes),
+                       "select": lambda: ops.kv_select(votes, cu, N, w, k, out=keep),
+                       "gather": lambda: ops.kv_gather(qkv[:, d:], cu, keep, seq, cache, Hkv, hd)}
+                for f in fns.values():                                      # warm-up, and select / gather read what votes / select wrote
+                    f()
+                ts = _timed_interleaved(fns, flush, reps)
+                med = {a: float(np.median(v)) for a, v in ts.items()}
+                out.append(dict(mode="kvpress_kernels", geo=geo, H=H, Hkv=Hkv, hd=hd, keys=n, B=B, budget=N, window=w, pool=k,
+                                votes_us=round(med["votes"], 2), select_us=round(med["select"], 2), gather_us=round(med["gather"], 2),
+                                total_us=round(sum(med.values()), 2),
+                                votes_p10_p90_us=[round(float(np.percentile(ts["votes"], q)), 2) for q in (10, 90)], reps=reps,
+                                kernel_src=_src_hash()))
+                del qkv, cache, votes, keep
+    return out
+
+
+def kvpress_e2e(geo, batches, prompt=7603, new=40, N=1024, w=32, k=7, reps=2):
+    """The decode step and the prompt pass with and without prompt_kv_budget=N at a `prompt`-position prompt on one engine (random token
+    prompts): ms per step (the median step of every pass, passes interleaved after one untimed pass of both arms), the cache's bytes,
+    and the prompt pass's time with the three kernels in its layer loop."""
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    press = (N, w, k)
+    recs = []
+    for B in batches:
+        ids = np.random.default_rng(0).integers(0, eng.vocab, (B, prompt))
+
+        def fill(arm):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            cache, _ = eng.prefill(ids, None, None, None, max_new_tokens=new, **({} if arm is None else dict(compress=arm)))
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, cache.nbytes()
+        ts, pf, nb = {None: [], press: []}, {None: [], press: []}, {}
+        for arm in (None, press):
+            fill(arm)
+        for _ in range(reps):
+            for arm in (None, press):
+                ms, nb[arm] = fill(arm)
+                pf[arm].append(ms)
+                ts[arm].append(float(np.median(_decode_loop(eng, ids, new, press=arm))))
+        a, b = float(np.median(ts[None])), float(np.median(ts[press]))
+        recs.append(dict(geo=geo, mode="kvpress_ab", B=B, prompt=prompt, new_tokens=new, budget=N, window=w, pool=k, reps=reps,
+                         full_ms_per_step=round(a, 3), pressed_ms_per_step=round(b, 3), speedup=round(a / b, 3),
+                         full_ms_all=[round(x, 3) for x in ts[None]], pressed_ms_all=[round(x, 3) for x in ts[press]],
+                         full_cache_bytes=int(nb[None]), pressed_cache_bytes=int(nb[press]),
+                         full_prefill_ms=round(float(np.median(pf[None])), 1), pressed_prefill_ms=round(float(np.median(pf[press])), 1),
+                         added_prefill_ms=round(float(np.median(pf[press]) - np.median(pf[None])), 1), kernel_src=_src_hash()))
+    return recs
+
+
+def kvpress_quality_toy(new=32, w=8, k=3):
+    """How far prompt_kv_budget moves the toy goldens' models, as kv8_quality_toy reports it: relative L2 of the logits of the first
+    decode step (the first that reads the compact cache; the prompt pass itself is uncompressed) and the share of greedy tokens that
+    agree with the uncompressed call, at budgets of a half and a quarter of each prompt.  Reported, never gated: random-init toys say
+    nothing about a trained checkpoint."""
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    recs = []
+    for geo, golden in (("toy", "toy_e2e"), ("toy_qwen", "toy_qwen_e2e")):
+        g = np.load(os.path.join(root, golden + ".npz"))
+        n = len([x for x in g.files if x.startswith("image") and x[5:].isdigit()])
+        images = [torch.from_numpy(g[f"image{i}"]) for i in range(n)]
+        sizes = [tuple(x) for x in g["image_sizes"].tolist()]
+        eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="portable", seed=0)
+
+        def run(frac):
+            out = []
+            for b in range(n):
+                p = g["input_ids"][b][g["attention_mask"][b].astype(bool)].astype(np.int64)
+                P = int(eng.plan(p[None], None, None, [images[b]], [sizes[b]])["lens"][0])
+                kw = {} if frac is None else dict(compress=(max(w + 1, int(P * frac)), w, k))
+                cache, logits = eng.prefill(p[None], None, [images[b]], [sizes[b]], max_new_tokens=new, **kw)
+                toks, nxt = [ops.argmax_rows(logits, eng.vocab)], None
+                for _ in range(new - 1):
+                    logits = eng.decode_step(cache, toks[-1].to(torch.int32))
+                    nxt = logits[0].clone() if nxt is None else nxt
+                    toks.append(ops.argmax_rows(logits, eng.vocab))
+                out.append((nxt, torch.cat(toks).cpu().numpy(), P))
+            return out
+        a = run(None)
+        for frac in (0.5, 0.25):
+            b = run(frac)
+            recs.append(dict(geo=geo, mode="kvpress_quality_toy", prompts=n, new_tokens=new, window=w, pool=k, budget_fraction=frac,
+                             prompt_positions=[x[2] for x in a],
+                             next_step_logits_rel_l2=[round(float((y[0] - x[0]).norm() / x[0].norm()), 5) for x, y in zip(a, b)],
+                             greedy_tokens_agree=[round(float((x[1] == y[1]).mean()), 4) for x, y in zip(a, b)]))
     return recs
 
 
@@ -1842,6 +1957,8 @@ def main():
     ap.add_argument("--kv8-shapes", action="store_true")
     ap.add_argument("--kv8-quality", action="store_true")
     ap.add_argument("--kv8-trace", action="store_true")
+    ap.add_argument("--kvpress", action="store_true")
+    ap.add_argument("--kvpress-shapes", action="store_true")
     ap.add_argument("--sample", action="store_true")
     ap.add_argument("--beams", action="store_true")
     ap.add_argument("--lookup", action="store_true")
@@ -1886,6 +2003,13 @@ def main():
         recs = kv8_quality_toy()
     elif a.kv8_trace:
         recs = [r for g in a.geos.split(",") for r in kv8_trace(g, int(a.batches.split(",")[-1]), a.prompt, a.new)]
+    elif a.kvpress_shapes:
+        recs = kvpress_shapes()
+    elif a.kvpress:
+        prompt = a.prompt if a.prompt != ap.get_default("prompt") else 7603
+        new = a.new if a.new != ap.get_default("new") else 40
+        recs = kvpress_quality_toy() + [r for g in a.geos.split(",") for r in kvpress_e2e(g, list(map(int, a.batches.split(","))), prompt, new,
+                                                                                       reps=min(a.reps, 2))]
     elif a.sample:
         recs = sample_kernel_ab() + [r for g in a.geos.split(",") for r in sample_ab(g, list(map(int, a.batches.split(","))), a.prompt, a.new)]
     elif a.beams:
