@@ -56,25 +56,16 @@ class GenerateDecoderOnlyOutput(SimpleNamespace):
 
 
 def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, lookup=False, attentions=False):
-    """Validate generate() keyword arguments; returns a namespace with the normalised settings (.sampling: None for greedy, else the
-    warper settings and the seed as given; sampling_seeds() resolves it per row).  Raises NotImplementedError for what this build does
-    not do (do_sample=True without seed=, beam search, streamers, caller-supplied inputs_embeds, LoRA engines, kv_cache_dtype="int8"
-    together with past_key_values or prompt_lookup_num_tokens), ValueError for a kv_cache_dtype other than None / "bf16" / "int8"
-    (.kv_cache_dtype: "bf16" or "int8") and TypeError for unknown names.  lookup: also take prompt_lookup_num_tokens / max_matching_ngram_size (.lookup: None, or .k and .max_ngram; .drafter: None,
+    """Validate generate() keyword arguments; returns a namespace with the normalised settings.  Every argument is checked on its own
+    first: TypeError for unknown names, ValueError for a bad value, NotImplementedError for what this build does not do at all
+    (do_sample=True without seed=, beam search, streamers, caller-supplied inputs_embeds, LoRA engines).  Then the combinations:
+    NotImplementedError for the first row of REFUSALS whose two features are both on (refuse_combinations).
+    .sampling: None for greedy, else the warper settings and the seed as given (sampling_seeds() resolves it per row).
+    lookup: also take prompt_lookup_num_tokens / max_matching_ngram_size (.lookup: None, or .k and .max_ngram; .drafter: None,
     greedy_generate then builds a PromptLookupDrafter; a test or a benchmark may set another object with propose(seq)).
-    Classifier-free guidance (.guidance: None when off, else .scale and the negative prompt as given, _parse_guidance): with
-    past_key_values or prompt_lookup_num_tokens NotImplementedError.
-    DoLa (.dola: None when off, else the validated dola_layers spec, _parse_dola; resolve_dola_layers turns it into layer numbers
-    once the call knows the engine's depth): with guidance_scale, past_key_values or prompt_lookup_num_tokens NotImplementedError.
-    Constrained decoding (.constraint: None when off, else a TokenConstraint or a list of them with None entries, _parse_constraint;
-    constraints.resolve_constraints checks it against the row count and the vocabulary once the call knows them): with
-    prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError.
-    attentions: also take output_attentions / attention_layers / attention_reduce (.attentions: None when off, else .layers and
-    .reduce, _parse_attentions; resolve_attention_layers turns .layers into layer numbers once the call knows the engine's depth):
-    with kv_cache_dtype="int8", past_key_values, prompt_lookup_num_tokens, guidance_scale or dola_layers NotImplementedError.
-    Prompt cache compression (.kvpress: None when off, else (N, w, k) from prompt_kv_budget / prompt_kv_window / prompt_kv_pool,
-    parse_prompt_kv): with past_key_values, prompt_lookup_num_tokens, guidance_scale, dola_layers, output_attentions or
-    kv_cache_dtype="int8" NotImplementedError."""
+    attentions: also take output_attentions / attention_layers / attention_reduce (.attentions: None, or .layers and .reduce).
+    .kv_cache_dtype: "bf16" or "int8"; .guidance (_parse_guidance), .dola (_parse_dola), .constraint (_parse_constraint) and .kvpress
+    ((N, w, k), parse_prompt_kv): None when off; the resolve_* functions finish them once the call knows the engine and the rows."""
     unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and k not in _DOLA and k not in _CONSTRAINT
                      and k not in _KVPRESS and not (lookup and k in _LOOKUP) and not (attentions and k in _ATTENTIONS))
     if unknown:
@@ -84,36 +75,6 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     constraint = _parse_constraint(kwargs)
     att = _parse_attentions(kwargs)
     press = parse_prompt_kv(kwargs)
-    if press is not None:
-        for name, on, why in (
-                ("past_key_values", kwargs.get("past_key_values") is not None, "the extend pass reads a cache whose slots are its positions"),
-                ("prompt_lookup_num_tokens", kwargs.get("prompt_lookup_num_tokens") is not None, "the verify step reads a cache whose "
-                 "slots are its positions"),
-                ("guidance_scale", guidance is not None, "compressing the two branches of a guided call is not implemented"),
-                ("dola_layers", dola is not None, "the compressed prompt pass hands out no tapped rows"),
-                ("output_attentions", att is not None, "a map over a compact cache's slots has no position axis"),
-                ("kv_cache_dtype='int8'", parse_kv_cache_dtype(kwargs.get("kv_cache_dtype")) == "int8", "the gather kernel writes bf16 "
-                 "rows only")):
-            if on:
-                raise NotImplementedError(f"prompt_kv_budget / prompt_kv_window with {name}: {why}")
-    if att is not None:
-        for name, on, why in (
-                ("kv_cache_dtype='int8'", parse_kv_cache_dtype(kwargs.get("kv_cache_dtype")) == "int8", "the probability kernel reads a "
-                 "bf16 cache only"),
-                ("past_key_values", kwargs.get("past_key_values") is not None, "the extend pass hands out no attention rows"),
-                ("prompt_lookup_num_tokens", kwargs.get("prompt_lookup_num_tokens") is not None, "the verify step hands out no "
-                 "attention rows"),
-                ("guidance_scale", guidance is not None, "maps of the two branches of a guided step are not implemented"),
-                ("dola_layers", dola is not None, "the tapped decode step hands out no attention rows")):
-            if on:
-                raise NotImplementedError(f"output_attentions with {name}: {why}")
-    if constraint is not None and kwargs.get("prompt_lookup_num_tokens") is not None:
-        raise NotImplementedError("constraint with prompt_lookup_num_tokens: every drafted row of a verify step would need its own "
-                                  "automaton state, which is not implemented")
-    if constraint is not None and guidance is not None:
-        raise NotImplementedError("constraint with guidance_scale: masking the two branches of a guided step is not implemented")
-    if constraint is not None and dola is not None:
-        raise NotImplementedError("constraint with dola_layers: masking the contrasted scores is not implemented")
     if kwargs.get("inputs_embeds") is not None:
         raise NotImplementedError("`inputs_embeds` is not supported")      # the reference's generate() raises the same
     if kwargs.get("do_sample") and kwargs.get("seed") is None:
@@ -136,23 +97,7 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
         raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
                                   "model.merge_and_unload() (the reference merges adapters before evaluation), or decode on the "
                                   "live adapters with model.enable_adapter_decoding()")
-    if guidance is not None and pkv is not None:
-        raise NotImplementedError("guidance_scale with past_key_values: a guided call fills one cache with both branches and keeps none "
-                                  "of it across calls")
-    if guidance is not None and kwargs.get("prompt_lookup_num_tokens") is not None:
-        raise NotImplementedError("guidance_scale with prompt_lookup_num_tokens: verifying drafts on two branches is not implemented")
-    if dola is not None and guidance is not None:
-        raise NotImplementedError("dola_layers with guidance_scale: contrasting layers on top of the guided scores is not implemented")
-    if dola is not None and pkv is not None:
-        raise NotImplementedError("dola_layers with past_key_values: the extend pass hands out no intermediate hidden states")
-    if dola is not None and kwargs.get("prompt_lookup_num_tokens") is not None:
-        raise NotImplementedError("dola_layers with prompt_lookup_num_tokens: the verify step hands out no intermediate hidden states")
     kv_dtype = parse_kv_cache_dtype(kwargs.get("kv_cache_dtype"))
-    if kv_dtype == "int8" and pkv is not None:
-        raise NotImplementedError("kv_cache_dtype='int8' with past_key_values: a GenerationCache is extended by the extend-attention "
-                                  "kernel, which reads a bf16 cache only")
-    if kv_dtype == "int8" and kwargs.get("prompt_lookup_num_tokens") is not None:
-        raise NotImplementedError("kv_cache_dtype='int8' with prompt_lookup_num_tokens: the verify-attention kernel reads a bf16 cache only")
     eos = kwargs.get("eos_token_id", config_eos)
     eos = [] if eos is None else ([int(eos)] if isinstance(eos, (int, np.integer)) else [int(e) for e in eos])
     pad = kwargs.get("pad_token_id", config_pad)
@@ -166,13 +111,72 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     for c in crit:
         if not callable(c):
             raise TypeError(f"stopping criterion {c!r} is not callable")
-    return SimpleNamespace(eos=eos, pad=int(pad), max_new_tokens=None if mnt is None else int(mnt), max_length=None if ml is None else int(ml),
-                           stopping_criteria=crit, output_scores=bool(kwargs.get("output_scores", False)),
-                           output_logits=bool(kwargs.get("output_logits", False)),
-                           return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
-                           past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
-                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola, constraint=constraint, attentions=att, kvpress=press,
-                           **_parse_processors(kwargs, eos))
+    cfg = SimpleNamespace(eos=eos, pad=int(pad), max_new_tokens=None if mnt is None else int(mnt), max_length=None if ml is None else int(ml),
+                          stopping_criteria=crit, output_scores=bool(kwargs.get("output_scores", False)),
+                          output_logits=bool(kwargs.get("output_logits", False)),
+                          return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
+                          past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
+                          kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola, constraint=constraint, attentions=att, kvpress=press,
+                          **_parse_processors(kwargs, eos))
+    refuse_combinations(features_of(cfg), "generate()")
+    return cfg
+
+
+# Combinations that are not implemented.  FEATURES: a feature's name in features_of() -> how a message names it.  REFUSALS: (feature,
+# feature, why); the message is "<feature> with <feature>: <why>".  The first row whose two features are both on is the one reported, so
+# the order is part of the behaviour.  A new feature adds its rows here and nowhere else.
+FEATURES = dict(kvpress="prompt_kv_budget / prompt_kv_window", attentions="output_attentions", constraint="constraint", guidance="guidance_scale",
+                dola="dola_layers", past_key_values="past_key_values", lookup="prompt_lookup_num_tokens", int8="kv_cache_dtype='int8'",
+                share_prefix="share_prefix=True", sampling="do_sample=True", lora="LoRA adapters")
+REFUSALS = (
+    ("kvpress", "past_key_values", "the extend pass reads a cache whose slots are its positions"),
+    ("kvpress", "lookup", "the verify step reads a cache whose slots are its positions"),
+    ("kvpress", "guidance", "compressing the two branches of a guided call is not implemented"),
+    ("kvpress", "dola", "the compressed prompt pass hands out no tapped rows"),
+    ("kvpress", "attentions", "a map over a compact cache's slots has no position axis"),
+    ("kvpress", "int8", "the gather kernel writes bf16 rows only"),
+    ("attentions", "int8", "the probability kernel reads a bf16 cache only"),
+    ("attentions", "past_key_values", "the extend pass hands out no attention rows"),
+    ("attentions", "lookup", "the verify step hands out no attention rows"),
+    ("attentions", "guidance", "maps of the two branches of a guided step are not implemented"),
+    ("attentions", "dola", "the tapped decode step hands out no attention rows"),
+    ("constraint", "lookup", "every drafted row of a verify step would need its own automaton state, which is not implemented"),
+    ("constraint", "guidance", "masking the two branches of a guided step is not implemented"),
+    ("constraint", "dola", "masking the contrasted scores is not implemented"),
+    ("guidance", "past_key_values", "a guided call fills one cache with both branches and keeps none of it across calls"),
+    ("guidance", "lookup", "verifying drafts on two branches is not implemented"),
+    ("dola", "guidance", "contrasting layers on top of the guided scores is not implemented"),
+    ("dola", "past_key_values", "the extend pass hands out no intermediate hidden states"),
+    ("dola", "lookup", "the verify step hands out no intermediate hidden states"),
+    ("int8", "past_key_values", "a GenerationCache is extended by the extend-attention kernel, which reads a bf16 cache only"),
+    ("int8", "lookup", "the verify-attention kernel reads a bf16 cache only"),
+    ("lookup", "sampling", "speculative sampling is not implemented"),
+    ("share_prefix", "int8", "the extend-attention and shared decode kernels read a bf16 cache only"),
+    ("share_prefix", "guidance", "sharing across the two branches of a guided call is not implemented"),
+    ("share_prefix", "dola", "the extend pass and the shared decode step hand out no intermediate hidden states"),
+    ("kvpress", "share_prefix", "a follower's copy and the extend pass read a cache whose slots are its positions"),
+    ("attentions", "lora", "attention maps on the live adapters are not implemented; merge them first with model.merge_and_unload()"),
+)
+
+
+def features_of(cfg, lora=False):
+    """The FEATURES that a cfg has on, parsed or built by hand (a missing attribute is off).  lora: the engine decodes on live
+    adapters."""
+    get = lambda name: getattr(cfg, name, None)
+    on = dict(kvpress=get("kvpress"), attentions=get("attentions"), constraint=get("constraint"), guidance=get("guidance"), dola=get("dola"),
+              past_key_values=get("past_key_values"), sampling=get("sampling"), lookup=get("lookup") if get("drafter") is None else True,
+              int8=get("kv_cache_dtype") == "int8" or None, share_prefix=get("share_prefix") or None, lora=lora or None)
+    return {name for name, v in on.items() if v is not None}
+
+
+def refuse_combinations(features_on, where):
+    """NotImplementedError for the first row of REFUSALS whose two features are both in features_on.  where: the caller, named when
+    features_on holds a name that is no feature."""
+    if not set(features_on) <= set(FEATURES):
+        raise ValueError(f"{where}: unknown features {sorted(set(features_on) - set(FEATURES))}")
+    for a, b, why in REFUSALS:
+        if a in features_on and b in features_on:
+            raise NotImplementedError(f"{FEATURES[a]} with {FEATURES[b]}: {why}")
 
 
 def _parse_attentions(kwargs):
@@ -444,8 +448,6 @@ def _parse_lookup(kwargs):
     ng = 2 if ng is None else ng
     if not _is_int(ng) or ng < 1:
         raise ValueError(f"`max_matching_ngram_size` has to be a strictly positive integer, but is {ng!r}")
-    if kwargs.get("do_sample"):
-        raise NotImplementedError("prompt_lookup_num_tokens with do_sample=True: speculative sampling is not implemented")
     return SimpleNamespace(k=int(k), max_ngram=int(ng))
 
 
@@ -645,6 +647,14 @@ class LogitsProcessors:
                 self._dev["bad"] = ((torch.from_numpy(tok).to(device), torch.from_numpy(off).to(device)) if self.multi else (None, None))
             self._dev[key] = torch.tensor(ban, dtype=torch.int32, device=device) if ban else None
         return (self._dev[key],) + self._dev["bad"]
+
+    def rows_device_args(self, device):
+        """(ban_always, ban_begin, ban_eos, bad_tok, bad_off) device int32 tensors of the per-row kernel (None where empty), which
+        composes a row's bans from the row's own step; uploaded by every call."""
+        i32 = lambda ids: torch.tensor(ids, dtype=torch.int32, device=device) if ids else None
+        bans = (i32(sorted(set(self.suppress) | set(self.one))), i32(sorted(set(self.begin))), i32(sorted(set(self.eos))))
+        tok, off = self.bad_csr()
+        return bans + ((torch.from_numpy(tok).to(device), torch.from_numpy(off).to(device)) if self.multi else (None, None))
 
 
 def new_token_budget(cfg, prompt_len):
@@ -873,10 +883,7 @@ def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
     hist = None
     if lp.active:
         hist = torch.zeros(1, T, dtype=torch.int32, device=dev)
-        i32 = lambda ids: torch.tensor(ids, dtype=torch.int32, device=dev) if ids else None
-        bans = (i32(sorted(set(lp.suppress) | set(lp.one))), i32(sorted(set(lp.begin))), i32(sorted(set(lp.eos))))
-        btok, boff = lp.bad_csr()
-        bad = (torch.from_numpy(btok).to(dev), torch.from_numpy(boff).to(dev)) if lp.multi else (None, None)
+        bans = lp.rows_device_args(dev)
     draft = np.zeros(0, dtype=np.int64)
     t, fed = 0, False                      # fed: the round's rows come from a step that wrote K|V rows (every round but the first)
     while True:
@@ -888,7 +895,7 @@ def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
             info = engine._dev(np.stack([np.zeros(R), t + np.arange(R), np.full(R, lp.min_new), np.append(draft, 0)]).astype(np.int32))
             if R > 1:                      # the drafts go behind the emitted tokens: row i reads hist[0, :t + i]
                 hist[0, t:t + R - 1] = info[3, :R - 1]
-            nxt = ops.logits_process_argmax_rows(logits, V, hist, info[0], info[1], info[2], lp.penalty, lp.ngram, *bans, *bad)
+            nxt = ops.logits_process_argmax_rows(logits, V, hist, info[0], info[1], info[2], lp.penalty, lp.ngram, *bans)
             hist[0, t:t + R] = nxt         # the choices: the drafts while they are accepted, then the token after them
         else:
             nxt = ops.argmax_rows(logits, V)
@@ -927,95 +934,54 @@ def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
         fed = True
 
 
-def _guided_generate(engine, ids, am, images, image_sizes, cfg):
-    """greedy_generate with classifier-free guidance (cfg.guidance): one KVCache of 2 * B rows, rows 0 .. B - 1 prefilled with the
-    prompts and rows B .. 2B - 1 with the negative prompts (resolve_negative_prompts), L_max = the longer spliced length + the budget.
-    Every decode step runs all 2 * B rows and feeds the emitted token (the pad of a finished row) to both halves, which is what HF's
-    processor does with input_ids[:, -1:].  Per step: output_logits clones the raw conditional rows; ops.cfg_guide_rows turns
-    (conditional, unconditional) into the guided rows in place; then the processors, the argmax or the seeded sampler, output_scores
-    and the stopping criteria run on the guided rows exactly as greedy_generate runs them on the raw ones (CFG is HF's first
-    processor).  min_length / max_length count the conditional prompt."""
+def _uniform_choice(engine, cfg, lp, B, T, seeds, keep_history):
+    """The token choice of a call whose rows are all at the same step, set up once per call: the processors and their argmax
+    (ops.logits_process_argmax over `hist`, the tokens generated so far with the pads of finished rows, HF's input_ids of inputs_embeds
+    generation: no prompt), the plain argmax, or the processors and then the seeded sampler (row b with seeds[b] at step t; the warped
+    scores are written back only when output_scores or a stopping criterion reads them).  Returns (choose, hist): choose(logits, t)
+    processes logits in place and returns the ids, a device tensor from an argmax and a host array from the sampler (-1: a row it could
+    not sample); the caller writes each step's emitted tokens into hist (None when no processor is active)."""
     from . import ops
-    gd = cfg.guidance
-    B, dev, V = ids.shape[0], engine.device, engine.vocab
-    if getattr(cfg, "lookup", None) is not None or getattr(cfg, "drafter", None) is not None:
-        raise NotImplementedError("guidance_scale with prompt_lookup_num_tokens: verifying drafts on two branches is not implemented")
-    nids, nam, nimgs, nsizes = resolve_negative_prompts(gd, ids, am)
-    imgs = list(images) if images is not None else []
-    plan = engine.plan(ids, am, None, imgs, image_sizes)
-    nplan = engine.plan(nids, nam, None, nimgs, nsizes)
-    S = int(plan["S"])
-    T = new_token_budget(cfg, S)
-    lp = LogitsProcessors(cfg, V, S)
-    st = GreedyState(B, cfg)
-    scores, raw = [], []
-    sm = cfg.sampling
+    dev, V, sm = engine.device, engine.vocab, cfg.sampling
     if sm is not None:
-        seeds = sampling_seeds(sm, B)
-    if T > 0:
-        kvd = getattr(cfg, "kv_cache_dtype", "bf16")
-        kv_args = () if kvd == "bf16" else (kvd,)
-        L_max = max(int(plan["lens"].max()), int(nplan["lens"].max())) + T
-        need, free = engine.kv_cache_bytes(2 * B, L_max, *kv_args), engine.free_device_bytes()
-        if free is not None and need > free:
-            raise ValueError(f"guided generate(): the KV cache of 2 x {B} rows x {L_max} positions needs {need} bytes, but only {free} "
-                             f"bytes of device memory are free: lower the batch or the token budget")
-        cache = engine.new_kv_cache(2 * B, L_max, *kv_args)
-        _, c = engine.prefill(ids, am, images, image_sizes, cache=cache, slots=np.arange(B))
-        _, u = engine.prefill(nids, nam, nimgs or None, nsizes, cache=cache, slots=B + np.arange(B))
-        if sm is not None:
-            sm_seed = torch.tensor(seeds, dtype=torch.int64, device=dev)
-            sm_t = torch.arange(T, dtype=torch.int32, device=dev)[:, None].expand(T, B).contiguous()
-            sm_write = cfg.output_scores or bool(cfg.stopping_criteria)
-            sm_ws = ops.sample_rows_workspace(B, dev)
-        hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active else None
-        gws = ops.cfg_guide_workspace(B, dev)
-        for t in range(T):
-            if cfg.output_logits:
-                raw.append(c.clone())
-            logits = ops.cfg_guide_rows(c, u, V, gd.scale, ws=gws)         # in place: the conditional rows become the guided scores
-            if lp.active:
-                nxt = ops.logits_process_argmax(logits, V, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
-            elif sm is None:
-                nxt = ops.argmax_rows(logits, V)
-            if sm is not None:
-                nxt = ops.sample_rows(logits, V, sm_seed, sm_t[t], sm.temperature, sm.top_k, sm.top_p, sm.min_p, write_scores=sm_write,
-                                      ws=sm_ws)
-                nxt = nxt.cpu().numpy()
-                _check_sampled(nxt, np.flatnonzero(st.unfinished))
-            if cfg.output_scores:
-                scores.append(logits.clone())
-            tok = st.step(nxt, logits, device=dev)
-            if hist is not None:
-                hist[:, t] = torch.from_numpy(tok.astype(np.int32)).to(dev)
-            if st.all_done or t == T - 1:
-                break
-            both = engine.decode_step(cache, torch.from_numpy(np.concatenate([tok, tok])))
-            c, u = both[:B], both[B:]
-        del cache
-    seq = torch.from_numpy(st.sequences()).to(dev)
-    if cfg.return_dict:
-        return GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
-                                         logits=tuple(raw) if cfg.output_logits else None, past_key_values=None)
-    return seq
+        seed = torch.tensor(seeds, dtype=torch.int64, device=dev)
+        steps = torch.arange(T, dtype=torch.int32, device=dev)[:, None].expand(T, B).contiguous()     # row t: every row at step t
+        write = cfg.output_scores or bool(cfg.stopping_criteria)
+    hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active and keep_history else None
+    ws = ops.sample_rows_workspace(B, dev) if sm is not None else None      # the sampler's scratch, once per call
+
+    def choose(logits, t):
+        if lp.active:                     # in place: logits become HF's processed scores
+            nxt = ops.logits_process_argmax(logits, V, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
+        elif sm is None:
+            nxt = ops.argmax_rows(logits, V)
+        if sm is not None:                # in place when someone reads them: the processed scores become HF's warped scores
+            nxt = ops.sample_rows(logits, V, seed, steps[t], sm.temperature, sm.top_k, sm.top_p, sm.min_p, write_scores=write, ws=ws)
+            nxt = nxt.cpu().numpy()
+        return nxt
+    return choose, hist
 
 
 def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg):
-    """prefill once, then decode_step per token until every row has finished or the budget is spent.  With cfg.past_key_values (a
-    GenerationCache) the prompt pass reuses what the cache holds (LlavaEngine.extend; an empty cache: prefill as without one) and the
-    cache keeps the prompt and every generated token but the last.  With cfg.sampling each step's token is drawn by ops.sample_rows
-    from the processed scores (row b with seed_b at step t) instead of their argmax; output_scores and the stopping criteria then get
-    the warped scores, output_logits the raw ones as before.  cfg.kv_cache_dtype "int8": the cache holds int8 K|V rows with one fp32
-    scale per (position, kv head, K / V) group; the first token comes from the unquantised prompt pass, every later one reads the
-    quantised rows.
+    """One prompt pass, then decode_step per token until every row has finished or the budget is spent: the prompt pass, one loop and
+    one output builder.  The prompt pass is a prefill; with cfg.past_key_values (a GenerationCache) it reuses what the cache holds
+    (LlavaEngine.extend; an empty cache: prefill as without one) and the cache keeps the prompt and every generated token but the
+    last; with cfg.guidance it is two prefills into one KVCache of 2 * B rows (below).  Each step of the loop: output_logits clones the
+    raw rows; guidance, DoLa or the constraint transform them in place; _uniform_choice picks the tokens (the processors, then the
+    argmax or the seeded sampler of cfg.sampling); output_scores and the stopping criteria get the rows as the choice left them;
+    GreedyState.step books the tokens and they are fed to decode_step.  The keywords of prefill and decode_step are built once, and a
+    keyword is passed only when its feature is on.  cfg.kv_cache_dtype "int8": the cache holds int8 K|V rows with one fp32 scale per
+    (position, kv head, K / V) group; the first token comes from the unquantised prompt pass, every later one reads the quantised rows.
+    cfg.guidance (classifier-free guidance): rows 0 .. B - 1 of the cache are prefilled with the prompts and rows B .. 2B - 1 with
+    the negative prompts (resolve_negative_prompts), L_max = the longer spliced length + the budget.  Every decode step runs all
+    2 * B rows and feeds the emitted token (the pad of a finished row) to both halves, which is what HF's processor does with
+    input_ids[:, -1:].  ops.cfg_guide_rows turns (conditional, unconditional) into the guided rows in place (CFG is HF's first
+    processor); output_logits holds the raw conditional rows.  min_length / max_length count the conditional prompt.
     cfg.dola (DoLa): the spec is resolved against the engine's depth once; prefill and every decode_step are asked for the candidate
-    layers' logits (tap_layers=) and ops.dola_contrast_rows turns each step's raw rows into the contrasted rows in place, after
-    output_logits has cloned the raw ones and before the processors, the argmax or the sampler, output_scores and the stopping
-    criteria, which all see the contrasted rows (the place guidance puts the guided rows).  The dict output then carries
-    dola_premature_layers, int64 [B, steps]: the layer each row chose, -1 at steps after the row has finished.
+    layers' logits (tap_layers=) and ops.dola_contrast_rows turns each step's raw rows into the contrasted rows in place.  The dict
+    output then carries dola_premature_layers, int64 [B, steps]: the layer each row chose, -1 at steps after the row has finished.
     cfg.constraint (constrained decoding): the rows' automata become one table and one int32 state per row on the device
-    (constraints.resolve_constraints), every call starting at the start states.  ops.constrain_rows runs on each step's logits after
-    output_logits has cloned the raw rows and before the processors, the argmax or the sampler: it advances every live state by the
+    (constraints.resolve_constraints), every call starting at the start states.  ops.constrain_rows advances every live state by the
     token the row emitted last (the device copy of the tokens that decode_step is fed) and writes -inf on what the new state does
     not allow, so output_scores, the stopping criteria and the sampler see the masked rows.  A row that took an EOS edge is free and
     no longer touched; a row finished by a stopping criterion is fed pads, which may kill its state, and its rows mean nothing
@@ -1026,119 +992,102 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
         ids = ids[None]
     am = cfg.attention_mask
     am = None if am is None else np.asarray(am.cpu() if torch.is_tensor(am) else am)
-    B = ids.shape[0]
-    if getattr(cfg, "guidance", None) is not None:
-        return _guided_generate(engine, ids, am, images, image_sizes, cfg)
-    gc = cfg.past_key_values
+    B, dev, V = ids.shape[0], engine.device, engine.vocab
+    gc, gd, att = cfg.past_key_values, getattr(cfg, "guidance", None), getattr(cfg, "attentions", None)
+    refuse_combinations(features_of(cfg, lora=att is not None and engine.lora), "generate()")          # protects a cfg built by hand
     if gc is not None:
         gc._bind(engine, B)
     lookup = getattr(cfg, "lookup", None) is not None or getattr(cfg, "drafter", None) is not None
     if lookup and B != 1:
         raise ValueError(f"prompt_lookup_num_tokens takes one prompt row (HF's assisted generation is batch-size-1 too), got {B}")
-    if lookup and cfg.sampling is not None:
-        raise NotImplementedError("prompt_lookup_num_tokens with do_sample=True: speculative sampling is not implemented")
     lookup_stats = dict(steps=0, drafted=0, accepted=0)
     st = GreedyState(B, cfg)
-    scores = []
-    dev = engine.device
+    scores, raw, picks, attns = [], [], [], []
+    step_kw = {}                          # the keywords of decode_step, and of prefill with prompt_kw: only those of a feature that is on
     dola = getattr(cfg, "dola", None)
-    tap, picks = {}, []
     if dola is not None:
-        if gc is not None or lookup:
-            raise NotImplementedError("dola_layers with past_key_values or prompt_lookup_num_tokens is not implemented")
         dola = resolve_dola_layers(dola, engine.l["layers"])
-        tap = dict(tap_layers=dola)
+        step_kw["tap_layers"] = dola
     ctab = None
     if getattr(cfg, "constraint", None) is not None:
-        if lookup or dola is not None:
-            raise NotImplementedError("constraint with prompt_lookup_num_tokens or dola_layers is not implemented")
         from .constraints import resolve_constraints
-        ctab, cstart = resolve_constraints(cfg.constraint, B, engine.vocab)
-    press = getattr(cfg, "kvpress", None)
-    ckw = {} if press is None else dict(compress=press)      # handed to prefill only when the keyword was given
-    if press is not None and (gc is not None or lookup or dola is not None or getattr(cfg, "attentions", None) is not None
-                              or getattr(cfg, "kv_cache_dtype", "bf16") == "int8"):
-        raise NotImplementedError("prompt_kv_budget / prompt_kv_window with past_key_values, prompt_lookup_num_tokens, dola_layers, "
-                                  "output_attentions or kv_cache_dtype='int8' is not implemented")
-    att = getattr(cfg, "attentions", None)
-    akw, amap, attns = {}, None, []
+        ctab, cstart = resolve_constraints(cfg.constraint, B, V)
     if att is not None:
-        if gc is not None or lookup or dola is not None or getattr(cfg, "kv_cache_dtype", "bf16") == "int8":
-            raise NotImplementedError("output_attentions with past_key_values, prompt_lookup_num_tokens, dola_layers or "
-                                      "kv_cache_dtype='int8' is not implemented")
-        if engine.lora:
-            raise NotImplementedError("output_attentions with LoRA adapters: attention maps on the live adapters are not implemented; "
-                                      "merge them first with model.merge_and_unload()")
         att_layers = resolve_attention_layers(att.layers, engine.l["layers"])
-        akw = dict(attn_layers=att_layers, attn_mean=att.reduce == "mean_heads")
+        step_kw.update(attn_layers=att_layers, attn_mean=att.reduce == "mean_heads")
+    kvd = getattr(cfg, "kv_cache_dtype", "bf16")
+    kv_args = () if kvd == "bf16" else (kvd,)                 # the default dtype keeps the two-argument calls
+    prompt_kw = dict(step_kw)
+    if kvd != "bf16":
+        prompt_kw["kv_dtype"] = kvd
+    if getattr(cfg, "kvpress", None) is not None:
+        prompt_kw["compress"] = cfg.kvpress
+    imgs = list(images) if images is not None else []
     # prompt length in HF's sense: the spliced inputs_embeds width (the longest spliced prompt of the batch)
-    plan_len = None
-    if (cfg.max_new_tokens is None and cfg.max_length is not None) or min_needs_prompt_len(cfg):
-        plan_len = int(engine.plan(ids, am, None, list(images) if images is not None else [], image_sizes)["S"])
-    T = new_token_budget(cfg, plan_len or 0)
-    lp = LogitsProcessors(cfg, engine.vocab, plan_len or 0)
-    raw = []
+    plan_len = 0
+    if gd is not None:
+        nids, nam, nimgs, nsizes = resolve_negative_prompts(gd, ids, am)
+        plan, nplan = engine.plan(ids, am, None, imgs, image_sizes), engine.plan(nids, nam, None, nimgs, nsizes)
+        plan_len = int(plan["S"])
+    elif (cfg.max_new_tokens is None and cfg.max_length is not None) or min_needs_prompt_len(cfg):
+        plan_len = int(engine.plan(ids, am, None, imgs, image_sizes)["S"])
+    T = new_token_budget(cfg, plan_len)
+    lp = LogitsProcessors(cfg, V, plan_len)
     sm = cfg.sampling
-    if sm is not None:
-        seeds = sampling_seeds(sm, B)
+    seeds = None if sm is None else sampling_seeds(sm, B)
     if T > 0:
-        if sm is not None:
-            sm_seed = torch.tensor(seeds, dtype=torch.int64, device=dev)
-            sm_t = torch.arange(T, dtype=torch.int32, device=dev)[:, None].expand(T, B).contiguous()     # row t: every row at step t
-            sm_write = cfg.output_scores or bool(cfg.stopping_criteria)
-        # the tokens generated so far, pads of finished rows included (HF's input_ids of inputs_embeds generation: no prompt)
-        hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if lp.active and not lookup else None      # the accept loop keeps its own
-        sm_ws = ops.sample_rows_workspace(B, dev) if sm is not None else None      # the sampler's scratch, once per call
-        if gc is None:
-            if getattr(cfg, "kv_cache_dtype", "bf16") == "int8":
-                if lookup:
-                    raise NotImplementedError("kv_cache_dtype='int8' with prompt-lookup decoding: the verify-attention kernel reads a bf16 "
-                                              "cache only")
-                cache, logits, *cand = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, kv_dtype="int8", **tap)
-            elif att is not None:
-                cache, logits, amap = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **akw)
+        # ---------------------------------------------------------------------------------------- the prompt pass
+        if gd is not None:
+            L_max = max(int(plan["lens"].max()), int(nplan["lens"].max())) + T
+            need, free = engine.kv_cache_bytes(2 * B, L_max, *kv_args), engine.free_device_bytes()
+            if free is not None and need > free:
+                raise ValueError(f"guided generate(): the KV cache of 2 x {B} rows x {L_max} positions needs {need} bytes, but only {free} "
+                                 f"bytes of device memory are free: lower the batch or the token budget")
+            cache = engine.new_kv_cache(2 * B, L_max, *kv_args)
+            _, logits = engine.prefill(ids, am, images, image_sizes, cache=cache, slots=np.arange(B))
+            _, uncond = engine.prefill(nids, nam, nimgs or None, nsizes, cache=cache, slots=B + np.arange(B))
+            choose, hist = _uniform_choice(engine, cfg, lp, B, T, seeds, True)
+            gws = ops.cfg_guide_workspace(B, dev)
+        else:
+            choose, hist = _uniform_choice(engine, cfg, lp, B, T, seeds, not lookup)       # the accept loop keeps its own history
+            if gc is None:
+                cache, logits, *extra = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **prompt_kw)
             else:
-                cache, logits, *cand = engine.prefill(ids, am, images, image_sizes, max_new_tokens=T, **tap, **ckw)
+                plan = engine.plan(ids, am, None, imgs, image_sizes)
+                uids = gc._image_uids(imgs, image_sizes)
+                recs = position_records(plan, uids)
+                reuse = np.zeros(B, dtype=np.int64) if gc.kv is None else reuse_lengths(gc.records, recs)
+                kv, gc.kv, gc.records = gc.kv, None, None         # an unused cache is freed before prefill allocates the new one
+                if not reuse.any():
+                    kv = None
+                cache, logits = engine.extend(kv, ids, am, images, image_sizes, reuse=reuse, max_new_tokens=T, plan=plan)
+                del kv
             if dola is not None:
                 dws = ops.dola_workspace(B, len(dola), dev)
-        else:
-            imgs = list(images) if images is not None else []
-            plan = engine.plan(ids, am, None, imgs, image_sizes)
-            uids = gc._image_uids(imgs, image_sizes)
-            recs = position_records(plan, uids)
-            reuse = np.zeros(B, dtype=np.int64) if gc.kv is None else reuse_lengths(gc.records, recs)
-            kv, gc.kv, gc.records = gc.kv, None, None         # an unused cache is freed before prefill allocates the new one
-            if not reuse.any():
-                kv = None
-            cache, logits = engine.extend(kv, ids, am, images, image_sizes, reuse=reuse, max_new_tokens=T, plan=plan)
-            del kv
-        if lookup:
+        if lookup:                        # the accept loop runs the whole generation
             if cfg.drafter is None:
-                cfg.drafter = PromptLookupDrafter(cfg.lookup.k, cfg.lookup.max_ngram, cfg.eos, engine.vocab)
+                cfg.drafter = PromptLookupDrafter(cfg.lookup.k, cfg.lookup.max_ngram, cfg.eos, V)
             prompt_ids = ids[0] if am is None else ids[0][np.asarray(am).reshape(B, -1)[0].astype(bool)]
             lookup_stats = _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
-        plain_steps = 0 if lookup else T     # the accept loop above has run the whole generation
         if ctab is not None:              # every call starts at the start states, a continued conversation too
             ctabs, cstate, ctok = ctab.device_tables(dev), engine._dev(cstart), None
             mirror = ConstraintMirror(ctab, B)
             mirror.state[:] = cstart
-        for t in range(plain_steps):
+        # ---------------------------------------------------------------------------------------- the loop
+        for t in range(0 if lookup else T):
             if cfg.output_logits:
                 raw.append(logits.clone())
             if att is not None:           # the maps of the step that gave these logits: HF's [B, H, 1, L_t]
-                attns.append(tuple(a[:, None, None, :] if a.dim() == 2 else a[:, :, None, :] for a in amap))
-            if dola is not None:          # in place: the raw mature rows become the contrasted rows
-                picks.append((ops.dola_contrast_rows(logits, cand[0], engine.vocab, ws=dws)[1], st.unfinished.copy()))
-            if ctab is not None:          # in place: each live row's state takes the row's last token, then bans what it does not allow
-                ops.constrain_rows(logits, engine.vocab, cstate, ctabs, tok=ctok)
-            if lp.active:                 # in place: logits become HF's processed scores
-                nxt = ops.logits_process_argmax(logits, engine.vocab, hist, t, lp.penalty, lp.ngram, *lp.device_args(t, dev))
-            elif sm is None:
-                nxt = ops.argmax_rows(logits, engine.vocab)
-            if sm is not None:            # in place when someone reads them: the processed scores become HF's warped scores
-                nxt = ops.sample_rows(logits, engine.vocab, sm_seed, sm_t[t], sm.temperature, sm.top_k, sm.top_p, sm.min_p, write_scores=sm_write,
-                                      ws=sm_ws)
-                nxt = nxt.cpu().numpy()
+                attns.append(tuple(a[:, None, None, :] if a.dim() == 2 else a[:, :, None, :] for a in extra[0]))
+            # the transforms, in place: the raw rows become the guided rows, the contrasted rows, the rows the automaton allows
+            if gd is not None:
+                ops.cfg_guide_rows(logits, uncond, V, gd.scale, ws=gws)
+            if dola is not None:
+                picks.append((ops.dola_contrast_rows(logits, extra[0], V, ws=dws)[1], st.unfinished.copy()))
+            if ctab is not None:          # each live row's state takes the row's last token first
+                ops.constrain_rows(logits, V, cstate, ctabs, tok=ctok)
+            nxt = choose(logits, t)
+            if sm is not None:
                 if ctab is not None:      # the sampler's -1 on a constrained row is a dead end, named as one
                     bad = np.flatnonzero(st.unfinished & (nxt < 0))
                     mirror.take(bad, nxt[bad], None, lambda k: f"row {bad[k]}", t)
@@ -1155,38 +1104,35 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             if st.all_done or t == T - 1:
                 break
             if ctab is not None:          # one upload serves the next step's advance and the decode step
-                ctok = engine._dev(tok)
-                if att is not None:
-                    logits, amap = engine.decode_step(cache, ctok, **akw)
-                else:
-                    logits = engine.decode_step(cache, ctok)
-            elif att is not None:
-                logits, amap = engine.decode_step(cache, torch.from_numpy(tok), **akw)
-            elif dola is None:
-                logits = engine.decode_step(cache, torch.from_numpy(tok))
-            else:
-                logits, *cand = engine.decode_step(cache, torch.from_numpy(tok), **tap)
+                feed = ctok = engine._dev(tok)
+            else:                         # a guided step feeds the token to both halves
+                feed = torch.from_numpy(tok if gd is None else np.concatenate([tok, tok]))
+            out = engine.decode_step(cache, feed, **step_kw)
+            logits, *extra = out if step_kw else (out,)
+            if gd is not None:
+                logits, uncond = logits[:B], logits[B:]
         if gc is not None:          # the prompt and the tokens fed to decode_step (every emitted one but the last; pads of finished rows)
             fed = st.sequences()[:, :int(cache.lens[0] - plan["lens"][0])]
             gc._store(cache, [np.concatenate([recs[b], fed[b]]) for b in range(B)], imgs, image_sizes, uids, engine)
         del cache
+    # -------------------------------------------------------------------------------------------- the output
     seq = torch.from_numpy(st.sequences()).to(dev)
-    if cfg.return_dict:
-        out = GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
-                                        logits=tuple(raw) if cfg.output_logits else None, past_key_values=cfg.past_key_values)
-        if lookup:
-            out.lookup_stats = lookup_stats
-        if att is not None:
-            out.attentions, out.attention_layers = tuple(attns), att_layers
-        if dola is not None:
-            lay = np.full((B, len(picks)), -1, dtype=np.int64)
-            if picks:
-                ch = torch.stack([c for c, _ in picks], 1).cpu().numpy()           # one copy: [B, steps] indices into `dola`
-                live = np.stack([u for _, u in picks], 1)
-                lay[live] = np.asarray(dola, dtype=np.int64)[ch[live]]
-            out.dola_premature_layers = torch.from_numpy(lay).to(dev)
-        return out
-    return seq
+    if not cfg.return_dict:
+        return seq
+    out = GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
+                                    logits=tuple(raw) if cfg.output_logits else None, past_key_values=gc)
+    if lookup:
+        out.lookup_stats = lookup_stats
+    if att is not None:
+        out.attentions, out.attention_layers = tuple(attns), att_layers
+    if dola is not None:
+        lay = np.full((B, len(picks)), -1, dtype=np.int64)
+        if picks:
+            ch = torch.stack([c for c, _ in picks], 1).cpu().numpy()           # one copy: [B, steps] indices into `dola`
+            live = np.stack([u for _, u in picks], 1)
+            lay[live] = np.asarray(dola, dtype=np.int64)[ch[live]]
+        out.dola_premature_layers = torch.from_numpy(lay).to(dev)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ continuous batching: generate_batch
@@ -1208,9 +1154,9 @@ class GenerationOutput(SimpleNamespace):
 def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
     """generate_batch() keywords: generate()'s greedy and sampling settings (seed: an int, or a list of n ints), validated by parse_generate_kwargs and applied per request;
     max_new_tokens may also be a list of n budgets (cfg.budgets).  TypeError for arguments without a per-request meaning.
-    share_prefix (cfg.share_prefix, default False): a bool, ValueError otherwise; NotImplementedError together with
-    kv_cache_dtype="int8", guidance_scale or dola_layers.  constraint (cfg.constraint): one TokenConstraint for every request or a
-    list of n entries, None for an unconstrained request; ValueError for another length."""
+    share_prefix (cfg.share_prefix, default False): a bool, ValueError otherwise; its rows of REFUSALS are checked here.  constraint
+    (cfg.constraint): one TokenConstraint for every request or a list of n entries, None for an unconstrained request; ValueError
+    for another length."""
     given = sorted(k for k in _NO_PER_REQUEST if kwargs.get(k) is not None and kwargs.get(k) is not False)
     if given:
         raise TypeError(f"generate_batch() got arguments without a per-request meaning: {given}")
@@ -1235,17 +1181,7 @@ def parse_batch_kwargs(kwargs, n, lora=False, config_eos=None, config_pad=None):
     cfg = parse_generate_kwargs(kw, lora=lora, config_eos=config_eos, config_pad=config_pad)
     cfg.budgets = budgets
     cfg.share_prefix = bool(share)
-    if cfg.share_prefix and cfg.kv_cache_dtype == "int8":
-        raise NotImplementedError("share_prefix=True with kv_cache_dtype='int8': the extend-attention and shared decode kernels read a bf16 "
-                                  "cache only")
-    if cfg.share_prefix and cfg.guidance is not None:
-        raise NotImplementedError("share_prefix=True with guidance_scale: sharing across the two branches of a guided call is not implemented")
-    if cfg.share_prefix and cfg.dola is not None:
-        raise NotImplementedError("share_prefix=True with dola_layers: the extend pass and the shared decode step hand out no intermediate "
-                                  "hidden states")
-    if cfg.share_prefix and cfg.kvpress is not None:
-        raise NotImplementedError("prompt_kv_budget / prompt_kv_window with share_prefix=True: a follower's copy and the extend pass "
-                                  "read a cache whose slots are its positions")
+    refuse_combinations(features_of(cfg), "generate_batch()")
     if cfg.guidance is not None:
         for k in ("negative_prompt_ids", "negative_images", "negative_image_sizes"):
             _per_request(k, getattr(cfg.guidance, k), n)      # a list of another length: ValueError here, before anything runs
@@ -1425,12 +1361,8 @@ class DevicePicker:
         self.penalty, self.ngram = lp.penalty, lp.ngram
         self.active = (lp.penalty != 1.0 or lp.ngram > 0 or bool(cfg.bad_words_ids) or bool(lp.suppress) or bool(lp.begin) or
                        (any_min_new and bool(lp.eos)))
-        dev = engine.device
-        i32 = lambda ids: torch.tensor(ids, dtype=torch.int32, device=dev) if ids else None
-        self.bans = (i32(sorted(set(lp.suppress) | set(lp.one))), i32(sorted(set(lp.begin))), i32(sorted(set(lp.eos))))
-        tok, off = lp.bad_csr()
-        self.bad = (torch.from_numpy(tok).to(dev), torch.from_numpy(off).to(dev)) if lp.multi else (None, None)
-        self.hist = torch.zeros(slots, max(int(max_budget), 1), dtype=torch.int32, device=dev) if self.active else None
+        self.bans = lp.rows_device_args(engine.device)
+        self.hist = torch.zeros(slots, max(int(max_budget), 1), dtype=torch.int32, device=engine.device) if self.active else None
         self.ws, self.ws_rows = None, 0                       # the sampler's scratch, kept across steps
 
     def __call__(self, logits, slot, t, min_new, seed=None):
@@ -1445,7 +1377,7 @@ class DevicePicker:
         info = self.engine._dev(np.stack([slot, t, min_new, slot * cols + t]).astype(np.int32))
         lpo = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device) if self.logprobs else None
         tok = ops.logits_process_argmax_rows(logits, self.vocab, self.hist, info[0], info[1], info[2], self.penalty, self.ngram, *self.bans,
-                                             *self.bad, logprob=lpo)
+                                             logprob=lpo)
         if self.hist is not None:
             self.hist.view(-1).index_copy_(0, info[3].long(), tok.to(torch.int32))
         return tok.cpu().numpy(), None if lpo is None else lpo.cpu().numpy()
@@ -1460,8 +1392,7 @@ class DevicePicker:
         d = self.engine._dev(host)
         info, seeds = d[:4 * rows].view(4, rows), d[4 * rows:].view(torch.int64)
         if self.active:
-            ops.logits_process_argmax_rows(logits, self.vocab, self.hist, info[0], info[1], info[2], self.penalty, self.ngram, *self.bans,
-                                           *self.bad)
+            ops.logits_process_argmax_rows(logits, self.vocab, self.hist, info[0], info[1], info[2], self.penalty, self.ngram, *self.bans)
         if self.ws is None or self.ws_rows < rows:            # grows to the largest step (all slots) and stays
             self.ws, self.ws_rows = ops.sample_rows_workspace(rows, logits.device), rows
         lpo = torch.empty(rows, dtype=torch.float32, device=logits.device) if self.logprobs else None
@@ -1523,6 +1454,7 @@ class BatchScheduler:
                  constrain=None):
         if not _is_int(max_batch_size) or max_batch_size < 1:
             raise ValueError(f"max_batch_size must be an int >= 1, got {max_batch_size!r}")
+        refuse_combinations(features_of(cfg), "generate_batch()")        # protects a cfg built by hand
         self.engine, self.reqs, self.cfg = engine, reqs, cfg
         self.logprobs = bool(return_logprobs)
         n = len(reqs)
@@ -1530,8 +1462,6 @@ class BatchScheduler:
         self.spliced = [int(pl["lens"][0]) for pl in plans]
         self.share = bool(getattr(cfg, "share_prefix", False))
         if self.share:
-            if getattr(cfg, "guidance", None) is not None or getattr(cfg, "kv_cache_dtype", "bf16") == "int8":
-                raise NotImplementedError("share_prefix=True takes a bf16 cache and no guidance_scale")
             held = []                                         # one uid table per call: (pixels, image_size) of every distinct image
             self.records = [position_records(pl, self._image_uids(held, r))[0] for pl, r in zip(plans, reqs)]
         del plans
@@ -1542,24 +1472,17 @@ class BatchScheduler:
         self.slots = min(int(max_batch_size), len(self.runs))
         self.L_max = max([self.spliced[i] + self.budget[i] for i in self.runs], default=0)
         self.press = getattr(cfg, "kvpress", None)
-        self.ckw = {}
         if self.press is not None:            # a request then takes min(spliced, N) slots: the cache and the memory check shrink with it
-            if self.share or getattr(cfg, "guidance", None) is not None or getattr(cfg, "dola", None) is not None \
-                    or getattr(cfg, "kv_cache_dtype", "bf16") == "int8":
-                raise NotImplementedError("prompt_kv_budget / prompt_kv_window with share_prefix=True, guidance_scale, dola_layers or "
-                                          "kv_cache_dtype='int8' is not implemented")
-            self.ckw = dict(compress=self.press)
             self.L_max = max([min(self.spliced[i], self.press[0]) + self.budget[i] for i in self.runs], default=0)
         self.guidance, self.guide = getattr(cfg, "guidance", None), guide
         self.dola, self.contrast = getattr(cfg, "dola", None), None
         if self.dola is not None:
-            if self.guidance is not None or self.share:
-                raise NotImplementedError("dola_layers with guidance_scale or share_prefix=True is not implemented")
             self.dola = resolve_dola_layers(self.dola, engine.l["layers"])
+        # the keywords of decode_step, and of prefill with compress=: only those of a feature that is on
+        self.step_kw = {} if self.dola is None else dict(tap_layers=self.dola)
+        self.prefill_kw = dict(self.step_kw) if self.press is None else dict(self.step_kw, compress=self.press)
         self.ctab, self.constrain = None, constrain
         if getattr(cfg, "constraint", None) is not None:
-            if self.guidance is not None or self.dola is not None:
-                raise NotImplementedError("constraint with guidance_scale or dola_layers is not implemented")
             from .constraints import resolve_constraints
             self.ctab, self.cstart = resolve_constraints(cfg.constraint, n, engine.vocab, what="request")
         if self.guidance is not None:
@@ -1614,6 +1537,8 @@ class BatchScheduler:
             from . import ops
             dws, V = ops.dola_workspace(S, len(self.dola), eng.device), eng.vocab
             self.contrast = lambda f, c: ops.dola_contrast_rows(f, c, V, ws=dws)
+        # what turns a step's rows into the rows the picker sees, in place: (conditional, unconditional) or (last layer, candidates)
+        self.transform = self.guide if self.guidance is not None else self.contrast
         if self.ctab is not None:
             self.mirror = ConstraintMirror(self.ctab, S)
             if self.constrain is None:
@@ -1639,36 +1564,53 @@ class BatchScheduler:
                 self._decode()
         del self.cache
 
+    @staticmethod
+    def _pack(requests, negative=False):
+        """The padded prompt batch of `requests` (negative: of their negative prompts), image requests first: in a batch the splice
+        gives a text-only prompt a (dummy) image slot, which must not shift later images.  Returns (order, ids, am, imgs, sizes): row b
+        holds requests[order[b]]; imgs is the flat image list in row order and sizes their sizes, None when no request gives any."""
+        part = (lambda r: (r.neg_ids, r.neg_images, r.neg_sizes)) if negative else (lambda r: (r.ids, r.images, r.sizes))
+        order = sorted(range(len(requests)), key=lambda j: not part(requests[j])[1])
+        rows = [part(requests[j]) for j in order]
+        ids = np.zeros((len(rows), max(p.size for p, _, _ in rows)), dtype=np.int64)
+        am = np.zeros(ids.shape, dtype=bool)
+        for b, (p, _, _) in enumerate(rows):
+            ids[b, :p.size], am[b, :p.size] = p, True
+        imgs = [im for _, ims, _ in rows for im in ims]
+        sizes = [s for _, _, sz in rows for s in (sz or [])] if any(sz is not None for _, _, sz in rows) else None
+        return order, ids, am, imgs, sizes
+
     def _admit(self, group, gslots):
+        """An admission, in up to two phases: the leaders (without share_prefix: everyone) through one prefill -- a guided call
+        prefills their negative prompts into rows slots + s after it -- then every follower's shared positions are copied into its
+        slot (one copy per layer) and one extend computes all the followers' suffixes.  _step runs once per phase."""
         eng = self.engine
         self.events.append(("admit", tuple(group), tuple(gslots)))
         for q, s in zip(group, gslots):
             self.owner[s], self.t[s], self.mn[s] = q, 0, self.min_new[q]
-        if self.share:
-            followers = self._match(group, gslots)
-            if followers:
-                self._admit_shared(group, gslots, followers)
-                return
-        # image requests first: in a batch the splice gives a text-only prompt a (dummy) image slot, which must not shift later images
-        order = sorted(range(len(group)), key=lambda j: not self.reqs[group[j]].images)
-        rq = [self.reqs[group[j]] for j in order]
-        rs = [gslots[j] for j in order]
-        T = max(r.ids.size for r in rq)
-        ids = np.zeros((len(rq), T), dtype=np.int64)
-        am = np.zeros((len(rq), T), dtype=bool)
-        for b, r in enumerate(rq):
-            ids[b, :r.ids.size], am[b, :r.ids.size] = r.ids, True
-        imgs = [im for r in rq for im in r.images]
-        sizes = [s for r in rq for s in (r.sizes or [])] if any(r.sizes is not None for r in rq) else None
-        if self.dola is not None:
-            _, logits, cand = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs, tap_layers=self.dola)
-            self.contrast(logits, cand)
+        followers = self._match(group, gslots) if self.share else {}
+        for phase in (False, True):
+            members = [j for j in range(len(group)) if (j in followers) == phase]
+            if not members:
+                continue
+            order, ids, am, imgs, sizes = self._pack([self.reqs[group[j]] for j in members])
+            rows = [members[j] for j in order]
+            rs = [gslots[j] for j in rows]
+            if not phase:
+                _, logits, *other = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs, **self.prefill_kw)
+                if self.guidance is not None:
+                    other = [self._prefill_negative([self.reqs[group[j]] for j in rows], rs)]
+            else:
+                reuse = np.array([followers[j][1] for j in rows], dtype=np.int64)
+                for j in members:                             # input order: a source is an older slot or a leader of phase 1
+                    src, p = followers[j]
+                    for layer in self.cache.layers:
+                        layer[gslots[j], :p] = layer[src, :p]
+                    self.cache.lens[gslots[j]] = p            # the slot holds these positions now: what extend(reuse=) checks
+                _, logits = eng.extend(self.cache, ids, am, imgs or None, sizes, reuse=reuse, slots=rs)
+            if self.transform is not None:
+                self.transform(logits, other[0])
             self._step(logits, rs)
-            return
-        _, logits = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs, **self.ckw)
-        if self.guidance is not None:
-            logits = self._admit_negative(logits, rq, rs)
-        self._step(logits, rs)
 
     def _match(self, group, gslots):
         """Sources of an admitted group (share_prefix): for each request in input order, the best source (best_source) among the active
@@ -1696,36 +1638,6 @@ class BatchScheduler:
         self.retile = True
         return followers
 
-    def _admit_shared(self, group, gslots, followers):
-        """An admission with followers, in two phases: the leaders through prefill as ever; then every follower's shared positions are
-        copied into its slot (one copy per layer) and one extend computes all the followers' suffixes.  _step runs once per phase."""
-        eng = self.engine
-        for part in (False, True):
-            members = [j for j in range(len(group)) if (j in followers) == part]
-            if not members:
-                continue
-            order = sorted(members, key=lambda j: not self.reqs[group[j]].images)      # the image-first rule of _admit
-            rq = [self.reqs[group[j]] for j in order]
-            rs = [gslots[j] for j in order]
-            T = max(r.ids.size for r in rq)
-            ids = np.zeros((len(rq), T), dtype=np.int64)
-            am = np.zeros((len(rq), T), dtype=bool)
-            for b, r in enumerate(rq):
-                ids[b, :r.ids.size], am[b, :r.ids.size] = r.ids, True
-            imgs = [im for r in rq for im in r.images]
-            sizes = [s for r in rq for s in (r.sizes or [])] if any(r.sizes is not None for r in rq) else None
-            if not part:
-                _, logits = eng.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=rs)
-            else:
-                reuse = np.array([followers[j][1] for j in order], dtype=np.int64)
-                for j in members:                             # input order: a source is an older slot or a leader of phase 1
-                    src, p = followers[j]
-                    for layer in self.cache.layers:
-                        layer[gslots[j], :p] = layer[src, :p]
-                    self.cache.lens[gslots[j]] = p            # the slot holds these positions now: what extend(reuse=) checks
-                _, logits = eng.extend(self.cache, ids, am, imgs or None, sizes, reuse=reuse, slots=rs)
-            self._step(logits, rs)
-
     def _shared_plan(self):
         """The decode step's tile table, rebuilt when an admission or a finish changed the active set and uploaded when it differs
         from the last one; None while no tile shares a chunk."""
@@ -1739,54 +1651,38 @@ class BatchScheduler:
                 self.plan = self.engine.shared_plan(c0, tile) if c0.any() else None
         return self.plan
 
-    def _admit_negative(self, logits, rq, rs):
-        """Prefill the negative prompts of the admitted requests rq (slots rs) into rows slots + s and guide the group's logits."""
-        order = sorted(range(len(rq)), key=lambda j: not rq[j].neg_images)     # the image-first rule, among the negative prompts
-        nq = [rq[j] for j in order]
-        T = max(r.neg_ids.size for r in nq)
-        ids = np.zeros((len(nq), T), dtype=np.int64)
-        am = np.zeros((len(nq), T), dtype=bool)
-        for b, r in enumerate(nq):
-            ids[b, :r.neg_ids.size], am[b, :r.neg_ids.size] = r.neg_ids, True
-        imgs = [im for r in nq for im in r.neg_images]
-        sizes = [s for r in nq for s in (r.neg_sizes or [])] if any(r.neg_sizes is not None for r in nq) else None
+    def _prefill_negative(self, rq, rs):
+        """Prefill the negative prompts of the admitted requests rq (slots rs) into rows slots + s; returns their logits in rq's order."""
+        order, ids, am, imgs, sizes = self._pack(rq, negative=True)
         _, un = self.engine.prefill(ids, am, imgs or None, sizes, cache=self.cache, slots=[self.slots + rs[j] for j in order])
         back = np.argsort(np.asarray(order))                                    # row j of the group is row back[j] of `un`
         if not np.array_equal(back, np.arange(len(order))):
             un = un[torch.as_tensor(back, device=un.device)]
-        self.guide(logits, un)
-        return logits
+        return un
 
     def _decode(self):
-        idle = self.owner < 0
+        """One decode step over every cache row: the slots, and under guidance the rows slots + s after them, fed the same tokens."""
+        idle, S = self.owner < 0, self.slots
         self.events.append(("decode", tuple(int(s) for s in np.flatnonzero(~idle))))
-        if self.guidance is not None:
-            idle2 = np.concatenate([idle, idle])
-            self.cache.lens[idle2] = 0
-            feed = np.where(idle, 0, self.pending)
-            logits = self.engine.decode_step(self.cache, np.concatenate([feed, feed]))
-            self.cache.lens[idle2] = 0
-            self.guide(logits[:self.slots], logits[self.slots:])
-            self._step(logits[:self.slots], list(range(self.slots)))
-            return
-        self.cache.lens[idle] = 0
-        if self.dola is not None:
-            logits, cand = self.engine.decode_step(self.cache, np.where(idle, 0, self.pending), tap_layers=self.dola)
-            self.cache.lens[idle] = 0
-            self.contrast(logits, cand)
-            self._step(logits, list(range(self.slots)))
-            return
+        idle_rows = idle if self.guidance is None else np.concatenate([idle, idle])
+        self.cache.lens[idle_rows] = 0
+        kw = self.step_kw
         plan = self._shared_plan() if self.share else None
-        feed = np.where(idle, 0, self.pending)
-        fed = None
+        if plan is not None:
+            kw = dict(kw, shared=plan)
+        feed, fed = np.where(idle, 0, self.pending), None
         if self.ctab is not None:         # one upload: the decode step's tokens are the ones the automaton states take
             feed = fed = self.engine._dev(feed.astype(np.int64))
-        if plan is None:
-            logits = self.engine.decode_step(self.cache, feed)
-        else:
-            logits = self.engine.decode_step(self.cache, feed, shared=plan)
-        self.cache.lens[idle] = 0
-        self._step(logits, list(range(self.slots)), fed)
+        if self.guidance is not None:
+            feed = np.concatenate([feed, feed])
+        out = self.engine.decode_step(self.cache, feed, **kw)
+        self.cache.lens[idle_rows] = 0
+        logits, *other = out if self.step_kw else (out,)
+        if self.guidance is not None:
+            logits, other = logits[:S], [logits[S:]]
+        if self.transform is not None:
+            self.transform(logits, other[0])
+        self._step(logits, list(range(S)), fed)
 
     def _device_constrain(self):
         """The default `constrain`: the call's table and one int32 state per slot on the device, ops.constrain_rows."""
