@@ -1,7 +1,6 @@
 """CPU tests of generate()'s greedy logits processors: the numpy restatement (tests/logits_ref.py) against transformers' own processor
 classes, keyword parsing and validation, the per-step ban lists, and the C-ABI declaration of rv_logits_process_argmax_f32."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -150,9 +149,7 @@ def test_static_ban_lists_per_step():
 
 def test_logits_process_symbol_declared_and_bound():
     from radvlm_amd import lib
-    hdr = open(os.path.join(ROOT, "include", "radvlm_hip.h")).read()
-    assert "rv_logits_process_argmax_f32" in set(re.findall(r"\b(rv_[a-z0-9_]+)\s*\(", hdr))
-    assert "rv_logits_process_argmax_f32" in lib.EXPORTED_SYMBOLS and "rv_logits_process_argmax_f32" in lib._SIGS
+    assert "rv_logits_process_argmax_f32" in lib.SIGNATURES
     from radvlm_amd import ops
     assert callable(ops.logits_process_argmax)
     so = os.path.join(ROOT, "radvlm_amd", "libradvlm_hip.so")

@@ -24,8 +24,7 @@ def test_merge_entry_point_declared_and_bound():
     from radvlm_amd import lib
     with open(os.path.join(ROOT, "include", "radvlm_hip.h")) as f:
         assert "int rv_lora_merge_bf16(void* W, int64_t ldw, const void* B, int64_t ldb, const void* A, int64_t lda" in f.read()
-    assert "rv_lora_merge_bf16" in lib._SIGS and "rv_lora_merge_bf16" in lib.EXPORTED_SYMBOLS
-    assert len(lib._SIGS["rv_lora_merge_bf16"]) == 11
+    assert len(lib.SIGNATURES["rv_lora_merge_bf16"][1]) == 11
 
 
 def test_adapter_config_scale_and_targets():

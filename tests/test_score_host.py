@@ -15,10 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_score_symbols_declared_and_bound():
     from radvlm_amd import lib
-    hdr = open(os.path.join(ROOT, "include", "radvlm_hip.h")).read()
-    declared = set(re.findall(r"\b(rv_[a-z0-9_]+)\s*\(", hdr))
-    for s in ("rv_attn_extend_prefix_bf16", "rv_token_logprob_rows_f32"):
-        assert s in declared and s in lib.EXPORTED_SYMBOLS and s in lib._SIGS, s
+    assert {"rv_attn_extend_prefix_bf16", "rv_token_logprob_rows_f32"} <= set(lib.SIGNATURES)
     build = open(os.path.join(ROOT, "radvlm_amd", "csrc", "build.sh")).read()
     assert re.search(r'SRCS="[^"]*\bscore\b', build) and '$(printf "$OBJ/%s.res " $SRCS)' in build          # built, and under the scratch gate
 

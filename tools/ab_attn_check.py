@@ -8,8 +8,7 @@ z = torch.zeros(64, dtype=torch.uint8, device="cuda")
 st = torch.cuda.current_stream().cuda_stream
 outs = {}
 for key in ("A", "B"):
-    l = ctypes.CDLL(os.path.join(root, "radvlm_amd", f"lib_{key}.so"))
-    l.rv_attn_fwd_nat.argtypes = L._SIGS["rv_attn_fwd_nat"]; l.rv_attn_fwd_nat.restype = ctypes.c_int
+    l = L.bind(os.path.join(root, "radvlm_amd", f"lib_{key}.so"))
     res = []
     for B, H, Hkv, S, lens in ((3, 4, 4, 704, [704, 500, 77]), (2, 8, 2, 1000, [1000, 999]), (1, 2, 2, 3056, None)):
         g = torch.Generator(device="cuda").manual_seed(S)

@@ -6,8 +6,7 @@ from radvlm_amd import lib as L
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 libs = {}
 for k in ("A", "B"):
-    l = ctypes.CDLL(os.path.join(root, "radvlm_amd", f"lib_{k}.so"))
-    l.rv_gemm_bf16.argtypes = L._SIGS["rv_gemm_bf16"]; l.rv_gemm_bf16.restype = ctypes.c_int
+    l = L.bind(os.path.join(root, "radvlm_amd", f"lib_{k}.so"))
     l.rv_gemm_select_kernel(2)
     libs[k] = l
 z = torch.zeros(64, dtype=torch.uint8, device="cuda")

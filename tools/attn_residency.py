@@ -7,8 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from radvlm_amd import lib as L
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-l = ctypes.CDLL(os.path.join(root, "radvlm_amd", "lib_S.so"))
-l.rv_attn_fwd_nat.argtypes = L._SIGS["rv_attn_fwd_nat"]; l.rv_attn_fwd_nat.restype = ctypes.c_int
+l = L.bind(os.path.join(root, "radvlm_amd", "lib_S.so"))
 l.rv_debug_set_attn_stamp_buffer.argtypes = [ctypes.c_void_p]
 z = torch.zeros(64, dtype=torch.uint8, device="cuda")
 st = torch.cuda.current_stream().cuda_stream

@@ -12,8 +12,7 @@ c = torch.empty(m, n, device="cuda", dtype=torch.bfloat16)
 z = torch.zeros(64, dtype=torch.uint8, device="cuda")
 st = torch.cuda.current_stream().cuda_stream
 prod = L.load()
-S = ctypes.CDLL(os.path.join(root, "radvlm_amd", "lib_S.so"))
-S.rv_gemm_bf16.argtypes = L._SIGS["rv_gemm_bf16"]; S.rv_gemm_bf16.restype = ctypes.c_int
+S = L.bind(os.path.join(root, "radvlm_amd", "lib_S.so"))
 S.rv_debug_set_stamp_buffer.argtypes = [ctypes.c_void_p]
 S.rv_gemm_select_kernel(2)
 buf = torch.zeros(4224 * 4, dtype=torch.int64, device="cuda")
