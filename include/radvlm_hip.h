@@ -401,6 +401,22 @@ int rv_add_pos_rows(void* x, const void* pos, int n, int P, int d, void* stream)
  * grads; grad is multiplied by *gscale (device scalar, e.g. the clip coefficient) if gscale != NULL. */
 int rv_adamw(void* p_bf16, float* master, const void* g_bf16, float* m, float* v, int64_t n, float lr, float b1,
              float b2, float eps, float wd, float bc1, float bc2, const float* gscale, void* stream);
+/* 8-bit AdamW state (optim="adamw_bnb_8bit", train/llava_trainer.py:416-431; csrc/adam8.hip): block-wise dynamic quantisation of the two
+ * moments, 256 elements per block counted from a tensor's first element, one fp32 absmax per block, the codebooks of
+ * csrc/adam8_codebook.h.  The rule is tests/adam8_ref.py and the kernels match it bit for bit.  kind 0: signed table (exp_avg, absmax =
+ * max |x|); kind 1: unsigned table (exp_avg_sq, absmax = max x) with the guard "a value > 0 never takes code 0".
+ * quantise: codes[n] and absmax[ceil(n / 256)] of one tensor x[n]; dequantise: x[i] = table[codes[i]] * absmax[i / 256]. */
+int rv_adam8_quantize_f32(const float* x, int64_t n, uint8_t* codes, float* absmax, int kind, void* stream);
+int rv_adam8_dequantize_f32(const uint8_t* codes, const float* absmax, int64_t n, int kind, float* x, void* stream);
+/* rv_adamw on a slice whose moments are 8-bit: per element dequantise m and v, the update of rv_adamw (the same device function),
+ * master and the bf16 parameter from the unquantised new moments, then the block maxima and the new codes.  Bit-identical to
+ * rv_adam8_dequantize_f32 -> rv_adamw -> rv_adam8_quantize_f32 per tensor.  table: device int64 [3, ntensors] = each tensor's first
+ * element in p / master / g, its length (> 0), its first block (0 for the first; tensor t owns ceil(length / 256) blocks, consecutive).
+ * Block b's codes are bytes [256 b, 256 b + 256) of codes_m / codes_v (nblocks * 256 bytes each; a short last block leaves its
+ * remaining bytes untouched), its scales absmax_m[b] / absmax_v[b].  One launch for the whole slice. */
+int rv_adamw8(void* p_bf16, float* master, const void* g_bf16, uint8_t* codes_m, uint8_t* codes_v, float* absmax_m, float* absmax_v,
+              const int64_t* table, int ntensors, int64_t nblocks, float lr, float b1, float b2, float eps, float wd, float bc1,
+              float bc2, const float* gscale, void* stream);
 /* partial[blk] = sum of squares of the block's slice (fp32); finish with rv_clip_coef. */
 int rv_sumsq_partial_bf16(const void* g, int64_t n, float* partial, int nblk, void* stream);
 /* norm = sqrt(sum partial); out[0] = norm, out[1] = min(1, max_norm / (norm + 1e-6))  (torch clip_grad_norm_). */

@@ -149,6 +149,7 @@ class LlavaEngine:
         self._rope = {}
         self._stats = {}
         self.master = self.m = self.vv = None
+        self._drop_state8()
         self.opt_step = 0
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
@@ -222,6 +223,7 @@ class LlavaEngine:
                 self.vis = new_lm
             self.grads = new_lm.like(BF16)
             self.master = self.m = self.vv = None
+            self._drop_state8()
             self.opt_step = 0
             self.grad_accum_started = False
             if self.sync is not None:
@@ -2035,7 +2037,10 @@ class LlavaEngine:
             bufs.append(("vision_tower", self.vis.flat))
         if self.base is not None:
             bufs.append(("frozen_language_model", self.base.flat))
-        return bufs + [("fp32_master", self.master), ("exp_avg", self.m), ("exp_avg_sq", self.vv)]
+        bufs += [("fp32_master", self.master), ("exp_avg", self.m), ("exp_avg_sq", self.vv)]
+        if self.state_bits == 8 and self.master is not None:
+            bufs += [("exp_avg_codes", self.m8), ("exp_avg_sq_codes", self.v8), ("exp_avg_absmax", self.am8), ("exp_avg_sq_absmax", self.av8)]
+        return [(n, t) for n, t in bufs if t is None or t.numel()]
 
     def broadcast_parameters(self):
         """Rank 0's parameters (and optimizer state, once it exists) become every rank's: the broadcast DistributedDataParallel performs
@@ -2056,11 +2061,135 @@ class LlavaEngine:
             torch.distributed.barrier(group=self.pg)
 
     # ------------------------------------------------------------------ optimizer
-    def init_optimizer(self):
-        if self.master is None:
+    state_bits = 32                          # width of the AdamW moments: 32 (fp32, the default) or 8 (optim8.py, csrc/adam8.hip)
+
+    def _drop_state8(self):
+        self.plan8 = None                    # optim8.StatePlan of self.lm while the moments are 8-bit
+        self.m8 = self.v8 = self.am8 = self.av8 = None
+        self._runs8 = {}
+
+    def init_optimizer(self, state_bits=None):
+        """Allocate the optimizer state on first use: the fp32 master copy and the two moments, fp32 (state_bits 32, the default) or
+        8-bit block-quantised (state_bits 8: uint8 codes m8 / v8 and per-block absmax am8 / av8 for the tensors optim8.takes_8bit
+        names; self.m / self.vv then hold the fp32 moments of the remaining tensors only, in the plan's compact layout).  state_bits
+        None keeps the width in use.  With a state of the other width present the moments are converted in place
+        (rv_adam8_quantize_f32 / rv_adam8_dequantize_f32 per tensor); the master copy is fp32 either way."""
+        bits = self.state_bits if state_bits is None else int(state_bits)
+        if bits not in (8, 32):
+            raise ValueError(f"init_optimizer(state_bits={state_bits!r}): 8 or 32")
+        if self.master is not None and bits == self.state_bits:
+            return
+        F = torch.float32
+        old_m, old_v, old_plan = self.m, self.vv, self.plan8
+        old8 = (self.m8, self.v8, self.am8, self.av8)
+        had = self.master is not None
+        if not had:
             self.master = ops.to_f32(self.lm.flat)
-            self.m = self.lm.like(torch.float32)
-            self.vv = self.lm.like(torch.float32)
+        if bits == 32:
+            self.m, self.vv = self.lm.like(F), self.lm.like(F)
+            if had:                                                     # 8 -> 32
+                for name, t in old_plan.tensors.items():
+                    off, n = t["off"], t["n"]
+                    if t["bits"] == 8:
+                        b, nb = t["block"], (n + 255) // 256
+                        ops.adam8_dequantize(old8[0][b * 256:b * 256 + n], old8[2][b:b + nb], n, 0, self.m[off:off + n])
+                        ops.adam8_dequantize(old8[1][b * 256:b * 256 + n], old8[3][b:b + nb], n, 1, self.vv[off:off + n])
+                    else:
+                        self.m[off:off + n].copy_(old_m[t["pos"]:t["pos"] + n])
+                        self.vv[off:off + n].copy_(old_v[t["pos"]:t["pos"] + n])
+            self._drop_state8()
+            self.state_bits = 32
+            return
+        from .optim8 import StatePlan
+        plan = StatePlan(self.lm.offsets, self.lm.shapes)
+        dev = self.device
+        self.m8 = torch.full((plan.ncodes,), 127, dtype=torch.uint8, device=dev)          # 127 / 0: the codes of 0 in the two tables
+        self.v8 = torch.zeros(plan.ncodes, dtype=torch.uint8, device=dev)
+        self.am8, self.av8 = torch.zeros(plan.nblocks, dtype=F, device=dev), torch.zeros(plan.nblocks, dtype=F, device=dev)
+        self.m, self.vv = torch.zeros(plan.n32, dtype=F, device=dev), torch.zeros(plan.n32, dtype=F, device=dev)
+        if had:                                                         # 32 -> 8
+            for name, t in plan.tensors.items():
+                off, n = t["off"], t["n"]
+                if t["bits"] == 8:
+                    b, nb = t["block"], (n + 255) // 256
+                    ops.adam8_quantize(old_m[off:off + n], 0, self.m8[b * 256:b * 256 + n], self.am8[b:b + nb])
+                    ops.adam8_quantize(old_v[off:off + n], 1, self.v8[b * 256:b * 256 + n], self.av8[b:b + nb])
+                else:
+                    self.m[t["pos"]:t["pos"] + n].copy_(old_m[off:off + n])
+                    self.vv[t["pos"]:t["pos"] + n].copy_(old_v[off:off + n])
+        self.state_bits, self.plan8, self._runs8 = 8, plan, {}
+
+    def optimizer_state_bytes(self):
+        """Bytes allocated for AdamW's two moments (codes and absmax arrays included; the fp32 master copy, 4 B per parameter at
+        either width, is not counted).  0 before the state exists."""
+        if self.master is None:
+            return 0
+        bufs = [self.m, self.vv] + ([self.m8, self.v8, self.am8, self.av8] if self.state_bits == 8 else [])
+        return sum(t.numel() * t.element_size() for t in bufs)
+
+    def optimizer_state_dict(self):
+        """(tensors, meta) of a checkpoint's optimizer.safetensors.  fp32 state: master, exp_avg, exp_avg_sq and meta None (the
+        layout every earlier checkpoint has).  8-bit state: master, the code and absmax arrays of the 8-bit tensors, the compact fp32
+        moments of the rest, and meta {"bits": 8, "block": 256, "codebook": sha of csrc/adam8_codebook.h's tables}."""
+        if self.state_bits == 32:
+            return {"master": self.master, "exp_avg": self.m, "exp_avg_sq": self.vv}, None
+        from .optim8 import BLOCK, codebook_sha
+        return ({"master": self.master, "exp_avg_codes": self.m8, "exp_avg_sq_codes": self.v8, "exp_avg_absmax": self.am8,
+                 "exp_avg_sq_absmax": self.av8, "exp_avg_fp32": self.m, "exp_avg_sq_fp32": self.vv},
+                {"bits": 8, "block": BLOCK, "codebook": codebook_sha()})
+
+    def load_optimizer_state_dict(self, st, meta=None, say=None):
+        """Load what optimizer_state_dict() gave, into a state of self.state_bits: the same width is a plain copy; a state of the other
+        width is loaded as it is and then converted by init_optimizer (quantised / dequantised on the device), which `say` is told."""
+        from .optim8 import BLOCK, codebook_sha
+        want = self.state_bits
+        have = 8 if "exp_avg_codes" in st else 32
+        if have == 8:
+            meta = meta or {}
+            if meta.get("codebook") != codebook_sha() or meta.get("block") != BLOCK:
+                raise ValueError(f"8-bit optimizer state of another format (block {meta.get('block')}, codebook {meta.get('codebook')}): "
+                                 f"this build has block {BLOCK}, codebook {codebook_sha()}")
+        self.master = self.m = self.vv = None
+        self._drop_state8()
+        self.init_optimizer(state_bits=have)
+        keys = {"master": self.master, "exp_avg": self.m, "exp_avg_sq": self.vv} if have == 32 else self.optimizer_state_dict()[0]
+        for k, dst in keys.items():
+            if tuple(st[k].shape) != tuple(dst.shape):
+                raise ValueError(f"optimizer state '{k}': shape {tuple(st[k].shape)}, this model needs {tuple(dst.shape)}")
+            dst.copy_(st[k])
+        if have != want:
+            if say is not None:
+                say(f"optimizer state: the checkpoint holds {have}-bit AdamW moments, this run keeps {want}-bit ones: "
+                    + ("quantising" if want == 8 else "dequantising") + " on load")
+            self.init_optimizer(state_bits=want)
+
+    def moment_views(self, name):
+        """The stored moments of one trainable tensor: {"exp_avg", "exp_avg_sq"} fp32 views [n] at 32 bits; at 8 bits the same two keys for
+        a tensor that keeps fp32 moments, else {"exp_avg_codes", "exp_avg_sq_codes" (uint8 [n]), "exp_avg_absmax", "exp_avg_sq_absmax"
+        (fp32 [ceil(n / 256)])}.  Views: writing them writes the state."""
+        off, n = self.lm.offsets[name]
+        if self.state_bits == 32:
+            return {"exp_avg": self.m[off:off + n], "exp_avg_sq": self.vv[off:off + n]}
+        t = self.plan8.tensors[name]
+        if t["bits"] == 32:
+            return {"exp_avg": self.m[t["pos"]:t["pos"] + n], "exp_avg_sq": self.vv[t["pos"]:t["pos"] + n]}
+        b, nb = t["block"], (n + 255) // 256
+        return {"exp_avg_codes": self.m8[b * 256:b * 256 + n], "exp_avg_sq_codes": self.v8[b * 256:b * 256 + n],
+                "exp_avg_absmax": self.am8[b:b + nb], "exp_avg_sq_absmax": self.av8[b:b + nb]}
+
+    def _adamw8_runs(self, s, e):
+        """The 8-bit and 32-bit runs of the parameter-group slice [s, e), with the device block tables of the 8-bit ones (built once)."""
+        if (s, e) not in self._runs8:
+            runs = []
+            for run in self.plan8.runs(s, e):
+                if run[0] == 8:
+                    first, last = self.plan8.tensors[run[1][0]], self.plan8.tensors[run[1][-1]]
+                    tab, nb = self.plan8.block_table(run[1], origin=first["off"])
+                    runs.append((8, first["off"], last["off"] + last["n"], first["block"], nb, torch.from_numpy(tab).to(self.device)))
+                else:
+                    runs.append(run)
+            self._runs8[(s, e)] = runs
+        return self._runs8[(s, e)]
 
     def param_groups(self, lr, weight_decay=0.0, mm_projector_lr=None, no_decay_1d=True, mm_vision_tower_lr=None):
         """Contiguous (start, end, lr, wd) slices following LLaVATrainer.create_optimizer (llava_trainer.py:369-418):
@@ -2101,8 +2230,20 @@ class LlavaEngine:
             self.last_grad_norm = nc[0:1]
             coef = nc[1:2]
         for s, e, glr, gwd in self.param_groups(lr, weight_decay, mm_projector_lr, mm_vision_tower_lr=mm_vision_tower_lr):
-            ops.adamw(self.lm.flat[s:e], self.master[s:e], self.grads[s:e], self.m[s:e], self.vv[s:e], glr, betas[0], betas[1],
-                      eps, gwd, self.opt_step, gscale=coef)
+            if self.state_bits == 32:
+                ops.adamw(self.lm.flat[s:e], self.master[s:e], self.grads[s:e], self.m[s:e], self.vv[s:e], glr, betas[0], betas[1],
+                          eps, gwd, self.opt_step, gscale=coef)
+                continue
+            for run in self._adamw8_runs(s, e):             # one rv_adamw8 launch per 8-bit run, one rv_adamw per fp32 run
+                if run[0] == 8:
+                    _, a, b, blk, nb, tab = run
+                    ops.adamw8(self.lm.flat[a:b], self.master[a:b], self.grads[a:b], self.m8[blk * 256:(blk + nb) * 256],
+                               self.v8[blk * 256:(blk + nb) * 256], self.am8[blk:blk + nb], self.av8[blk:blk + nb], tab, nb, glr,
+                               betas[0], betas[1], eps, gwd, self.opt_step, gscale=coef)
+                else:
+                    _, a, b, pos = run
+                    ops.adamw(self.lm.flat[a:b], self.master[a:b], self.grads[a:b], self.m[pos:pos + b - a], self.vv[pos:pos + b - a],
+                              glr, betas[0], betas[1], eps, gwd, self.opt_step, gscale=coef)
         self.weights_changed(tower=self.train_tower)
         self.zero_grad()
 
@@ -2178,7 +2319,7 @@ class LlavaEngine:
         new = FlatParams(OrderedDict((n, old.shapes[n]) for n in keep), self.device)
         for n in keep:
             new.view(n).copy_(old.view(n))
-        if self.master is not None:
+        if self.master is not None and self.state_bits == 32:
             state = []
             for buf in (self.master, self.m, self.vv):
                 nb = new.like(torch.float32)
@@ -2186,7 +2327,22 @@ class LlavaEngine:
                     new.view(n, nb).copy_(old.view(n, buf))
                 state.append(nb)
             self.master, self.m, self.vv = state
+        saved8 = None
+        if self.master is not None and self.state_bits == 8:            # per-tensor blocks: a plain copy per name into the new plan
+            saved8 = {n: {k: v.clone() for k, v in self.moment_views(n).items()} for n in keep}
+            nb = new.like(torch.float32)
+            for n in keep:
+                new.view(n, nb).copy_(old.view(n, self.master))
+            saved8["master"] = nb
         self.lm = new
+        if saved8 is not None:
+            self.master = self.m = self.vv = None
+            self._drop_state8()
+            self.init_optimizer(state_bits=8)
+            self.master = saved8.pop("master")
+            for n, views in saved8.items():
+                for k, v in self.moment_views(n).items():
+                    v.copy_(views[k])
         self.grads = new.like(BF16)
         self.grad_accum_started = False
         self.ctx = None

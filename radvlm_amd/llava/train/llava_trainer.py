@@ -282,6 +282,24 @@ class LLaVATrainer:
         self.model, self.tokenizer, self.args = model, tokenizer, args
         self.train_dataset, self.data_collator = train_dataset, data_collator
         self.state = {"global_step": 0, "log_history": []}
+        self._select_optimizer()
+
+    def _say(self, msg):
+        if getattr(self.args, "process_index", 0) == 0:
+            print(msg, flush=True)
+
+    def _select_optimizer(self):
+        """--optim (llava_trainer.py:416-431): adamw_bnb_8bit / adamw_8bit keep AdamW's moments 8-bit (embedding tables, small and 1-D
+        tensors stay fp32: optim8.takes_8bit), the fp32 AdamW spellings keep them fp32; anything else trains with fp32 AdamW and says so."""
+        from ...optim8 import optim_state_bits
+        bits = optim_state_bits(getattr(self.args, "optim", "adamw_torch") or "adamw_torch", warn=self._say)
+        eng = getattr(self.model, "engine", None)
+        if eng is None:
+            return
+        if eng.master is None:
+            eng.state_bits = bits
+        else:
+            eng.init_optimizer(state_bits=bits)
 
     def _get_train_sampler(self):
         a = self.args
@@ -423,11 +441,13 @@ class LLaVATrainer:
                 proj = {k: v.detach().clone().cpu() for k, v in eng.state_dict().items() if "mm_projector" in k}
                 torch.save(proj, os.path.join(path, "mm_projector.bin"))
         if eng.master is not None and not getattr(self.args, "save_only_model", False):
-            save_file({"master": eng.master.detach().cpu(), "exp_avg": eng.m.detach().cpu(), "exp_avg_sq": eng.vv.detach().cpu()},
-                      os.path.join(path, "optimizer.safetensors"))
+            tensors, optim_meta = eng.optimizer_state_dict()
+            save_file({k: v.detach().cpu() for k, v in tensors.items()}, os.path.join(path, "optimizer.safetensors"))
+        else:
+            optim_meta = None
         with open(os.path.join(path, "trainer_state.json"), "w") as f:
             json.dump({"global_step": self.state["global_step"], "opt_step": eng.opt_step, "lora_step": eng.lora_step,
-                       "log_history": self.state["log_history"]}, f)
+                       "log_history": self.state["log_history"], **({"optim_state": optim_meta} if optim_meta else {})}, f)
 
     def _rotate_checkpoints(self, output_dir, rank=0):
         """--save_total_limit N (HF Trainer._rotate_checkpoints; finetune_radio_7b.sh:72 passes 1): keep the N newest checkpoint-* directories
@@ -462,12 +482,10 @@ class LLaVATrainer:
         else:       # projector-only checkpoint: the frozen parts are those the run started from
             eng.load_state_dict(torch.load(os.path.join(path, "mm_projector.bin"), map_location="cpu", weights_only=True))
         opt = os.path.join(path, "optimizer.safetensors")
-        if os.path.exists(opt):
-            eng.init_optimizer()
-            st = load_file(opt)
-            eng.master.copy_(st["master"]), eng.m.copy_(st["exp_avg"]), eng.vv.copy_(st["exp_avg_sq"])
         with open(os.path.join(path, "trainer_state.json")) as f:
             ts = json.load(f)
+        if os.path.exists(opt):
+            eng.load_optimizer_state_dict(load_file(opt), ts.get("optim_state"), say=self._say)
         eng.opt_step = ts["opt_step"] if os.path.exists(opt) else 0      # save_only_model checkpoints: a fresh optimizer, as HF restarts it
         eng.lora_step = ts.get("lora_step", eng.lora_step)      # the dropout masks of a resumed LoRA run continue their counter
         self.state["global_step"] = ts["global_step"]

@@ -603,6 +603,37 @@ def adamw(p, master, g, m, v, lr, b1, b2, eps, wd, step, gscale=None):
     lib.call("rv_adamw", p, master, g, m, v, n, lr, b1, b2, eps, wd, 1.0 - b1 ** step, 1.0 - b2 ** step, gscale)
 
 
+def adam8_quantize(x, kind, codes=None, absmax=None):
+    """fp32 tensor -> (uint8 codes [n], fp32 absmax [ceil(n / 256)]) of the 8-bit AdamW state; kind 0 = exp_avg, 1 = exp_avg_sq."""
+    n = x.numel()
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and n > 0
+    codes = torch.empty(n, dtype=torch.uint8, device=x.device) if codes is None else codes
+    absmax = torch.empty((n + 255) // 256, dtype=torch.float32, device=x.device) if absmax is None else absmax
+    assert codes.dtype == torch.uint8 and codes.numel() >= n and absmax.dtype == torch.float32 and absmax.numel() >= (n + 255) // 256
+    lib.call("rv_adam8_quantize_f32", x, n, codes, absmax, int(kind))
+    return codes, absmax
+
+
+def adam8_dequantize(codes, absmax, n, kind, out=None):
+    assert codes.is_cuda and codes.dtype == torch.uint8 and codes.numel() >= n and absmax.dtype == torch.float32
+    assert absmax.numel() >= (n + 255) // 256 and n > 0
+    out = torch.empty(n, dtype=torch.float32, device=codes.device) if out is None else out
+    assert out.dtype == torch.float32 and out.numel() >= n and out.is_contiguous()
+    lib.call("rv_adam8_dequantize_f32", codes, absmax, n, int(kind), out)
+    return out
+
+
+def adamw8(p, master, g, codes_m, codes_v, absmax_m, absmax_v, table, nblocks, lr, b1, b2, eps, wd, step, gscale=None):
+    """rv_adamw8 on one slice: `table` is the device int64 [3, T] block table of optim8.StatePlan.block_table, the code buffers hold
+    nblocks * 256 bytes and the absmax buffers nblocks floats (checked here: the kernel trusts them)."""
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[0] == 3 and table.is_contiguous()
+    assert min(codes_m.numel(), codes_v.numel()) >= nblocks * 256 and min(absmax_m.numel(), absmax_v.numel()) >= nblocks
+    assert codes_m.dtype == codes_v.dtype == torch.uint8 and absmax_m.dtype == absmax_v.dtype == torch.float32
+    assert p.numel() == master.numel() == g.numel()
+    lib.call("rv_adamw8", p, master, g, codes_m, codes_v, absmax_m, absmax_v, table, int(table.shape[1]), int(nblocks), lr, b1, b2, eps,
+             wd, 1.0 - b1 ** step, 1.0 - b2 ** step, gscale)
+
+
 def grad_norm_clip_coef(g, max_norm):
     """Returns fp32[2] device tensor: (global grad norm, clip coefficient) with no host sync."""
     nblk = 1024
