@@ -297,6 +297,36 @@ int rv_sum_f32(const float* in, int64_t n, float scale, float* out, void* stream
 int rv_policy_loss_bf16(const void* logits, int64_t ld, const int64_t* labels, const float* adv, const float* lweight,
                         const float* gweight, const float* old_logp, const float* ref_logp, float eps_low, float eps_high, float beta,
                         float* stats, void* dlogits, int64_t ld_d, int rows, int V, void* stream);
+/* Knowledge distillation (csrc/distill.hip): the generalised Jensen-Shannon divergence of TRL's GKDTrainer.generalized_jsd_loss between
+ * a student row z and a teacher row u over the whole vocabulary, on the rows rv_cross_entropy takes (bf16, ld / ld_t >= ceil8(V)
+ * columns).  teacher_row: int32 [rows], student row -> teacher row, -1 for none (the row is then ignored); NULL: row r <-> row r.
+ * labels[r] only says whether row r is scored: outside [0, V) the row is ignored -- zeros in its four statistics and its dlogits row,
+ * none of its floats is read.  Per live row, in fp32, with it = 1 / temperature formed once on the host and each logit multiplied by it
+ * as it is read:
+ *   s = it z - lse(it z);  lt = it u - lse(it u);  p = exp(s);  t = exp(lt);  d = lt - s      (lse: rv_cross_entropy's statements)
+ *   beta == 0 (forward KL):  L = sum_j t_j d_j;                     dL/dz_j = (p_j - t_j) it
+ *   beta == 1 (reverse KL):  L = sum_j p_j r_j, r_j = -d_j;         dL/dz_j = p_j (r_j - L) it
+ *   0 < beta < 1:  r_j = -log((1 - beta) + beta exp(d_j)), evaluated without the exponential of a positive number;
+ *                  KL_S = sum_j p_j r_j;  KL_T = sum_j t_j (d_j + r_j);  L = beta KL_T + (1 - beta) KL_S;
+ *                  dL/dz_j = (1 - beta) p_j (r_j - KL_S) it      (the terms through the mixture cancel)
+ * The end points are TRL's special cases, not the limits of the middle formula (which tends to 0 at both ends).  No tau^2 factor.
+ * dlogits[r][j] = gweight[r] dL/dz_j (the product gweight[r] it is formed once per row) and zeros in the pad columns up to
+ * ceil8(V).  dlogits may be the logits buffer (a thread overwrites only vectors it alone reads), another buffer with its own
+ * ld_d, or NULL (statistics only).  Pad columns are never summed.
+ * stats: four fp32 planes of `rows` entries -- jsd = L, lweight[r] * L, kl_teacher, kl_student (beta 0: L, ., L, 0; beta 1: L, ., 0, L).
+ * One workgroup per row; every sum is taken per thread in ascending column order, then across lanes, then across waves 0..3: no
+ * atomics, and a row's bits depend on the row pair and the scalars alone -- not on rows, the grid, teacher_row or the buffer form.
+ * Bit promises: at temperature 1 the student's lse and p are rv_cross_entropy's; so with beta = 0, temperature = 1 and a teacher row
+ * whose label logit is so far above the rest (200) that every other t_j underflows to 0, jsd == loss_rows of rv_cross_entropy and,
+ * with gweight = c, dlogits == its dlogits with inv_count = c.  A teacher row equal to the student row gives jsd == 0 and a zero
+ * gradient row at beta 0 and 1.
+ * Finite logits only; the result stays finite for |d| up to the range of the logits themselves.
+ * Refused (RV_ERR_ARG, nothing launched): a null logits / teacher / labels / lweight / gweight / stats, rows < 1, V < 1, ld, ld_t or
+ * ld_d not a multiple of 8 or below ceil8(V), logits, teacher or dlogits not 16-byte aligned, beta outside [0, 1] or NaN, temperature
+ * <= 0 or not finite. */
+int rv_distill_loss_bf16(const void* logits, int64_t ld, const void* teacher, int64_t ld_t, const int32_t* teacher_row,
+                         const int64_t* labels, const float* lweight, const float* gweight, float beta, float temperature, float* stats,
+                         void* dlogits, int64_t ld_d, int rows, int V, void* stream);
 
 /* ---- DPO preference training (csrc/preference.hip) -------------------------------------------------------------------
  * The sequence-level part of the DPO loss, between two calls of rv_policy_loss_bf16: (A) with dlogits = NULL gives the logp plane,

@@ -1,6 +1,7 @@
-// The row sweeps of the bf16 cross entropy, shared by cross_entropy_kernel (ops.hip) and policy_loss_kernel (policy.hip): the policy
-// loss is the cross entropy with a per-row gradient coefficient, and its lse, its target log-prob and its softmax p must carry the bits
-// rv_cross_entropy computes, so both kernels run these statements.  A CE_TPB-thread workgroup owns the row; 16-byte row vectors.
+// The row sweeps of the bf16 cross entropy, shared by cross_entropy_kernel (ops.hip), policy_loss_kernel (policy.hip) and
+// distill_kernel (distill.hip): the policy loss is the cross entropy with a per-row gradient coefficient, the distillation loss at
+// temperature 1 against a one-hot teacher is the cross entropy itself, and their lse, target log-prob and softmax p must carry the bits
+// rv_cross_entropy computes, so all three kernels run these statements.  A CE_TPB-thread workgroup owns the row; 16-byte row vectors.
 // V need not be a multiple of 8 (a vocabulary grown by a few special tokens): rows are padded to ld >= ceil8(V) columns, the pad
 // columns are ignored on read (-inf) and their gradient is written as zero.
 // In place (dlogits == logits) is the engine's call: a kernel reads its target logit BEFORE ce_row_lse, because other waves of the
@@ -24,12 +25,19 @@ DEVINL void st8(bf16* p, const float (&v)[8]) {
 
 // log(sum exp) of the row lr[0 .. V), known to every thread on return: a running (max, sum) per thread, then lanes, then waves 0..3.
 // red: 8 floats of LDS.
-DEVINL float ce_row_lse(const bf16* lr, int V, float* red) {
+// SCALED (distill.hip): the row is scale * lr, each logit multiplied once in fp32 as it is read (scale 1 gives the unscaled bits).
+// An unscaled caller's code is unchanged.
+template <bool SCALED = false>
+DEVINL float ce_row_lse(const bf16* lr, int V, float* red, float scale = 1.f) {
     const int nvec = (V + 7) / 8;
     float m = -INFINITY, s = 0.f;
     for (int i = threadIdx.x; i < nvec; i += CE_TPB) {
         float v[8];
         ld8(lr + i * 8, v);
+        if (SCALED) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] *= scale;
+        }
         if (i * 8 + 8 > V) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) if (i * 8 + j >= V) v[j] = -INFINITY;

@@ -163,6 +163,7 @@ class LlavaEngine:
         self.ctx = None
         self.last_preference = None           # pair terms of the last forward(preference=)
         self.last_policy = None               # per-scored-token statistics of the last forward(policy=) / token_logps()
+        self.last_distill = None              # per-scored-token divergences of the last forward(distill=)
         self.grad_accum_started = False
         self.loss_scale = 1.0
         import os
@@ -663,7 +664,7 @@ class LlavaEngine:
         return pix.contiguous()
 
     def forward(self, input_ids, attention_mask, labels, images, image_sizes=None, want_logits=False, loss_scale=None, policy=None,
-                preference=None, _score_only=False):
+                preference=None, _score_only=False, distill=None, _label_logits=False):
         """One training forward. Returns loss (fp32 device tensor [1], never scaled); keeps the context for backward().
         loss_scale multiplies the GRADIENTS only (default: self.loss_scale; a trainer sets 1 / gradient_accumulation_steps, which is
         what HF Trainer.training_step back-propagates, HF:trainer.py training_step `loss / gradient_accumulation_steps`).
@@ -673,7 +674,11 @@ class LlavaEngine:
         preference: None or a preference.PreferenceTerms: the batch is P (chosen, rejected) pairs as 2 P sequences and the DPO loss takes
         the cross entropy's place the same way, as three launches on the same logits buffer (see _preference_loss); the loss returned
         is dpo_alpha * mean pair loss + gamma * SFT, and self.last_preference holds the pair terms.
-        _score_only (token_logps): the same pass with the statistics alone -- no dlogits, no activations kept, no context."""
+        distill: None or a distill.DistillTerms: knowledge distillation takes the cross entropy's place the same way, one launch of
+        rv_distill_loss_bf16 on the logits buffer and the teacher's rows (see _distill_loss); the loss returned is sum(weight * jsd) over
+        the scored tokens, and self.last_distill holds the per-token divergences.  It combines with none of the other three.
+        _score_only (token_logps): the same pass with the statistics alone -- no dlogits, no activations kept, no context.
+        _label_logits (label_logits, with _score_only): no loss at all; self.last_label_logits gets the scored rows of the logits buffer."""
         dev = self.device
         l = self.l
         d, F, H, V, L = l["d"], l["ffn"], l["heads"], l["vocab"], l["layers"]
@@ -781,7 +786,17 @@ class LlavaEngine:
             logits_out = logits_out.view(B, S, V)[..., :self.vocab]
         # CE writes dlogits (scaled by loss_scale/count/world) over the logits buffer
         gscale = (self.loss_scale if loss_scale is None else loss_scale) / self.world
-        if preference is not None:
+        if distill is not None and (policy is not None or preference is not None or _score_only):
+            raise ValueError("distill= does not combine with policy=, preference= or a score-only pass")
+        if _label_logits:
+            assert _score_only and policy is None and preference is None
+            n, _, _ = self._scored_rows(logits.shape[0], lab_rows, head_idx is not None, scored)
+            sel = slice(n) if head_idx is not None else self._dev(lab_rows.astype(np.int64))
+            self.last_label_logits = dict(logits=logits[sel], scored=np.asarray(scored))
+            loss = None
+        elif distill is not None:
+            loss = self._distill_loss(logits, tgt_t, lab_rows, head_idx is not None, scored, distill, gscale)
+        elif preference is not None:
             if policy is not None or _score_only:
                 raise ValueError("preference= does not combine with policy= or a score-only pass")
             loss = self._preference_loss(logits, tgt_t, lab_rows, head_idx is not None, scored, preference, gscale)
@@ -1731,6 +1746,43 @@ class LlavaEngine:
                                 scored=np.asarray(scored), ratio_one=torch.full((n,), old is None, dtype=torch.bool, device=dev),
                                 coefs=coefs, seq_logratio=plane["logratio"], seq_ratio=plane["ratio"], seq_clip=plane["clip"])
         return batch[:1].to(torch.float32)
+
+    def _distill_loss(self, logits, tgt, lab_rows, gathered, scored, terms, gscale):
+        """Knowledge distillation in the cross entropy's place (arguments as _policy_loss): one launch of rv_distill_loss_bf16 on
+        forward()'s head rows, in place, against terms.teacher_logits, whose row j belongs to scored token j.  Gathered head: scored
+        token j is head row j and the pad rows map to -1; all-rows head: teacher_row maps head row lab_rows[j] to teacher row j and
+        every other row to -1.
+        Leaves self.last_distill: jsd, kl_teacher, kl_student fp32 [n_scored] on the device in scored order, and scored (host counts).
+        Returns sum(weight * jsd) as fp32 [1]."""
+        rows = logits.shape[0]
+        n, per_row, pick = self._scored_rows(rows, lab_rows, gathered, scored)
+        w = terms.per_token(scored, self.vocab)
+        teacher = terms.teacher_logits
+        if teacher.device != logits.device:
+            teacher = teacher.to(logits.device)
+        if n and (teacher.stride(1) != 1 or teacher.stride(0) % 8 or teacher.data_ptr() % 16 or teacher.shape[1] < _ru(self.vocab, 8)):
+            wide = torch.zeros(n, _ru(teacher.shape[1], 8), dtype=BF16, device=logits.device)      # rows of whole 16-byte vectors
+            wide[:, :teacher.shape[1]] = teacher
+            teacher = wide
+        if n == 0:                           # nothing is scored: no row is paired, the kernel only zeroes dlogits
+            teacher = logits
+        tmap = np.full(rows, -1, dtype=np.int32)
+        tmap[slice(n) if gathered else lab_rows] = np.arange(n, dtype=np.int32)
+        tmap = self._dev(tmap)
+        loss, stats = ops.distill_loss(logits, teacher, tgt, self.vocab, per_row(w), gscale, terms.beta, terms.temperature, teacher_row=tmap)
+        st, = pick(stats)
+        self.last_distill = dict(jsd=st[0], kl_teacher=st[2], kl_student=st[3], scored=np.asarray(scored))
+        return loss
+
+    def label_logits(self, input_ids, attention_mask, labels, images, image_sizes=None):
+        """The bf16 logits rows of the scored tokens, [n_scored, table columns >= ceil8(vocab)] on the device, in scored order (the
+        order token_logps() documents): what forward() hands to its loss -- the tiled GEMMs, the same labelled-rows head, the bf16
+        store -- in a score-only pass, so a teacher's rows are the bits its own training step would read.  LoRA engines run it in eval
+        form.  No context is kept and the training state is not touched.  The per-sample scored counts are left in
+        self.last_label_logits["scored"]."""
+        with self._eval_form("lora_step", "ctx"):
+            self.forward(input_ids, attention_mask, labels, images, image_sizes=image_sizes, _score_only=True, _label_logits=True)
+        return self.last_label_logits["logits"]
 
     def token_logps(self, input_ids, attention_mask, labels, images, image_sizes=None):
         """log p(label) of every scored token (the positions of each spliced row whose shifted target is not -100, sample by sample,

@@ -316,6 +316,50 @@ class LlavaLlamaForCausalLM:
         ids, am, lab, imgs = self._host_batch(input_ids, attention_mask, labels, images)
         return self.engine.token_logps(ids, am, lab, imgs, image_sizes=image_sizes)
 
+    def distill_loss(self, input_ids, attention_mask, labels, images, image_sizes=None, *, teacher=None, teacher_logits=None, beta=0.5,
+                     temperature=1.0, weights=None):
+        """Knowledge distillation (TRL's GKDTrainer.generalized_jsd_loss) on a batch of prompt + completion rows; labels mark the
+        completion tokens, as for forward().  At every scored token (policy_loss's order) the student's and the teacher's distributions
+        over the whole vocabulary, both at `temperature`, are compared by the generalised Jensen-Shannon divergence with interpolation
+        `beta` -- 0: forward KL(teacher || student), 1: reverse KL(student || teacher), between: beta KL(teacher || m) + (1 - beta)
+        KL(student || m), m = (1 - beta) student + beta teacher -- and the loss is sum(weight * divergence); weights None: 1 / number
+        of scored tokens (TRL's batchmean); no temperature^2 factor.
+        Give exactly one of `teacher` (another model with the same vocabulary: its label_logits() on this batch are used; a quantised
+        teacher works as it is) and `teacher_logits` (bf16 [n_scored, >= vocab] on the device, row j the teacher's logits at scored
+        token j).  ValueError: both or neither; a vocabulary mismatch; a teacher whose scored counts per sample differ from the
+        student's (another image-token count); teacher_logits of another shape or dtype; beta outside [0, 1]; a temperature that is
+        not finite and positive; weights that do not match the scored counts, are negative or non-finite.
+        Returns an output with .loss (fp32 scalar; .loss.backward() runs the engine's backward, gradients scaled by engine.loss_scale
+        as in forward()), .jsd / .kl_teacher / .kl_student per scored token (fp32 device tensors; at beta 0 and 1 the divergence sits
+        in kl_teacher / kl_student and the other is zero) and .stats: n_scored and the device scalars jsd, kl_teacher, kl_student
+        (means over the scored tokens)."""
+        from ...distill import DistillTerms
+        if (teacher is None) == (teacher_logits is None):
+            raise ValueError("distill_loss: give exactly one of teacher= and teacher_logits=")
+        ids, am, lab, imgs = self._host_batch(input_ids, attention_mask, labels, images)
+        terms = DistillTerms(teacher_logits=teacher_logits, beta=beta, temperature=temperature, weights=weights)
+        if teacher is not None:
+            if teacher.engine.vocab != self.engine.vocab:
+                raise ValueError(f"the teacher's vocabulary ({teacher.engine.vocab}) is not the student's ({self.engine.vocab}): "
+                                 "distillation compares the two distributions token by token")
+            terms.teacher_logits = teacher.label_logits(ids, am, lab, imgs, image_sizes=image_sizes)
+            terms.teacher_scored = teacher.engine.last_label_logits["scored"]      # checked against the student's counts in forward()
+        loss = self.engine.forward(ids, am, lab, imgs, image_sizes=image_sizes, distill=terms)
+        ld = self.engine.last_distill
+        n = int(ld["jsd"].numel())
+        mean = lambda t: t.mean() if n else torch.zeros((), device=self.engine.device)
+        stats = {"n_scored": n, "jsd": mean(ld["jsd"]), "kl_teacher": mean(ld["kl_teacher"]), "kl_student": mean(ld["kl_student"])}
+        return SimpleNamespace(loss=_StepFunction.apply(self._anchor, self.engine, loss), jsd=ld["jsd"], kl_teacher=ld["kl_teacher"],
+                               kl_student=ld["kl_student"], stats=stats)
+
+    @torch.no_grad()
+    def label_logits(self, input_ids, attention_mask, labels, images, image_sizes=None):
+        """The bf16 logits of every scored token of the batch, [n_scored, >= ceil8(vocab)] on the device, in scored order (see
+        policy_loss), computed by the training path's own arithmetic (LlavaEngine.label_logits): the teacher_logits of distill_loss.
+        No gradient, and no training state is touched."""
+        ids, am, lab, imgs = self._host_batch(input_ids, attention_mask, labels, images)
+        return self.engine.label_logits(ids, am, lab, imgs, image_sizes=image_sizes)
+
     def preference_loss(self, chosen_input_ids, chosen_attention_mask, chosen_labels, rejected_input_ids, rejected_attention_mask,
                         rejected_labels, images, image_sizes=None, *, ref_chosen_logps=None, ref_rejected_logps=None, beta=0.1, dpo_alpha=1.0,
                         gamma=1.0, loss_type="sigmoid", label_smoothing=0.0, reference_free=False):

@@ -472,6 +472,33 @@ def policy_loss(logits, labels_shifted, V, adv, weight, gscale=1.0, old_logp=Non
     return loss, stats
 
 
+DISTILL_STATS = ("jsd", "wloss", "kl_teacher", "kl_student")       # the planes of rv_distill_loss_bf16's stats buffer, in order
+
+
+def distill_loss(logits, teacher, labels_shifted, V, weight, gscale=1.0, beta=0.5, temperature=1.0, teacher_row=None, dlogits="inplace"):
+    """The generalised JSD between bf16 student rows `logits` and bf16 teacher rows `teacher` (rv_distill_loss_bf16; beta 0 / 1: forward /
+    reverse KL).  labels_shifted only marks the scored rows (a label outside [0, V): ignored).  weight: per-row host or device floats;
+    the loss value is weighted by fp32(weight), the gradient by fp32(weight * gscale) formed in double -- policy_loss's convention.
+    teacher_row: int32 [rows] student row -> teacher row (-1: none) or None (row r <-> row r).
+    dlogits: "inplace" (the logits buffer is overwritten), a bf16 buffer, or None (statistics only).
+    Returns (loss fp32 [1] = sum of weight * jsd, stats fp32 [4, rows] in DISTILL_STATS order)."""
+    _chk(logits), _chk(teacher)
+    rows, dev = logits.shape[0], logits.device
+    w64 = torch.as_tensor(weight).detach().to("cpu", torch.float64)
+    assert w64.numel() == rows and labels_shifted.numel() == rows and labels_shifted.dtype == torch.int64
+    assert teacher_row is None or (teacher_row.dtype == torch.int32 and teacher_row.numel() == rows)
+    assert teacher_row is not None or teacher.shape[0] >= rows          # the map's entries are the caller's to keep inside the teacher
+    lweight, gweight = w64.to(torch.float32).to(dev).contiguous(), (w64 * float(gscale)).to(torch.float32).to(dev).contiguous()
+    dl = logits if isinstance(dlogits, str) else dlogits
+    assert not isinstance(dlogits, str) or dlogits == "inplace"
+    stats = torch.empty(len(DISTILL_STATS), rows, dtype=torch.float32, device=dev)
+    lib.call("rv_distill_loss_bf16", logits, logits.stride(0), teacher, teacher.stride(0), teacher_row, labels_shifted, lweight, gweight,
+             float(beta), float(temperature), stats, dl, dl.stride(0) if dl is not None else 0, rows, V)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    lib.call("rv_sum_f32", stats[1], rows, 1.0, loss)
+    return loss, stats
+
+
 def seq_logp_sums(logp, seg_off, row_idx=None):
     """fp64 [B] sums of the scored tokens' log-probs of every sequence, in the fixed order include/radvlm_hip.h documents
     (rv_seq_logp_sums_f64).  logp fp32 rows; seg_off int32 [B + 1] in scored order; row_idx int32 (scored token -> row) or None."""
