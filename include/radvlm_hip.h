@@ -676,6 +676,48 @@ int rv_sample_rows_f32(float* x, int64_t ld, int rows, int n, const uint64_t* se
 int64_t rv_sample_ws_bytes(int rows);
 /* Host function: the 24 bits b of the draw above for (seed, t), the same code the kernel runs. */
 uint32_t rv_sample_uniform24(uint64_t seed, int32_t t);
+/* rv_sample_rows_f32 drawing from another stream: b is the top 24 bits of portable_rng._stream(seed, tag, t + 1)[t], that is
+ * splitmix64(t * 0xD1342543DE82EF95 + splitmix64(seed * 1000003 + tag)), tag >= 0.  The same kernels; tag 0 is rv_sample_rows_f32 bit
+ * for bit (it calls this entry).  Assisted sampling draws the draft model's tokens with tag 2, see rv_spec_accept_rows_f32. */
+int rv_sample_rows_tagged_f32(float* x, int64_t ld, int rows, int n, const uint64_t* seed, const int32_t* t, int32_t tag, float temperature,
+                              int top_k, float top_p, float min_p, int write_scores, int64_t* out, float* logprob, void* ws,
+                              int64_t ws_bytes, void* stream);
+/* Host function: rv_sample_uniform24 for the stream `tag`. */
+uint32_t rv_sample_uniform24_tagged(uint64_t seed, int32_t tag, int32_t t);
+
+/* ---- speculative sampling (generate(assistant_model=..., do_sample=True), radvlm_amd/csrc/spec.hip) ---------------------------------
+ * The accept / resample step of assisted generation under sampling (HF: generation/utils.py _speculative_sampling; Leviathan et al.
+ * 2023).  Group g holds R target rows p[g * R + i, :n] and R - 1 draft rows q[g * (R - 1) + i, :n], fp32 warped scores as
+ * rv_sample_rows_f32(write_scores = 1) leaves them (finite where kept, -inf where removed), and the R - 1 drafted ids draft[g, i]
+ * (int32).  P_i / Q_i: the softmax over the finite entries of p-row / q-row i.  For i = 0 .. R - 2 and x = draft[g, i]:
+ *   draft i is accepted iff 0 <= x < n, P_i(x) > 0 and u_a * Q_i(x) <= P_i(x);
+ *   n_accept[g] = a = the drafts accepted before the first one that is not;
+ *   a < R - 1: token[g] is drawn from r(j) ~ max(0, P_a(j) - Q_a(j)), and from P_a when r is identically 0;  a = R - 1: from P_{R-1};
+ *   either way it is the lowest id j whose cumulative sum in TOKEN-ID order exceeds u_r times the total (the sampler's draw rule);
+ *   logprob[g] = log P_a(token[g]), under the target's distribution.
+ * u_a of draft i is the uniform (2 b + 1) / 2^25 of rv_sample_uniform24_tagged(seed[g], 1, t0[g] + i), u_r that of (seed[g], 0,
+ * t0[g] + a): t0 (int32 [groups]) is the step of row 0, seed uint64 [groups].  The draft model's own draws use tag 2
+ * (rv_sample_rows_tagged_f32): three distinct streams, since a draft's draw and its accept test must be independent.  R = 1 (no
+ * drafts; q and draft may be NULL) is the plain draw from P_0 with tag 0.
+ * A p-row or q-row on the path (rows 0 .. a) that holds a NaN or +inf, or no finite entry, ends it: n_accept[g] = the drafts accepted
+ * before that row, token[g] = -1, logprob[g] = NaN.  Columns >= n are never read; rows need 4-byte alignment only.
+ * Exact cases: bitwise equal p-row i and q-row i accept draft i for every seed (both sides of the test are then one double times u_a <
+ * 1 and times 1); a draft with p = -inf is never accepted.  Elsewhere an accept test or a draw may differ from exact arithmetic on the
+ * fp32 scores only inside a band of delta = 2^-25, relative to the larger side: for a test the sides are u_a * Q_i(x) and P_i(x); for a
+ * draw at id j they are sum{P : ids <= j} + u_r * sum{Q} and sum{Q : ids <= j} + u_r * sum{P} over the ids with P > Q (Q = 0 for a draw
+ * from P).  Derivation (csrc/spec.hip): exp in float64; a row's normaliser Z = sum rne(exp(s_j - max s) * 2^44) as a 64-bit integer,
+ * within n * 2^-45 <= 2^-27 of exact; float64 products and sums over <= 263,168 terms add < 2^-34.  delta is below rv_sample_rows_f32's
+ * (depth + 4) * 2^-23.
+ * One workgroup per row for max and Z, then one per group: thread k adds the weights of its fixed run of ids in id order, one thread
+ * adds the 1024 run sums in order and walks the run that holds the target.  No float atomics, no global atomics: n_accept, token and
+ * logprob of a group are the same bits on every launch, for every `groups` and whatever the other groups hold.  ws: device scratch of
+ * ws_bytes >= rv_spec_ws_bytes(groups, R) bytes, 8-byte aligned, contents arbitrary.  RV_ERR_ARG: a null pointer, R outside 1 .. 32, n
+ * outside 1 .. 262144, ld_p < n or ld_q < n, a short or misaligned ws. */
+int rv_spec_accept_rows_f32(const float* p, int64_t ld_p, const float* q, int64_t ld_q, const int32_t* draft, const uint64_t* seed,
+                            const int32_t* t0, int groups, int R, int n, int32_t* n_accept, int64_t* token, float* logprob, void* ws,
+                            int64_t ws_bytes, void* stream);
+/* Host function: the bytes of scratch rv_spec_accept_rows_f32 needs. */
+int64_t rv_spec_ws_bytes(int groups, int R);
 
 /* ---- beam search (generate_beams(), radvlm_amd/csrc/beam.hip) ----------------------------------------------------------------------
  * The reference reaches beam search through HF generate(num_beams=...) (finetuning/llava/eval/model_vqa.py --num_beams ->

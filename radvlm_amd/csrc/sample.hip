@@ -28,6 +28,7 @@
 // rounding is <= 2^-41 per term, <= 2^-23 of Z (>= 2^40) over 262,144 terms, in C and in Z: <= 5 * 2^-23 = (depth + 4) * 2^-23.
 #include "common.h"
 #include "radvlm_hip.h"
+#include "sample_rng.h"
 
 #include <math.h>
 
@@ -43,19 +44,6 @@ constexpr int SM_TILE = 256;                     // entries per tile: one float4
 constexpr int SM_REP = 16;                       // interleaved copies of each histogram bin
 constexpr int SM_PER_LANE = 17;                  // tile sums a lane of the last scan owns
 constexpr int SM_TILES_CAP = 64 * SM_PER_LANE;   // >= (SM_MAX_N + 3 + 255) / 256 = 1025
-
-__host__ __device__ inline uint64_t sm_splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// the top 24 bits of portable_rng._stream(seed, 0, t + 1)[t]
-__host__ __device__ inline uint32_t sm_uniform24(uint64_t seed, int32_t t) {
-    const uint64_t base = sm_splitmix64(seed * 1000003ull);
-    return (uint32_t)(sm_splitmix64((uint64_t)(int64_t)t * 0xD1342543DE82EF95ull + base) >> 40);
-}
 
 DEVINL unsigned sm_key(float s) {
     const unsigned u = __float_as_uint(s + 0.0f);                // -0 -> +0: equal scores get equal keys
@@ -361,7 +349,7 @@ __global__ __launch_bounds__(SM_T) void sample_pass_kernel(float* x, long ld, in
 __global__ __launch_bounds__(64) void sample_draw_kernel(float* x, long ld, int n, const uint64_t* __restrict__ seed,
                                                          const int32_t* __restrict__ tv, float T, float min_p, int write_scores,
                                                          const u64* __restrict__ ws, int pf, int64_t* __restrict__ out,
-                                                         float* __restrict__ logprob) {
+                                                         float* __restrict__ logprob, uint64_t tag) {
     const int lane = lane_id();
     const u64* wr = ws + (long)blockIdx.x * SM_WS_WORDS;
     const u64* tsum = wr + SM_WS_TSUM;
@@ -389,7 +377,7 @@ __global__ __launch_bounds__(64) void sample_draw_kernel(float* x, long ld, int 
     }
     const u64 inc = wave_scan64(ls);
     const u64 Z = shfl64(inc, 63);
-    const u64 r2 = 2ull * sm_uniform24(seed[blockIdx.x], tv[blockIdx.x]) + 1ull;       // u = r2 * 2^-25
+    const u64 r2 = 2ull * sm_uniform24(seed[blockIdx.x], tag, tv[blockIdx.x]) + 1ull;      // u = r2 * 2^-25
     const u64 target = (__umul64hi(r2, Z) << 39) | ((r2 * Z) >> 25);                   // floor(u * Z) < Z
     const bool mine = (inc - ls) <= target && target < inc;
     const u64 owner = __ballot(mine);
@@ -462,14 +450,15 @@ __global__ __launch_bounds__(64) void sample_draw_kernel(float* x, long ld, int 
 
 }  // namespace
 
-extern "C" uint32_t rv_sample_uniform24(uint64_t seed, int32_t t) { return sm_uniform24(seed, t); }
+extern "C" uint32_t rv_sample_uniform24(uint64_t seed, int32_t t) { return sm_uniform24(seed, 0, t); }
+extern "C" uint32_t rv_sample_uniform24_tagged(uint64_t seed, int32_t tag, int32_t t) { return sm_uniform24(seed, (uint64_t)(int64_t)tag, t); }
 
 extern "C" int64_t rv_sample_ws_bytes(int rows) { return rows > 0 ? (int64_t)rows * SM_WS_WORDS * 8 : 0; }
 
-extern "C" int rv_sample_rows_f32(float* x, int64_t ld, int rows, int n, const uint64_t* seed, const int32_t* t, float temperature, int top_k,
-                                  float top_p, float min_p, int write_scores, int64_t* out, float* logprob, void* ws, int64_t ws_bytes,
-                                  void* stream) {
-    if (!x || !seed || !t || !out || rows <= 0 || n <= 0 || n > SM_MAX_N || ld < n || (reinterpret_cast<uintptr_t>(x) & 3u) ||
+extern "C" int rv_sample_rows_tagged_f32(float* x, int64_t ld, int rows, int n, const uint64_t* seed, const int32_t* t, int32_t tag,
+                                         float temperature, int top_k, float top_p, float min_p, int write_scores, int64_t* out,
+                                         float* logprob, void* ws, int64_t ws_bytes, void* stream) {
+    if (!x || !seed || !t || !out || rows <= 0 || n <= 0 || n > SM_MAX_N || ld < n || (reinterpret_cast<uintptr_t>(x) & 3u) || tag < 0 ||
         !(temperature > 0.f) || !(temperature < INFINITY) || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f) || !(min_p >= 0.f && min_p <= 1.f) ||
         !ws || (reinterpret_cast<uintptr_t>(ws) & 7u) || ws_bytes < rv_sample_ws_bytes(rows))
         return RV_ERR_ARG;
@@ -489,6 +478,13 @@ extern "C" int rv_sample_rows_f32(float* x, int64_t ld, int rows, int n, const u
         for (int l = 0; l < 4; ++l) pass(SM_PSEL, l);
     pass(SM_FINAL, 0);
     hipLaunchKernelGGL(sample_draw_kernel, dim3(rows), dim3(64), 0, ST, x, (long)ld, n, seed, t, temperature, min_p, write_scores,
-                       (const u64*)ws, p - 1, out, logprob);
+                       (const u64*)ws, p - 1, out, logprob, (uint64_t)tag);
     return rv_check_launch();
+}
+
+extern "C" int rv_sample_rows_f32(float* x, int64_t ld, int rows, int n, const uint64_t* seed, const int32_t* t, float temperature, int top_k,
+                                  float top_p, float min_p, int write_scores, int64_t* out, float* logprob, void* ws, int64_t ws_bytes,
+                                  void* stream) {
+    return rv_sample_rows_tagged_f32(x, ld, rows, n, seed, t, 0, temperature, top_k, top_p, min_p, write_scores, out, logprob, ws, ws_bytes,
+                                     stream);
 }

@@ -28,6 +28,9 @@ _ACCEPTED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "at
              "inputs_embeds", "past_key_values", "seed", "kv_cache_dtype") + _PROCESSORS + _IGNORED_WHEN_GREEDY
 # prompt-lookup decoding (HF's names): generate() alone takes them, generate_batch() and generate_beams() reject them as unknown
 _LOOKUP = ("prompt_lookup_num_tokens", "max_matching_ngram_size")
+# assisted generation (HF's names): a draft model proposes, the model verifies; generate() alone takes them, as the lookup names
+_ASSIST = ("assistant_model", "num_assistant_tokens")
+ASSIST_DEFAULT_TOKENS = 5     # HF's num_assistant_tokens default, kept constant (no "heuristic" schedule)
 # classifier-free guidance (HF's names; negative_images / negative_image_sizes are ours: HF's negative prompt cannot carry an image)
 _GUIDANCE = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "negative_images", "negative_image_sizes")
 # DoLa, decoding by contrasting layers (HF's name); _parse_dola / resolve_dola_layers
@@ -63,11 +66,13 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
     .sampling: None for greedy, else the warper settings and the seed as given (sampling_seeds() resolves it per row).
     lookup: also take prompt_lookup_num_tokens / max_matching_ngram_size (.lookup: None, or .k and .max_ngram; .drafter: None,
     greedy_generate then builds a PromptLookupDrafter; a test or a benchmark may set another object with propose(seq)).
+    lookup also takes assistant_model / num_assistant_tokens (.assistant: None, or .model and .k; greedy_generate then checks the model
+    against the engine and builds an assist.ModelDrafter).
     attentions: also take output_attentions / attention_layers / attention_reduce (.attentions: None, or .layers and .reduce).
     .kv_cache_dtype: "bf16" or "int8"; .guidance (_parse_guidance), .dola (_parse_dola), .constraint (_parse_constraint) and .kvpress
     ((N, w, k), parse_prompt_kv): None when off; the resolve_* functions finish them once the call knows the engine and the rows."""
     unknown = sorted(k for k in kwargs if k not in _ACCEPTED and k not in _GUIDANCE and k not in _DOLA and k not in _CONSTRAINT
-                     and k not in _KVPRESS and not (lookup and k in _LOOKUP) and not (attentions and k in _ATTENTIONS))
+                     and k not in _KVPRESS and not (lookup and k in _LOOKUP + _ASSIST) and not (attentions and k in _ATTENTIONS))
     if unknown:
         raise TypeError(f"generate() got unexpected keyword arguments {unknown}")
     guidance = _parse_guidance(kwargs)
@@ -116,6 +121,7 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
                           output_logits=bool(kwargs.get("output_logits", False)),
                           return_dict=bool(kwargs.get("return_dict_in_generate", False)), attention_mask=kwargs.get("attention_mask"),
                           past_key_values=pkv, sampling=_parse_sampling(kwargs), lookup=_parse_lookup(kwargs), drafter=None,
+                          assistant=_parse_assistant(kwargs),
                           kv_cache_dtype=kv_dtype, guidance=guidance, dola=dola, constraint=constraint, attentions=att, kvpress=press,
                           **_parse_processors(kwargs, eos))
     refuse_combinations(features_of(cfg), "generate()")
@@ -127,7 +133,7 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
 # the order is part of the behaviour.  A new feature adds its rows here and nowhere else.
 FEATURES = dict(kvpress="prompt_kv_budget / prompt_kv_window", attentions="output_attentions", constraint="constraint", guidance="guidance_scale",
                 dola="dola_layers", past_key_values="past_key_values", lookup="prompt_lookup_num_tokens", int8="kv_cache_dtype='int8'",
-                share_prefix="share_prefix=True", sampling="do_sample=True", lora="LoRA adapters")
+                share_prefix="share_prefix=True", sampling="do_sample=True", lora="LoRA adapters", assistant="assistant_model")
 REFUSALS = (
     ("kvpress", "past_key_values", "the extend pass reads a cache whose slots are its positions"),
     ("kvpress", "lookup", "the verify step reads a cache whose slots are its positions"),
@@ -156,6 +162,14 @@ REFUSALS = (
     ("share_prefix", "dola", "the extend pass and the shared decode step hand out no intermediate hidden states"),
     ("kvpress", "share_prefix", "a follower's copy and the extend pass read a cache whose slots are its positions"),
     ("attentions", "lora", "attention maps on the live adapters are not implemented; merge them first with model.merge_and_unload()"),
+    ("assistant", "lookup", "a call takes one drafter: the draft model or the n-gram lookup"),
+    ("kvpress", "assistant", "the verify step reads a cache whose slots are its positions"),
+    ("attentions", "assistant", "the verify step hands out no attention rows"),
+    ("constraint", "assistant", "every drafted row of a verify step would need its own automaton state, which is not implemented"),
+    ("guidance", "assistant", "verifying drafts on two branches is not implemented"),
+    ("dola", "assistant", "the verify step hands out no intermediate hidden states"),
+    ("int8", "assistant", "the verify-attention kernel reads a bf16 cache only"),
+    ("assistant", "past_key_values", "the draft model's cache is not kept across calls"),
 )
 
 
@@ -163,8 +177,10 @@ def features_of(cfg, lora=False):
     """The FEATURES that a cfg has on, parsed or built by hand (a missing attribute is off).  lora: the engine decodes on live
     adapters."""
     get = lambda name: getattr(cfg, name, None)
-    on = dict(kvpress=get("kvpress"), attentions=get("attentions"), constraint=get("constraint"), guidance=get("guidance"), dola=get("dola"),
-              past_key_values=get("past_key_values"), sampling=get("sampling"), lookup=get("lookup") if get("drafter") is None else True,
+    # a drafter set by hand counts as the lookup; the draft model's drafter is the assistant's, and sampling composes with it
+    lookup = get("lookup") if get("drafter") is None or get("assistant") is not None else True
+    on = dict(assistant=get("assistant"), kvpress=get("kvpress"), attentions=get("attentions"), constraint=get("constraint"), guidance=get("guidance"), dola=get("dola"),
+              past_key_values=get("past_key_values"), sampling=get("sampling"), lookup=lookup,
               int8=get("kv_cache_dtype") == "int8" or None, share_prefix=get("share_prefix") or None, lora=lora or None)
     return {name for name, v in on.items() if v is not None}
 
@@ -451,6 +467,24 @@ def _parse_lookup(kwargs):
     return SimpleNamespace(k=int(k), max_ngram=int(ng))
 
 
+def _parse_assistant(kwargs):
+    """assistant_model (a model of this project's classes: it has an .engine) and num_assistant_tokens (an int in 1 .. 31, default
+    ASSIST_DEFAULT_TOKENS, constant over the call); None when no assistant is given.  ValueError for a bad k, for k without a model
+    and for an object without an engine."""
+    m, k = kwargs.get("assistant_model"), kwargs.get("num_assistant_tokens")
+    if m is None:
+        if k is not None:
+            raise ValueError("`num_assistant_tokens` given without `assistant_model`")
+        return None
+    if getattr(m, "engine", None) is None:
+        raise ValueError(f"`assistant_model` has to be a model of this package (LlavaLlamaForCausalLM or LlavaQwenForCausalLM), not "
+                         f"{type(m).__name__}")
+    k = ASSIST_DEFAULT_TOKENS if k is None else k
+    if not _is_int(k) or not 1 <= k <= LOOKUP_MAX_TOKENS:
+        raise ValueError(f"`num_assistant_tokens` has to be an integer in [1, {LOOKUP_MAX_TOKENS}], but is {k!r}")
+    return SimpleNamespace(model=m, k=int(k))
+
+
 def _is_int(v):
     return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
@@ -519,13 +553,14 @@ def sampling_seeds(sampling, n):
     return seeds
 
 
-def sample_uniform(seed, t):
+def sample_uniform(seed, t, tag=0):
     """The uniform of row seed `seed` at its step t (the tokens it has generated so far), in (0, 1):
-    ((portable_rng._stream(seed, 0, t + 1)[t] >> 40) + 0.5) * 2^-24, an odd multiple of 2^-25 (exact in float64; rv_sample_rows_f32
-    restates it on the device and keeps it as an integer)."""
+    ((portable_rng._stream(seed, tag, t + 1)[t] >> 40) + 0.5) * 2^-24, an odd multiple of 2^-25 (exact in float64; rv_sample_rows_f32
+    restates it on the device and keeps it as an integer).  tag: the stream -- 0 the sampler's and speculative sampling's resample /
+    bonus draw, 1 its accept tests, 2 the draft model's own draws (rv_sample_uniform24_tagged)."""
     from .portable_rng import _splitmix64
     with np.errstate(over="ignore"):
-        base = _splitmix64(np.array([(int(seed) * 1000003) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))
+        base = _splitmix64(np.array([(int(seed) * 1000003 + int(tag)) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))
         v = _splitmix64(np.array([int(t)], dtype=np.uint64) * np.uint64(0xD1342543DE82EF95) + base)[0]
     return (float(int(v) >> 40) + 0.5) * 2.0 ** -24
 
@@ -865,7 +900,7 @@ def clamp_draft(draft, limit, vocab=None):
     return d[:int(bad[0])].copy() if bad.size else d.copy()
 
 
-def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw):
+def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw, seed=None):
     """The accept loop of prompt-lookup decoding on one sequence, from the prompt pass's logits to the end of generation.  Each round
     holds fp32 logits [R, vocab]: row 0 from feeding the last emitted token, row i from feeding draft i - 1 after it, so row i is the
     plain loop's step t + i provided the drafts before it were right.  The R token choices run in one launch (rv_argmax_rows_f32, or
@@ -875,15 +910,23 @@ def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
     budget or where a criterion says so.  The next round feeds the last emitted token and a new draft: verify_step, or decode_step when
     the draft is empty.  cache.lens advances by the tokens emitted, so it always counts the prompt and every emitted token but the
     last; the K|V rows of rejected drafts stay past it.  Returns dict(steps=, drafted=, accepted=): engine steps after the prompt pass,
-    draft tokens fed and draft tokens that matched."""
+    draft tokens fed and draft tokens that matched.
+    cfg.sampling (a draft model only; seed: the row's seed): the rows and the loop are the same, the round differs only in how the R
+    processed rows become "accepted count, next token".  The seeded sampler warps the R rows in place (row i at step t + i; its own
+    draws are not used), ops.spec_accept_rows tests draft i against the drafter's warped row i (cfg.drafter.q_rows) and draws the token
+    after the accepted ones, and (accepted, token) come to the host in one copy.  scores then holds the target's warped rows."""
     from . import ops
-    dev, V = engine.device, engine.vocab
+    dev, V, sm = engine.device, engine.vocab, cfg.sampling
     stats = dict(steps=0, drafted=0, accepted=0)
     seq = [int(v) for v in prompt_ids]
     hist = None
     if lp.active:
         hist = torch.zeros(1, T, dtype=torch.int32, device=dev)
         bans = lp.rows_device_args(dev)
+    if sm is not None:
+        seed1 = torch.tensor([seed], dtype=torch.int64, device=dev)
+        seedR = seed1.expand(ops.SPEC_MAX_R).contiguous()
+        sws, aws = ops.sample_rows_workspace(ops.SPEC_MAX_R, dev), ops.spec_accept_workspace(1, ops.SPEC_MAX_R, dev)
     draft = np.zeros(0, dtype=np.int64)
     t, fed = 0, False                      # fed: the round's rows come from a step that wrote K|V rows (every round but the first)
     while True:
@@ -896,15 +939,29 @@ def _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
             if R > 1:                      # the drafts go behind the emitted tokens: row i reads hist[0, :t + i]
                 hist[0, t:t + R - 1] = info[3, :R - 1]
             nxt = ops.logits_process_argmax_rows(logits, V, hist, info[0], info[1], info[2], lp.penalty, lp.ngram, *bans)
-            hist[0, t:t + R] = nxt         # the choices: the drafts while they are accepted, then the token after them
-        else:
+            if sm is None:
+                hist[0, t:t + R] = nxt     # the choices: the drafts while they are accepted, then the token after them
+        elif sm is None:
             nxt = ops.argmax_rows(logits, V)
+        if sm is not None:
+            # one upload: the rows' steps, then the drafts
+            si = engine._dev(np.concatenate([t + np.arange(R), draft]).astype(np.int32))
+            # the sampler is run for its warp only (write_scores): its R draws are deliberately unused, the tokens come from the
+            # accept kernel below
+            ops.sample_rows(logits, V, seedR[:R], si[:R], sm.temperature, sm.top_k, sm.top_p, sm.min_p, write_scores=True, ws=sws)
+            n_acc, tok, _ = ops.spec_accept_rows(logits, cfg.drafter.q_rows[:R - 1] if R > 1 else None, si[R:], seed1, si[:1], V, ws=aws)
+            if lp.active:                  # the token after the accepted drafts goes behind them
+                hist[0].scatter_(0, n_acc.long() + t, tok.int())
+            a, token = (int(v) for v in torch.stack([n_acc.long(), tok]).cpu().reshape(-1))
+            _check_sampled([token])
+            choice = np.append(draft[:a], token)
         if cfg.output_scores:
             score_rows = logits.clone()
-        choice = np.asarray(nxt.cpu() if torch.is_tensor(nxt) else nxt, dtype=np.int64).reshape(-1)
-        a = 0
-        while a < R - 1 and draft[a] == choice[a]:
-            a += 1
+        if sm is None:
+            choice = np.asarray(nxt.cpu() if torch.is_tensor(nxt) else nxt, dtype=np.int64).reshape(-1)
+            a = 0
+            while a < R - 1 and draft[a] == choice[a]:
+                a += 1
         stats["drafted"] += R - 1
         stats["accepted"] += a
         n_emit = 0
@@ -997,9 +1054,14 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
     refuse_combinations(features_of(cfg, lora=att is not None and engine.lora), "generate()")          # protects a cfg built by hand
     if gc is not None:
         gc._bind(engine, B)
-    lookup = getattr(cfg, "lookup", None) is not None or getattr(cfg, "drafter", None) is not None
+    assist = getattr(cfg, "assistant", None)
+    lookup = getattr(cfg, "lookup", None) is not None or getattr(cfg, "drafter", None) is not None or assist is not None
     if lookup and B != 1:
-        raise ValueError(f"prompt_lookup_num_tokens takes one prompt row (HF's assisted generation is batch-size-1 too), got {B}")
+        raise ValueError(f"{'prompt_lookup_num_tokens' if assist is None else 'assistant_model'} takes one prompt row (HF's assisted "
+                         f"generation is batch-size-1 too), got {B}")
+    if assist is not None and cfg.drafter is None:
+        from .assist import check_assistant
+        check_assistant(engine, assist.model.engine)
     lookup_stats = dict(steps=0, drafted=0, accepted=0)
     st = GreedyState(B, cfg)
     scores, raw, picks, attns = [], [], [], []
@@ -1065,10 +1127,14 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
             if dola is not None:
                 dws = ops.dola_workspace(B, len(dola), dev)
         if lookup:                        # the accept loop runs the whole generation
-            if cfg.drafter is None:
-                cfg.drafter = PromptLookupDrafter(cfg.lookup.k, cfg.lookup.max_ngram, cfg.eos, V)
             prompt_ids = ids[0] if am is None else ids[0][np.asarray(am).reshape(B, -1)[0].astype(bool)]
-            lookup_stats = _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw)
+            if cfg.drafter is None and assist is not None:
+                from .assist import ModelDrafter
+                cfg.drafter = ModelDrafter(assist.model.engine, assist.k, cfg, T, len(prompt_ids), plan_len, None if sm is None else seeds[0])
+                cfg.drafter.start(ids, am, images, image_sizes)
+            elif cfg.drafter is None:
+                cfg.drafter = PromptLookupDrafter(cfg.lookup.k, cfg.lookup.max_ngram, cfg.eos, V)
+            lookup_stats = _lookup_loop(engine, cache, logits, prompt_ids, st, lp, cfg, T, scores, raw, None if sm is None else seeds[0])
         if ctab is not None:              # every call starts at the start states, a continued conversation too
             ctabs, cstate, ctok = ctab.device_tables(dev), engine._dev(cstart), None
             mirror = ConstraintMirror(ctab, B)
@@ -1121,7 +1187,9 @@ def greedy_generate(engine, input_ids, attention_mask, images, image_sizes, cfg)
         return seq
     out = GenerateDecoderOnlyOutput(sequences=seq, scores=tuple(scores) if cfg.output_scores else None,
                                     logits=tuple(raw) if cfg.output_logits else None, past_key_values=gc)
-    if lookup:
+    if assist is not None:
+        out.assist_stats = lookup_stats
+    elif lookup:
         out.lookup_stats = lookup_stats
     if att is not None:
         out.attentions, out.attention_layers = tuple(attns), att_layers

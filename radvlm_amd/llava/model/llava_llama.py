@@ -436,6 +436,17 @@ class LlavaLlamaForCausalLM:
         only (ValueError otherwise, HF's assisted generation is batch-size-1 too); with do_sample=True NotImplementedError; k outside
         1 .. 31 or a non-int ValueError.  Every other greedy keyword keeps its meaning; stopping criteria are called once per emitted
         token, in order, with that token's own score row.
+        Assisted generation: assistant_model=m (HF's name; another model of this package with the same vocabulary size and the same
+        image inputs, any decoder geometry or weight format; m may be the model itself) drafts num_assistant_tokens=k tokens per
+        round (an int, 1 .. 31, default 5, constant) on a KV cache of its own, prefilled with the same prompt and images, and the
+        model verifies them in one k + 1 row step.  Greedy, the result is bit for bit that of the call without it.  With
+        do_sample=True and seed= the round is speculative sampling (HF's _speculative_sampling on rv_spec_accept_rows_f32): the
+        call is reproducible for a given (seed, assistant, k) and draws from the same distribution as the plain call, but does
+        not emit the same tokens.  scores are the model's processed (warped) rows, logits its raw rows; with
+        return_dict_in_generate the output gains .assist_stats = dict(steps=, drafted=, accepted=).  One prompt row only
+        (ValueError); a vocabulary or image-input mismatch is a ValueError naming it, before any device work; with
+        prompt_lookup_num_tokens, past_key_values, kv_cache_dtype="int8", guidance_scale, dola_layers, constraint,
+        output_attentions or prompt_kv_budget NotImplementedError.
         kv_cache_dtype: None or "bf16" (today's cache) or "int8": each cached position's K and V are stored per kv head as int8 with
         one fp32 scale (s = max|x| / 127), 0.516x the cache bytes, read by an int8 decode-attention kernel.  The first token still
         comes from the unquantised prompt pass; later tokens see the rounded keys and values, so they may differ from the bf16

@@ -1178,12 +1178,12 @@ def sample_rows_workspace(rows, device):
     return torch.empty(lib.load().rv_sample_ws_bytes(int(rows)) // 8, dtype=torch.int64, device=device)
 
 
-def sample_rows(x, n, seed, t, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, write_scores=False, out=None, logprob=None, ws=None):
+def sample_rows(x, n, seed, t, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, write_scores=False, out=None, logprob=None, ws=None, tag=0):
     """Seeded sampling (rv_sample_rows_f32): one token per fp32 row x[r, :n] after HF's warpers temperature -> top-k -> top-p -> min-p,
     drawn with the counter-based uniform of (seed[r], t[r]) (seed: int64 [rows] holding the uint64 bits, t: int32 [rows]).  write_scores:
     x[:, :n] becomes the warped scores (-inf where removed), else x is only read.  Returns int64 [rows]; -1 marks a row that cannot be
     sampled (NaN, +inf or no finite entry).  logprob (fp32 [rows]): log q of the drawn token.  ws: sample_rows_workspace(>= rows), allocated
-    here when not given."""
+    here when not given.  tag: another stream of the same seed (rv_sample_rows_tagged_f32; 0 is the plain entry point)."""
     _chk(x, torch.float32)
     rows = x.shape[0]
     assert x.dim() == 2 and x.stride(1) == 1 and 0 < n <= min(x.shape[1], LOGITS_PROCESS_MAX_N)
@@ -1197,9 +1197,50 @@ def sample_rows(x, n, seed, t, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, w
     ws = sample_rows_workspace(rows, x.device) if ws is None else ws
     _chk(ws, torch.int64)
     assert ws.is_contiguous() and ws.numel() * 8 >= lib.load().rv_sample_ws_bytes(rows)
-    lib.call("rv_sample_rows_f32", x, x.stride(0), rows, int(n), seed, t, float(temperature), int(top_k or 0), float(top_p), float(min_p),
-             1 if write_scores else 0, out, logprob, ws, ws.numel() * 8)
+    args = (float(temperature), int(top_k or 0), float(top_p), float(min_p), 1 if write_scores else 0, out, logprob, ws, ws.numel() * 8)
+    if tag:
+        lib.call("rv_sample_rows_tagged_f32", x, x.stride(0), rows, int(n), seed, t, int(tag), *args)
+    else:
+        lib.call("rv_sample_rows_f32", x, x.stride(0), rows, int(n), seed, t, *args)
     return out
+
+
+SPEC_MAX_R = 32               # rows per group of spec_accept_rows: up to 31 drafts and the row after them
+
+
+def spec_accept_workspace(groups, R, device):
+    """Scratch for spec_accept_rows on up to `groups` groups of R rows (int64, never zeroed)."""
+    return torch.empty(max(lib.load().rv_spec_ws_bytes(int(groups), int(R)) // 8, 1), dtype=torch.int64, device=device)
+
+
+def spec_accept_rows(p, q, draft, seed, t0, n, ws=None):
+    """Speculative sampling's accept / resample step (rv_spec_accept_rows_f32).  p: fp32 [groups * R, >= n], the target's warped score
+    rows; q: fp32 [groups * (R - 1), >= n], the draft's (None when R == 1); draft: int32 [groups, R - 1]; seed: int64 [groups] holding
+    the uint64 bits; t0: int32 [groups], the step of each group's row 0.  Returns (n_accept int32 [groups], token int64 [groups],
+    logprob fp32 [groups]): the drafts accepted, the token drawn after them (-1: an unusable row) and its log-probability under the
+    target's row."""
+    _chk(p, torch.float32), _chk(seed, torch.int64), _chk(t0, torch.int32)
+    groups = seed.numel()
+    assert p.dim() == 2 and p.stride(1) == 1 and groups > 0 and p.shape[0] % groups == 0 and 0 < n <= min(p.shape[1], LOGITS_PROCESS_MAX_N)
+    R = p.shape[0] // groups
+    assert 1 <= R <= SPEC_MAX_R and seed.is_contiguous() and t0.is_contiguous() and t0.numel() == groups
+    ld_q = 0
+    if R > 1:
+        _chk(q, torch.float32), _chk(draft, torch.int32)
+        assert q.dim() == 2 and q.stride(1) == 1 and q.shape[0] == groups * (R - 1) and q.shape[1] >= n
+        assert draft.is_contiguous() and draft.numel() == groups * (R - 1)
+        ld_q = q.stride(0)
+    else:
+        q = draft = None
+    ws = spec_accept_workspace(groups, R, p.device) if ws is None else ws
+    _chk(ws, torch.int64)
+    assert ws.is_contiguous() and ws.numel() * 8 >= lib.load().rv_spec_ws_bytes(groups, R)
+    n_accept = torch.empty(groups, dtype=torch.int32, device=p.device)
+    token = torch.empty(groups, dtype=torch.int64, device=p.device)
+    logprob = torch.empty(groups, dtype=torch.float32, device=p.device)
+    lib.call("rv_spec_accept_rows_f32", p, p.stride(0), q, ld_q, draft, seed, t0, groups, R, int(n), n_accept, token, logprob, ws,
+             ws.numel() * 8)
+    return n_accept, token, logprob
 
 
 def attn_decode_beam(q, cache, kv_len, prefix_row, prefix_len, tail_src, H, Hkv, hd, v_off, tail_cols=None, out=None, chunk=128, scale=None):

@@ -116,6 +116,12 @@
         # device time, median of 50, warm; (2) the decode step (decode_step + constrain + argmax) with a from_choices constraint of
         # 8 choices of --new tokens, so that every row stays live for the whole loop, beside the plain step on one engine: one untimed
         # pass of both arms, then the arms alternated three times; median ms per step per arm, the plain arm's spread, the added ms
+  python tools/decode_bench.py --assistant [--geos llava15_7b] [--draft-layers 4] [--prompt 704] [--new 128] [--out profiles/assist_bench.jsonl]
+        # assisted generation at B = 1 with a draft of the target's width and --draft-layers layers: the plain step, the draft step,
+        # verify_step at R = k + 1 for k = 3, 5, 7, 15 and the accept kernel (alone, and with the sampler's warp of the R rows), wall ms,
+        # medians; then greedy generate(assistant_model=) end to end with a drafter that runs the draft engine for real and proposes
+        # scripted tokens, at acceptance 0, k // 2 and k of k: ms per token, tokens / s, speed-up over the plain call on the same box and
+        # in the same run, and the break-even accepted drafts per round (random weights have no acceptance rate of their own)
   python tools/decode_bench.py --lora [--geos ..] [--batches 1,32] [--prompt 704] [--new 40] [--out FILE]
         # decoding on live LoRA adapters (r = 64): the decode step on merged weights, on the live adapters and on the live adapters
         # switched off, interleaved on one box; median and p10 / p90 of 20 samples per arm (a sample: the median step of one loop),
@@ -964,6 +970,134 @@ def lookup_e2e(geo, prompt, new, reps=3, ks=(3, 7, 15)):
                 real_drafter_random_weights_ms_per_token=round(r, 3), real_drafter_random_weights_stats=stats[f"real_k{k}"])
         recs.append(rec)
     return recs
+
+
+def _scripted_model_drafter(draft, k, cfg, new, prompt, ref, j):
+    """An assist.ModelDrafter that runs the draft engine for real -- catch-up, k chained draft steps, the copy to the host -- and then
+    proposes the plain run's next j tokens followed by wrong ones (the Scripted idea of tests/test_generate_lookup_gpu.py: random
+    weights have no acceptance rate of their own).  Its bookkeeping is told that it fed the scripted tokens, so the next round's
+    catch-up feeds what a real assistant with that acceptance would feed."""
+    from radvlm_amd.assist import ModelDrafter
+
+    class Scripted(ModelDrafter):
+        def propose(self, seq):
+            own = super().propose(seq)
+            t = len(seq) - self.P
+            out = np.array([(ref[t + i] if t + i < len(ref) else 0) if i < j else ((ref[t + i] if t + i < len(ref) else 0) + 1) % self.engine.vocab
+                            for i in range(len(own))], dtype=np.int64)
+            self.fed = self.fed[:t] + [int(v) for v in out[:max(len(own) - 1, 0)]]
+            return out
+    return Scripted(draft, k, cfg, new, prompt)
+
+
+def assistant_bench(geo, prompt, new, reps=3, ks=(3, 5, 7, 15), draft_layers=4, warm=8):
+    """--assistant: B = 1, a draft of the target's width with draft_layers decoder layers.  (1) step times on one box, wall ms with a
+    synchronize around each step, medians after `warm` steps: the target's plain step (decode_step + argmax), the draft's step, the
+    target's verify_step at R = k + 1, and the sampled round's extra launches (the sampler's warp of R rows + rv_spec_accept_rows_f32).
+    (2) greedy generate(assistant_model=) end to end with the scripted drafter at acceptance 0, k // 2 and k of k: ms per token after
+    the two prefills, tokens / s, speed-up over the plain call, and the break-even number of accepted drafts per round,
+    never_ms_per_round / plain_ms_per_token - 1."""
+    from types import SimpleNamespace
+    from radvlm_amd.generation import greedy_generate, parse_generate_kwargs
+    eng = LlavaEngine(GEOMETRIES[geo], device="cuda:0", init="fast", seed=0)
+    dgeo = dict(GEOMETRIES[geo])
+    dgeo["lm"] = dict(dgeo["lm"], layers=draft_layers)
+    draft = LlavaEngine(dgeo, device="cuda:0", init="fast", seed=1)
+    V = eng.vocab
+    ids = np.random.default_rng(0).integers(0, V, (1, prompt))
+
+    def timed(f, n):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts[warm:]))
+
+    # ---- (1) the steps
+    steps = {}
+    for name, e in (("plain_step_ms", eng), ("draft_step_ms", draft)):
+        cache, logits = e.prefill(ids, None, None, None, max_new_tokens=new)
+        tok = [ops.argmax_rows(logits, V)]
+
+        def step(e=e, cache=cache, tok=tok):
+            tok[0] = ops.argmax_rows(e.decode_step(cache, tok[0]), V)
+        steps[name] = timed(step, new - 1)
+        del cache
+    cache, logits = eng.prefill(ids, None, None, None, max_new_tokens=new)
+    seed1 = torch.tensor([7], dtype=torch.int64, device="cuda")
+    for k in ks:
+        R = k + 1
+        feed = np.random.default_rng(k).integers(0, V, R)
+        steps[f"verify_step_ms_k{k}"] = timed(lambda: eng.verify_step(cache, feed), warm + 20)       # lens is not advanced: every call is the same step
+        p = eng.verify_step(cache, feed).clone()
+        q = (p[:k] + 0.5 * torch.randn_like(p[:k])).contiguous()
+        si = torch.arange(R, dtype=torch.int32, device="cuda")
+        dr = torch.from_numpy(feed[:k].astype(np.int32)).cuda()
+        sws, aws = ops.sample_rows_workspace(R, "cuda"), ops.spec_accept_workspace(1, R, "cuda")
+        seedR = seed1.expand(R).contiguous()
+
+        def accept():
+            x = p.clone()
+            ops.sample_rows(x, V, seedR, si, 0.8, 50, 0.9, 0.0, write_scores=True, ws=sws)
+            ops.spec_accept_rows(x, q, dr, seed1, si[:1], V, ws=aws)
+        steps[f"warp_and_accept_ms_k{k}"] = timed(accept, warm + 20)
+        steps[f"accept_kernel_ms_k{k}"] = timed(lambda: ops.spec_accept_rows(p, q, dr, seed1, si[:1], V, ws=aws), warm + 20)
+    del cache
+
+    # ---- (2) end to end, greedy, scripted acceptance
+    def call(n, k=None, j=0, ref=None):
+        kw = dict(max_new_tokens=n, eos_token_id=None, return_dict_in_generate=True)
+        if k is not None:
+            kw.update(assistant_model=SimpleNamespace(engine=draft), num_assistant_tokens=k)
+        cfg = parse_generate_kwargs(kw, lookup=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            if k is not None:
+                cfg.drafter = _scripted_model_drafter(draft, k, cfg, n, prompt, ref, j)
+                cfg.drafter.start(ids, None, None, None)
+            out = greedy_generate(eng, ids, None, None, None, cfg)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    _, plain = call(new)
+    ref = plain.sequences[0].cpu().numpy().tolist()
+    arms = {"prefill": lambda: call(1), "prefill_both": lambda: call(1, ks[0], 0, ref), "plain": lambda: call(new)}
+    for k in ks:
+        for j in (0, k // 2, k):
+            arms[f"k{k}_a{j}"] = lambda k=k, j=j: call(new, k, j, ref)
+    ts, stats = {a: [] for a in arms}, {}
+    for a, f in arms.items():                                          # one untimed repetition of every arm
+        _, out = f()
+        if not a.startswith("prefill"):
+            assert torch.equal(out.sequences, plain.sequences), a
+        stats[a] = getattr(out, "assist_stats", None)
+    for _ in range(reps):
+        for a, f in arms.items():
+            ts[a].append(f()[0])
+    pre = {a: float(np.median(ts[a])) for a in ("prefill", "prefill_both")}
+    per_tok = {a: [(v - pre["prefill" if a == "plain" else "prefill_both"]) / (new - 1) for v in ts[a]] for a in arms if not a.startswith("prefill")}
+    med = {a: float(np.median(v)) for a, v in per_tok.items()}
+    spread = max(per_tok["plain"]) - min(per_tok["plain"])
+    rec = dict(geo=geo, mode="assistant_bench", B=1, prompt=prompt, new_tokens=new, reps=reps, draft_layers=draft_layers,
+               target_layers=eng.l["layers"], prefill_ms=round(pre["prefill"], 2), prefill_both_ms=round(pre["prefill_both"], 2),
+               steps={n: round(v, 3) for n, v in steps.items()}, plain_ms_per_token=round(med["plain"], 3),
+               plain_tokens_per_s=round(1e3 / med["plain"], 1), plain_spread_ms=round(spread, 3), arms={}, kernel_src=_src_hash())
+    for k in ks:
+        cell = {}
+        for j in (0, k // 2, k):
+            m = med[f"k{k}_a{j}"]
+            cell[f"accept_{j}_of_{k}"] = dict(ms_per_token=round(m, 3), tokens_per_s=round(1e3 / m, 1), speedup=round(med["plain"] / m, 3),
+                                             ms_all=[round(v, 3) for v in per_tok[f"k{k}_a{j}"]], stats=stats[f"k{k}_a{j}"],
+                                             differs_by_more_than_plain_spread=bool(abs(med["plain"] - m) > spread))
+        never = med[f"k{k}_a0"]                                         # a never-right round emits one token: its time is the round's
+        cell["break_even_accepted_per_round"] = round(max(never / med["plain"] - 1.0, 0.0), 3)
+        cell["break_even_acceptance_rate"] = round(max(never / med["plain"] - 1.0, 0.0) / k, 4)
+        rec["arms"][f"k{k}"] = cell
+    return [rec]
 
 
 def lookup_kernel_ab(geo, reps=40, rounds=3):
@@ -1963,6 +2097,8 @@ def main():
     ap.add_argument("--beams", action="store_true")
     ap.add_argument("--lookup", action="store_true")
     ap.add_argument("--lookup-kernel-ab", action="store_true")
+    ap.add_argument("--assistant", action="store_true")
+    ap.add_argument("--draft-layers", type=int, default=4)
     ap.add_argument("--cfg", action="store_true")
     ap.add_argument("--cfg-kernel-ab", action="store_true")
     ap.add_argument("--dola", action="store_true")
@@ -2015,6 +2151,10 @@ def main():
     elif a.beams:
         new = a.new if a.new != ap.get_default("new") else 48
         recs = [r for g in a.geos.split(",") for r in beams_kernel_ab(g, a.prompt, new) + beams_step_ab(g, a.prompt, new, reps=min(a.reps, 3))]
+    elif a.assistant:
+        geos = a.geos if a.geos != ap.get_default("geos") else "llava15_7b"
+        a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "assist_bench.jsonl")
+        recs = [r for g in geos.split(",") for r in assistant_bench(g, a.prompt, a.new, reps=min(a.reps, 3), draft_layers=a.draft_layers)]
     elif a.lookup_kernel_ab:
         recs = [r for g in a.geos.split(",") for r in lookup_kernel_ab(g)]
     elif a.lookup:
