@@ -207,7 +207,11 @@ int rv_attn_bwd_gqa(const void* q, int64_t ld_q, const void* k, int64_t ld_k, co
 /* The same with the adjoint of the rotary embedding folded into the dQ / dK epilogues (the backward of apply_rotary_pos_emb,
  * modeling_llama.py:167-198, on q and k that are stored rotated): dq and dk come out as gradients of the UN-rotated projections,
  * no separate pass over d(q|k|v).  rope_cos_sin: fp32 [positions, hd/2, 2] (NULL = plain rv_attn_bwd_gqa); position of a token row =
- * rope_positions[row] (required for packed batches) or its index inside the sample. */
+ * rope_positions[row] (required for packed batches) or its index inside the sample.
+ * ld_dq, ld_dk, ld_dv: multiples of 4 elements.  With grouped-query heads and a workspace the per-query-head dK/dV launch shape (partials
+ * summed by a second kernel that stores 16-byte vectors) is only taken when ld_dk and ld_dv are multiples of 8 and dk, dv are 16-byte
+ * aligned; otherwise the register-accumulating shape runs, whose results differ from it only in bf16 rounding points.  The same rule
+ * holds for rv_attn_bwd_nat. */
 int rv_attn_bwd_gqa_rope(const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t ld_v, const void* o,
                          int64_t ld_o, const void* dout, int64_t ld_do, const void* qT, const void* kT, const void* doT,
                          const float* lse, float* delta, void* dq, int64_t ld_dq, void* dk, int64_t ld_dk, void* dv,

@@ -1490,8 +1490,10 @@ extern "C" int rv_attn_bwd_gqa_rope(const void* q, int64_t ld_q, const void* k, 
     const long rows_all = cu_rows ? (long)total_rows : (long)B * S;      // token rows of q/k/v (packed: cu_rows[B])
     if (cu_rows && total_rows <= 0) return RV_ERR_ARG;
     const int64_t need = 2 * (int64_t)rows_all * H * HD * 2;
+    // group_sum_heads_kernel stores 16-byte vectors into dk / dv: strides of 4 elements (enough for the epilogues' 8-byte stores) or bases
+    // that are only 8-byte aligned keep the register-accumulating shape
     const bool expand = P.nrep > 1 && workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 15) == 0 &&
-                        (long)grid_dkv.x * H_kv * B < 2048;
+                        !(ld_dk & 7) && !(ld_dv & 7) && aligned_ok(dk) && aligned_ok(dv) && (long)grid_dkv.x * H_kv * B < 2048;
     if (expand) {
         PK.kdiv = P.nrep; PK.qrep = 1; PK.rope_dk = 0;       // partial dK rows are summed first, then un-rotated once
         PK.dk = (bf16*)workspace; PK.dv = (bf16*)workspace + (int64_t)rows_all * H * HD;
@@ -1546,6 +1548,7 @@ extern "C" int rv_attn_bwd_nat(const void* q, int64_t ld_q, const void* k, int64
     if (cu_rows && total_rows <= 0) return RV_ERR_ARG;
     const int64_t need = 2 * (int64_t)rows_all * H * HD * 2;
     const bool expand = P.nrep > 1 && workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 15) == 0 &&
+                        !(ld_dk & 7) && !(ld_dv & 7) && aligned_ok(dk) && aligned_ok(dv) &&      // group_sum_heads_kernel: 16-byte stores
                         (long)grid_dkv.x * H_kv * B < 4096;
     if (expand) {     // few key/value heads and a long causal sequence: per-query-head blocks + a group sum balance better
         PK.kdiv = P.nrep; PK.qrep = 1; PK.rope_dk = 0;

@@ -18,6 +18,19 @@ rounding moves delta by up to 2^-8 D -- that is the D term of W.  The gate of an
 store), 2 for dQ and dK (the dS rounding and the delta error share one 2^-8 W term; the store), 3 for dK / dV when the per-query-head
 partials are stored and summed by group_sum_heads_kernel.  2^-16 covers fp32 accumulation and the hardware exp / log.  lse is fp32 and is
 held to the project's fp32 figure, 1e-4 max(1, |ref|).
+
+Rotary adjoint (rope= of the backward: dq / dk come out as gradients of the UN-rotated q / k).  unrope() turns a gradient g of the rotated
+q or k and its budget A into g' = R^T g and A' = |R^T| A, per pair (lo, hi) = (e, e + hd/2) with (c, s) = cs[pos[row], e]:
+
+    g'_lo = g_lo c + g_hi s     g'_hi = g_hi c - g_lo s     A'_lo = |c| A_lo + |s| A_hi     A'_hi = |c| A_hi + |s| A_lo
+
+The gate stays the one above with ONE more rounding: 3 for dq, 3 for dk on the register-accumulating shape, 4 for dk on the per-query-head
++ group-sum shape; dv is untouched (2 and 3).  Why one: the un-rotated path's terms (the dS rounding and the delta error) move g by at most
+2^-8 A element-wise, which the rotation carries to at most 2^-8 A'.  The kernels then round the gradient to bf16 BEFORE they rotate it
+(the unfused sequence stored it first): one 2^-8 rounding of a value bounded by A -- |g| <= A holds element-wise because |dS| <= W --
+which the rotation again carries to 2^-8 A'.  That rounding takes the place of the un-rotated path's store.  The rotated value is rounded
+once more on the store: one 2^-8 rounding of a value bounded by A'.  cos / sin are the caller's fp32 table (values rounded through bf16,
+as the ABI says), read as float64: they are inputs, not errors, and the two fp32 products and their sum fall under the 2^-16 term.
 """
 import math
 
@@ -159,6 +172,21 @@ def reference(q, k, v, dout, B, S, H, Hkv, hd, causal, lens=None, cu=None, scale
         if keep_scores:
             res["scores2"].append(s * LOG2E)
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------- rotary adjoint
+def unrope(g, A, cs, pos, heads, hd):
+    """Adjoint of the rotary embedding on a gradient g [M, heads hd] of the ROTATED q or k and on its budget A (module docstring), in
+    float64.  cs: the [positions, hd/2, 2] (cos, sin) table handed to the kernel; pos [M]: the table row of every token row.
+    Returns (g', A')."""
+    M, half = g.shape[0], hd // 2
+    t = cs.detach().cpu().double()[torch.as_tensor(np.asarray(pos), dtype=torch.long)]          # [M, hd/2, 2]
+    c, s = t[:, None, :, 0], t[:, None, :, 1]
+    g, A = g.double().view(M, heads, hd), A.double().view(M, heads, hd)
+    lo, hi, a_lo, a_hi = g[..., :half], g[..., half:], A[..., :half], A[..., half:]
+    out = torch.cat((lo * c + hi * s, hi * c - lo * s), -1)
+    bound = torch.cat((c.abs() * a_lo + s.abs() * a_hi, c.abs() * a_hi + s.abs() * a_lo), -1)
+    return out.reshape(M, heads * hd), bound.reshape(M, heads * hd)
 
 
 # ---------------------------------------------------------------------------------------------------------------- gates
