@@ -451,6 +451,22 @@ int rv_adam8_dequantize_f32(const uint8_t* codes, const float* absmax, int64_t n
 int rv_adamw8(void* p_bf16, float* master, const void* g_bf16, uint8_t* codes_m, uint8_t* codes_v, float* absmax_m, float* absmax_v,
               const int64_t* table, int ntensors, int64_t nblocks, float lr, float b1, float b2, float eps, float wd, float bc1,
               float bc2, const float* gscale, void* stream);
+/* NF4 frozen decoder base of a LoRA run (QLoRA: --bits 4 --quant_type nf4; csrc/nf4.hip).  A block is 64 consecutive elements of one tensor
+ * counted from its first element (the last may be short), one fp32 absmax = max |x| per block (an all-zero block divides by 1), the
+ * sixteen levels of csrc/nf4_codebook.h, two codes per byte with element 2j in the high nibble (an odd length leaves the last low nibble
+ * 0).  The rule is tests/nf4_ref.py and the kernels match it bit for bit.
+ * quantise: codes[ceil(n / 2)] and absmax[ceil(n / 64)] of one bf16 tensor x[n]; code = the number of fp32 midpoints strictly below
+ * fp32(x) / absmax. */
+int rv_nf4_quantize_bf16(const void* x_bf16, int64_t n, uint8_t* codes, float* absmax, void* stream);
+/* One launch dequantises every tensor of a table into dst: dst[first destination + i] = bf16(level[code_i] * absmax of i's block), one fp32
+ * multiply and one rounding.  table: device int64 [6, ntensors] = each tensor's first chunk (0 for the first; a tensor owns ceil(length /
+ * 2048) consecutive chunks, nchunks in all), first code byte in `codes`, first absmax entry, length (> 0), first element in dst, first
+ * second-level scale.  Two modes.  absmax != NULL: plain fp32 absmax[first absmax entry + block].  absmax == NULL (double quantisation):
+ * the block's absmax is fp32(signed8[absmax_codes[first absmax entry + block]] * scale2[first scale + block / 256]) + offset[tensor], the
+ * signed table of csrc/adam8_codebook.h.  The destinations of the tensors need not be adjacent; nothing outside them is written.  Code
+ * bytes at a 4-byte and destinations at a 16-byte aligned address take vector accesses, anything else masked narrow ones. */
+int rv_nf4_dequant_bf16(const uint8_t* codes, const float* absmax, const uint8_t* absmax_codes, const float* scale2, const float* offset,
+                        const int64_t* table, int ntensors, int64_t nchunks, void* dst_bf16, void* stream);
 /* partial[blk] = sum of squares of the block's slice (fp32); finish with rv_clip_coef. */
 int rv_sumsq_partial_bf16(const void* g, int64_t n, float* partial, int nblk, void* stream);
 /* norm = sqrt(sum partial); out[0] = norm, out[1] = min(1, max_norm / (norm + 1e-6))  (torch clip_grad_norm_). */

@@ -6,7 +6,7 @@
 # scratch memory: a rolled epilogue loop once turned the GEMM accumulators into a scratch array and cost 18 % unnoticed.
 set -e
 cd "$(dirname "$0")"
-SRCS="gemm_bf16 attention ops gemv decode lora_merge extend sample beam lookup kvq cfg prefix score dola constrain policy preference lora_decode attn_probs kvpress adam8 distill spec"
+SRCS="gemm_bf16 attention ops gemv decode lora_merge extend sample beam lookup kvq cfg prefix score dola constrain policy preference lora_decode attn_probs kvpress adam8 distill spec nf4"
 OUT=${1:-libradvlm_hip.so}
 VARFLAGS="${*:2}"
 OBJ=build; [ $# -gt 0 ] && OBJ=build/${OUT%.so}

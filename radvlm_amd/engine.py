@@ -41,6 +41,7 @@ class LlavaEngine:
         self.weights_version = 0              # bumped by every write to the weights (weights_changed): a GenerationCache of an older one is stale
         self.w4 = None                        # per layer {name: (packed nibbles, E8M0 scale bytes)} after quantize_decoder_("mxfp4"); likewise
         self.w8 = None                        # per layer {name: (packed int8, fp32 scale)} after quantize_decoder_(); dropped by weights_changed
+        self.nf4 = None                       # the NF4 store of the frozen base after quantize_base_() (QLoRA); dequantize_base_() drops it
         assert recompute in (False, True, "auto")
         self.recompute = recompute            # activation recompute policy of the decoder layers (_recompute_layers)
         self.head_rows = "labeled"            # final norm + lm_head + cross entropy on the rows that carry a label ("all": every row)
@@ -252,6 +253,8 @@ class LlavaEngine:
         out = {}
         if self.l.get("qkv_bias"):
             out["bqkv"] = f.fused(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias", 1, d + 2 * self.kvd, flat).view(-1)
+        if self.nf4 is not None:       # the matrices are views of the one-layer scratch, valid until another layer is asked for
+            return dict(out, ln1=f.view(p + "input_layernorm.weight"), ln2=f.view(p + "post_attention_layernorm.weight"), **self._nf4_layer(i))
         return dict(
             out,
             ln1=f.view(p + "input_layernorm.weight", flat),
@@ -975,6 +978,116 @@ class LlavaEngine:
                     off, n = self.lm.offsets[f"model.layers.{i}.{t}.weight"]
                     self.master[off:off + n].copy_(ops.to_f32(self.lm.flat[off:off + n]))
 
+    # ------------------------------------------------------------------ NF4 frozen base (QLoRA)
+    def quantize_base_(self, quant_type="nf4", double_quant=False):
+        """QLoRA (the reference's --bits 4 --quant_type nf4 with --lora_enable): the seven decoder matrices of every layer of the frozen
+        base are quantised to NF4 (rv_nf4_quantize_bf16; 64 weights per block, one fp32 absmax each: 4.5 bits per weight) and the frozen
+        store is rebuilt WITHOUT them -- embeddings, norms, q/k/v biases and lm_head stay bf16.  double_quant: the absmax values are
+        themselves stored as one byte each, with one fp32 scale per 256 blocks and one fp32 mean per tensor (4.127 bits per weight); the
+        dequantised weights then use the rebuilt absmax, so the setting changes the model (tests/nf4_ref.py says exactly how).
+        From then on _layer_views(i) dequantises layer i into the one-layer bf16 scratch with one rv_nf4_dequant_bf16 launch and returns
+        views of it: forward, recompute and backward run through the unchanged GEMMs.  state_dict() gives the dequantised matrices;
+        dequantize_base_() makes the engine a plain LoRA engine on exactly those weights.  A one-time act (a second call raises
+        RuntimeError), LoRA engines only (ValueError otherwise).  During the act the bf16 base and the NF4 store are both resident: the
+        peak is bf16 + NF4, the saving comes after it.  Generation, scoring and the cached steps are refused on an NF4 base
+        (NotImplementedError); the forward-only training-path calls work.  Non-finite weights are outside the contract."""
+        from collections import OrderedDict
+        from . import nf4 as N
+        if quant_type != "nf4":
+            raise ValueError(f"quantize_base_(quant_type={quant_type!r}): only 'nf4' is built")
+        if not self.lora:
+            raise ValueError("quantize_base_() needs a LoRA engine: a 4-bit base is frozen, only adapters on top of it can train")
+        if self.nf4 is not None:
+            raise RuntimeError("quantize_base_(): the base is already NF4; a second pass would round the weights again")
+        plan = N.BasePlan(self.geo, double_quant)
+        dev, u8, f32 = self.device, torch.uint8, torch.float32
+        st = dict(plan=plan, codes=torch.zeros(plan.code_bytes, dtype=u8, device=dev), absmax=None, absmax_codes=None, scale2=None, offset=None)
+        if plan.double_quant:
+            st.update(absmax_codes=torch.zeros(plan.nblocks, dtype=u8, device=dev), scale2=torch.zeros(plan.nscale2, dtype=f32, device=dev))
+            offsets = np.zeros(len(plan.tensors), np.float32)
+            tmp = torch.empty(max(t["nblocks"] for t in plan.tensors.values()), dtype=f32, device=dev)
+        else:
+            st["absmax"] = torch.zeros(plan.nblocks, dtype=f32, device=dev)
+        for name, t in plan.tensors.items():
+            w = self.base.view(name).reshape(-1)
+            codes = st["codes"][t["code"]:t["code"] + (t["n"] + 1) // 2]
+            if not plan.double_quant:
+                ops.nf4_quantize(w, codes, st["absmax"][t["block"]:t["block"] + t["nblocks"]])
+                continue
+            # the second level, once per tensor at load: the mean in its fixed float64 order on the host (nf4.absmax_offset), the
+            # subtraction in fp32 there too, the 8-bit codes and scales by the optimizer state's own quantiser
+            ops.nf4_quantize(w, codes, tmp[:t["nblocks"]])
+            am = tmp[:t["nblocks"]].cpu().numpy()
+            offsets[t["slot"]] = off = N.absmax_offset(am)
+            ops.adam8_quantize(self._dev((am - off).astype(np.float32)), 0, codes=st["absmax_codes"][t["block"]:t["block"] + t["nblocks"]],
+                               absmax=st["scale2"][t["scale2"]:t["scale2"] + t["nscale2"]])
+        if plan.double_quant:
+            st["offset"] = self._dev(offsets)
+        keep = OrderedDict((k, v) for k, v in self.base.shapes.items() if k not in plan.tensors)
+        new = FlatParams(keep, dev)
+        for k in keep:
+            new.view(k).copy_(self.base.view(k))
+        self.base = new                        # the bf16 matrices go with the old store
+        # One scratch, one stream.  INVARIANT: no caller holds two layers' views at once -- _layer_forward, backward and the recompute
+        # inside it take layer i's views, finish every GEMM that reads them, and only then ask for another layer; the launches are
+        # ordered on the one stream the engine enqueues on.  `resident` is the layer the scratch holds (an immediately repeated request
+        # for it, as by backward after a recomputed forward, launches nothing).
+        tabs = [plan.table(plan.names(i)) for i in range(plan.layers)]
+        scratch = torch.zeros(plan.scratch_numel, dtype=BF16, device=dev)
+        views = {}
+        for key, first, last in (("qkv", "self_attn.q_proj", "self_attn.v_proj"), ("o", "self_attn.o_proj", "self_attn.o_proj"),
+                                 ("gu", "mlp.gate_proj", "mlp.up_proj"), ("down", "mlp.down_proj", "mlp.down_proj")):
+            a, b = plan.tensors[f"model.layers.0.{first}.weight"], plan.tensors[f"model.layers.0.{last}.weight"]
+            cols = a["shape"][1]
+            views[key] = scratch[a["dst"]:b["dst"] + b["n"]].view(-1, cols)
+        st.update(scratch=scratch, views=views, tables=tabs, tables_dev=[self._dev(tab) for tab, _ in tabs], resident=-1)
+        self.nf4 = st
+        self.weights_changed(tower=False)
+
+    def _nf4_dequant(self, i, dst, table=None):
+        """One rv_nf4_dequant_bf16 launch for layer i into the bf16 buffer dst; table: (host table, chunks) with other destinations
+        than the scratch offsets."""
+        st = self.nf4
+        per = st["plan"].per_layer
+        tab, nch = st["tables"][i] if table is None else table
+        tab_dev = st["tables_dev"][i] if table is None else self._dev(tab)
+        if st["plan"].double_quant:
+            ops.nf4_dequant(st["codes"], tab_dev, tab, nch, dst, absmax_codes=st["absmax_codes"], scale2=st["scale2"],
+                            offset=st["offset"][i * per:(i + 1) * per])
+        else:
+            ops.nf4_dequant(st["codes"], tab_dev, tab, nch, dst, absmax=st["absmax"])
+
+    def _nf4_layer(self, i):
+        """Layer i's four matrices as views of the scratch, dequantised now unless the scratch already holds that layer."""
+        st = self.nf4
+        if st["resident"] != i:
+            st["resident"] = -1
+            self._nf4_dequant(i, st["scratch"])
+            st["resident"] = i
+        return st["views"]
+
+    def dequantize_base_(self):
+        """The inverse act of quantize_base_() as far as there is one: the engine becomes a plain LoRA engine whose bf16 base holds
+        exactly the dequantised weights (what state_dict() gave), the NF4 store and the scratch are dropped.  RuntimeError without an
+        NF4 base."""
+        if self.nf4 is None:
+            raise RuntimeError("dequantize_base_(): the base is not quantised")
+        plan = self.nf4["plan"]
+        full = FlatParams(lm_param_shapes(self.geo, False), self.device)
+        for k in self.base.names():
+            full.view(k).copy_(self.base.view(k))
+        for i in range(plan.layers):
+            names = plan.names(i)
+            self._nf4_dequant(i, full.flat, table=plan.table(names, dst={k: full.offsets[k][0] for k in names}))
+        self.base, self.nf4 = full, None
+        self.weights_changed(tower=False)
+
+    def base_weight_bytes(self):
+        """Bytes of the seven decoder matrices of every layer as this engine stores them: the NF4 store after quantize_base_()
+        (nf4.BasePlan.base_weight_bytes; the one-layer scratch is not part of it), 2 bytes per weight otherwise."""
+        from . import nf4 as N
+        return self.nf4["plan"].base_weight_bytes() if self.nf4 is not None else N.bf16_matrix_bytes(self.geo)
+
     # Generation on unmerged adapters (model.enable_adapter_decoding()): off, every generation entry point refuses a LoRA engine as it
     # always has; on, prefill() runs the training path's adapted linears in eval form and the cached steps go through
     # _decode_lora_linear.  The adapters are read from self.lm on every call, so an optimizer_step() is seen by the next token.
@@ -984,6 +1097,9 @@ class LlavaEngine:
     adapters_off = False
 
     def _check_generation(self):
+        if self.nf4 is not None:             # the refusal table's row: no decode kernel reads the NF4 store
+            from .generation import refuse_combinations
+            refuse_combinations({"nf4"}, "generation")
         if self.lora and not self.adapter_decoding:
             raise NotImplementedError("generation with LoRA adapters: merge them into the base weights first with "
                                       "model.merge_and_unload() (the reference merges adapters before evaluation), or decode on the "
@@ -2089,6 +2205,8 @@ class LlavaEngine:
             bufs.append(("vision_tower", self.vis.flat))
         if self.base is not None:
             bufs.append(("frozen_language_model", self.base.flat))
+        if self.nf4 is not None:
+            bufs += [("nf4_" + k, self.nf4[k]) for k in ("codes", "absmax", "absmax_codes", "scale2", "offset") if self.nf4.get(k) is not None]
         bufs += [("fp32_master", self.master), ("exp_avg", self.m), ("exp_avg_sq", self.vv)]
         if self.state_bits == 8 and self.master is not None:
             bufs += [("exp_avg_codes", self.m8), ("exp_avg_sq_codes", self.v8), ("exp_avg_absmax", self.am8), ("exp_avg_sq_absmax", self.av8)]
@@ -2310,6 +2428,14 @@ class LlavaEngine:
                 if n in out:
                     continue        # the projector lives in the trainable buffer; the base store's copy of it is unused
                 out[n] = fp.view(n)[:self.vocab] if n in ("model.embed_tokens.weight", "lm_head.weight") else fp.view(n)
+        if self.nf4 is not None:            # an NF4 base: the dequantised bf16 matrices, which is what the model computes with
+            plan = self.nf4["plan"]
+            for i in range(plan.layers):
+                buf = torch.zeros(plan.scratch_numel, dtype=BF16, device=self.device)
+                self._nf4_dequant(i, buf)
+                for n in plan.names(i):
+                    t = plan.tensors[n]
+                    out[n] = buf[t["dst"]:t["dst"] + t["n"]].view(t["shape"])
         return out
 
     def lora_state_dict(self):
@@ -2359,6 +2485,8 @@ class LlavaEngine:
         the projector-only semantics (tune_mm_mlp_adapter): the projector trains, image_newline and the decoder are frozen."""
         if not self.lora:
             raise ValueError("merge_lora(): this engine has no LoRA adapters")
+        if self.nf4 is not None:            # the merged weight is bf16(deq(W) + s B A); it is not requantised
+            self.dequantize_base_()
         from collections import OrderedDict
         pairs = {}
         for i in range(self.l["layers"]):
@@ -2411,6 +2539,12 @@ class LlavaEngine:
 
     def load_state_dict(self, sd, strict=False):
         from .params import load_named
+        if self.nf4 is not None:
+            from .config import canonical_name
+            hit = [k for k in sd if canonical_name(k) in self.nf4["plan"].tensors]
+            if hit:
+                raise RuntimeError(f"load_state_dict(): {hit[0]} (and {len(hit) - 1} more) are decoder matrices of an NF4 base, which holds "
+                                   "codes, not bf16 weights; load before quantize_base_(), or call dequantize_base_() first")
         missing, rest = load_named(self.lm, sd)
         for fp in ([] if self.vis is self.lm else [self.vis]) + ([self.base] if self.base is not None else []):
             m, rest2 = load_named(fp, {k: v for k, v in sd.items() if k in rest})

@@ -133,7 +133,8 @@ def parse_generate_kwargs(kwargs, lora=False, config_eos=None, config_pad=None, 
 # the order is part of the behaviour.  A new feature adds its rows here and nowhere else.
 FEATURES = dict(kvpress="prompt_kv_budget / prompt_kv_window", attentions="output_attentions", constraint="constraint", guidance="guidance_scale",
                 dola="dola_layers", past_key_values="past_key_values", lookup="prompt_lookup_num_tokens", int8="kv_cache_dtype='int8'",
-                share_prefix="share_prefix=True", sampling="do_sample=True", lora="LoRA adapters", assistant="assistant_model")
+                share_prefix="share_prefix=True", sampling="do_sample=True", lora="LoRA adapters", assistant="assistant_model",
+                nf4="an NF4 base (quantize_base_())")
 REFUSALS = (
     ("kvpress", "past_key_values", "the extend pass reads a cache whose slots are its positions"),
     ("kvpress", "lookup", "the verify step reads a cache whose slots are its positions"),
@@ -170,6 +171,9 @@ REFUSALS = (
     ("dola", "assistant", "the verify step hands out no intermediate hidden states"),
     ("int8", "assistant", "the verify-attention kernel reads a bf16 cache only"),
     ("assistant", "past_key_values", "the draft model's cache is not kept across calls"),
+    # a row whose second feature is None refuses its first feature on its own: "<feature>: <why>"
+    ("nf4", None, "generation, scoring and the cached decode steps read bf16 (or int8 / MXFP4 decode) weights and there is no NF4 decode "
+                  "kernel; call model.dequantize_base_() to keep training on the dequantised bf16 base, or model.merge_and_unload()"),
 )
 
 
@@ -191,6 +195,8 @@ def refuse_combinations(features_on, where):
     if not set(features_on) <= set(FEATURES):
         raise ValueError(f"{where}: unknown features {sorted(set(features_on) - set(FEATURES))}")
     for a, b, why in REFUSALS:
+        if a in features_on and b is None:
+            raise NotImplementedError(f"{FEATURES[a]}: {why}")
         if a in features_on and b in features_on:
             raise NotImplementedError(f"{FEATURES[a]} with {FEATURES[b]}: {why}")
 

@@ -667,10 +667,26 @@ class LlavaLlamaForCausalLM:
     def is_quantized(self):
         return self.engine.is_quantized
 
+    def quantize_base_(self, quant_type="nf4", double_quant=False):
+        """QLoRA, the reference's --bits 4 --quant_type nf4 with --lora_enable: the frozen base's decoder matrices become NF4 codes (4.5
+        bits per weight, 4.127 with double_quant) and every training pass dequantises one layer at a time into a bf16 scratch
+        (LlavaEngine.quantize_base_).  Needs a model with LoRA adapters (ValueError); a one-time act (RuntimeError).  forward(),
+        token_logps(), sequence_logps(), label_logits(), preference_loss() and disable_adapter() work on it; generate*, score() and
+        everything built on the KV cache raise NotImplementedError until dequantize_base_() or merge_and_unload().  state_dict() holds
+        the dequantised bf16 matrices.  Returns self."""
+        self.engine.quantize_base_(quant_type, double_quant)
+        return self
+
+    def dequantize_base_(self):
+        """Back to a plain LoRA model whose bf16 base holds exactly the dequantised weights (LlavaEngine.dequantize_base_).  Returns self."""
+        self.engine.dequantize_base_()
+        return self
+
     def merge_and_unload(self):
         """peft's merge_and_unload: W += (alpha / r) B A for every adapted linear (rv_lora_merge_bf16), the adapters are dropped and the
         model is a plain one (config.lora cleared; save_pretrained then writes the full model.safetensors).  The engine keeps the
-        projector-only layout (LlavaEngine.merge_lora).  Returns self."""
+        projector-only layout (LlavaEngine.merge_lora).  On an NF4 base it is dequantize_base_() followed by the same merge: the merged
+        weight is bf16(deq(W) + (alpha / r) B A) and is NOT requantised.  Returns self."""
         if not self.engine.lora:
             raise ValueError("merge_and_unload() needs a model with LoRA adapters")
         self.engine.merge_lora()
@@ -679,7 +695,10 @@ class LlavaLlamaForCausalLM:
 
     @property
     def _lora_refused(self):
-        """What the generation parsers take as `lora=`: unmerged adapters that generation may not read."""
+        """What the generation parsers take as `lora=`: unmerged adapters that generation may not read.  Every generation entry point
+        reads it first, so an NF4 base is refused here by its own row of the refusal table, before the adapters are looked at."""
+        if self.engine.nf4 is not None:
+            self.engine._check_generation()
         return bool(self.engine.lora) and not self.engine.adapter_decoding
 
     def enable_adapter_decoding(self, on=True):

@@ -53,6 +53,9 @@ class GKDTrainer(LLaVATrainer):
             raise ValueError(f"max_new_tokens must be >= 1, got {self.max_new_tokens}")
         if teacher_model.engine.vocab != model.engine.vocab:
             raise ValueError(f"the teacher's vocabulary ({teacher_model.engine.vocab}) is not the student's ({model.engine.vocab})")
+        if getattr(model.engine, "nf4", None) is not None:
+            raise NotImplementedError("GKD with an NF4 student: on-policy samples need generation, which has no NF4 decode kernel; "
+                                      "model.dequantize_base_() or merge_and_unload() first")
         live = bool(model.engine.lora) and model.engine.adapter_decoding    # samples from the unmerged adapters
         if model.engine.lora and self.lmbda > 0 and not live:
             raise NotImplementedError("GKD with lmbda > 0 on a LoRA engine: generation refuses unmerged adapters; merge_and_unload() first, "

@@ -47,6 +47,9 @@ class GRPOTrainer(LLaVATrainer):
         if self.G < 2:
             raise ValueError(f"num_generations must be at least 2 (the group is the baseline), got {self.G}")
         self.beta = float(getattr(a, "beta", 0.0) or 0.0)
+        if getattr(model.engine, "nf4", None) is not None:
+            raise NotImplementedError("GRPO on an NF4 base: rollouts need generation, which has no NF4 decode kernel; "
+                                      "model.dequantize_base_() or merge_and_unload() first")
         live = bool(model.engine.lora) and model.engine.adapter_decoding    # rollouts on the unmerged adapters
         if self.beta > 0 and ref_model is None and not live:
             raise ValueError("beta > 0 needs ref_model (the KL term is taken against its token_logps)")

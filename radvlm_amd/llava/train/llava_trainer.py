@@ -447,7 +447,17 @@ class LLaVATrainer:
             optim_meta = None
         with open(os.path.join(path, "trainer_state.json"), "w") as f:
             json.dump({"global_step": self.state["global_step"], "opt_step": eng.opt_step, "lora_step": eng.lora_step,
-                       "log_history": self.state["log_history"], **({"optim_state": optim_meta} if optim_meta else {})}, f)
+                       "log_history": self.state["log_history"], **({"optim_state": optim_meta} if optim_meta else {}),
+                       **({"base_quant": self._base_quant()} if self._base_quant() else {})}, f)
+
+    def _base_quant(self):
+        """The NF4 base's record for trainer_state.json (None on a bf16 base): a LoRA checkpoint does not hold the base, so a resume
+        quantises it again from the same source -- which gives the same store only under the same setting and tables."""
+        st = getattr(self.model.engine, "nf4", None)
+        if st is None:
+            return None
+        from ...nf4 import base_quant_record
+        return base_quant_record(st["plan"].double_quant)
 
     def _rotate_checkpoints(self, output_dir, rank=0):
         """--save_total_limit N (HF Trainer._rotate_checkpoints; finetune_radio_7b.sh:72 passes 1): keep the N newest checkpoint-* directories
@@ -475,6 +485,11 @@ class LLaVATrainer:
         import json
         from safetensors.torch import load_file
         eng = self.model.engine
+        with open(os.path.join(path, "trainer_state.json")) as f:
+            saved_quant = json.load(f).get("base_quant")
+        if saved_quant != self._base_quant():
+            raise ValueError(f"{path} was trained on the base {saved_quant or 'bf16'}, this run has {self._base_quant() or 'bf16'}: the adapters "
+                             "were fitted to other weights (pass the same --bits / --quant_type / --double_quant)")
         if eng.lora:
             self.model.load_adapter(path)
         elif os.path.exists(os.path.join(path, "model.safetensors")):

@@ -5,7 +5,9 @@ Mirrors the surface of reference finetuning/llava/train/train.py (SURVEY.md sect
 preprocess_qwen (:560-633, ChatML masking), preprocess (:904-952), LazySupervisedDataset (:955-1239),
 DataCollatorForSupervisedDataset (:1243-1286), make_supervised_data_module (:1289-1293), find_all_linear_names
 (:242-255), the tunable-parts policy (:1613-1665) and train() (:1449-1725).  Flags that configure machinery this
-build replaces (DeepSpeed, torch.compile, bits/quantisation) are accepted and ignored; --gradient_checkpointing selects the
+build replaces (DeepSpeed, torch.compile) are accepted and ignored; --bits 4 --quant_type nf4 [--double_quant] with --lora_enable is
+QLoRA (the frozen base's decoder matrices are NF4, LlavaEngine.quantize_base_), every other --bits / --quant_type combination trains
+on the bf16 base and says so once; --gradient_checkpointing selects the
 engine's activation-recompute policy ("auto": layers recompute only when their activations would not fit in HBM).
 """
 import argparse
@@ -599,6 +601,19 @@ def train(attn_implementation=None, argv=None, tokenizer=None, arg_groups=None, 
     # DDP broadcasts rank 0's parameters when it wraps the model (HF Trainer / accelerate): here every rank initialised or
     # loaded its own copy -- one broadcast makes the replicas identical by construction, the check below proves it from then on
     model.engine.broadcast_parameters()
+    # --bits 4 --quant_type nf4 with --lora_enable (train/train.py:1466-1503: the base loaded through 4-bit bitsandbytes, QLoRA): the frozen
+    # base's decoder matrices become NF4 now that the weights are loaded.  Every rank quantises the same weights to the same bits, so
+    # nothing new is synchronised; a resumed run quantises the same source again and gets the same store.
+    from ...nf4 import base_quant_choice
+    if base_quant_choice(training_args.bits, training_args.quant_type, training_args.lora_enable,
+                         say=(lambda msg: print(msg, flush=True)) if rank == 0 else None) == "nf4":
+        before = model.engine.base_weight_bytes()
+        model.quantize_base_("nf4", double_quant=bool(training_args.double_quant))
+        if rank == 0:
+            after = model.engine.base_weight_bytes()
+            print(f"[train] --bits 4 --quant_type nf4 --double_quant {bool(training_args.double_quant)}: the frozen decoder matrices are NF4, "
+                  f"{after / 2**30:.3f} GiB instead of {before / 2**30:.3f} GiB of bf16 ({(before - after) / 2**30:.3f} GiB saved; one layer's "
+                  f"bf16 scratch of {model.engine.nf4['plan'].scratch_bytes() / 2**20:.1f} MiB is dequantised per layer pass)", flush=True)
     model.config.use_cache = False
     model.get_model().initialize_vision_modules(model_args)
     if model_args.version in conversation_lib.conv_templates:

@@ -650,6 +650,42 @@ def adam8_dequantize(codes, absmax, n, kind, out=None):
     return out
 
 
+def nf4_quantize(x, codes=None, absmax=None):
+    """bf16 tensor -> (packed NF4 codes uint8 [ceil(n / 2)], fp32 absmax [ceil(n / 64)]) of the frozen QLoRA base (csrc/nf4.hip)."""
+    n = x.numel()
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and n > 0
+    codes = torch.empty((n + 1) // 2, dtype=torch.uint8, device=x.device) if codes is None else codes
+    absmax = torch.empty((n + 63) // 64, dtype=torch.float32, device=x.device) if absmax is None else absmax
+    assert codes.dtype == torch.uint8 and codes.numel() >= (n + 1) // 2 and codes.is_contiguous()
+    assert absmax.dtype == torch.float32 and absmax.numel() >= (n + 63) // 64 and absmax.is_contiguous()
+    lib.call("rv_nf4_quantize_bf16", x, n, codes, absmax)
+    return codes, absmax
+
+
+def nf4_dequant(codes, table, host_table, nchunks, dst, absmax=None, absmax_codes=None, scale2=None, offset=None):
+    """rv_nf4_dequant_bf16: one launch writes every tensor of `table` (device int64 [6, T], nf4.BasePlan.table) into the bf16 buffer
+    `dst`.  absmax: the plain mode; absmax_codes + scale2 + offset (one per tensor of the table): double quantisation.  host_table is
+    the same table on the host: every range the kernel will touch is checked against the buffers here, the kernel trusts the table."""
+    T = int(host_table.shape[1])
+    assert table.dtype == torch.int64 and tuple(table.shape) == (6, T) and table.is_contiguous() and table.is_cuda
+    assert codes.dtype == torch.uint8 and dst.dtype == torch.bfloat16 and dst.is_contiguous() and codes.is_contiguous()
+    dq = absmax is None
+    if dq:
+        assert absmax_codes.dtype == torch.uint8 and scale2.dtype == torch.float32 and offset.dtype == torch.float32 and offset.numel() >= T
+    else:
+        assert absmax.dtype == torch.float32 and absmax_codes is None and scale2 is None and offset is None
+    chunk0, code0, blk0, n, dst0, s20 = (host_table[k] for k in range(6))
+    nch = (n + 2047) // 2048
+    assert n.min() > 0 and chunk0[0] == 0 and (chunk0[1:] == (chunk0 + nch)[:-1]).all() and int((chunk0 + nch)[-1]) == int(nchunks)
+    nb = (n + 63) // 64
+    assert min(code0.min(), blk0.min(), dst0.min(), s20.min()) >= 0
+    assert int((code0 + (n + 1) // 2).max()) <= codes.numel() and int((dst0 + n).max()) <= dst.numel()
+    assert int((blk0 + nb).max()) <= (absmax_codes if dq else absmax).numel()
+    assert not dq or int((s20 + (nb + 255) // 256).max()) <= scale2.numel()
+    lib.call("rv_nf4_dequant_bf16", codes, absmax, absmax_codes, scale2, offset, table, T, int(nchunks), dst)
+    return dst
+
+
 def adamw8(p, master, g, codes_m, codes_v, absmax_m, absmax_v, table, nblocks, lr, b1, b2, eps, wd, step, gscale=None):
     """rv_adamw8 on one slice: `table` is the device int64 [3, T] block table of optim8.StatePlan.block_table, the code buffers hold
     nblocks * 256 bytes and the absmax buffers nblocks floats (checked here: the kernel trusts them)."""
